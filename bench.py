@@ -2,6 +2,16 @@
 """bench.py — MC energy-evaluations/sec of the MI355X backend on the BASELINE.json workload.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (+ every secondary figure and cross-check listed below)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's results as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step) with the run's configuration.  `--full` adds, after the timed region, everything listed under "The ONE JSON line
+carries" below (with N > 1 also `per_rank`, `gather_verified` and the check of each rank's gathered block against its own results).
+`--dump-outputs DIR` writes what a caller of the timed path receives after the last timed step: per-chain energies and their
+ensemble std (float32 words and float64), per-atom forces and their std (float32), and for N > 1 the gathered per-chain
+(E, sigma_E) of every rank (float64); rank 0 writes its own block.  The inputs are fixed (seeded chains), so two builds can be
+compared file for file.
 
 One "step" = one lock-step energy+force evaluation of every resident chain: neighbor list +
 3-model PaiNN ensemble forward + reverse pass (what one BFGS step costs in the reference,
@@ -16,7 +26,7 @@ paths), `--chains-per-gpu B`.  `--streams S` (default 2): a GPU's chains are spl
 handle each) that run concurrently -- the latency-bound node kernels of one half fill issue slots under the edge kernels of
 the other; `config.streams_per_gpu` says what ran.
 
-The ONE JSON line carries, besides the contract fields:
+The ONE JSON line carries, besides the contract fields (with `--full` only):
   roofline      dominant kernel = reverse neighbor pass: `achieved` = ALGORITHMIC flops per launch (2 x 17 408 flop
                 per real directed edge and model) / launch time, `peak` = 2.5 PFLOP/s dense fp16 (the pipe the contraction
                 executes on); `executed_pipe` = matrix-pipe occupancy (static MFMA count x 16x16x32x2 / launch time: ~2.9 x the
@@ -295,13 +305,67 @@ def cpu_baseline(blobs, chains, table, const, budget_s=12.0):
     return best
 
 
+def headline(args, world, count, chains, elapsed, stats, n_str, sharded, dist_backend, n_models):
+    """The contract fields of the JSON line and the run's configuration: everything a plain run prints."""
+    return {
+        "metric": "MC energy-evaluations/sec (SrTiO3(001) ~250-atom slabs, 3-model PaiNN ensemble E+F incl. neighbor list)",
+        "value": world * count * args.steps / elapsed, "unit": "evaluations/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "full": bool(args.full),
+        "config": {"workload": (f"SrTiO3(001) PaiNN x3, {count} batched independent chains per GPU "
+                                f"(BASELINE configs[{3 if world == 1 else 4}]), 248-272 atoms/chain"
+                                if args.atoms_per_chain == 260 else
+                                f"SECONDARY (not the BASELINE workload): SrTiO3(001) PaiNN x3, {count} chains per GPU, "
+                                f"{min(len(c) for c in chains)}-{max(len(c) for c in chains)} atoms/chain"),
+                   "chains_per_gpu": count, "atoms_per_gpu": stats["atoms"], "edges_per_gpu": stats["edges"],
+                   "slots_per_gpu": stats["slots"], "models": n_models, "streams_per_gpu": n_str,
+                   "streams_note": (f"the {count} chains of a GPU are split over {n_str} engines (own HIP streams) that run "
+                                    "concurrently; results bit-identical to one engine ("
+                                    + ("checked in this run)" if args.full else "checked by --full runs)")
+                                    if n_str > 1 else "one engine, one HIP stream"),
+                   "result_path": sharded.result_path, "dist_backend": dist_backend if world > 1 else None,
+                   "gather_transport": (sharded._gather.transport if sharded._gather is not None else None),
+                   "gathered_dtype": "f64 (E, sigma_E as the device forms them; results[\"energy\"] stays float32)" if world > 1 else None,
+                   "timed_region_note": ("K steps, then ONE ShardedEnsemble.check() (device result path: a host read of the "
+                                         "gathered overflow column, returns at once when no rank overflowed) and the closing "
+                                         "fence are inside the timed region") if world > 1 else
+                                        "K steps + the closing fence; check() returns at once without a gather",
+                   "parallelism": ("one GPU, no collective" if world == 1 else
+                                   f"chains sharded x{world} (rank r owns chains [{count} r, {count} r + {count})), "
+                                   + ("RCCL" if dist_backend == "nccl" else dist_backend)
+                                   + " all_gather of per-chain (E, sigma_E)"
+                                   + (" from device buffers" if sharded.result_path == "device" else " (host result path)"))},
+    }
+
+
+DUMPED = ("energy", "energy_std", "energy_f64", "energy_std_f64", "forces", "forces_std")
+
+
+def dump_outputs(out_dir, res, gathered=None):
+    """What a caller of the timed path receives after the last timed step, one .npy per array (float32 / float64 as returned):
+    this rank's per-chain energies + ensemble std, per-atom forces + std, and for N > 1 the gathered per-chain (E, sigma_E)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: res[k] for k in DUMPED}
+    if gathered is not None:
+        arrays["gathered"] = np.asarray(gathered[:, :2], dtype=np.float64)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)     # SURVEY §8(d): 200 timed lock-step evaluations ...
     ap.add_argument("--warmup", type=int, default=20)     # ... after 20 warm-up
     ap.add_argument("--chains-per-gpu", type=int, default=CHAINS_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kernel pass (roofline, north_star, kernel_ms_per_step), the "
+                         "host round-trip pass (pcie_inclusive), the CPU baseline, the engine-split check and, for N > 1, the "
+                         "per-rank diagnostics and the cross-rank verification; a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (what a caller of the timed path receives) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--atoms-per-chain", type=int, default=260,
                     help="secondary lines: larger slabs (e.g. 480: 4 x 2 tiling, served by the 8-feature-slice neighbor kernels); "
                          "the default 260 is the BASELINE workload")
@@ -309,11 +373,11 @@ def main():
                     help="split this GPU's chains over S engines (own HIP streams) that run concurrently (default 2: +2.5 .. 4 %% "
                          "over one stream, DESIGN.md section 5); the per-kernel launch times of `roofline` always come from a "
                          "separate single-stream pass after the timed region")
-    ap.add_argument("--profile-steps", type=int, default=20, help="steps of the single-stream per-kernel timing pass")
+    ap.add_argument("--profile-steps", type=int, default=20, help="--full: steps of the single-stream per-kernel timing pass")
     ap.add_argument("--verify-ranks", type=int, default=2,
-                    help="N > 1: rank 0 re-evaluates chains of this many OTHER ranks' blocks and compares them bit-exactly with the "
+                    help="--full, N > 1: rank 0 re-evaluates chains of this many OTHER ranks' blocks and compares them bit-exactly with the "
                          "gathered rows (0 = off); mismatch = non-zero exit")
-    ap.add_argument("--verify-chains", type=int, default=4, help="chains per verified rank (at least 4)")
+    ap.add_argument("--verify-chains", type=int, default=4, help="--full: chains per verified rank (at least 4)")
     ap.add_argument("--dump-gathered", default=None,
                     help="rank 0 writes the last step's gathered per-chain [n_chains, >= 2] (E, sigma_E) array to this .npy (tests)")
     args = ap.parse_args()
@@ -423,16 +487,30 @@ def main():
     g = None
     if world > 1:
         g = gathered.detach().cpu().numpy()       # float64 [n_chains, 2 or 3]: (E, sigma_E[, overflow flag]) of EVERY rank's chains
-        if not (np.array_equal(g[first:first + count, 0], res["energy_f64"])
-                and np.array_equal(g[first:first + count, 1], res["energy_std_f64"])
-                and np.array_equal(g[first:first + count, 0].astype(np.float32), res["energy"])):
+        if args.full and not (np.array_equal(g[first:first + count, 0], res["energy_f64"])
+                              and np.array_equal(g[first:first + count, 1], res["energy_std_f64"])
+                              and np.array_equal(g[first:first + count, 0].astype(np.float32), res["energy"])):
             print(f"bench.py: rank {rank}: the gathered block of this rank differs from its own results", file=sys.stderr, flush=True)
             raise SystemExit(4)
         if rank == 0 and args.dump_gathered:
             np.save(args.dump_gathered, g)
     elif args.dump_gathered:
         np.save(args.dump_gathered, np.stack([res["energy_f64"], res["energy_std_f64"]], axis=1))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, g)
 
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, count, chains, elapsed, stats, n_str, sharded, dist_backend, len(blobs))),
+                  flush=True)
+        for e in engs:
+            e.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ======== --full: everything below runs after the timed region and only with --full ========================================
     per_rank = None
     if world > 1:   # first-contact diagnostics, outside the timed region (rank_diagnostics)
         per_rank = rank_diagnostics(sharded, dist, elapsed_local, args.steps, want, dev if dist_backend == "nccl" else "cpu")
@@ -513,8 +591,6 @@ def main():
                 "per_step": "vssr_batch_set_positions (66.5 k x 24 B up) + run + vssr_batch_download (E, sigma_E, F, sigma_F down)"}
 
     if rank == 0:
-        total_evals = world * count * args.steps
-        value = total_evals / elapsed
         M = len(blobs)
 
         def launch_ms(cls):
@@ -548,33 +624,8 @@ def main():
         step_ms = sum(v["total_ms"] for v in prof.values()) / k_prof
         step_flops = 33.0e6 * N     # 33 MFLOP per atom and ensemble evaluation (fp32-equivalent algorithmic work)
         prof_c = committed_profile()
-        line = {
-            "metric": "MC energy-evaluations/sec (SrTiO3(001) ~250-atom slabs, 3-model PaiNN ensemble E+F incl. neighbor list)",
-            "value": value, "unit": "evaluations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-            "config": {"workload": (f"SrTiO3(001) PaiNN x3, {count} batched independent chains per GPU "
-                                    f"(BASELINE configs[{3 if world == 1 else 4}]), 248-272 atoms/chain"
-                                    if args.atoms_per_chain == 260 else
-                                    f"SECONDARY (not the BASELINE workload): SrTiO3(001) PaiNN x3, {count} chains per GPU, "
-                                    f"{min(len(c) for c in chains)}-{max(len(c) for c in chains)} atoms/chain"),
-                       "chains_per_gpu": count, "atoms_per_gpu": stats["atoms"], "edges_per_gpu": stats["edges"],
-                       "slots_per_gpu": stats["slots"], "models": M, "streams_per_gpu": n_str,
-                       "streams_note": (f"the {count} chains of a GPU are split over {n_str} engines (own HIP streams) that run "
-                                        "concurrently; results bit-identical to one engine (checked in this run)"
-                                        if n_str > 1 else "one engine, one HIP stream"),
-                       "result_path": sharded.result_path, "dist_backend": dist_backend if world > 1 else None,
-                       "gather_transport": (sharded._gather.transport if sharded._gather is not None else None),
-                       "gathered_dtype": "f64 (E, sigma_E as the device forms them; results[\"energy\"] stays float32)" if world > 1 else None,
-                       "timed_region_note": ("K steps, then ONE ShardedEnsemble.check() (device result path: a host read of the "
-                                             "gathered overflow column, returns at once when no rank overflowed) and the closing "
-                                             "fence are inside the timed region") if world > 1 else
-                                            "K steps + the closing fence; check() returns at once without a gather",
-                       "parallelism": ("one GPU, no collective" if world == 1 else
-                                       f"chains sharded x{world} (rank r owns chains [{count} r, {count} r + {count})), "
-                                       + ("RCCL" if dist_backend == "nccl" else dist_backend)
-                                       + " all_gather of per-chain (E, sigma_E)"
-                                       + (" from device buffers" if sharded.result_path == "device" else " (host result path)"))},
+        line = headline(args, world, count, chains, elapsed, stats, n_str, sharded, dist_backend, M)
+        line.update({
             # Dominant kernel: the reverse neighbor pass (k_edge_bwd_mfma, layers 2 and 1; layer 0 is factorised by species and
             # has its own profiler class), priced on the pipe it executes on.
             "roofline": {"bound": "mfma",
@@ -636,7 +687,7 @@ def main():
             "pcie_inclusive": pcie,
             "gather_verified": gather_verified,
             "per_rank": per_rank,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(blobs, chains, table, const)
         else:

@@ -472,3 +472,23 @@ def test_bench_quotes_counter_profiles_only_for_the_kernels_they_measured(tmp_pa
     monkeypatch.undo()
     d = bench.csrc_digest()
     assert len(d) == 64 and d == bench.csrc_digest()
+
+
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """`bench.py --dump-outputs DIR`: one .npy per returned array, float32 / float64 as the caller receives them; for N > 1 the
+    gathered per-chain (E, sigma_E) without the overflow column."""
+    import bench
+
+    rng = np.random.default_rng(0)
+    res = {"energy": rng.random(4, dtype=np.float32), "energy_std": rng.random(4, dtype=np.float32),
+           "energy_f64": rng.random(4), "energy_std_f64": rng.random(4), "forces": rng.random((10, 3), dtype=np.float32),
+           "forces_std": rng.random((10, 3), dtype=np.float32), "cfg_start": np.arange(5), "saturated": np.zeros(4, bool)}
+    g = np.column_stack([rng.random(8), rng.random(8), np.zeros(8)])
+    bench.dump_outputs(str(tmp_path / "a"), res)
+    bench.dump_outputs(str(tmp_path / "b"), res, g)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(f"{k}.npy" for k in bench.DUMPED)
+    for k in bench.DUMPED:
+        a = np.load(tmp_path / "a" / f"{k}.npy")
+        assert a.dtype == res[k].dtype and np.array_equal(a, res[k])
+    gb = np.load(tmp_path / "b" / "gathered.npy")
+    assert gb.dtype == np.float64 and np.array_equal(gb, g[:, :2])

@@ -358,7 +358,7 @@ def _rccl_comes_up(timeout_s):
 
 
 def _run_bench_ranks(tmp_path, world, chains_per_gpu, result_path, steps=3):
-    """`python -m torch.distributed.run --nproc-per-node <world> bench.py --gpus <world> ...` as a FRESH subprocess (torchrun
+    """`python -m torch.distributed.run --nproc-per-node <world> bench.py --gpus <world> --full ...` as a FRESH subprocess (torchrun
     starts the ranks before anything touches the GPU; this process never re-execs), all ranks on device 0 over gloo."""
     import json
     import subprocess
@@ -373,7 +373,7 @@ def _run_bench_ranks(tmp_path, world, chains_per_gpu, result_path, steps=3):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps),
-           "--warmup", "1", "--chains-per-gpu", str(chains_per_gpu), "--no-cpu-baseline", "--dump-gathered", str(dump)]
+           "--warmup", "1", "--chains-per-gpu", str(chains_per_gpu), "--full", "--no-cpu-baseline", "--dump-gathered", str(dump)]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -441,6 +441,47 @@ def test_bench_entry_point_eight_ranks_on_one_gpu(tmp_path):
     assert gathered.shape == (64, 3) and not gathered[:, 2].any()
     full = _one_engine_reference(64)
     assert np.array_equal(gathered[:, 0], full["energy_f64"]) and np.array_equal(gathered[:, 1], full["energy_std_f64"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`` without ``--full``: ONE JSON line with the contract fields
+    and none of the ``--full`` figures, ``value`` = chains x K / (K x ms_per_step), and the dumped arrays are what one engine
+    computes for the same chains, bit for bit (the default run splits them over two engines)."""
+    import json
+    import subprocess
+
+    import bench
+    from surface_sampling_amd import backend
+    from surface_sampling_amd.calculators import stoich_offset_table
+
+    out = tmp_path / "out"
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--chains-per-gpu", "16",
+           "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "evaluations/s" and line["higher_is_better"] is True and line["dtype"] == bench.DTYPE
+    assert abs(line["value"] - 16 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "north_star", "kernel_ms_per_step", "pcie_inclusive", "cpu_baseline", "gather_verified"} & set(line)
+    blobs, S, offset_data = bench.load_golden()
+    table, const = stoich_offset_table(offset_data)
+    chains = bench.build_chains(S, 0, 16)
+    eng = backend.PainnEngine(blobs, device=0, offset_per_z=table, offset_const=const)
+    full = eng.evaluate([(c.numbers, c.positions, c.cell, c.pbc) for c in chains],
+                        backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_STD)
+    eng.close()
+    assert sorted(f.name for f in out.iterdir()) == sorted(f"{k}.npy" for k in bench.DUMPED)
+    for k in bench.DUMPED:
+        a = np.load(out / f"{k}.npy")
+        assert a.dtype == full[k].dtype and a.dtype in (np.float32, np.float64) and np.array_equal(a, full[k]), k
 
 
 @pytest.mark.gpu

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 for rep in $(seq 1 ${AB_REPS:-2}); do
 for f in build/variants/lib_*.so; do
-  VSSR_EVAL_LIB=$PWD/$f python bench.py --steps ${AB_STEPS:-8} --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
+  VSSR_EVAL_LIB=$PWD/$f python bench.py --full --steps ${AB_STEPS:-8} --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernel_ms_per_step']

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 var=$1; shift
 for rep in $(seq 1 ${AB_REPS:-2}); do
 for v in "$@"; do
-  env $var=$v python bench.py --steps ${AB_STEPS:-10} --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | python -c "
+  env $var=$v python bench.py --full --steps ${AB_STEPS:-10} --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernel_ms_per_step']

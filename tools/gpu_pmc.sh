@@ -12,7 +12,7 @@ rc=0
 run_pass () {
   name=$1; shift
   rm -rf "$O/pmc_$name"
-  timeout 600 rocprofv3 --pmc "$@" --kernel-include-regex "$KREGEX" --output-format csv -d "$O/pmc_$name" -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --streams 1 > /dev/null 2> "$O/pmc_$name.err"
+  timeout 600 rocprofv3 --pmc "$@" --kernel-include-regex "$KREGEX" --output-format csv -d "$O/pmc_$name" -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --streams 1 > /dev/null 2> "$O/pmc_$name.err"
   if ! find "$O/pmc_$name" -name '*counter_collection.csv' | grep -q .; then
     echo "gpu_pmc.sh: pass $name produced no counter CSV:" >&2; tail -3 "$O/pmc_$name.err" >&2; rc=1
   fi

@@ -51,7 +51,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
     out["_meta"] = {"csrc_sha256": bench.csrc_digest(), "collected_by": "tools/gpu_pmc.sh (rocprofv3 --pmc passes of "
-                    "`bench.py --steps 1 --warmup 1 --streams 1`, one pass per counter set, no tracing flags)"}
+                    "`bench.py --full --steps 1 --warmup 1 --streams 1`, one pass per counter set, no tracing flags)"}
     json.dump(out, open(os.path.join(root, "pmc_summary.json"), "w"), indent=1, sort_keys=True)
     cols = ("cycles_per_launch", "matrix_pipe_busy_pct_of_simd_cycles", "valu_active_pct_of_simd_cycles", "wait_inst_any_pct_of_wave_cycles",
             "wait_any_pct_of_wave_cycles", "ta_busy_pct", "l1_accesses_per_cu_cycle", "hbm_traffic_bytes_per_launch")
