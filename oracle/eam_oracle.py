@@ -56,13 +56,18 @@ def eam(funcfl, pos, cell, pbc):
     F = build_spline(funcfl.frho, funcfl.drho)
     R = build_spline(funcfl.rhor, funcfl.dr)
     Z2 = build_spline(27.2 * 0.529 * np.asarray(funcfl.zr, float) ** 2, funcfl.dr)
-    # periodic images that can reach the cutoff
+    # wrap along the periodic axes first (atoms may sit many cells away; forces and energies do not change), then the
+    # periodic images that can reach the cutoff: |df_k + s_k| <= cutoff / h_k with |df_k| < 1
+    if any(pbc):
+        frac = pos @ np.linalg.inv(cell)
+        pos = pos - (np.floor(frac) * np.asarray(pbc, bool)) @ cell
     vol = abs(np.linalg.det(cell))
     reps = []
     for k in range(3):
         if pbc[k]:
             cr = np.cross(cell[(k + 1) % 3], cell[(k + 2) % 3])
-            reps.append(range(-int(np.ceil(funcfl.cutoff * np.linalg.norm(cr) / vol)), int(np.ceil(funcfl.cutoff * np.linalg.norm(cr) / vol)) + 1))
+            b = int(np.ceil(funcfl.cutoff * np.linalg.norm(cr) / vol)) + 1
+            reps.append(range(-b, b + 1))
         else:
             reps.append(range(0, 1))
     ii, jj, rr = [], [], []
