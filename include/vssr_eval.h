@@ -19,6 +19,9 @@
  *   vssr_tersoff_create / vssr_tersoff_eval_batch
  *                                   <- LAMMMPSCalc.run_lammps_calc / run_lammps_energy with
  *                                      pair_style tersoff (mcmc/calculators/calculators.py:507-640)
+ *   vssr_sw_create / vssr_sw_eval_batch
+ *                                   <- the same with pair_style sw, or pair_style kim with the
+ *                                      Stillinger-Weber Si model (tutorials/Si_111_5x5)
  *
  * Conventions
  *   - All arrays are caller-allocated and borrowed only for the duration of the call.
@@ -323,6 +326,23 @@ int vssr_tersoff_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atom
                             const uint8_t *pbc, uint32_t want, vssr_out *out,
                             double *energy_f64 /*[B] or NULL*/, double *energy_atoms_f64,
                             double *forces_f64);
+
+/* ---- Stillinger-Weber (pair_style sw; the Si(111) 5x5 config's KIM model SW_StillingerWeber_1985_Si__MO_405512056662_005) --- */
+/* params: n_types^3 entries ordered [i][j][k], 11 doubles each, LAMMPS column order
+ * (eps sig a lambda gamma costheta0 A B p q tol); tol is read and has no effect.  Refused with VSSR_E_BADARG: non-finite numbers,
+ * eps / sig / a <= 0, negative lambda / gamma / A / B / p / q / tol, and entries (i,j,k), (i,k,j) that differ in eps, lambda or
+ * costheta0 (LAMMPS' energy would then depend on the order of its neighbor list).  Cutoff: the largest a * sig.
+ * pe/atom as LAMMPS: pair terms half / half, three-body terms in thirds between the three atoms. */
+int vssr_sw_create(int32_t device, int32_t n_types, const double *params, vssr_handle **out);
+/* The same from the text of a LAMMPS .sw file and the species in LAMMPS type order: entries
+ * `e1 e2 e3 eps sig a lambda gamma costheta0 A B p q tol` may span lines, `#` starts a comment; every triplet of the given species
+ * must be present.  The input is checked before any device is touched. */
+int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
+                             vssr_handle **out);
+/* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
+int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                       const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                       double *energy_atoms_f64, double *forces_f64);
 
 #ifdef __cplusplus
 }

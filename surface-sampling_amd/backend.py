@@ -30,7 +30,7 @@ EXPORTS = (
     "vssr_tersoff_create_from_text", "vssr_batch_relax_cg", "vssr_batch_saturated",
     "vssr_batch_embedding", "vssr_batch_traj_configure", "vssr_batch_traj_read",
     "vssr_device_context", "vssr_batch_stress", "vssr_batch_energy_f64", "vssr_batch_device_results_f64",
-    "vssr_batch_relax_counts",
+    "vssr_batch_relax_counts", "vssr_sw_create", "vssr_sw_create_from_text", "vssr_sw_eval_batch",
 )
 
 
@@ -177,6 +177,12 @@ def load_library():
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_eval_batch.restype = C.c_int
     L.vssr_eam_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
+    L.vssr_sw_create.restype = C.c_int
+    L.vssr_sw_create.argtypes = [C.c_int32, C.c_int32, dp, C.POINTER(vp)]
+    L.vssr_sw_create_from_text.restype = C.c_int
+    L.vssr_sw_create_from_text.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.vssr_sw_eval_batch.restype = C.c_int
+    L.vssr_sw_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_batch_relax_fire.restype = C.c_int
     L.vssr_batch_relax_fire.argtypes = [vp, C.POINTER(FireParams), u8p, C.c_uint32, dp, ip, u8p]
     L.vssr_batch_relax_bfgs.restype = C.c_int
@@ -504,7 +510,7 @@ class PainnEngine(_Handle):
 
 
 class _AnalyticEngine(_Handle):
-    """Shared fp64 interface of the analytic potentials (Tersoff, EAM): types instead of atomic numbers."""
+    """Shared fp64 interface of the analytic potentials (Tersoff, EAM, Stillinger-Weber): types instead of atomic numbers."""
 
     has_device_results = False    # fp64 results: sharding uses the host result path
 
@@ -596,6 +602,36 @@ class TersoffEngine(_AnalyticEngine):
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"vssr_tersoff_create failed ({rc}): {msg.decode() if msg else '?'}")
+
+
+class SWEngine(_AnalyticEngine):
+    """Stillinger-Weber (LAMMPS ``pair_style sw``) evaluator, fp64 on device.  Relaxes with FIRE / BFGS and the lock-step CG driver
+    (the chain-resident minimiser serves Tersoff handles only)."""
+
+    def __init__(self, params, device=0, species=None):
+        """``params``: array [nt, nt, nt, 11] (LAMMPS columns eps sig a lambda gamma costheta0 A B p q tol), or the TEXT of a
+        ``.sw`` file together with ``species`` (LAMMPS type order) -- then the file is parsed by the library
+        (vssr_sw_create_from_text)."""
+        super().__init__()
+        if isinstance(params, (str, bytes)):
+            if not species:
+                raise ValueError("species (LAMMPS type order) are required with a potential text")
+            text = params if isinstance(params, bytes) else params.encode()
+            arr = (C.c_char_p * len(species))(*[s.encode() for s in species])
+            self.n_types = len(species)
+            rc = self._lib.vssr_sw_create_from_text(int(device), text, len(species), arr, C.byref(self._h))
+            if rc != 0:
+                msg = self._lib.vssr_last_error(None)
+                raise BackendError(f"vssr_sw_create_from_text failed ({rc}): {msg.decode() if msg else '?'}")
+            return
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.ndim != 4 or params.shape[3] != 11 or not (params.shape[0] == params.shape[1] == params.shape[2]):
+            raise ValueError("params must be [nt, nt, nt, 11]")
+        self.n_types = params.shape[0]
+        rc = self._lib.vssr_sw_create(int(device), self.n_types, _ptr(params, C.c_double), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_sw_create failed ({rc}): {msg.decode() if msg else '?'}")
 
 
 class EAMEngine(_AnalyticEngine):

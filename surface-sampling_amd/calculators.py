@@ -29,7 +29,7 @@ from collections import Counter
 
 import numpy as np
 
-from . import backend, checkpoint, structures, tersoff as tersoff_io
+from . import backend, checkpoint, structures, sw as sw_io, tersoff as tersoff_io
 
 EV_TO_KCAL_MOL = 23.0605   # nff/utils/constants.py
 HARTREE_TO_EV = 27.2114    # nff/utils/constants.py (reference import: calculators.py:21)
@@ -914,9 +914,14 @@ class _AnalyticSurfCalc(_Base):
             types = np.array([idx[int(z)] for z in Z], dtype=np.int32)
         except KeyError as e:
             raise ValueError(f"element Z={e.args[0]} is not covered by the potential {self.species}") from None
-        if self.all_periodic:
-            pbc = np.ones(3, np.uint8)
+        fixed_pbc = self._fixed_pbc()
+        if fixed_pbc is not None:
+            pbc = fixed_pbc.copy()
         return types, pos, cell, pbc
+
+    def _fixed_pbc(self):
+        """The boundary the run directory's template (or ``all_periodic``) imposes on every slab, None: the atoms' own ``pbc``."""
+        return np.ones(3, np.uint8) if self.all_periodic else None
 
     def get_surface_energy(self, atoms=None) -> float:
         """Currently the same as the potential energy (reference ``calculators.py:707-719``)."""
@@ -1067,7 +1072,8 @@ class _AnalyticSurfCalc(_Base):
         types = self._types_of(Z)
         pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
         cell = np.asarray(cell, dtype=np.float64).reshape(B, 9)
-        pbc = np.ones((B, 3), np.uint8) if self.all_periodic else np.asarray(pbc).astype(np.uint8).reshape(B, 3)
+        fixed_pbc = self._fixed_pbc()
+        pbc = np.tile(fixed_pbc, (B, 1)) if fixed_pbc is not None else np.asarray(pbc).astype(np.uint8).reshape(B, 3)
         eng = self._get_engine()
         extra = {}
         if not relax:
@@ -1124,6 +1130,42 @@ class TersoffSurfCalc(_AnalyticSurfCalc):
         return backend.TersoffEngine(self.params, device=_device_index(self.device))
 
 
+class SWSurfCalc(_AnalyticSurfCalc):
+    """Stillinger-Weber energy / per-atom energies / forces on MI355X (LAMMPS ``pair_style sw``, or ``pair_style kim`` with a
+    built-in SW model such as ``SW_StillingerWeber_1985_Si__MO_405512056662_005`` of the reference's Si(111) 5x5 run directory).
+    ``per_atom_energies`` follow LAMMPS ``pe/atom`` for ``pair_style sw`` (pair terms half / half, three-body terms in thirds).
+    Relaxations (``run_lammps_opt``, ``relax_batch``, ``evaluate_packed(relax=True)``) use the lock-step CG / FIRE / BFGS drivers.
+    ``all_periodic=False`` keeps the atoms' own ``pbc`` (the Si templates say ``boundary p p f``)."""
+
+    name = "sw_mi355x"
+
+    def __init__(self, potential, species=None, device="cuda", all_periodic=False, logger=None, **kwargs):
+        """potential: path or text of a ``.sw`` file, a params array [nt,nt,nt,11], or a built-in model name (``sw.MODELS``);
+        species: symbols in LAMMPS type order (e.g. ["Si"]; a built-in model's own species when omitted)."""
+        if isinstance(potential, np.ndarray):
+            if species is None:
+                raise ValueError("species (LAMMPS type order) are required with a params array")
+            self.params = np.ascontiguousarray(potential, dtype=np.float64)
+            sw_io.check_params(self.params, list(species))
+        elif sw_io.is_builtin(potential):
+            species = sw_io.builtin_species(potential) if species is None else species
+            self.params = sw_io.parse_sw(sw_io.builtin_text(potential), list(species))
+        else:
+            if species is None:
+                raise ValueError("species (LAMMPS type order) are required with a .sw file")
+            text = potential
+            if "\n" not in str(potential):
+                with open(potential) as fh:
+                    text = fh.read()
+            self.params = sw_io.parse_sw(text, list(species))
+        self.species = list(species)
+        self._init_common(device, all_periodic, logger)
+        super().__init__(**kwargs)
+
+    def _make_engine(self):
+        return backend.SWEngine(self.params, device=_device_index(self.device))
+
+
 class EAMSurfCalc(_AnalyticSurfCalc):
     """One-element EAM on MI355X: drop-in for ``LAMMPSRunSurfCalc`` (reference ``calculators.py:755-811``, a modified ASE
     ``lammpsrun`` that pipes ``pair_style eam`` / ``pair_coeff * * Cu_u3.eam`` to an ``lmp`` subprocess; used by
@@ -1169,7 +1211,12 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
     * ``lammps_config.json``: ``potential_file``, ``atoms`` (species in LAMMPS type order), ``bulk_index`` (atoms with id <=
       bulk_index form the group the relaxation template holds with ``fix ... setforce 0``);
     * ``lammps_energy_template.txt`` / ``lammps_opt_template.txt``: the ``pair_style`` line selects the potential -- ``tersoff``
-      (multi-element file) or ``eam`` (one funcfl element) are evaluated on the device, anything else raises.
+      (multi-element file), ``eam`` (one funcfl element), ``sw`` (Stillinger-Weber file) or ``kim <model>`` with a built-in SW
+      model (``sw.MODELS``: the Si(111) 5x5 tutorial's ``SW_StillingerWeber_1985_Si__MO_405512056662_005``; no
+      ``potential_file`` needed, the species come from ``atoms``) are evaluated on the device, anything else raises.  For the SW
+      styles the energy template's ``boundary`` applies (``p`` periodic; ``f``, ``s``, ``m`` open) and pe/atom follows LAMMPS
+      ``pair_style sw`` (a KIM model's own per-particle split is not reproduced; totals do not depend on it).  When the opt
+      template names another potential the backend lacks (the Si tutorial's SRS model), relaxations raise; single points work.
 
     The potential file is looked up like LAMMPS does (as given, in the run directory, in the working directory, in
     ``$LAMMPS_POTENTIALS``) and additionally in ``potential_dirs`` and in the reference's ``mcmc/potentials`` when that package
@@ -1182,6 +1229,9 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self.species = []
         self.bulk_index = 0
         self.pair_style = None
+        self.boundary = None          # SW styles: the energy template's boundary as pbc flags
+        self.relax_refused = None     # SW styles: the opt template's potential when the backend lacks it
+        self.kim_model = None
         self._cfg_key = None
         self._init_common(device, True, logger)
         self.run_dir = os.getcwd()        # the reference's default (calculators.py:502)
@@ -1207,6 +1257,44 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
                 return c
         raise FileNotFoundError(f"potential file {name!r} not found; looked in: " + ", ".join(cands))
 
+    @staticmethod
+    def _template_lines(run_dir):
+        """{template name: (pair_style arguments or None, boundary tokens or None)} of the run directory's templates."""
+        out = {}
+        for tmpl in ("lammps_energy_template.txt", "lammps_opt_template.txt"):
+            tp = os.path.join(run_dir, tmpl)
+            if os.path.isfile(tp):
+                with open(tp, encoding="utf-8") as fh:
+                    text = fh.read()
+                m = re.search(r"^\s*pair_style\s+([^#\n]+)", text, re.M)
+                b = re.search(r"^\s*boundary\s+([^#\n]+)", text, re.M)
+                out[tmpl] = (m.group(1).split() if m else None, b.group(1).split() if b else None)
+        return out
+
+    @staticmethod
+    def _boundary_pbc(tokens):
+        """LAMMPS ``boundary`` (one token per axis): ``p`` periodic; ``f``, ``s``, ``m`` (or lower / upper pairs of them) not."""
+        if tokens is None:
+            return np.ones(3, np.uint8)          # the LAMMPS default: p p p
+        if len(tokens) != 3 or not all(t == "p" or (t and set(t) <= set("fsm") and len(t) <= 2) for t in tokens):
+            raise ValueError(f"boundary {' '.join(tokens)!r}: expected three of p, f, s, m")
+        return np.array([t == "p" for t in tokens], np.uint8)
+
+    def _sw_source(self, args, cfg):
+        """(params source, key) of an SW pair style (``sw`` + potential_file, ``kim <built-in model>``); None for other styles."""
+        kp = self.parameters.get("kim_potential")
+        if (args and args[0] == "kim") or kp:
+            model = args[1] if args and args[0] == "kim" and len(args) > 1 else (kp if isinstance(kp, str) else None)
+            if model is None or not sw_io.is_builtin(model):
+                raise backend.BackendError(f"KIM model {model!r} is not provided by this backend (built in: "
+                                           + ", ".join(sorted(sw_io.MODELS)) + "; pair styles tersoff, eam and sw are)")
+            return ("kim", model)
+        if args and args[0] == "sw":
+            if "potential_file" not in cfg:
+                raise KeyError("lammps_config.json: pair_style sw needs potential_file")
+            return ("sw", self._find_potential(cfg["potential_file"], str(self.run_dir)))
+        return None
+
     def _configure(self):
         run_dir = str(self.run_dir)
         cfg_path = os.path.join(run_dir, "lammps_config.json")
@@ -1215,19 +1303,15 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
                                     "(potential_file, atoms, bulk_index)")
         with open(cfg_path, encoding="utf-8") as fh:
             cfg = json.load(fh)
-        style = None
-        for tmpl in ("lammps_energy_template.txt", "lammps_opt_template.txt"):
-            tp = os.path.join(run_dir, tmpl)
-            if os.path.isfile(tp):
-                with open(tp, encoding="utf-8") as fh:
-                    m = re.search(r"^\s*pair_style\s+(\S+)", fh.read(), re.M)
-                if m:
-                    style = m.group(1)
-                    break
-        if style is None:
+        tmpls = self._template_lines(run_dir)
+        args = next((a for a, _ in tmpls.values() if a), None)
+        if args is None:
             raise FileNotFoundError(f"{run_dir}: no lammps_energy_template.txt / lammps_opt_template.txt with a pair_style line")
-        if self.parameters.get("kim_potential") or style.startswith("kim"):
-            raise backend.BackendError("KIM potentials are not provided by this backend (tersoff and eam/funcfl are)")
+        src = self._sw_source(args, cfg)
+        if src is not None:
+            self._configure_sw(cfg_path, cfg, tmpls, args, src)
+            return
+        style = args[0]
         pot = self._find_potential(cfg["potential_file"], run_dir)
         key = (cfg_path, os.path.getmtime(cfg_path), pot, style)
         if key == self._cfg_key:
@@ -1235,6 +1319,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self.species = list(cfg["atoms"])
         self.bulk_index = int(cfg.get("bulk_index", 0))
         self.pair_style = style
+        self.boundary = None
+        self.relax_refused = None
         with open(pot, encoding="utf-8") as fh:
             text = fh.read()
         if style == "tersoff":
@@ -1248,13 +1334,64 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             if self.species != [structures.SYMBOLS[self.funcfl.atomic_number]]:
                 raise ValueError(f"pair_style eam (funcfl) holds one element, lammps_config.json lists {self.species}")
         else:
-            raise backend.BackendError(f"pair_style {style!r} is not provided by this backend (tersoff and eam are)")
+            raise backend.BackendError(f"pair_style {style!r} is not provided by this backend (tersoff, eam and sw are)")
         if self._engine is not None:
             self._engine.close()
             self._engine = None
         self._cfg_key = key
 
+    def _configure_sw(self, cfg_path, cfg, tmpls, args, src):
+        """``pair_style sw`` (``potential_file`` + ``atoms``) or ``pair_style kim <built-in SW model>`` (species from ``atoms``: the
+        reference's KIM templates write ``pair_coeff * * {}`` with the element names).  The energy template's ``boundary`` applies.
+        An opt template that names another potential the backend lacks makes relaxations refuse (single points still work)."""
+        energy_args, energy_bnd = tmpls.get("lammps_energy_template.txt", (None, None))
+        if energy_args is None:
+            energy_args, energy_bnd = args, tmpls.get("lammps_opt_template.txt", (None, None))[1]
+        opt_args = tmpls.get("lammps_opt_template.txt", (None, None))[0]
+        key = (cfg_path, os.path.getmtime(cfg_path), src, tuple(energy_args), tuple(opt_args or ()), tuple(energy_bnd or ()))
+        if key == self._cfg_key:
+            return
+        species = list(cfg["atoms"])
+        if src[0] == "kim":
+            text = sw_io.builtin_text(src[1])
+            if not set(species) <= set(sw_io.builtin_species(src[1])):
+                raise ValueError(f"KIM model {src[1]} covers {sw_io.builtin_species(src[1])}, lammps_config.json lists {species}")
+        else:
+            with open(src[1], encoding="utf-8") as fh:
+                text = fh.read()
+        refused = None
+        if opt_args is not None and opt_args != energy_args:
+            name = opt_args[1] if opt_args[0] == "kim" and len(opt_args) > 1 else " ".join(opt_args)
+            if not (opt_args[0] == "kim" and len(opt_args) > 1 and sw_io.is_builtin(opt_args[1])):
+                refused = name
+        self.params = sw_io.parse_sw(text, species)
+        self.funcfl = None
+        self.species = species
+        self.bulk_index = int(cfg.get("bulk_index", 0))
+        self.pair_style = src[0]
+        self.kim_model = src[1] if src[0] == "kim" else None
+        self.boundary = self._boundary_pbc(energy_bnd)
+        self.relax_refused = refused
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
+        self._cfg_key = key
+
+    def _fixed_pbc(self):
+        if self.pair_style in ("sw", "kim") and self.boundary is not None:
+            return self.boundary
+        return super()._fixed_pbc()
+
+    def _check_relax(self):
+        self._configure()
+        if self.relax_refused is not None:
+            raise backend.BackendError(f"the run directory's lammps_opt_template.txt relaxes with {self.relax_refused}, which this "
+                                       f"backend does not provide (single-point energies use the energy template's potential; "
+                                       f"an SW relaxation is available through SWSurfCalc)")
+
     def _make_engine(self):
+        if self.pair_style in ("sw", "kim"):
+            return backend.SWEngine(self.params, device=_device_index(self.device))
         if self.pair_style == "tersoff":
             return backend.TersoffEngine(self.params, device=_device_index(self.device))
         return backend.EAMEngine(self.funcfl, device=_device_index(self.device))
@@ -1272,7 +1409,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         the first ``bulk_index`` atoms are held."""
         if run_dir is not None and str(run_dir) != str(self.run_dir):
             self.run_dir = run_dir
-        self._configure()
+        self._check_relax()
         if fixed_indices is None and self.bulk_index > 0:
             fixed_indices = np.arange(min(self.bulk_index, len(slab)))
         return super().run_lammps_opt(slab, run_dir=run_dir, fixed_indices=fixed_indices, optimizer=optimizer, **kwargs)
@@ -1283,7 +1420,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         return super().run_lammps_energy(slab, run_dir=run_dir, **kwargs)
 
     def relax_batch(self, atoms_list, fixed_indices=None, **kwargs):
-        self._configure()
+        self._check_relax()
         if fixed_indices is None and self.bulk_index > 0:
             fixed_indices = [np.arange(min(self.bulk_index, len(a))) for a in atoms_list]
         return super().relax_batch(atoms_list, fixed_indices=fixed_indices, **kwargs)
@@ -1291,6 +1428,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
     def evaluate_packed(self, n_atoms, Z, pos, cell, pbc, relax: bool = False, fixed_mask=None, **kwargs) -> dict:
         """As the base class; relaxations without a mask hold the template's bulk group (the first ``bulk_index`` atoms of every slab)."""
         self._configure()
+        if relax:
+            self._check_relax()
         if relax and fixed_mask is None and self.bulk_index > 0:
             n_atoms = np.asarray(n_atoms, dtype=np.int64)
             start = np.concatenate([[0], np.cumsum(n_atoms)])

@@ -3,6 +3,7 @@
 #include <cstdarg>
 
 #include "vssr_internal.h"
+#include "sw_dev.h"
 
 namespace vssr {
 
@@ -247,12 +248,12 @@ static void cell_host_setup(const double *cell, const uint8_t *pbc, double cutof
 }
 
 static double handle_cutoff(const vssr_handle *h) {
-    return h->kind == 2 ? h->ters_cutmax : h->kind == 3 ? h->eam_grid.cutoff : (double)h->cutoff;
+    return (h->kind == 2 || h->kind == 4) ? h->ters_cutmax : h->kind == 3 ? h->eam_grid.cutoff : (double)h->cutoff;
 }
 
 static int run_any(vssr_handle *h, uint32_t want) {
     h->last_want = want;
-    return h->kind == 2 ? tersoff_run(h, want) : h->kind == 3 ? eam_run(h, want) : painn_run(h, want);
+    return is_f64_kind(h) ? f64_run(h, want) : painn_run(h, want);
 }
 
 // synchronise; if the neighbor capacity overflowed, grow and rerun
@@ -370,32 +371,36 @@ int vssr_tersoff_create(int32_t device, int32_t n_types, const double *params, v
     return VSSR_OK;
 }
 
+// whitespace-separated tokens of a LAMMPS potential file; `#` starts a comment
+static std::vector<std::string> potential_tokens(const char *param_text) {
+    std::vector<std::string> tok;
+    std::string line, text(param_text);
+    size_t pos = 0;
+    while (pos <= text.size()) {
+        size_t nl = text.find('\n', pos);
+        if (nl == std::string::npos) nl = text.size();
+        line = text.substr(pos, nl - pos);
+        pos = nl + 1;
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        size_t i = 0;
+        while (i < line.size()) {
+            while (i < line.size() && isspace((unsigned char)line[i])) ++i;
+            size_t j = i;
+            while (j < line.size() && !isspace((unsigned char)line[j])) ++j;
+            if (j > i) tok.push_back(line.substr(i, j - i));
+            i = j;
+        }
+    }
+    return tok;
+}
+
 int vssr_tersoff_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
                                   vssr_handle **out) {
     if (!param_text || !species || !out || n_species < 1 || n_species > 8)
         return set_err(nullptr, VSSR_E_BADARG, "bad tersoff arguments");
     *out = nullptr;
-    std::vector<std::string> tok;
-    {
-        std::string line, text(param_text);
-        size_t pos = 0;
-        while (pos <= text.size()) {
-            size_t nl = text.find('\n', pos);
-            if (nl == std::string::npos) nl = text.size();
-            line = text.substr(pos, nl - pos);
-            pos = nl + 1;
-            const size_t hash = line.find('#');
-            if (hash != std::string::npos) line.erase(hash);
-            size_t i = 0;
-            while (i < line.size()) {
-                while (i < line.size() && isspace((unsigned char)line[i])) ++i;
-                size_t j = i;
-                while (j < line.size() && !isspace((unsigned char)line[j])) ++j;
-                if (j > i) tok.push_back(line.substr(i, j - i));
-                i = j;
-            }
-        }
-    }
+    const std::vector<std::string> tok = potential_tokens(param_text);
     if (tok.empty() || tok.size() % 17) return set_err(nullptr, VSSR_E_BADARG, "tersoff file: token count is not a multiple of 17");
     auto index_of = [&](const std::string &s) {
         for (int t = 0; t < n_species; ++t)
@@ -624,7 +629,7 @@ int vssr_batch_download(vssr_handle *h, uint32_t want, vssr_out *out) {
     int rc = sync_and_check(h);
     if (rc) return rc;
     const size_t B = h->n_cfg, N = h->n_atoms, M = h->n_models;
-    if (h->kind == 2 || h->kind == 3) {
+    if (is_f64_kind(h)) {
         std::vector<double> e(B), ea(N), f(3 * N);
         VSSR_HIP(h, hipMemcpy(e.data(), h->d_ters_e.p, sizeof(double) * B, hipMemcpyDeviceToHost));
         if (out->energy) for (size_t b = 0; b < B; ++b) out->energy[b] = (float)e[b];
@@ -675,7 +680,7 @@ int vssr_tersoff_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atom
                             const double *pos, const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out,
                             double *energy_f64, double *energy_atoms_f64, double *forces_f64) {
     if (!h) return VSSR_E_BADARG;
-    if (h->kind != 2 && h->kind != 3) return set_err(h, VSSR_E_STATE, "not a Tersoff / EAM handle");
+    if (!is_f64_kind(h)) return set_err(h, VSSR_E_STATE, "not a Tersoff / EAM / SW handle");
     vssr_out dummy;
     memset(&dummy, 0, sizeof dummy);
     int rc = vssr_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out ? out : &dummy);
@@ -722,6 +727,139 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
 int vssr_eam_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                         const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                         double *energy_atoms_f64, double *forces_f64) {
+    return vssr_tersoff_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64,
+                                   forces_f64);
+}
+
+// ---- Stillinger-Weber ------------------------------------------------------------------------------------------------------
+static const char *const kSwField[11] = {"eps", "sig", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"};
+
+// Checks an [i][j][k] table of 11 LAMMPS columns and derives the kernels' entries (sw_dev.h SwP).  Refused: non-finite numbers,
+// eps / sig / a <= 0, negative lambda / gamma / A / B / p / q / tol (pair_sw.cpp refuses those as well), and (i, j, k) / (i, k, j)
+// pairs that differ in eps, lambda or costheta0 (the LAMMPS energy would depend on the order of its neighbor list).
+static int sw_derive(int nt, const double *params, const char *const *species, std::vector<SwP> &out, double &cutmax) {
+    const size_t np = (size_t)nt * nt * nt;
+    auto name = [&](size_t e, char *buf, size_t n) {
+        const int a = (int)(e / ((size_t)nt * nt)), b = (int)(e / nt % nt), c = (int)(e % nt);
+        if (species) snprintf(buf, n, "%s %s %s", species[a], species[b], species[c]);
+        else snprintf(buf, n, "(%d,%d,%d)", a, b, c);
+    };
+    char nm[96];
+    out.assign(np, SwP{});
+    cutmax = 0.0;
+    for (size_t e = 0; e < np; ++e) {
+        const double *p = params + 11 * e;
+        for (int k = 0; k < 11; ++k) {
+            const bool pos = k == 0 || k == 1 || k == 2;   // eps, sig, a
+            const bool any = k == 5;                       // costheta0: any finite value
+            if (!std::isfinite(p[k]) || (pos && !(p[k] > 0)) || (!pos && !any && !(p[k] >= 0))) {
+                name(e, nm, sizeof nm);
+                return set_err(nullptr, VSSR_E_BADARG, "sw entry %s: bad %s = %g (%s)", nm, kSwField[k], p[k],
+                               pos ? "must be > 0" : any ? "must be finite" : "must be >= 0");
+            }
+        }
+        const double eps = p[0], sig = p[1], a = p[2], lam = p[3], gam = p[4], A = p[6], B = p[7], pp = p[8], qq = p[9];
+        SwP &d = out[e];
+        d.cut = a * sig; d.sig = sig; d.gs = gam * sig;
+        d.c5 = A * eps * B * pow(sig, pp); d.c6 = A * eps * pow(sig, qq);
+        d.p = pp; d.q = qq; d.le = lam * eps; d.c0 = p[5]; d.pad0 = 0.0; d.pad1 = 0.0;
+        if (!std::isfinite(d.c5) || !std::isfinite(d.c6)) {
+            name(e, nm, sizeof nm);
+            return set_err(nullptr, VSSR_E_BADARG, "sw entry %s: A eps B sig^p / A eps sig^q overflow", nm);
+        }
+        cutmax = std::max(cutmax, d.cut);
+    }
+    for (int i = 0; i < nt; ++i)
+        for (int j = 0; j < nt; ++j)
+            for (int k = j + 1; k < nt; ++k) {
+                const double *x = params + 11 * (((size_t)i * nt + j) * nt + k), *y = params + 11 * (((size_t)i * nt + k) * nt + j);
+                for (int f : {0, 3, 5})
+                    if (x[f] != y[f]) {
+                        name(((size_t)i * nt + j) * nt + k, nm, sizeof nm);
+                        char nm2[96];
+                        name(((size_t)i * nt + k) * nt + j, nm2, sizeof nm2);
+                        return set_err(nullptr, VSSR_E_BADARG,
+                                       "sw entries %s and %s differ in %s (%g vs %g): the three-body term would depend on neighbor order",
+                                       nm, nm2, kSwField[f], x[f], y[f]);
+                    }
+            }
+    return VSSR_OK;
+}
+
+static int sw_create_checked(int32_t device, int32_t n_types, const double *params, const char *const *species, vssr_handle **out) {
+    if (!params || !out || n_types < 1 || n_types > 8) return set_err(nullptr, VSSR_E_BADARG, "bad sw arguments (1 .. 8 types)");
+    *out = nullptr;
+    std::vector<SwP> tab;
+    double cutmax = 0.0;
+    int rc = sw_derive(n_types, params, species, tab, cutmax);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return set_err(nullptr, VSSR_E_DEVICE, "no HIP device available (this backend has no CPU fallback)");
+    if (device < 0 || device >= ndev) return set_err(nullptr, VSSR_E_BADARG, "device %d out of range", device);
+    vssr_handle *h = new vssr_handle();
+    h->kind = 4;
+    h->n_types = n_types;
+    h->n_embed = n_types;
+    h->ters_cutmax = cutmax;
+    rc = common_init(h, device);
+    if (!rc && h->ters_params.ensure(sizeof(SwP) * tab.size())) rc = set_err(h, VSSR_E_NOMEM, "sw params");
+    if (!rc && hipMemcpy(h->ters_params.p, tab.data(), sizeof(SwP) * tab.size(), hipMemcpyHostToDevice) != hipSuccess)
+        rc = set_err(h, VSSR_E_DEVICE, "sw params upload failed");
+    if (rc) {
+        g_create_error = h->err;
+        vssr_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return VSSR_OK;
+}
+
+int vssr_sw_create(int32_t device, int32_t n_types, const double *params, vssr_handle **out) {
+    return sw_create_checked(device, n_types, params, nullptr, out);
+}
+
+int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
+                             vssr_handle **out) {
+    if (!param_text || !species || !out || n_species < 1 || n_species > 8)
+        return set_err(nullptr, VSSR_E_BADARG, "bad sw arguments (1 .. 8 species)");
+    *out = nullptr;
+    for (int t = 0; t < n_species; ++t)
+        if (!species[t] || !species[t][0]) return set_err(nullptr, VSSR_E_BADARG, "sw: species %d has no name", t);
+    const std::vector<std::string> tok = potential_tokens(param_text);
+    if (tok.empty() || tok.size() % 14)
+        return set_err(nullptr, VSSR_E_BADARG, "sw file: %zu tokens, not a multiple of 14 (e1 e2 e3 + 11 numbers)", tok.size());
+    auto index_of = [&](const std::string &s) {
+        for (int t = 0; t < n_species; ++t)
+            if (s == species[t]) return t;
+        return -1;
+    };
+    const size_t np = (size_t)n_species * n_species * n_species;
+    std::vector<double> params(11 * np, 0.0);
+    std::vector<char> seen(np, 0);
+    for (size_t o = 0; o < tok.size(); o += 14) {
+        const int a = index_of(tok[o]), b = index_of(tok[o + 1]), c = index_of(tok[o + 2]);
+        if (a < 0 || b < 0 || c < 0) continue;   // entry of another element
+        const size_t e = ((size_t)a * n_species + b) * n_species + c;
+        for (int k = 0; k < 11; ++k) {
+            char *end = nullptr;
+            params[11 * e + k] = strtod(tok[o + 3 + k].c_str(), &end);
+            if (!end || *end || end == tok[o + 3 + k].c_str())
+                return set_err(nullptr, VSSR_E_BADARG, "sw file: entry %s %s %s: bad number '%s' for %s", tok[o].c_str(),
+                               tok[o + 1].c_str(), tok[o + 2].c_str(), tok[o + 3 + k].c_str(), kSwField[k]);
+        }
+        seen[e] = 1;
+    }
+    for (size_t e = 0; e < np; ++e)
+        if (!seen[e])
+            return set_err(nullptr, VSSR_E_BADARG, "sw file lacks the entry %s %s %s", species[e / ((size_t)n_species * n_species)],
+                           species[e / n_species % n_species], species[e % n_species]);
+    return sw_create_checked(device, n_species, params.data(), species, out);
+}
+
+int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                       const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                       double *energy_atoms_f64, double *forces_f64) {
     return vssr_tersoff_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64,
                                    forces_f64);
 }
@@ -866,7 +1004,7 @@ int vssr_batch_energy_f64(vssr_handle *h, double *energy, double *energy_std, do
     int rc = sync_and_check(h);
     if (rc) return rc;
     const size_t B = h->n_cfg, M = h->n_models;
-    if (h->kind == 2 || h->kind == 3) {   // one analytic potential: no spread, the "model" is the potential
+    if (is_f64_kind(h)) {   // one analytic potential: no spread, the "model" is the potential
         if (energy) VSSR_HIP(h, hipMemcpy(energy, h->d_ters_e.p, sizeof(double) * B, hipMemcpyDeviceToHost));
         if (energy_models) VSSR_HIP(h, hipMemcpy(energy_models, h->d_ters_e.p, sizeof(double) * B, hipMemcpyDeviceToHost));
         if (energy_std) for (size_t b = 0; b < B; ++b) energy_std[b] = 0.0;

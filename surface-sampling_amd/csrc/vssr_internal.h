@@ -232,7 +232,7 @@ struct Profiler {
 }  // namespace vssr
 
 struct vssr_handle {
-    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl)
+    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in ters_params
     int device = 0;
     hipStream_t stream = nullptr;
@@ -266,10 +266,10 @@ struct vssr_handle {
     vssr::DevBuf model_table;    // ModelW[n_models]
     vssr::DevBuf offset_per_z;   // double[n_embed]
 
-    // tersoff
+    // tersoff / Stillinger-Weber
     int n_types = 0;
     double ters_cutmax = 0;
-    vssr::DevBuf ters_params;    // double[nt^3][14]
+    vssr::DevBuf ters_params;    // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h)
 
     // resident batch
     bool batch_valid = false, ran = false;
@@ -364,6 +364,13 @@ int painn_stress(vssr_handle *h);   // enqueues k_stress: d_stress from the edge
 int tersoff_run(vssr_handle *h, uint32_t want);
 // EAM (eam.hip)
 int eam_run(vssr_handle *h, uint32_t want);
+// Stillinger-Weber (sw.hip; profiled under KC_TERSOFF)
+int sw_run(vssr_handle *h, uint32_t want);
+// the fp64 analytic potentials (Tersoff, EAM, SW): same result buffers (d_ters_e / _ea / _f), same drivers
+inline bool is_f64_kind(const vssr_handle *h) { return h->kind == 2 || h->kind == 3 || h->kind == 4; }
+inline int f64_run(vssr_handle *h, uint32_t want) {
+    return h->kind == 2 ? tersoff_run(h, want) : h->kind == 3 ? eam_run(h, want) : sw_run(h, want);
+}
 void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1][7]*/);
 // lock-step FIRE relaxation (relax.hip)
 // method 0: FIRE (fp), 1: BFGS (bp)
