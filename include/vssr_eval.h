@@ -85,8 +85,9 @@ typedef struct {
     const float *const *weights; /* n_models blobs in the layout above */
     uint64_t weights_len;        /* floats per blob */
     /* PaiNN hyper-parameters (params.json of the reference checkpoints) */
-    int32_t feat_dim;       /* 128 (the only compiled value) */
-    int32_t n_rbf;          /* 20 */
+    int32_t feat_dim;       /* 128; any multiple of 16 in 16 .. 256 is accepted */
+    int32_t n_rbf;          /* 20; 1 .. 32.  (128, 20) runs the specialised path, every other shape the general-width fp32
+                               path (painn_gen.hip); the environment variable VSSR_PAINN_PATH=general sends (128, 20) there too */
     int32_t num_conv;       /* 3 */
     int32_t n_embed;        /* rows of the embedding table, 100 */
     int32_t readout_hidden; /* 64 */

@@ -221,16 +221,21 @@ class EnsembleNFFSurface(_Base):
         device: ``"cuda"``, ``"cuda:N"`` or an int ordinal.
         model_units / prediction_units / offset_units: as in the reference (``"kcal/mol"``, ``"eV"``,
             ``"atomic"``).
-        cutoff: neighbor cutoff in Å (the reference passes it through ``get_atoms_batch``).
+        cutoff: neighbor cutoff in Å (the reference passes it through ``get_atoms_batch``); default 5.0, or with
+            ``hparams="auto"`` the models' own cutoff (``params.json`` / the checkpoint's module attribute).  A cutoff that
+            differs from the one the models were trained with raises ``ValueError``.
         position_dtype: ``"float64"`` (default: the caller's positions as they are) or ``"float32"``: positions are rounded to
             float32 before an evaluation, the way nff's ``AtomsBatch`` holds them (``nxyz`` is a float32 tensor, reference
             ``mcmc/utils/misc.py:34-42``) -- single-point results then reproduce the reference's prints to the last printed
             digit of fmax (1e-5 eV/A).  Applies to ``calculate``, ``calculate_batch`` and the
             single-point form of ``evaluate_packed``; relaxations move fp64 positions on the device either way.
         properties: like nff's ``NeuralFF(properties=[...])``; with ``"embedding"`` in it ``results["embedding"]`` holds the
-            per-atom latent features ``[N, 128]`` (final scalar state) of the first model -- the reference computes them
-            with ``NeuralFF(models[0], properties=["energy", "forces", "embedding"])`` -- and ``results["embedding_models"]``
-            those of every ensemble member ``[M, N, 128]``.
+            per-atom latent features ``[N, F]`` (final scalar state, F = the models' ``feat_dim``) of the first model -- the
+            reference computes them with ``NeuralFF(models[0], properties=["energy", "forces", "embedding"])`` -- and
+            ``results["embedding_models"]`` those of every ensemble member ``[M, N, F]``.
+        hparams: PaiNN hyper-parameters (``checkpoint.DEFAULT_HPARAMS`` keys), or ``"auto"``: every model must then be a
+            checkpoint (path or module) and its shapes are read from its tensors (``checkpoint.infer_hparams``), with a
+            ``params.json`` next to a ``best_model`` file read as well; all models must agree.
     """
 
     # "stress" / "stress_std" like nff's EnsembleNFF (the reference's class attribute, calculators.py:369, inherits them): the
@@ -239,14 +244,29 @@ class EnsembleNFFSurface(_Base):
     name = "ensemble_nff_surface_mi355x"
 
     def __init__(self, models, device="cuda", model_units="kcal/mol", prediction_units="eV",
-                 offset_units="atomic", cutoff=5.0, hparams=None, logger=None, properties=("energy", "forces"),
+                 offset_units="atomic", cutoff=None, hparams=None, logger=None, properties=("energy", "forces"),
                  position_dtype="float64", **kwargs):
         # a single model is accepted as well: the reference's NFFPourbaix is a NeuralFF and is constructed with ONE module,
         # NFFPourbaix(models[0], device=..., model_units=..., prediction_units="eV") (scripts/sample_pourbaix_surface.py:253-258)
         if isinstance(models, (str, bytes)) or hasattr(models, "__fspath__") or hasattr(models, "state_dict") \
                 or (isinstance(models, np.ndarray) and models.ndim == 1):
             models = [models]
-        self.models = [self._load_model(m, hparams) for m in models]
+        if isinstance(hparams, str):
+            if hparams != "auto":
+                raise ValueError(f"hparams must be a dict, None or 'auto', not {hparams!r}")
+            loaded = [self._load_model_auto(m) for m in models]
+            hparams = loaded[0][1]
+            for _, hp in loaded[1:]:
+                if hp != hparams:
+                    raise ValueError(f"ensemble members disagree on their hyper-parameters: {hparams} vs {hp}")
+            self.models = [blob for blob, _ in loaded]
+            model_cutoff = float(hparams["cutoff"])
+            if cutoff is None:
+                cutoff = model_cutoff
+            elif abs(float(cutoff) - model_cutoff) > 1e-9:
+                raise ValueError(f"cutoff={cutoff!r} differs from the models' cutoff {model_cutoff!r} (hparams='auto')")
+        else:
+            self.models = [self._load_model(m, hparams) for m in models]
         # like NeuralFF(properties=[...]) in the reference's clustering script (scripts/clustering.py:150-158): "embedding" in
         # this list makes every calculate() also return the latent features
         self.properties = tuple(properties)
@@ -254,7 +274,7 @@ class EnsembleNFFSurface(_Base):
         self.model_units = model_units
         self.prediction_units = prediction_units
         self.offset_units = offset_units
-        self.cutoff = float(cutoff)
+        self.cutoff = 5.0 if cutoff is None else float(cutoff)
         if str(np.dtype(position_dtype)) not in ("float64", "float32"):
             raise ValueError(f"position_dtype must be float64 or float32, not {position_dtype!r}")
         self.position_dtype = str(np.dtype(position_dtype))
@@ -287,6 +307,27 @@ class EnsembleNFFSurface(_Base):
         blob = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
         checkpoint.blob_to_fields(blob, hparams)
         return blob
+
+    @staticmethod
+    def _load_model_auto(m):
+        """(blob, hparams) of a checkpoint path or an nff ``Painn`` module, shapes inferred from the tensors."""
+        if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__"):
+            return checkpoint.load_painn_blob_auto(str(m))
+        if hasattr(m, "state_dict") and callable(m.state_dict):
+            sd = {}
+            for k, v in m.state_dict().items():
+                for attr in ("detach", "cpu", "numpy"):
+                    if hasattr(v, attr):
+                        v = getattr(v, attr)()
+                sd[k] = np.asarray(v, dtype=np.float32)
+            hp = checkpoint.infer_hparams(sd)
+            attrs = {a: getattr(m, a) for a in ("excl_vol", "power", "sigma", "cutoff") if hasattr(m, a)}
+            for attr, key in (("excl_vol", "excl_vol"), ("power", "V_ex_power"), ("sigma", "V_ex_sigma"), ("cutoff", "cutoff")):
+                if attr in attrs and attrs[attr] is not None:
+                    hp[key] = attrs[attr]
+            checkpoint.check_model_against_hparams(type(m).__name__, sd, hp, attrs=attrs)
+            return checkpoint.state_dict_to_blob(sd, hp), hp
+        raise ValueError("hparams='auto' needs checkpoints (paths or modules): a raw blob does not carry its shape")
 
     # -- engine lifetime (lazy: created on first use, re-created when the offset config changes) ----
     def _offset_config(self):

@@ -315,6 +315,70 @@ def check_model_against_hparams(path: str, sd: dict, hp: dict | None = None, att
             raise ValueError(f"{path}: parameter {key} {tuple(arr.shape)} is not part of the supported PaiNN layout")
 
 
+# params.json keys (the reference's model directories) that this backend takes over
+_PARAMS_JSON_KEYS = ("feat_dim", "n_rbf", "num_conv", "cutoff", "excl_vol", "V_ex_power", "V_ex_sigma", "readout_hidden", "n_embed")
+_SHAPE_KEYS = ("feat_dim", "n_rbf", "num_conv", "readout_hidden", "n_embed")
+
+
+def infer_hparams(sd: dict) -> dict:
+    """Shape hyper-parameters of a PaiNN state dict: ``n_embed`` and ``feat_dim`` from the embedding, ``n_rbf`` from the
+    radial filter of message block 0, ``num_conv`` from the number of message blocks and ``readout_hidden`` from the
+    readout.  The other entries (cutoff, excluded volume) are the defaults; a ``params.json`` or the caller supplies them."""
+    def shape(key):
+        if key not in sd:
+            raise ValueError(f"state dict has no {key}: not a PaiNN checkpoint of the supported layout")
+        return tuple(np.asarray(sd[key]).shape)
+
+    emb = shape("embed_block.atom_embed.weight")
+    wd = shape("message_blocks.0.inv_message.dist_embed.block.1.weight")
+    w5 = shape("readout_blocks.0.readoutdict.energy.0.weight")
+    if len(emb) != 2 or len(wd) != 2 or len(w5) != 2:
+        raise ValueError("embedding, radial filter and readout weights must be matrices")
+    num_conv = 0
+    while f"message_blocks.{num_conv}.inv_message.inv_dense.layers.0.weight" in sd:
+        num_conv += 1
+    return {**DEFAULT_HPARAMS, "n_embed": emb[0], "feat_dim": emb[1], "n_rbf": wd[1], "num_conv": num_conv,
+            "readout_hidden": w5[0]}
+
+
+def read_params_json(path: str) -> dict | None:
+    """The ``params.json`` next to a checkpoint file (the reference's model directory layout), or None."""
+    import json
+    import os
+
+    pj = os.path.join(os.path.dirname(os.path.abspath(path)), "params.json")
+    if not os.path.isfile(pj):
+        return None
+    with open(pj) as fh:
+        params = json.load(fh)
+    if not isinstance(params, dict):
+        raise ValueError(f"{pj}: not a JSON object")
+    return {k: params[k] for k in _PARAMS_JSON_KEYS if k in params}
+
+
+def load_painn_blob_auto(path: str) -> tuple[np.ndarray, dict]:
+    """``best_model`` archive -> (canonical blob, hyper-parameters inferred from its tensors).  A ``params.json`` next to
+    the file is read; its shapes must agree with the tensors and its cutoff / excluded-volume settings with the pickled
+    module attributes, else ``ValueError``.  Without a ``params.json`` the cutoff and excluded-volume settings are the
+    module's attributes."""
+    if not zipfile.is_zipfile(path):
+        raise ValueError(f"{path}: hparams='auto' needs a checkpoint archive (a raw blob does not carry its shape)")
+    sd = read_state_dict(path)
+    hp = infer_hparams(sd)
+    params = read_params_json(path) or {}
+    for k in _SHAPE_KEYS:
+        if k in params and int(params[k]) != int(hp[k]):
+            raise ValueError(f"{path}: params.json has {k}={params[k]!r} but the checkpoint tensors have {k}={hp[k]}")
+    hp.update(params)
+    # cutoff / excluded volume: params.json first, else the pickled module's own attributes; the two must agree (checked below)
+    attrs = read_model_attrs(path)
+    for attr, key in _ATTR_TO_HPARAM:
+        if key not in params and attrs.get(attr) is not None:
+            hp[key] = attrs[attr]
+    check_model_against_hparams(path, sd, hp, attrs=attrs)
+    return state_dict_to_blob(sd, hp), hp
+
+
 def load_painn_blob(path: str, hp: dict | None = None) -> np.ndarray:
     """``best_model`` (torch zip) or ``.f32`` raw blob -> canonical fp32 blob."""
     if zipfile.is_zipfile(path):

@@ -491,7 +491,8 @@ int build_neighbors(vssr_handle *h, double cutoff) {
     if (lpc_rev == 16) hipLaunchKernelGGL(k_rev<16>, grid_for(16), wblk, 0, st, REV_ARGS);
     else hipLaunchKernelGGL(k_rev<32>, grid_for(32), wblk, 0, st, REV_ARGS);
 #undef REV_ARGS
-    if (h->kind == 1) {   // PaiNN: per-slot geometry tables shared by all layers / models / slices
+    if (h->kind == 1 && !h->painn_general) {   // PaiNN 128 / 20: per-slot geometry tables shared by all layers / models / slices
+                                                // (the general path computes its radial functions on the fly)
         // layer-0 factorisation with at most 4 species: its T blocks are accumulated by k_edge_geom (h->l0T_by_geom); with more species
         // a separate kernel builds them from the fp32 table and the per-slot unit vectors, which are only written for it
         const int nzf = (h->l0_enabled && h->l0_nz >= 1 && h->l0_nz <= 4) ? h->l0_nz : 0;

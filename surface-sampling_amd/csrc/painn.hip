@@ -600,6 +600,12 @@ int painn_alloc_state(vssr_handle *h) {
         (compact && h->d_gpart.ensure(sizeof(float) * 3 * M * groups * (size_t)h->slot_cap + 256)))
         return set_err(h, VSSR_E_NOMEM, "edge-gradient buffer: out of device memory");
     sv.gbar = h->d_gbar.as<float4>();
+    return painn_alloc_results(h);
+}
+
+// result buffers and saturation flags of a PaiNN run (both paths)
+int painn_alloc_results(vssr_handle *h) {
+    const size_t N = h->n_atoms, M = h->n_models;
     if (h->d_energy.ensure(sizeof(float) * h->n_cfg) || h->d_energy_std.ensure(sizeof(float) * h->n_cfg) ||
         h->d_energy_models.ensure(sizeof(float) * h->n_cfg * M) || h->d_energy64.ensure(sizeof(double) * h->n_cfg * (2 + M)) ||
         h->d_forces.ensure(sizeof(float) * 3 * N) ||
@@ -615,6 +621,7 @@ int painn_alloc_state(vssr_handle *h) {
 }
 
 int painn_run(vssr_handle *h, uint32_t want) {
+    if (h->painn_general) return painn_gen_run(h, want);   // any other (feat_dim, n_rbf): painn_gen.hip
     const int N = h->n_atoms, M = h->n_models, L = h->num_conv, H = h->readout_hidden;
     hipStream_t st = h->stream;
     h->h_sat_valid = false;   // (the host copy of the saturation report belongs to the previous evaluation)
@@ -824,6 +831,20 @@ int painn_run(vssr_handle *h, uint32_t want) {
     P.end(st);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;
+}
+
+// force assembly and energy reduction of the general path (painn_gen.hip): its reverse pass leaves one reduced edge-gradient
+// buffer per model (model stride gbar_model_stride), as the compact records of this path do after k_reduce_gpart
+void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want, long long gbar_model_stride) {
+    const int N = h->n_atoms, M = h->n_models;
+    hipStream_t st = h->stream;
+    if (want & VSSR_WANT_FORCES)
+        hipLaunchKernelGGL(k_finalize_forces, dim3((N + 3) / 4), dim3(256), 0, st, N, M, G, h->d_counters.as<int>(), h->sv.gbar,
+                           gbar_model_stride, h->units_per_ev, h->d_forces.as<float>(), h->d_forces_std.as<float>());
+    hipLaunchKernelGGL(k_finalize_energy, dim3(h->n_cfg), dim3(256), 0, st, N, M, h->active_mask, G.cfg_start, h->d_Z.as<int>(),
+                       h->sv.e_atom, h->units_per_ev, h->has_offset ? h->offset_per_z.as<double>() : (const double *)nullptr,
+                       h->offset_const, h->d_energy.as<float>(), h->d_energy_std.as<float>(), h->d_energy_models.as<float>(),
+                       h->d_energy64.as<double>(), h->d_e_atoms.as<float>(), h->d_sat.as<unsigned>(), h->d_sat_out.as<unsigned>());
 }
 
 // vssr_batch_stress: the virial of the last evaluation (forces must have been computed: gbar holds the reduced edge gradients)

@@ -288,9 +288,10 @@ int vssr_create(const vssr_painn_config *cfg, vssr_handle **out) {
     if (cfg->struct_size != sizeof(vssr_painn_config))
         return set_err(nullptr, VSSR_E_BADARG, "vssr_painn_config size mismatch (%u vs %zu)", cfg->struct_size,
                        sizeof(vssr_painn_config));
-    if (cfg->feat_dim != F || cfg->n_rbf != 20)
-        return set_err(nullptr, VSSR_E_BADARG, "only feat_dim=128, n_rbf=20 are compiled (got %d, %d)", cfg->feat_dim,
-                       cfg->n_rbf);
+    // accepted shapes: (128, 20) takes the specialised path, every other one the general-width path (painn_gen.hip)
+    if (cfg->feat_dim < 16 || cfg->feat_dim > 256 || cfg->feat_dim % 16 != 0 || cfg->n_rbf < 1 || cfg->n_rbf > 32)
+        return set_err(nullptr, VSSR_E_BADARG,
+                       "feat_dim must be a multiple of 16 in 16..256 and n_rbf in 1..32 (got %d, %d)", cfg->feat_dim, cfg->n_rbf);
     if (cfg->n_models < 1 || cfg->n_models > MAX_MODELS || cfg->num_conv < 1 || cfg->num_conv > MAX_LAYERS ||
         cfg->readout_hidden < 1 || cfg->readout_hidden > F || cfg->n_embed < 1 || !cfg->weights ||
         !(cfg->cutoff > 0) || !(cfg->model_units_per_ev > 0))
@@ -307,13 +308,21 @@ int vssr_create(const vssr_painn_config *cfg, vssr_handle **out) {
     h->n_models = cfg->n_models; h->n_rbf = cfg->n_rbf; h->num_conv = cfg->num_conv; h->n_embed = cfg->n_embed;
     h->readout_hidden = cfg->readout_hidden; h->cutoff = cfg->cutoff; h->excl_vol = cfg->excl_vol;
     h->excl_power = cfg->excl_power; h->excl_sigma = cfg->excl_sigma; h->units_per_ev = cfg->model_units_per_ev;
+    h->feat_dim = cfg->feat_dim;
+    h->painn_general = !(cfg->feat_dim == F && cfg->n_rbf == 20);
+    if (const char *e = getenv("VSSR_PAINN_PATH")) h->painn_general = h->painn_general || strcmp(e, "general") == 0;   // (tests: A/B at 128 / 20)
     int rc = common_init(h, cfg->device);
-    if (!rc) rc = upload_weights(h, cfg);
-    if (!rc) rc = node_mfma_init(h);
-    if (!rc) rc = edge_mfma_init(h);
-    if (!rc) rc = l0_mfma_init(h);
+    if (h->painn_general) {   // none of the fp16-split / sliced / species-factorised machinery of the 128 / 20 path
+        h->l0_enabled = 0;
+        if (!rc) rc = painn_gen_upload(h, cfg);
+    } else {
+        if (!rc) rc = upload_weights(h, cfg);
+        if (!rc) rc = node_mfma_init(h);
+        if (!rc) rc = edge_mfma_init(h);
+        if (!rc) rc = l0_mfma_init(h);
+    }
     if (const char *e = getenv("VSSR_EDGE_IMPL")) h->edge_impl = (strcmp(e, "gather") == 0) ? 0 : 1;
-    if (const char *e = getenv("VSSR_L0_FACTORISE")) h->l0_enabled = atoi(e);
+    if (const char *e = getenv("VSSR_L0_FACTORISE")) h->l0_enabled = h->painn_general ? 0 : atoi(e);
     if (const char *e = getenv("VSSR_UPD_SAVE")) h->upd_save = atoi(e);
     if (const char *e = getenv("VSSR_DEBUG_KEEP")) h->debug_keep = atoi(e);
     // test knobs: send chains above these atom counts to the next class (8-feature slices / gather kernels) although they fit
@@ -1062,7 +1071,7 @@ int vssr_batch_embedding(vssr_handle *h, int32_t model, float *dst, int64_t cap,
     VSSR_HIP(h, hipSetDevice(h->device));
     int rc = sync_and_check(h);
     if (rc) return rc;
-    const size_t per_model = (size_t)h->n_atoms * F, n = model < 0 ? per_model * h->n_models : per_model;
+    const size_t per_model = (size_t)h->n_atoms * h->feat_dim, n = model < 0 ? per_model * h->n_models : per_model;
     if (n_out) *n_out = (int64_t)n;
     if (!dst) return VSSR_OK;
     if ((int64_t)n > cap) return set_err(h, VSSR_E_BADARG, "embedding buffer too small (%lld < %zu floats)", (long long)cap, n);
@@ -1139,6 +1148,7 @@ int vssr_debug_read(vssr_handle *h, const char *name, int32_t model, float *dst,
     if (!h || !name || !n_out) return VSSR_E_BADARG;
     if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
     if (model < 0 || model >= h->n_models) return set_err(h, VSSR_E_BADARG, "model index out of range");
+    if (h->painn_general) return set_err(h, VSSR_E_STATE, "per-layer intermediates are not kept by the general-width PaiNN path");
     if (h->graph_partial)
         return set_err(h, VSSR_E_STATE, "the resident graph covers only the chains of the last relaxation iteration: run the batch once (vssr_batch_run) first");
     int rc = sync_and_check(h);

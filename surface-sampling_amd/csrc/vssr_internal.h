@@ -252,6 +252,9 @@ struct vssr_handle {
 
     // configuration
     int n_models = 0, n_rbf = 20, num_conv = 3, n_embed = 100, readout_hidden = 64;
+    int feat_dim = vssr::F;      // the handle's own feature width (the compiled F on the 128 / 20 path)
+    bool painn_general = false;  // PaiNN served by the general-width fp32 path (painn_gen.hip): every (feat_dim, n_rbf) but (128, 20),
+                                 // or any shape with VSSR_PAINN_PATH=general
     float cutoff = 5.f;
     int excl_vol = 1, excl_power = 12;
     float excl_sigma = 1.5f;
@@ -360,6 +363,12 @@ int build_neighbors(vssr_handle *h, double cutoff);
 int painn_alloc_state(vssr_handle *h);
 int painn_run(vssr_handle *h, uint32_t want);
 int painn_stress(vssr_handle *h);   // enqueues k_stress: d_stress from the edge gradients of the last run (forces wanted)
+int painn_alloc_results(vssr_handle *h);   // result buffers and saturation flags (both PaiNN paths)
+// energy reduction and force assembly from sv.e_atom / sv.gbar (one reduced edge-gradient buffer per model)
+void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want, long long gbar_model_stride);
+// general-width PaiNN path (painn_gen.hip): weights of any accepted (feat_dim, n_rbf), and the run
+int painn_gen_upload(vssr_handle *h, const vssr_painn_config *cfg);
+int painn_gen_run(vssr_handle *h, uint32_t want);
 // Tersoff (tersoff.hip)
 int tersoff_run(vssr_handle *h, uint32_t want);
 // EAM (eam.hip)

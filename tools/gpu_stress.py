@@ -10,7 +10,7 @@ table, const = g.offset_table()
 base = g.structure("SrTiO3_2x2_pristine")
 chains = [structures.as_arrays(structures.synth_chain(base, c, grid=(4, 4))) for c in range(int(os.environ.get("NCHAIN", "64")))]
 reps = int(os.environ.get("REPS", "30"))
-for env in ({}, {"VSSR_L0_FACTORISE": "0"}):
+for env in ({}, {"VSSR_L0_FACTORISE": "0"}, {"VSSR_PAINN_PATH": "general"}):   # (the last: the general-width fp32 path)
     os.environ.update(env)
     bad_e = bad_f = 0
     ref = None
