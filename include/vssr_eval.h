@@ -22,6 +22,9 @@
  *   vssr_sw_create / vssr_sw_eval_batch
  *                                   <- the same with pair_style sw, or pair_style kim with the
  *                                      Stillinger-Weber Si model (tutorials/Si_111_5x5)
+ *   vssr_gmm_create / vssr_gmm_score_rows / vssr_gmm_score_batch
+ *                                   <- GMMUncertainty.estimate_log_prob / negative_log_likelihood
+ *                                      (mcmc/uncertainty/uncertainty.py:238-463)
  *
  * Conventions
  *   - All arrays are caller-allocated and borrowed only for the duration of the call.
@@ -344,6 +347,42 @@ int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_s
 int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                        const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                        double *energy_atoms_f64, double *forces_f64);
+
+/* ---- Gaussian-mixture uncertainty of PaiNN latent embeddings (reference mcmc.uncertainty.GMMUncertainty,
+ *      mcmc/uncertainty/uncertainty.py:238-463; scripts/clustering.py --clustering_metric gmm) ---------------------------------- */
+/* For a row x (fp64), component k with mean mu_k, precision Cholesky factor P_k ([D][D]) and weight w_k:
+ *   s_k(x)  = sum_j ((x P_k)_j - (mu_k P_k)_j)^2
+ *   logp_k  = -0.5 (D log_2pi + s_k) + sum_d log P_k[d][d]
+ *   NLL(x)  = -(m + log sum_k exp(logp_k + log w_k - m)),  m = max_k (logp_k + log w_k)
+ * All arithmetic is fp64 (v_mfma_f64_16x16x4_f64 for x P_k).  log_2pi is an input: GMMUncertainty evaluates it in float32
+ * (1.8378770351409912), sklearn / gmm.py in fp64 (1.8378770664093453).  Covariance types other than "full" are expanded to
+ * per-component full P_k by the caller. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(vssr_gmm_config) */
+    int32_t device;       /* HIP device ordinal */
+    int32_t n_components; /* K, 1 .. 256 */
+    int32_t dim;          /* D, 1 .. 256 */
+    const double *means;     /* [K][D] */
+    const double *prec_chol; /* [K][D][D], row-major: P_k[i][j] multiplies x_i into column j */
+    const double *weights;   /* [K] */
+    double log_2pi;
+} vssr_gmm_config;
+/* Handle kind 5 (freed by vssr_destroy).  Refused with VSSR_E_BADARG before any device is touched: K or D out of range, null
+ * arrays, non-finite numbers, a non-positive diagonal entry of any P_k, a negative weight or no positive one.  The 16 x 16 blocks of
+ * every P_k that are exactly zero are found here and skipped by the kernel (they add exactly 0: sklearn's factors are triangular).
+ * Every entry point other than vssr_gmm_*, vssr_destroy and vssr_last_error refuses a GMM handle. */
+int vssr_gmm_create(const vssr_gmm_config *cfg, vssr_handle **out);
+/* Score n_rows caller rows x [n_rows][D] (fp64): nll [n_rows]; log_prob [n_rows][K] (logp_k, unweighted) may be NULL. */
+int vssr_gmm_score_rows(vssr_handle *g, int64_t n_rows, const double *x, double *nll, double *log_prob);
+/* Score the resident embedding of a PaiNN handle (the features vssr_batch_embedding returns) of ensemble member `model`, read in
+ * place on the device.  rows: 0 = every atom (nll_rows [sum N]), 1 = one mean row per structure (nll_rows [B], summed in fp64 in
+ * atom order).  order: 0 atomic, 1 system_sum, 2 system_mean, 3 system_max, 4 system_min, 5 system_mean_squared,
+ * 6 system_root_mean_squared; for order >= 1, system [B] receives the true per-structure reduction of the row NLLs (rows = 1: the
+ * structure's own NLL).  Deterministic: one workgroup reduces one structure in a fixed order.  Either output may be NULL.
+ * Runs on the PaiNN handle's stream and synchronises.  VSSR_E_STATE as vssr_batch_embedding (no PaiNN run, or a partial graph
+ * after a relaxation); VSSR_E_BADARG when D != feat_dim or the handles live on different devices. */
+int vssr_gmm_score_batch(vssr_handle *g, vssr_handle *painn, int32_t model, int32_t rows, int32_t order, double *nll_rows,
+                         double *system);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@ EXPORTS = (
     "vssr_batch_embedding", "vssr_batch_traj_configure", "vssr_batch_traj_read",
     "vssr_device_context", "vssr_batch_stress", "vssr_batch_energy_f64", "vssr_batch_device_results_f64",
     "vssr_batch_relax_counts", "vssr_sw_create", "vssr_sw_create_from_text", "vssr_sw_eval_batch",
+    "vssr_gmm_create", "vssr_gmm_score_rows", "vssr_gmm_score_batch",
 )
 
 
@@ -85,6 +86,18 @@ class BfgsParams(C.Structure):
     @classmethod
     def default(cls, max_steps=20, fmax=0.01):
         return cls(int(max_steps), float(fmax), 70.0, 0.2)
+
+
+class GmmConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_components", C.c_int32), ("dim", C.c_int32),
+                ("means", C.POINTER(C.c_double)), ("prec_chol", C.POINTER(C.c_double)), ("weights", C.POINTER(C.c_double)),
+                ("log_2pi", C.c_double)]
+
+
+# order / rows codes of vssr_gmm_score_batch
+GMM_ORDERS = {"atomic": 0, "system_sum": 1, "system_mean": 2, "system_max": 3, "system_min": 4, "system_mean_squared": 5,
+              "system_root_mean_squared": 6}
+GMM_ROWS = {"atoms": 0, "mean": 1}
 
 
 class Out(C.Structure):
@@ -209,6 +222,12 @@ def load_library():
     L.vssr_device_context.argtypes = [vp, ip, C.POINTER(vp), C.POINTER(vp)]
     L.vssr_debug_capacity.restype = C.c_int
     L.vssr_debug_capacity.argtypes = [vp, C.c_int32, C.c_int32, ip]
+    L.vssr_gmm_create.restype = C.c_int
+    L.vssr_gmm_create.argtypes = [C.POINTER(GmmConfig), C.POINTER(vp)]
+    L.vssr_gmm_score_rows.restype = C.c_int
+    L.vssr_gmm_score_rows.argtypes = [vp, C.c_int64, dp, dp, dp]
+    L.vssr_gmm_score_batch.restype = C.c_int
+    L.vssr_gmm_score_batch.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     if L.vssr_abi_version() != 1:
         raise BackendError("libvssr_eval.so ABI version mismatch")
     _lib = L
@@ -649,3 +668,57 @@ class EAMEngine(_AnalyticEngine):
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"vssr_eam_create failed ({rc}): {msg.decode() if msg else '?'}")
+
+
+class GMMEngine(_Handle):
+    """Gaussian-mixture negative log-likelihood of embedding rows on one GPU (vssr_gmm_*): fp64 throughout.
+
+    ``means [K, D]``, ``prec_chol [K, D, D]`` (full precision Cholesky factors; other covariance types are expanded by
+    ``uncertainty.full_precision_cholesky``), ``weights [K]``; ``log_2pi`` is the constant of the Gaussian normaliser (the
+    reference's ``GMMUncertainty`` evaluates it in float32, ``uncertainty.LOG2PI_F32``)."""
+
+    def __init__(self, means, prec_chol, weights, device=0, log_2pi=1.8378770351409912):
+        super().__init__()
+        self._means = np.ascontiguousarray(means, dtype=np.float64)
+        if self._means.ndim != 2:
+            raise ValueError("means must be [K, D]")
+        K, D = self._means.shape
+        self._prec = np.ascontiguousarray(prec_chol, dtype=np.float64)
+        self._weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if self._prec.shape != (K, D, D) or self._weights.shape != (K,):
+            raise ValueError(f"prec_chol must be [K, D, D] and weights [K] for means of shape {(K, D)}")
+        cfg = GmmConfig(C.sizeof(GmmConfig), int(device), K, D, _ptr(self._means, C.c_double), _ptr(self._prec, C.c_double),
+                        _ptr(self._weights, C.c_double), float(log_2pi))
+        rc = self._lib.vssr_gmm_create(C.byref(cfg), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_gmm_create failed ({rc}): {msg.decode() if msg else '?'}")
+        self.n_components, self.dim, self.device = K, D, int(device)
+
+    def score_rows(self, x, log_prob=False):
+        """NLL [n] of rows ``x [n, D]`` (any float dtype; scored in fp64); with ``log_prob=True`` also logp_k [n, K]."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}], got {x.shape}")
+        n = x.shape[0]
+        nll = np.zeros(n, np.float64)
+        lp = np.zeros((n, self.n_components), np.float64) if log_prob else None
+        self._check(self._lib.vssr_gmm_score_rows(self._h, n, _ptr(x, C.c_double), _ptr(nll, C.c_double), _ptr(lp, C.c_double)))
+        return (nll, lp) if log_prob else nll
+
+    def score_batch(self, painn_engine, model=0, rows="atoms", order="atomic"):
+        """Score the resident embedding of ``painn_engine``'s last run (ensemble member ``model``) in place on the device.
+        ``rows``: "atoms" (one row per atom) or "mean" (one mean row per structure).  Returns ``(nll_rows, system)``:
+        ``nll_rows`` [sum N] or [B]; ``system`` [B], the TRUE per-structure reduction named by ``order`` (None for "atomic")."""
+        if rows not in GMM_ROWS:
+            raise ValueError(f"rows must be one of {sorted(GMM_ROWS)}, got {rows!r}")
+        if order not in GMM_ORDERS:
+            raise ValueError(f"order must be one of {sorted(GMM_ORDERS)}, got {order!r}")
+        B, N = painn_engine._n_cfg, painn_engine._n_atoms
+        nll = np.zeros(N if rows == "atoms" else B, np.float64)
+        sysv = np.zeros(B, np.float64) if order != "atomic" else None
+        self._check(self._lib.vssr_gmm_score_batch(self._h, painn_engine._h, int(model), GMM_ROWS[rows], GMM_ORDERS[order],
+                                                   _ptr(nll, C.c_double), _ptr(sysv, C.c_double)))
+        return nll, sysv

@@ -475,15 +475,25 @@ class EnsembleNFFSurface(_Base):
 
     # -- new capability: many independent chains in one lock-step evaluation ----------------------------
     def calculate_batch(self, atoms_list, want_surface_energy: bool = False, want_embedding: bool | None = None,
-                        want_stress: bool = False) -> list[dict]:
+                        want_stress: bool = False, uncertainty=None, uncertainty_rows: str = "atoms",
+                        uncertainty_model: int = 0) -> list[dict]:
         """Evaluate B independent configurations at once; returns one results dict per configuration
-        (``want_embedding``: default = ``"embedding" in self.properties``; ``want_stress``: also ``stress`` / ``stress_std``)."""
+        (``want_embedding``: default = ``"embedding" in self.properties``; ``want_stress``: also ``stress`` / ``stress_std``).
+        ``uncertainty``: a fitted ``uncertainty.GMMUncertainty``; adds ``results["uncertainty"]`` per structure, scored on the
+        GPU from the resident embedding of ensemble member ``uncertainty_model`` (``uncertainty_rows``: "atoms" = every atom,
+        reduced by the instance's order; "mean" = the structure's mean embedding row) -- what the instance returns for the
+        same batch on the host.  The embedding is not downloaded for it."""
         eng = self._get_engine()
         res = eng.evaluate([self._arrays(a) for a in atoms_list])
         stress = eng.stress() if want_stress else None
         if want_embedding is None:
             want_embedding = "embedding" in self.properties
         emb = eng.embedding() if want_embedding else None
+        unc = None
+        if uncertainty is not None:
+            _, unc = uncertainty.score_resident(eng, model=uncertainty_model, rows=uncertainty_rows)
+            unc = unc.numpy()
+        per_atom_unc = unc is not None and uncertainty_rows == "atoms" and "system" not in uncertainty.order
         out = []
         for b, atoms in enumerate(atoms_list):
             r = self._fill_results(res, b)
@@ -495,6 +505,9 @@ class EnsembleNFFSurface(_Base):
                 a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
                 r["embedding"] = emb[0, a0:a1].copy()
                 r["embedding_models"] = emb[:, a0:a1].copy()
+            if unc is not None:
+                a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
+                r["uncertainty"] = unc[a0:a1].copy() if per_atom_unc else np.float64(unc.reshape(-1)[b])
             out.append(r)
         return out
 

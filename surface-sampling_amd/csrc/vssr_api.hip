@@ -272,6 +272,12 @@ static int sync_and_check(vssr_handle *h) {
     return set_err(h, VSSR_E_CAPACITY, "neighbor list capacity could not be satisfied");
 }
 
+// a Gaussian-mixture handle (kind 5) serves vssr_gmm_*, vssr_destroy and vssr_last_error only: every other entry point refuses it
+#define VSSR_REFUSE_GMM(h)                                                                                               \
+    do {                                                                                                                 \
+        if ((h)->kind == 5) return set_err((h), VSSR_E_BADARG, "%s: a Gaussian-mixture handle serves the vssr_gmm_* calls only", __func__); \
+    } while (0)
+
 }  // namespace vssr
 
 using namespace vssr;
@@ -483,7 +489,8 @@ void vssr_destroy(vssr_handle *h) {
                       &h->d_wrap, &h->d_Z, &h->d_atom_cfg, &h->d_cfg_start, &h->d_cell, &h->d_invcell, &h->d_nimg,
                       &h->d_pbc, &h->d_deg, &h->d_row_start, &h->d_edge, &h->d_edge_S, &h->d_rev, &h->d_counters, &h->d_tile_sums, &h->d_erec, &h->d_rho, &h->d_dist, &h->d_rho16, &h->d_drho16, &h->d_zslot, &h->d_bundle, &h->d_excl, &h->d_hits, &h->wd16, &h->node16, &h->d_l0A, &h->d_l0At, &h->d_zmap, &h->d_zlist, &h->d_l0T, &h->d_l0Q, &h->d_vel, &h->d_fire, &h->d_fixed, &h->d_relax_steps, &h->d_relax_conv, &h->d_active, &h->d_bfgs_q, &h->d_bfgs_b,
                       &h->d_state, &h->d_gbar, &h->d_energy, &h->d_energy_std, &h->d_energy_models, &h->d_forces,
-                      &h->d_forces_std, &h->d_e_atoms, &h->d_ters_e, &h->d_ters_ea, &h->d_ters_f, &h->d_sat, &h->d_sat_out, &h->d_stress, &h->d_traj_pos, &h->d_traj_f, &h->d_traj_e, &h->d_traj_n, &h->d_chain_class, &h->d_class_list, &h->d_upd_save, &h->d_gpart, &h->d_energy64, &h->d_cmp, &h->d_cm, &h->d_bundle_sub, &h->d_bundle_subb};
+                      &h->d_forces_std, &h->d_e_atoms, &h->d_ters_e, &h->d_ters_ea, &h->d_ters_f, &h->d_sat, &h->d_sat_out, &h->d_stress, &h->d_traj_pos, &h->d_traj_f, &h->d_traj_e, &h->d_traj_n, &h->d_chain_class, &h->d_class_list, &h->d_upd_save, &h->d_gpart, &h->d_energy64, &h->d_cmp, &h->d_cm, &h->d_bundle_sub, &h->d_bundle_subb,
+                      &h->d_gmm_P, &h->d_gmm_c, &h->d_gmm_kc, &h->d_gmm_mask, &h->d_gmm_x, &h->d_gmm_lp, &h->d_gmm_nll, &h->d_gmm_sys, &h->d_gmm_start};
     for (DevBuf *b : bufs) b->release();
     if (h->h_counters) (void)hipHostFree(h->h_counters);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -493,6 +500,7 @@ void vssr_destroy(vssr_handle *h) {
 int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *Z, const double *pos,
                       const double *cell, const uint8_t *pbc) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (n_cfg < 1 || !n_atoms || !Z || !pos || !cell || !pbc) return set_err(h, VSSR_E_BADARG, "null or empty batch");
     VSSR_HIP(h, hipSetDevice(h->device));
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
@@ -602,6 +610,7 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
 
 int vssr_batch_set_positions(vssr_handle *h, const double *pos) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "no resident batch");
     if (!pos) return set_err(h, VSSR_E_BADARG, "null positions");
     VSSR_HIP(h, hipSetDevice(h->device));
@@ -613,6 +622,7 @@ int vssr_batch_set_positions(vssr_handle *h, const double *pos) {
 
 int vssr_batch_run(vssr_handle *h, uint32_t want) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_run before vssr_batch_upload");
     VSSR_HIP(h, hipSetDevice(h->device));
     int rc = run_any(h, want);
@@ -624,12 +634,14 @@ int vssr_batch_run(vssr_handle *h, uint32_t want) {
 
 int vssr_synchronize(vssr_handle *h) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     VSSR_HIP(h, hipSetDevice(h->device));
     return sync_and_check(h);
 }
 
 int vssr_batch_download(vssr_handle *h, uint32_t want, vssr_out *out) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran) return set_err(h, VSSR_E_STATE, "vssr_batch_download before vssr_batch_run");
     if (!out) return set_err(h, VSSR_E_BADARG, "null output");
     VSSR_HIP(h, hipSetDevice(h->device));
@@ -689,6 +701,7 @@ int vssr_tersoff_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atom
                             const double *pos, const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out,
                             double *energy_f64, double *energy_atoms_f64, double *forces_f64) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!is_f64_kind(h)) return set_err(h, VSSR_E_STATE, "not a Tersoff / EAM / SW handle");
     vssr_out dummy;
     memset(&dummy, 0, sizeof dummy);
@@ -707,6 +720,7 @@ static int relax_finish(vssr_handle *h, double *pos_out, int32_t *n_steps, uint8
 int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint8_t *fixed, uint32_t want, double *pos_out,
                         int32_t *n_iter, int32_t *n_eval, int32_t *stop_reason) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_cg before vssr_batch_upload");
     if (!params || params->max_iter < 0 || params->max_eval < 1 || !(params->etol >= 0) || !(params->ftol >= 0) || !(params->dmax > 0))
         return set_err(h, VSSR_E_BADARG, "bad CG parameters");
@@ -876,6 +890,7 @@ int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, co
 int vssr_batch_relax_bfgs(vssr_handle *h, const vssr_bfgs_params *params, const uint8_t *fixed, uint32_t want,
                           double *pos_out, int32_t *n_steps, uint8_t *converged) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_bfgs before vssr_batch_upload");
     if (!params || params->max_steps < 0 || !(params->fmax > 0) || !(params->alpha > 0) || !(params->maxstep > 0))
         return set_err(h, VSSR_E_BADARG, "bad BFGS parameters");
@@ -890,6 +905,7 @@ int vssr_batch_relax_bfgs(vssr_handle *h, const vssr_bfgs_params *params, const 
 int vssr_batch_relax_fire(vssr_handle *h, const vssr_fire_params *params, const uint8_t *fixed, uint32_t want,
                           double *pos_out, int32_t *n_steps, uint8_t *converged) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_fire before vssr_batch_upload");
     if (!params || params->max_steps < 0 || !(params->fmax > 0) || !(params->dt > 0) || !(params->maxstep > 0))
         return set_err(h, VSSR_E_BADARG, "bad FIRE parameters");
@@ -913,6 +929,7 @@ static int relax_finish(vssr_handle *h, double *pos_out, int32_t *n_steps, uint8
 // ---- introspection ---------------------------------------------------------------------------------------
 int vssr_profile_enable(vssr_handle *h, int enable) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
     h->prof.collect();
     h->prof.enabled = enable != 0;
@@ -920,6 +937,7 @@ int vssr_profile_enable(vssr_handle *h, int enable) {
 }
 int vssr_profile_reset(vssr_handle *h) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
     h->prof.reset();
     return VSSR_OK;
@@ -927,6 +945,7 @@ int vssr_profile_reset(vssr_handle *h) {
 int vssr_profile_read(vssr_handle *h, int32_t cap, const char **names, int64_t *launches, double *total_ms,
                       int32_t *n_out) {
     if (!h || !n_out) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
     h->prof.collect();
     int n = 0;
@@ -942,6 +961,7 @@ int vssr_profile_read(vssr_handle *h, int32_t cap, const char **names, int64_t *
 
 int vssr_batch_stats(vssr_handle *h, int64_t *n_atoms, int64_t *n_edges, int64_t *n_slots) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran) return set_err(h, VSSR_E_STATE, "no completed run");
     if (h->graph_partial)
         return set_err(h, VSSR_E_STATE, "the resident graph covers only the chains of the last relaxation iteration: run the batch once (vssr_batch_run) first");
@@ -956,6 +976,7 @@ int vssr_batch_stats(vssr_handle *h, int64_t *n_atoms, int64_t *n_edges, int64_t
 int vssr_batch_neighbors(vssr_handle *h, int64_t cap, int32_t *ei, int32_t *ej, int32_t *eS, float *er,
                          int64_t *n_edges) {
     if (!h || !n_edges) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran) return set_err(h, VSSR_E_STATE, "no completed run");
     if (h->graph_partial)
         return set_err(h, VSSR_E_STATE, "the resident graph covers only the chains of the last relaxation iteration: run the batch once (vssr_batch_run) first");
@@ -992,6 +1013,7 @@ int vssr_batch_neighbors(vssr_handle *h, int64_t cap, int32_t *ei, int32_t *ej, 
 
 int vssr_batch_device_results(vssr_handle *h, const float **energy, const float **energy_std) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
     if (energy) *energy = h->d_energy.as<float>();
     if (energy_std) *energy_std = h->d_energy_std.as<float>();
@@ -1000,6 +1022,7 @@ int vssr_batch_device_results(vssr_handle *h, const float **energy, const float 
 
 int vssr_batch_device_results_f64(vssr_handle *h, const double **energy, const double **energy_std) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
     if (energy) *energy = h->d_energy64.as<double>();
     if (energy_std) *energy_std = h->d_energy64.as<double>() + h->n_cfg;
@@ -1008,6 +1031,7 @@ int vssr_batch_device_results_f64(vssr_handle *h, const double **energy, const d
 
 int vssr_batch_energy_f64(vssr_handle *h, double *energy, double *energy_std, double *energy_models) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran) return set_err(h, VSSR_E_STATE, "vssr_batch_energy_f64 before a run");
     VSSR_HIP(h, hipSetDevice(h->device));
     int rc = sync_and_check(h);
@@ -1028,6 +1052,7 @@ int vssr_batch_energy_f64(vssr_handle *h, double *energy, double *energy_std, do
 
 int vssr_device_context(vssr_handle *h, int32_t *device, void **stream, const int32_t **overflow_flag) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (device) *device = h->device;
     if (stream) *stream = (void *)h->stream;
     if (overflow_flag) *overflow_flag = h->d_counters.p ? h->d_counters.as<int>() + 2 : nullptr;
@@ -1036,6 +1061,7 @@ int vssr_device_context(vssr_handle *h, int32_t *device, void **stream, const in
 
 int vssr_batch_traj_configure(vssr_handle *h, int32_t record_interval) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (record_interval < 0) return set_err(h, VSSR_E_BADARG, "record_interval must be >= 0");
     h->traj_interval = record_interval;
     return VSSR_OK;
@@ -1044,6 +1070,7 @@ int vssr_batch_traj_configure(vssr_handle *h, int32_t record_interval) {
 int vssr_batch_traj_read(vssr_handle *h, int32_t cap_records, int32_t *n_records, double *pos, float *forces, double *energy,
                          int32_t *max_records) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (max_records) *max_records = h->traj_records;
     if (!h->traj_records) {
         if (n_records || pos || forces || energy) return set_err(h, VSSR_E_STATE, "the last relaxation recorded no trajectory");
@@ -1064,6 +1091,7 @@ int vssr_batch_traj_read(vssr_handle *h, int32_t cap_records, int32_t *n_records
 
 int vssr_batch_embedding(vssr_handle *h, int32_t model, float *dst, int64_t cap, int64_t *n_out) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
     if (model < -1 || model >= h->n_models) return set_err(h, VSSR_E_BADARG, "model index out of range");
     if (h->graph_partial)   // (chains that converged early keep the features of THEIR last iteration, or of a buffer a regrow replaced)
@@ -1083,6 +1111,7 @@ int vssr_batch_embedding(vssr_handle *h, int32_t model, float *dst, int64_t cap,
 
 int vssr_batch_stress(vssr_handle *h, double *stress, double *stress_std) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
     if (!(h->last_want & VSSR_WANT_FORCES))
         return set_err(h, VSSR_E_STATE, "stress needs the edge gradients of a run that produced forces; the last run was asked for energies only");
@@ -1102,6 +1131,7 @@ int vssr_batch_stress(vssr_handle *h, double *stress, double *stress_std) {
 
 int vssr_batch_saturated(vssr_handle *h, uint8_t *flags, int32_t *n_flagged) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran) return set_err(h, VSSR_E_STATE, "no completed run");
     VSSR_HIP(h, hipSetDevice(h->device));
     int count = 0;
@@ -1127,6 +1157,7 @@ int vssr_batch_saturated(vssr_handle *h, uint8_t *flags, int32_t *n_flagged) {
 
 int vssr_debug_capacity(vssr_handle *h, int32_t slots_per_atom, int32_t tight, int32_t *n_regrows) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (slots_per_atom > 0) {
         h->cap_per_atom = slots_per_atom;
         h->cm_cap_per_atom = 0;   // (the chain-resident minimiser's pools start from the new value as well)
@@ -1139,6 +1170,7 @@ int vssr_debug_capacity(vssr_handle *h, int32_t slots_per_atom, int32_t tight, i
 
 int vssr_batch_relax_counts(vssr_handle *h, int64_t *lockstep_evaluations, int64_t *chain_evaluations) {
     if (!h) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (lockstep_evaluations) *lockstep_evaluations = h->relax_lockstep;
     if (chain_evaluations) *chain_evaluations = h->relax_chain_evals;
     return VSSR_OK;
@@ -1146,6 +1178,7 @@ int vssr_batch_relax_counts(vssr_handle *h, int64_t *lockstep_evaluations, int64
 
 int vssr_debug_read(vssr_handle *h, const char *name, int32_t model, float *dst, int64_t cap, int64_t *n_out) {
     if (!h || !name || !n_out) return VSSR_E_BADARG;
+    VSSR_REFUSE_GMM(h);
     if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
     if (model < 0 || model >= h->n_models) return set_err(h, VSSR_E_BADARG, "model index out of range");
     if (h->painn_general) return set_err(h, VSSR_E_STATE, "per-layer intermediates are not kept by the general-width PaiNN path");
@@ -1187,6 +1220,118 @@ int vssr_debug_read(vssr_handle *h, const char *name, int32_t model, float *dst,
     if (!dst) return VSSR_OK;
     if ((int64_t)n > cap) return set_err(h, VSSR_E_BADARG, "buffer too small for '%s'", name);
     VSSR_HIP(h, hipMemcpy(dst, src + (size_t)model * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    return VSSR_OK;
+}
+
+
+// ---- Gaussian-mixture uncertainty (gmm.hip) -------------------------------------------------------------------------------------
+int vssr_gmm_create(const vssr_gmm_config *cfg, vssr_handle **out) {
+    if (!cfg || !out) return set_err(nullptr, VSSR_E_BADARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(vssr_gmm_config))
+        return set_err(nullptr, VSSR_E_BADARG, "vssr_gmm_config size mismatch (%u vs %zu)", cfg->struct_size, sizeof(vssr_gmm_config));
+    const int K = cfg->n_components, D = cfg->dim;
+    if (K < 1 || K > 256 || D < 1 || D > 256)
+        return set_err(nullptr, VSSR_E_BADARG, "GMM: n_components must be in 1..256 and dim in 1..256 (got %d, %d)", K, D);
+    if (!cfg->means || !cfg->prec_chol || !cfg->weights) return set_err(nullptr, VSSR_E_BADARG, "GMM: null parameter array");
+    if (!std::isfinite(cfg->log_2pi)) return set_err(nullptr, VSSR_E_BADARG, "GMM: log_2pi is not finite");
+    for (size_t i = 0; i < (size_t)K * D; ++i)
+        if (!std::isfinite(cfg->means[i])) return set_err(nullptr, VSSR_E_BADARG, "GMM: non-finite mean (component %zu)", i / D);
+    for (size_t i = 0; i < (size_t)K * D * D; ++i)
+        if (!std::isfinite(cfg->prec_chol[i]))
+            return set_err(nullptr, VSSR_E_BADARG, "GMM: non-finite precision Cholesky entry (component %zu)", i / ((size_t)D * D));
+    for (int k = 0; k < K; ++k)
+        for (int d = 0; d < D; ++d)
+            if (!(cfg->prec_chol[((size_t)k * D + d) * D + d] > 0))
+                return set_err(nullptr, VSSR_E_BADARG, "GMM: diagonal entry %d of the precision Cholesky factor of component %d is not positive", d, k);
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+        if (!std::isfinite(cfg->weights[k]) || cfg->weights[k] < 0)
+            return set_err(nullptr, VSSR_E_BADARG, "GMM: weight %d is negative or not finite", k);
+        any = any || cfg->weights[k] > 0;
+    }
+    if (!any) return set_err(nullptr, VSSR_E_BADARG, "GMM: no positive weight");
+    vssr_handle *h = new vssr_handle();
+    h->kind = 5;
+    h->gmm_K = K;
+    h->gmm_D = D;
+    h->gmm_Dp = 16 * ((D + 15) / 16);
+    h->gmm_log2pi = cfg->log_2pi;
+    int rc = common_init(h, cfg->device);
+    if (!rc) rc = gmm_upload(h, cfg->means, cfg->prec_chol, cfg->weights);
+    if (rc) {
+        if (!h->err.empty()) set_err(nullptr, rc, "%s", h->err.c_str());
+        vssr_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return VSSR_OK;
+}
+
+int vssr_gmm_score_rows(vssr_handle *g, int64_t n_rows, const double *x, double *nll, double *log_prob) {
+    if (!g) return VSSR_E_BADARG;
+    if (g->kind != 5) return set_err(g, VSSR_E_BADARG, "not a GMM handle");
+    if (n_rows < 0 || n_rows > (int64_t)INT32_MAX - 64) return set_err(g, VSSR_E_BADARG, "n_rows %lld out of range", (long long)n_rows);
+    if (n_rows > 0 && !x) return set_err(g, VSSR_E_BADARG, "null rows");
+    if (n_rows == 0) return VSSR_OK;
+    VSSR_HIP(g, hipSetDevice(g->device));
+    const int D = g->gmm_D, Dp = g->gmm_Dp, K = g->gmm_K;
+    const size_t n = (size_t)n_rows;
+    if (g->d_gmm_x.ensure(sizeof(double) * n * Dp)) return set_err(g, VSSR_E_NOMEM, "device allocation failed (GMM rows)");
+    if (Dp == D) {
+        VSSR_HIP(g, hipMemcpy(g->d_gmm_x.p, x, sizeof(double) * n * D, hipMemcpyHostToDevice));
+    } else {   // zero-padded columns D .. Dp-1 (one strided copy)
+        VSSR_HIP(g, hipMemset(g->d_gmm_x.p, 0, sizeof(double) * n * Dp));
+        VSSR_HIP(g, hipMemcpy2D(g->d_gmm_x.p, sizeof(double) * Dp, x, sizeof(double) * D, sizeof(double) * D, n, hipMemcpyHostToDevice));
+    }
+    int rc = gmm_score_f64(g, g->stream, n_rows, g->d_gmm_x.as<double>());
+    if (rc) return rc;
+    VSSR_HIP(g, hipStreamSynchronize(g->stream));
+    if (nll) VSSR_HIP(g, hipMemcpy(nll, g->d_gmm_nll.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (log_prob) VSSR_HIP(g, hipMemcpy(log_prob, g->d_gmm_lp.p, sizeof(double) * n * K, hipMemcpyDeviceToHost));
+    return VSSR_OK;
+}
+
+int vssr_gmm_score_batch(vssr_handle *g, vssr_handle *painn, int32_t model, int32_t rows, int32_t order, double *nll_rows,
+                         double *system) {
+    if (!g || !painn) return g ? set_err(g, VSSR_E_BADARG, "null PaiNN handle") : VSSR_E_BADARG;
+    if (g->kind != 5) return set_err(g, VSSR_E_BADARG, "not a GMM handle");
+    if (painn->kind != 1) return set_err(g, VSSR_E_BADARG, "the second handle is not a PaiNN ensemble");
+    if (rows != 0 && rows != 1) return set_err(g, VSSR_E_BADARG, "rows must be 0 (atoms) or 1 (structure means), got %d", rows);
+    if (order < 0 || order > 6) return set_err(g, VSSR_E_BADARG, "order must be in 0..6, got %d", order);
+    if (model < 0 || model >= painn->n_models)
+        return set_err(g, VSSR_E_BADARG, "model index %d out of range (%d models)", model, painn->n_models);
+    if (g->device != painn->device)
+        return set_err(g, VSSR_E_BADARG, "the GMM handle is on device %d, the PaiNN handle on device %d", g->device, painn->device);
+    if (g->gmm_D != painn->feat_dim)
+        return set_err(g, VSSR_E_BADARG, "GMM dimension %d differs from the PaiNN feat_dim %d", g->gmm_D, painn->feat_dim);
+    if (!painn->ran) return set_err(g, VSSR_E_STATE, "no completed PaiNN run");
+    if (painn->graph_partial)
+        return set_err(g, VSSR_E_STATE, "the resident activations cover only the chains of the last relaxation iteration: run the batch once (vssr_batch_run) first");
+    VSSR_HIP(g, hipSetDevice(g->device));
+    int rc = sync_and_check(painn);   // (a capacity overflow is repaired here: the features below are those of the repeated run)
+    if (rc) return set_err(g, rc, "PaiNN run failed: %s", painn->err.c_str());
+    const int B = painn->n_cfg, N = painn->n_atoms;
+    const hipStream_t st = painn->stream;
+    if (g->d_gmm_start.ensure(sizeof(int) * (B + 1))) return set_err(g, VSSR_E_NOMEM, "device allocation failed (GMM offsets)");
+    VSSR_HIP(g, hipMemcpyAsync(g->d_gmm_start.p, painn->h_cfg_start.data(), sizeof(int) * (B + 1), hipMemcpyHostToDevice, st));
+    const float *emb = painn->sv.s_in[painn->num_conv] + (size_t)model * N * painn->feat_dim;
+    const int *start = g->d_gmm_start.as<int>();
+    if (rows == 0) {
+        rc = gmm_score_f32(g, st, N, emb);
+        if (!rc && order > 0) rc = gmm_reduce(g, st, B, start, order);
+    } else {
+        rc = gmm_mean_rows(g, st, B, start, emb);
+        if (!rc) rc = gmm_score_f64(g, st, B, g->d_gmm_x.as<double>());
+    }
+    if (rc) return rc;
+    VSSR_HIP(g, hipStreamSynchronize(st));
+    const size_t n_out = rows == 0 ? (size_t)N : (size_t)B;
+    if (nll_rows) VSSR_HIP(g, hipMemcpy(nll_rows, g->d_gmm_nll.p, sizeof(double) * n_out, hipMemcpyDeviceToHost));
+    if (system && order > 0) {
+        const void *src = rows == 0 ? g->d_gmm_sys.p : g->d_gmm_nll.p;   // one mean row per structure: its own NLL
+        VSSR_HIP(g, hipMemcpy(system, src, sizeof(double) * B, hipMemcpyDeviceToHost));
+    }
     return VSSR_OK;
 }
 

@@ -232,7 +232,7 @@ struct Profiler {
 }  // namespace vssr
 
 struct vssr_handle {
-    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber
+    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber, 5 = Gaussian mixture (gmm.hip)
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in ters_params
     int device = 0;
     hipStream_t stream = nullptr;
@@ -344,6 +344,15 @@ struct vssr_handle {
     std::vector<unsigned> h_sat;     // host copy of d_sat_out taken by vssr_batch_download (vssr_batch_saturated serves it: no second
     bool h_sat_valid = false;        // synchronisation / copy per download, advisor r3); void after every run
     vssr::DevBuf d_stress;           // [2][n_cfg][6] double: virial stress (mean, std over models) of the last evaluation (vssr_batch_stress)
+
+    // Gaussian mixture (kind 5, gmm.hip): K components of dimension D, zero-padded to Dp = 16 ceil(D / 16)
+    int gmm_K = 0, gmm_D = 0, gmm_Dp = 0;
+    double gmm_log2pi = 0.0;
+    vssr::DevBuf d_gmm_P;     // double [K][Dp][Dp]  precision Cholesky factors
+    vssr::DevBuf d_gmm_c;     // double [K][Dp]      c_k = mu_k P_k
+    vssr::DevBuf d_gmm_kc;    // double [2][K]       log det P_k, log w_k
+    vssr::DevBuf d_gmm_mask;  // uint8 [K][Dp/16][Dp/16]  1 = the 16 x 16 block of P_k holds a non-zero entry
+    vssr::DevBuf d_gmm_x, d_gmm_lp, d_gmm_nll, d_gmm_sys, d_gmm_start;   // per-call workspaces
 };
 
 namespace vssr {
@@ -375,6 +384,15 @@ int tersoff_run(vssr_handle *h, uint32_t want);
 int eam_run(vssr_handle *h, uint32_t want);
 // Stillinger-Weber (sw.hip; profiled under KC_TERSOFF)
 int sw_run(vssr_handle *h, uint32_t want);
+// Gaussian-mixture scoring (gmm.hip).  Rows: caller fp64 rows [n][Dp] (padded), or fp32 rows with leading dimension ldx = Dp;
+// writes g->d_gmm_lp [n][K] (logp_k) and g->d_gmm_nll [n] on stream st
+int gmm_upload(vssr_handle *g, const double *means, const double *prec_chol, const double *weights);
+int gmm_score_f64(vssr_handle *g, hipStream_t st, int64_t n, const double *x_dev);
+int gmm_score_f32(vssr_handle *g, hipStream_t st, int64_t n, const float *x_dev);
+// per-structure mean rows of fp32 features [N][D] into g->d_gmm_x ([B][Dp]); start: device [B + 1] atom offsets
+int gmm_mean_rows(vssr_handle *g, hipStream_t st, int B, const int *start, const float *emb);
+// per-structure reductions of g->d_gmm_nll (order 1 .. 6 as vssr_gmm_score_batch) into g->d_gmm_sys [B]
+int gmm_reduce(vssr_handle *g, hipStream_t st, int B, const int *start, int order);
 // the fp64 analytic potentials (Tersoff, EAM, SW): same result buffers (d_ters_e / _ea / _f), same drivers
 inline bool is_f64_kind(const vssr_handle *h) { return h->kind == 2 || h->kind == 3 || h->kind == 4; }
 inline int f64_run(vssr_handle *h, uint32_t want) {

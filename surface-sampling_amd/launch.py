@@ -35,6 +35,36 @@ REPLACEMENTS = {
 }
 
 
+# reference uncertainty names (mcmc.uncertainty, mcmc/uncertainty/uncertainty.py) -> attribute of surface_sampling_amd.uncertainty:
+# scripts/clustering.py --clustering_metric gmm scores with Uncertainty.load(...) on the GPU
+UNCERTAINTY_REPLACEMENTS = ("Uncertainty", "GMMUncertainty", "EnsembleUncertainty", "ConformalPrediction", "get_system_val")
+
+
+def install_uncertainty(keep=(), package: str = "mcmc.uncertainty") -> dict:
+    """Replace the uncertainty classes of ``mcmc.uncertainty`` and ``mcmc.uncertainty.uncertainty`` (where the reference resolves
+    them); nothing happens when the reference's package is not importable.  Returns {name: replacement} of what was replaced."""
+    from . import uncertainty as ours
+
+    try:
+        pkg = importlib.import_module(package)
+    except ImportError:
+        return {}
+    targets = [pkg]
+    try:
+        targets.append(importlib.import_module(package + ".uncertainty"))
+    except ImportError:
+        pass
+    done = {}
+    for name in UNCERTAINTY_REPLACEMENTS:
+        if name in keep:
+            continue
+        repl = getattr(ours, name)
+        for mod in targets:
+            setattr(mod, name, repl)
+        done[name] = repl
+    return done
+
+
 def install(keep=(), package: str = "mcmc.calculators") -> dict:
     """Patch the reference's calculator namespace; returns {name: replacement} of what was replaced."""
     from . import calculators as ours
@@ -78,6 +108,7 @@ def main(argv=None) -> int:
     done = install(keep)
     if not done:
         raise SystemExit("mcmc.calculators exposes none of the classes this backend replaces")
+    install_uncertainty(keep)
     script = argv[0]
     sys.argv = argv                      # the script parses its own arguments
     runpy.run_path(script, run_name="__main__")
