@@ -307,6 +307,15 @@ typedef struct {
 } vssr_eam_grid;
 int vssr_eam_create(int32_t device, const vssr_eam_grid *grid, const double *frho, const double *zr, const double *rhor,
                     vssr_handle **out);
+/* Several elements (LAMMPS pair_style eam/alloy, eam/fs, or funcfl files mixed per type, brought to one common grid by the
+ * caller): n_elem in 1 .. 8 tables on one grid.  frho [n_elem][nrho] embedding energies F_t(rho); rhor [n_elem][nr] (fs = 0:
+ * the density an atom of type t contributes) or [n_elem][n_elem][nr] (fs != 0: entry [a][b] = the density an atom of type a
+ * contributes at a site of type b); z2r [n_elem (n_elem + 1) / 2][nr] r * phi in eV A of the pairs (0,0), (1,0), (1,1), (2,0), ...
+ * (setfl order).  Cutoff: grid->cutoff.  Same splines, linear continuation of F and pe/atom split as vssr_eam_create; evaluate
+ * with vssr_eam_eval_batch, type[i] = the atom's table index (VSSR_E_BADARG outside [0, n_elem)).  The input is checked before
+ * any device is touched: VSSR_E_BADARG for a bad grid, n_elem outside 1 .. 8 or a non-finite table entry. */
+int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
+                          const double *rhor, const double *z2r, vssr_handle **out);
 /* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
 int vssr_eam_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                         const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,

@@ -31,7 +31,7 @@ EXPORTS = (
     "vssr_batch_embedding", "vssr_batch_traj_configure", "vssr_batch_traj_read",
     "vssr_device_context", "vssr_batch_stress", "vssr_batch_energy_f64", "vssr_batch_device_results_f64",
     "vssr_batch_relax_counts", "vssr_sw_create", "vssr_sw_create_from_text", "vssr_sw_eval_batch",
-    "vssr_gmm_create", "vssr_gmm_score_rows", "vssr_gmm_score_batch",
+    "vssr_gmm_create", "vssr_gmm_score_rows", "vssr_gmm_score_batch", "vssr_eam_create_alloy",
 )
 
 
@@ -188,6 +188,8 @@ def load_library():
     L.vssr_batch_relax_cg.argtypes = [vp, C.POINTER(CgParams), u8p, C.c_uint32, dp, ip, ip, ip]
     L.vssr_eam_create.restype = C.c_int
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
+    L.vssr_eam_create_alloy.restype = C.c_int
+    L.vssr_eam_create_alloy.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_eval_batch.restype = C.c_int
     L.vssr_eam_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_sw_create.restype = C.c_int
@@ -654,10 +656,14 @@ class SWEngine(_AnalyticEngine):
 
 
 class EAMEngine(_AnalyticEngine):
-    """One-element EAM (LAMMPS funcfl tables) evaluator, fp64 on device; every atom has type 0."""
+    """EAM evaluator, fp64 on device.  ``funcfl``: one funcfl element (every atom has type 0, vssr_eam_create), or an
+    ``eam.EamTables`` of up to 8 types -- eam/alloy, eam/fs or mixed funcfl files (type = table index, vssr_eam_create_alloy)."""
 
     def __init__(self, funcfl, device=0):
         super().__init__()
+        if hasattr(funcfl, "z2r"):
+            self._create_typed(funcfl, device)
+            return
         grid = EamGrid(int(funcfl.nrho), int(funcfl.nr), float(funcfl.drho), float(funcfl.dr), float(funcfl.cutoff))
         frho, zr, rhor = (np.ascontiguousarray(a, dtype=np.float64) for a in (funcfl.frho, funcfl.zr, funcfl.rhor))
         if frho.size != funcfl.nrho or zr.size != funcfl.nr or rhor.size != funcfl.nr:
@@ -668,6 +674,19 @@ class EAMEngine(_AnalyticEngine):
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"vssr_eam_create failed ({rc}): {msg.decode() if msg else '?'}")
+
+    def _create_typed(self, t, device):
+        n = len(t.frho)
+        grid = EamGrid(int(t.nrho), int(t.nr), float(t.drho), float(t.dr), float(t.cutoff))
+        frho, rhor, z2r = (np.ascontiguousarray(a, dtype=np.float64) for a in (t.frho, t.rhor, t.z2r))
+        if frho.size != n * t.nrho or rhor.size != (n * n if t.fs else n) * t.nr or z2r.size != n * (n + 1) // 2 * t.nr:
+            raise ValueError("EAM tables do not match their grid / element count")
+        self.n_types = n
+        rc = self._lib.vssr_eam_create_alloy(int(device), n, 1 if t.fs else 0, C.byref(grid), _ptr(frho, C.c_double),
+                                             _ptr(rhor, C.c_double), _ptr(z2r, C.c_double), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_eam_create_alloy failed ({rc}): {msg.decode() if msg else '?'}")
 
 
 class GMMEngine(_Handle):

@@ -950,7 +950,7 @@ class _AnalyticSurfCalc(_Base):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            setattr(new, k, None if k == "_engine" else (v if k in ("params", "funcfl", "logger") else copy.deepcopy(v, memo)))
+            setattr(new, k, None if k == "_engine" else (v if k in ("params", "funcfl", "tables", "logger") else copy.deepcopy(v, memo)))
         return new
 
     def set(self, **kwargs) -> dict:
@@ -1220,13 +1220,96 @@ class SWSurfCalc(_AnalyticSurfCalc):
         return backend.SWEngine(self.params, device=_device_index(self.device))
 
 
+EAM_STYLES = ("eam", "eam/alloy", "eam/fs")
+
+
+def _parse_pair_coeff(lines):
+    """``pair_coeff`` lines -> list of (i, j, file, element names) with LAMMPS type fields as given (``*`` or integers)."""
+    out = []
+    for ln in ([lines] if isinstance(lines, str) else list(lines or [])):
+        tok = str(ln).split()
+        if len(tok) < 3:
+            raise ValueError(f"pair_coeff {ln!r}: expected 'i j file [elements]'")
+        out.append((tok[0], tok[1], tok[2], tok[3:]))
+    return out
+
+
+def eam_tables(style, pair_coeff, resolve, specorder=None):
+    """The potential of ``pair_style eam | eam/alloy | eam/fs`` with LAMMPS ``pair_coeff`` lines: ``(species, source)`` where
+    ``species`` are the symbols of the types (``specorder`` when given, else the elements the lines name) and ``source`` is a
+    ``eam.Funcfl`` (pair_style eam with one funcfl element: the one-element path) or ``eam.EamTables``.  ``resolve(name)``
+    returns a file's text.  Refused with ValueError: other styles, NULL types, unknown elements, malformed files, a type without a
+    file, two types of one symbol (atoms map to types by symbol)."""
+    from . import eam as eam_io
+
+    style = str(style).split()[0]
+    if style not in EAM_STYLES:
+        raise ValueError(f"pair_style {style!r}: this calculator evaluates pair_style {', '.join(EAM_STYLES)}")
+    coeffs = _parse_pair_coeff(pair_coeff)
+    if not coeffs:
+        raise ValueError(f"pair_style {style}: pair_coeff is required")
+    if style in ("eam/alloy", "eam/fs"):
+        if len(coeffs) != 1 or coeffs[0][:2] != ("*", "*"):
+            raise ValueError(f"pair_style {style}: expected one 'pair_coeff * * file el_1 ... el_n'")
+        setfl = eam_io.parse_setfl(resolve(coeffs[0][2]), fs=style == "eam/fs")
+        tables = eam_io.tables_from_setfl(setfl, coeffs[0][3] or setfl.elements)
+        source, names = tables, list(tables.elements)
+    else:
+        per_type = {}
+        for i, j, name, rest in coeffs:
+            if "NULL" in [x.upper() for x in rest]:
+                raise ValueError("pair_style eam: NULL types (pair_style hybrid) are not supported")
+            if i != j:
+                raise ValueError(f"pair_style eam: pair_coeff {i} {j}: LAMMPS accepts only i i (one funcfl file per type)")
+            f = eam_io.parse_funcfl(resolve(name))
+            if i == "*":
+                per_type = {"*": f}
+            else:
+                try:
+                    t = int(i)
+                except ValueError:
+                    raise ValueError(f"pair_style eam: bad type {i!r}") from None
+                if t < 1 or t > 8:
+                    raise ValueError(f"pair_style eam: type {t} outside 1 .. 8")
+                per_type.pop("*", None)
+                per_type[t] = f
+        if "*" in per_type:
+            source = per_type["*"]
+            n = len(specorder) if specorder else 1
+            files = [source] * n
+        else:
+            n = max(per_type)
+            missing = [t for t in range(1, n + 1) if t not in per_type]
+            if missing:
+                raise ValueError(f"pair_style eam: types {missing} have no pair_coeff file")
+            files = [per_type[t] for t in range(1, n + 1)]
+        names = [structures.SYMBOLS[f.atomic_number] for f in files]
+        source = files[0] if len(files) == 1 else eam_io.tables_from_funcfl(files)
+    species = list(specorder) if specorder else names
+    if len(species) != len(names):
+        raise ValueError(f"specorder {list(specorder)} has {len(species)} symbols, pair_coeff names {len(names)} types")
+    unknown = [x for x in species if x not in structures.ATOMIC_NUMBERS]
+    if unknown:
+        raise ValueError(f"unknown elements {unknown}")
+    dup = sorted({x for x in species if species.count(x) > 1})
+    if dup:
+        raise ValueError(f"several types are {dup}: atoms map to types by symbol")
+    return species, source
+
+
 class EAMSurfCalc(_AnalyticSurfCalc):
-    """One-element EAM on MI355X: drop-in for ``LAMMPSRunSurfCalc`` (reference ``calculators.py:755-811``, a modified ASE
-    ``lammpsrun`` that pipes ``pair_style eam`` / ``pair_coeff * * Cu_u3.eam`` to an ``lmp`` subprocess; used by
-    ``tests/test_Cu.py`` and ``tutorials/example.ipynb``).  Constructor keeps the reference's keywords: ``files=[potential
-    file]`` (funcfl), ``keep_tmp_files`` / ``keep_alive`` / ``tmp_dir`` are accepted and unused (nothing is written to
-    disk); ``set(pair_style="eam", pair_coeff=[...])`` is recorded in ``parameters``.  Boundary conditions follow the
-    atoms' ``pbc`` (ASE lammpsrun derives ``boundary`` from it)."""
+    """EAM on MI355X: drop-in for ``LAMMPSRunSurfCalc`` (reference ``calculators.py:755-811``, a modified ASE ``lammpsrun``
+    that pipes ``pair_style eam`` / ``pair_coeff * * Cu_u3.eam`` to an ``lmp`` subprocess; used by ``tests/test_Cu.py`` and
+    ``tutorials/example.ipynb``).  Constructor keeps the reference's keywords: ``files=[potential files]``, ``keep_tmp_files``
+    / ``keep_alive`` / ``tmp_dir`` are accepted and unused (nothing is written to disk).  Without ``pair_coeff`` the first file is
+    one funcfl element.  ``set(pair_style=..., pair_coeff=[...], specorder=[...])`` selects the potential as LAMMPS would:
+
+    * ``eam`` with ``* * file`` (one funcfl element) or ``i i file_i`` per type (funcfl files mixed on one grid);
+    * ``eam/alloy`` / ``eam/fs`` with ``* * file el_1 ... el_n`` (setfl / Finnis-Sinclair file, up to 8 types).
+
+    Atoms map to types by symbol: ``specorder`` (ASE's keyword) when given, else the elements ``pair_coeff`` names; an atom of
+    another element is refused.  ``pair_coeff`` file names are matched against ``files`` (path or base name), else opened as
+    given.  Boundary conditions follow the atoms' ``pbc`` (ASE lammpsrun derives ``boundary`` from it)."""
 
     name = "eam_mi355x"
 
@@ -1236,21 +1319,61 @@ class EAMSurfCalc(_AnalyticSurfCalc):
 
         src = potential if potential is not None else (list(files)[0] if files else None)
         if src is None:
-            raise ValueError("EAMSurfCalc needs files=[<funcfl potential file>]")
-        self.funcfl = src if isinstance(src, eam_io.Funcfl) else (
-            eam_io.parse_funcfl(src) if "\n" in str(src) else eam_io.read_funcfl(src))
-        self.species = [structures.SYMBOLS[self.funcfl.atomic_number]]
+            raise ValueError("EAMSurfCalc needs files=[<potential file>]")
+        self.files = [src] if potential is not None else list(files)
+        self.tables = None
+        try:   # the reference's default: the first file is one funcfl element
+            self.funcfl = src if isinstance(src, eam_io.Funcfl) else (
+                eam_io.parse_funcfl(src) if "\n" in str(src) else eam_io.read_funcfl(src))
+            self.species = [structures.SYMBOLS[self.funcfl.atomic_number]]
+        except ValueError:   # a setfl / fs file: set(pair_style=..., pair_coeff=[...]) says how to read it
+            self.funcfl = None
+            self.species = []
         self._init_common(device, all_periodic, logger)
         super().__init__(**kwargs)
 
+    def _file_text(self, name):
+        from . import eam as eam_io
+
+        for f in self.files:
+            if isinstance(f, eam_io.Funcfl):
+                continue
+            f = str(f)
+            if "\n" not in f and (f == name or os.path.basename(f) == os.path.basename(name)):
+                with open(f, encoding="utf-8") as fh:
+                    return fh.read()
+        if os.path.isfile(name):
+            with open(name, encoding="utf-8") as fh:
+                return fh.read()
+        if len(self.files) == 1 and "\n" in str(self.files[0]):
+            return str(self.files[0])
+        raise ValueError(f"pair_coeff names {name!r}, which is neither among files={self.files} nor a file")
+
     def set(self, **kwargs) -> dict:
         style = kwargs.get("pair_style")
-        if style is not None and str(style).split()[0] != "eam":
-            raise ValueError(f"pair_style {style!r}: this calculator evaluates `pair_style eam` (funcfl) only")
-        return super().set(**kwargs)
+        if style is not None and str(style).split()[0] not in EAM_STYLES:
+            raise ValueError(f"pair_style {style!r}: this calculator evaluates pair_style {', '.join(EAM_STYLES)}")
+        if "files" in kwargs:
+            self.files = list(kwargs.pop("files"))
+        changed = super().set(**kwargs)
+        if self.parameters.get("pair_coeff") and any(k in kwargs for k in ("pair_style", "pair_coeff", "specorder")):
+            self._configure_potential()
+        return changed
+
+    def _configure_potential(self):
+        from . import eam as eam_io
+
+        p = self.parameters
+        self.species, source = eam_tables(p.get("pair_style", "eam"), p["pair_coeff"], self._file_text, p.get("specorder"))
+        self.funcfl, self.tables = (source, None) if isinstance(source, eam_io.Funcfl) else (None, source)
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
 
     def _make_engine(self):
-        return backend.EAMEngine(self.funcfl, device=_device_index(self.device))
+        if self.funcfl is None and self.tables is None:
+            raise ValueError(f"{self.files[0]} is no funcfl file: set(pair_style=..., pair_coeff=[...]) first")
+        return backend.EAMEngine(self.funcfl if self.tables is None else self.tables, device=_device_index(self.device))
 
 
 LAMMPSRunSurfCalc = EAMSurfCalc   # the reference's class name for this role
@@ -1265,7 +1388,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
     * ``lammps_config.json``: ``potential_file``, ``atoms`` (species in LAMMPS type order), ``bulk_index`` (atoms with id <=
       bulk_index form the group the relaxation template holds with ``fix ... setforce 0``);
     * ``lammps_energy_template.txt`` / ``lammps_opt_template.txt``: the ``pair_style`` line selects the potential -- ``tersoff``
-      (multi-element file), ``eam`` (one funcfl element), ``sw`` (Stillinger-Weber file) or ``kim <model>`` with a built-in SW
+      (multi-element file), ``eam`` (one funcfl element, or a list ``potential_file`` of one funcfl file per species),
+      ``eam/alloy`` / ``eam/fs`` (setfl / Finnis-Sinclair file, elements = ``atoms``), ``sw`` (Stillinger-Weber file) or ``kim <model>`` with a built-in SW
       model (``sw.MODELS``: the Si(111) 5x5 tutorial's ``SW_StillingerWeber_1985_Si__MO_405512056662_005``; no
       ``potential_file`` needed, the species come from ``atoms``) are evaluated on the device, anything else raises.  For the SW
       styles the energy template's ``boundary`` applies (``p`` periodic; ``f``, ``s``, ``m`` open) and pe/atom follows LAMMPS
@@ -1286,6 +1410,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self.boundary = None          # SW styles: the energy template's boundary as pbc flags
         self.relax_refused = None     # SW styles: the opt template's potential when the backend lacks it
         self.kim_model = None
+        self.tables = None            # EAM with several elements (eam/alloy, eam/fs, funcfl files per species)
         self._cfg_key = None
         self._init_common(device, True, logger)
         self.run_dir = os.getcwd()        # the reference's default (calculators.py:502)
@@ -1366,8 +1491,10 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             self._configure_sw(cfg_path, cfg, tmpls, args, src)
             return
         style = args[0]
-        pot = self._find_potential(cfg["potential_file"], run_dir)
-        key = (cfg_path, os.path.getmtime(cfg_path), pot, style)
+        pf = cfg["potential_file"]
+        pots = [self._find_potential(x, run_dir) for x in (pf if isinstance(pf, (list, tuple)) else [pf])]
+        pot = pots[0]
+        key = (cfg_path, os.path.getmtime(cfg_path), tuple(pots), style)
         if key == self._cfg_key:
             return
         self.species = list(cfg["atoms"])
@@ -1375,20 +1502,43 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self.pair_style = style
         self.boundary = None
         self.relax_refused = None
+        self.tables = None
+        if len(pots) > 1 and style != "eam":
+            raise ValueError(f"pair_style {style}: lammps_config.json lists {len(pots)} potential files, the style reads one")
         with open(pot, encoding="utf-8") as fh:
             text = fh.read()
         if style == "tersoff":
             self.params = tersoff_io.parse_tersoff(text, self.species)
             self.funcfl = None
-        elif style == "eam":
+        elif style == "eam" and len(pots) == 1:
             from . import eam as eam_io
 
             self.funcfl = eam_io.parse_funcfl(text)
             self.params = None
             if self.species != [structures.SYMBOLS[self.funcfl.atomic_number]]:
                 raise ValueError(f"pair_style eam (funcfl) holds one element, lammps_config.json lists {self.species}")
+        elif style == "eam":   # one funcfl file per species (pair_coeff t t file_t), mixed on one grid
+            from . import eam as eam_io
+
+            if len(pots) != len(self.species):
+                raise ValueError(f"pair_style eam: {len(pots)} funcfl files for the species {self.species}")
+            files = []
+            for name, sym in zip(pots, self.species):
+                with open(name, encoding="utf-8") as fh:
+                    f = eam_io.parse_funcfl(fh.read())
+                if structures.SYMBOLS[f.atomic_number] != sym:
+                    raise ValueError(f"pair_style eam: {name} holds {structures.SYMBOLS[f.atomic_number]}, not {sym}")
+                files.append(f)
+            self.tables = eam_io.tables_from_funcfl(files)
+            self.funcfl = self.params = None
+        elif style in ("eam/alloy", "eam/fs"):
+            from . import eam as eam_io
+
+            self.tables = eam_io.tables_from_setfl(eam_io.parse_setfl(text, fs=style == "eam/fs"), self.species)
+            self.funcfl = self.params = None
         else:
-            raise backend.BackendError(f"pair_style {style!r} is not provided by this backend (tersoff, eam and sw are)")
+            raise backend.BackendError(f"pair_style {style!r} is not provided by this backend "
+                                       "(tersoff, eam, eam/alloy, eam/fs and sw are)")
         if self._engine is not None:
             self._engine.close()
             self._engine = None
@@ -1419,7 +1569,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             if not (opt_args[0] == "kim" and len(opt_args) > 1 and sw_io.is_builtin(opt_args[1])):
                 refused = name
         self.params = sw_io.parse_sw(text, species)
-        self.funcfl = None
+        self.funcfl = self.tables = None
         self.species = species
         self.bulk_index = int(cfg.get("bulk_index", 0))
         self.pair_style = src[0]
@@ -1448,7 +1598,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             return backend.SWEngine(self.params, device=_device_index(self.device))
         if self.pair_style == "tersoff":
             return backend.TersoffEngine(self.params, device=_device_index(self.device))
-        return backend.EAMEngine(self.funcfl, device=_device_index(self.device))
+        return backend.EAMEngine(self.funcfl if self.tables is None else self.tables, device=_device_index(self.device))
 
     def _get_engine(self):
         self._configure()

@@ -137,6 +137,95 @@ void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1
     }
 }
 
+// ---- several elements (pair_style eam/alloy, eam/fs, funcfl files mixed per type) ----------------------------------------------
+// Tables (vssr_eam_create_alloy): F_t [n][nrho + 1][7] | rho [n or n * n][nr + 1][7] | r phi [n (n + 1) / 2][nr + 1][7].
+// rho index of the density an atom of type a contributes at a site of type b: a (alloy) or a * n + b (fs); r phi of the pair
+// (a, b) at max(a,b) (max(a,b) + 1) / 2 + min(a,b).  The element of a neighbour comes from the resident type array.
+struct EamTyped {
+    const double *frho, *rhor, *z2r;
+    int n, fs;
+    size_t sF, sR;   // doubles per F row set / per r-table
+    __device__ const double *rho_tab(int from, int at) const { return rhor + sR * (size_t)(fs ? from * n + at : from); }
+    __device__ const double *z2r_tab(int a, int b) const {
+        const int hi = max(a, b), lo = min(a, b);
+        return z2r + sR * (size_t)(hi * (hi + 1) / 2 + lo);
+    }
+};
+
+__global__ void k_eam_density_typed(int N, vssr_eam_grid g, EamTyped T, const int *__restrict__ type,
+                                    const int *__restrict__ atom_cfg, const double *__restrict__ cell,
+                                    const double *__restrict__ wpos, const int *__restrict__ row_start,
+                                    const float4 *__restrict__ edge, const int *__restrict__ edge_S,
+                                    const int *__restrict__ counters, double *__restrict__ e_embed, double *__restrict__ fp,
+                                    ActiveView av) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N || counters[2] || !av.atom(i)) return;
+    const double *C = cell + 9 * atom_cfg[i];
+    const int ti = type[i];
+    double rho = 0.0;
+    for (int e = row_start[i]; e < row_start[i + 1]; ++e) {
+        const int j = __float_as_int(edge[e].w);
+        if (j < 0) continue;
+        double r[3];
+        eam_edge(wpos, C, i, j, edge_S[e], r);
+        const double d = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        if (d >= g.cutoff) continue;
+        double v, dv;
+        eam_eval(T.rho_tab(type[j], ti), g.nr, d, 1.0 / g.dr, false, v, dv);
+        rho += v;
+    }
+    double F, dF;
+    eam_eval(T.frho + T.sF * ti, g.nrho, rho, 1.0 / g.drho, true, F, dF);
+    const double rhomax = (g.nrho - 1) * g.drho;
+    if (rho > rhomax) F += dF * (rho - rhomax);
+    e_embed[i] = F;
+    fp[i] = dF;
+}
+
+__global__ void k_eam_force_typed(int N, vssr_eam_grid g, EamTyped T, const int *__restrict__ type,
+                                  const int *__restrict__ atom_cfg, const double *__restrict__ cell,
+                                  const double *__restrict__ wpos, const int *__restrict__ row_start,
+                                  const float4 *__restrict__ edge, const int *__restrict__ edge_S,
+                                  const int *__restrict__ counters, const double *__restrict__ e_embed,
+                                  const double *__restrict__ fp, double *__restrict__ e_atom, double *__restrict__ forces,
+                                  ActiveView av) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N || counters[2] || !av.atom(i)) return;
+    const double *C = cell + 9 * atom_cfg[i];
+    const int ti = type[i];
+    const double fpi = fp[i];
+    double ea = e_embed[i], f0 = 0.0, f1 = 0.0, f2 = 0.0;
+    for (int e = row_start[i]; e < row_start[i + 1]; ++e) {
+        const int j = __float_as_int(edge[e].w);
+        if (j < 0) continue;
+        double r[3];
+        eam_edge(wpos, C, i, j, edge_S[e], r);
+        const double d = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        if (d >= g.cutoff) continue;
+        const int tj = type[j];
+        double rh, drh_ji, z, dz;
+        eam_eval(T.rho_tab(tj, ti), g.nr, d, 1.0 / g.dr, false, rh, drh_ji);   // rho of j at i
+        eam_eval(T.z2r_tab(ti, tj), g.nr, d, 1.0 / g.dr, false, z, dz);
+        double dE;
+        if (ti == tj) {   // one density table serves both directions
+            dE = (fpi + fp[j]) * drh_ji;
+        } else {
+            double rh2, drh_ij;
+            eam_eval(T.rho_tab(ti, tj), g.nr, d, 1.0 / g.dr, false, rh2, drh_ij);   // rho of i at j
+            dE = fpi * drh_ji + fp[j] * drh_ij;
+        }
+        const double recip = 1.0 / d;
+        const double phi = z * recip;
+        const double phip = dz * recip - phi * recip;
+        const double psip = dE + phip;
+        ea += 0.5 * phi;
+        const double s = psip * recip;
+        f0 += s * r[0]; f1 += s * r[1]; f2 += s * r[2];
+    }
+    e_atom[i] = ea;
+    forces[3 * i] = f0; forces[3 * i + 1] = f1; forces[3 * i + 2] = f2;
+}
+
 int eam_run(vssr_handle *h, uint32_t want) {
     (void)want;
     const int N = h->n_atoms;
@@ -153,6 +242,24 @@ int eam_run(vssr_handle *h, uint32_t want) {
     h->prof.begin(KC_TERSOFF, st);
     dim3 blk(64), grd((N + 63) / 64);
     const ActiveView av{h->active_mask, h->d_atom_cfg.as<int>()};
+    if (h->eam_nel > 0) {
+        const int n = h->eam_nel;
+        const EamTyped T{frho, frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n,
+                         frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n + 7 * (size_t)(h->eam_grid.nr + 1) * (h->eam_fs ? n * n : n),
+                         n, h->eam_fs, 7 * (size_t)(h->eam_grid.nrho + 1), 7 * (size_t)(h->eam_grid.nr + 1)};
+        hipLaunchKernelGGL(k_eam_density_typed, grd, blk, 0, st, N, h->eam_grid, T, h->d_Z.as<int>(), h->d_atom_cfg.as<int>(),
+                           h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
+                           h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, av);
+        hipLaunchKernelGGL(k_eam_force_typed, grd, blk, 0, st, N, h->eam_grid, T, h->d_Z.as<int>(), h->d_atom_cfg.as<int>(),
+                           h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
+                           h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, h->d_ters_ea.as<double>(),
+                           h->d_ters_f.as<double>(), av);
+        hipLaunchKernelGGL(k_eam_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(),
+                           h->d_ters_ea.as<double>(), h->d_ters_e.as<double>(), h->active_mask);
+        h->prof.end(st);
+        VSSR_HIP(h, hipGetLastError());
+        return VSSR_OK;
+    }
     hipLaunchKernelGGL(k_eam_density, grd, blk, 0, st, N, h->eam_grid, frho, rhor, h->d_atom_cfg.as<int>(),
                        h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
                        h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, av);

@@ -480,6 +480,53 @@ int vssr_eam_create(int32_t device, const vssr_eam_grid *grid, const double *frh
     return VSSR_OK;
 }
 
+int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
+                          const double *rhor, const double *z2r, vssr_handle **out) {
+    if (!grid || !frho || !rhor || !z2r || !out) return set_err(nullptr, VSSR_E_BADARG, "null EAM argument");
+    *out = nullptr;
+    if (n_elem < 1 || n_elem > 8) return set_err(nullptr, VSSR_E_BADARG, "EAM: %d elements (1 .. 8 are supported)", n_elem);
+    if (grid->nrho < 5 || grid->nr < 5 || !(grid->drho > 0) || !(grid->dr > 0) || !(grid->cutoff > 0) ||
+        !std::isfinite(grid->drho) || !std::isfinite(grid->dr) || !std::isfinite(grid->cutoff))
+        return set_err(nullptr, VSSR_E_BADARG, "bad EAM grid");
+    const int nR = fs ? n_elem * n_elem : n_elem, nP = n_elem * (n_elem + 1) / 2;
+    const size_t cF = (size_t)n_elem * grid->nrho, cR = (size_t)nR * grid->nr, cP = (size_t)nP * grid->nr;
+    for (size_t k = 0; k < cF; ++k)
+        if (!std::isfinite(frho[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (F)");
+    for (size_t k = 0; k < cR; ++k)
+        if (!std::isfinite(rhor[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (rho)");
+    for (size_t k = 0; k < cP; ++k)
+        if (!std::isfinite(z2r[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (r phi)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return set_err(nullptr, VSSR_E_DEVICE, "no HIP device available (this backend has no CPU fallback)");
+    if (device < 0 || device >= ndev) return set_err(nullptr, VSSR_E_BADARG, "device %d out of range", device);
+    vssr_handle *h = new vssr_handle();
+    h->kind = 3;
+    h->n_types = n_elem;
+    h->n_embed = n_elem;   // vssr_batch_upload refuses types outside [0, n_elem)
+    h->eam_nel = n_elem;
+    h->eam_fs = fs ? 1 : 0;
+    h->eam_grid = *grid;
+    int rc = common_init(h, device);
+    // spline tables (eam.hip EamTyped): F [n][nrho + 1][7] | rho [nR][nr + 1][7] | r phi [nP][nr + 1][7]
+    const size_t sF = 7 * (size_t)(grid->nrho + 1), sR = 7 * (size_t)(grid->nr + 1);
+    std::vector<double> tab(sF * n_elem + sR * (nR + nP));
+    for (int t = 0; t < n_elem; ++t) eam_build_spline(frho + (size_t)t * grid->nrho, grid->nrho, grid->drho, tab.data() + sF * t);
+    double *R = tab.data() + sF * n_elem;
+    for (int t = 0; t < nR; ++t) eam_build_spline(rhor + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * t);
+    for (int t = 0; t < nP; ++t) eam_build_spline(z2r + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * (nR + t));
+    if (!rc && h->ters_params.ensure(sizeof(double) * tab.size())) rc = set_err(h, VSSR_E_NOMEM, "EAM tables");
+    if (!rc && hipMemcpy(h->ters_params.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess)
+        rc = set_err(h, VSSR_E_DEVICE, "EAM table upload failed");
+    if (rc) {
+        g_create_error = h->err;
+        vssr_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return VSSR_OK;
+}
+
 void vssr_destroy(vssr_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);

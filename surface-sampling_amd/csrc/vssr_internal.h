@@ -234,6 +234,7 @@ struct Profiler {
 struct vssr_handle {
     int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber, 5 = Gaussian mixture (gmm.hip)
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in ters_params
+    int eam_nel = 0, eam_fs = 0;   // EAM with typed tables (vssr_eam_create_alloy): elements, 1 = eam/fs densities; 0 = one funcfl
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

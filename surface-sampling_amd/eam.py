@@ -1,10 +1,14 @@
-"""LAMMPS ``pair_style eam`` potential files in *funcfl* format (host side, data format only).
+"""LAMMPS ``pair_style eam`` / ``eam/alloy`` / ``eam/fs`` potential files (host side, data formats only).
 
 The reference hands ``mcmc/potentials/Cu_u3.eam`` to LAMMPS through ``LAMMPSRunSurfCalc.set(pair_style="eam",
 pair_coeff=["* * Cu_u3.eam"])`` (``tests/test_Cu.py:41,65-70``, ``tutorials/example.ipynb`` cell 3).  Layout of a funcfl
 file: line 1 comment; line 2 ``Z mass lattice-constant lattice-type``; line 3 ``Nrho drho Nr dr cutoff``; then ``Nrho``
 values of the embedding energy F(rho) [eV], ``Nr`` values of the effective charge Z(r) [sqrt(Hartree Bohr)] and ``Nr``
 values of the electron density rho(r), free format.
+
+Several elements (``setfl``, ``eam/alloy``; ``eam/fs``; funcfl files mixed per type as LAMMPS ``pair_coeff i i file``) end in one
+:class:`EamTables`: the typed arrays of ``vssr_eam_create_alloy`` on one common grid (restated from LAMMPS ``pair_eam.cpp``,
+``pair_eam_alloy.cpp``, ``pair_eam_fs.cpp`` ``read_file`` / ``file2array``).
 """
 
 from __future__ import annotations
@@ -53,3 +57,251 @@ def parse_funcfl(text: str) -> Funcfl:
 def read_funcfl(path) -> Funcfl:
     with open(path) as fh:
         return parse_funcfl(fh.read())
+
+
+# ---- several elements -------------------------------------------------------------------------------------------------------
+HARTREE_BOHR = 27.2 * 0.529   # funcfl Z(r) Z(r) -> r * phi in eV A (pair_eam.cpp)
+
+
+@dataclasses.dataclass
+class Setfl:
+    """A setfl file (``eam/alloy``) or its Finnis-Sinclair variant (``fs=True``).  ``rhor``: [N][Nr] (alloy) or [N][N][Nr]
+    (fs: block I, entry J = the density an atom of element I contributes at a site of element J); ``z2r``: [N (N + 1) / 2][Nr]
+    r * phi in eV A of the pairs (1,1), (2,1), (2,2), (3,1), ... (lower triangle, file order)."""
+    elements: list
+    atomic_numbers: list
+    masses: list
+    lattice_constants: list
+    lattices: list
+    nrho: int
+    drho: float
+    nr: int
+    dr: float
+    cutoff: float
+    frho: np.ndarray
+    rhor: np.ndarray
+    z2r: np.ndarray
+    fs: bool = False
+    comments: tuple = ("", "", "")
+
+
+@dataclasses.dataclass
+class EamTables:
+    """What the device evaluates: one grid and per-TYPE tables (LAMMPS type order).  ``frho`` [n][nrho]; ``rhor`` [n][nr]
+    (alloy) or [n * n][nr] (fs: row a * n + b = density of type a at a site of type b); ``z2r`` [n (n + 1) / 2][nr] (r * phi,
+    pair (a, b) at max(a,b) (max(a,b) + 1) / 2 + min(a,b)); ``elements``: element symbol of every type."""
+    elements: list
+    fs: bool
+    nrho: int
+    drho: float
+    nr: int
+    dr: float
+    cutoff: float
+    frho: np.ndarray
+    rhor: np.ndarray
+    z2r: np.ndarray
+
+
+def pair_index(a: int, b: int) -> int:
+    hi, lo = max(a, b), min(a, b)
+    return hi * (hi + 1) // 2 + lo
+
+
+class _Lines:
+    """LAMMPS PotentialFileReader: header lines are read whole, tables fill from as many lines as they need (values left over
+    on a table's last line are dropped, as there)."""
+
+    def __init__(self, text, what):
+        self.lines = text.splitlines()
+        self.k = 0
+        self.what = what
+
+    def line(self):
+        while self.k < len(self.lines):
+            ln = self.lines[self.k]
+            self.k += 1
+            if ln.strip():
+                return ln.split()
+        raise ValueError(f"{self.what}: file ends early")
+
+    def values(self, n):
+        out = []
+        while len(out) < n:
+            out.extend(self.line()[:n - len(out)])
+        try:
+            v = np.array(out, dtype=np.float64)
+        except ValueError:
+            raise ValueError(f"{self.what}: bad number in a table") from None
+        if not np.isfinite(v).all():
+            raise ValueError(f"{self.what}: non-finite table value")
+        return v
+
+
+def parse_setfl(text: str, fs: bool = False) -> Setfl:
+    what = "eam/fs file" if fs else "setfl file"
+    rd = _Lines(text, what)
+    lines = text.splitlines()
+    if len(lines) < 5:
+        raise ValueError(f"{what}: too short")
+    comments = tuple(ln.rstrip("\n") for ln in lines[:3])
+    rd.k = 3
+    head = rd.line()
+    try:
+        n = int(head[0])
+    except ValueError:
+        raise ValueError(f"{what}: line 4 must be 'N el1 ... elN'") from None
+    if n < 1 or len(head) != n + 1:
+        raise ValueError(f"{what}: line 4 announces {head[0]} elements and lists {len(head) - 1}")
+    elements = head[1:]
+    grid = rd.line()
+    if len(grid) < 5:
+        raise ValueError(f"{what}: malformed grid line")
+    try:
+        nrho, drho, nr, dr, cutoff = int(grid[0]), float(grid[1]), int(grid[2]), float(grid[3]), float(grid[4])
+    except ValueError:
+        raise ValueError(f"{what}: malformed grid line") from None
+    if nrho < 5 or nr < 5 or not (np.isfinite([drho, dr, cutoff]).all() and drho > 0 and dr > 0 and cutoff > 0):
+        raise ValueError(f"{what}: bad grid")
+    zs, masses, lats, ltypes = [], [], [], []
+    frho = np.zeros((n, nrho))
+    rhor = np.zeros((n, n, nr) if fs else (n, nr))
+    for i in range(n):
+        h = rd.line()
+        if len(h) < 2:
+            raise ValueError(f"{what}: malformed header of element {elements[i]}")
+        try:
+            zs.append(int(float(h[0])))
+            masses.append(float(h[1]))
+            lats.append(float(h[2]) if len(h) > 2 else 0.0)
+        except ValueError:
+            raise ValueError(f"{what}: malformed header of element {elements[i]}") from None
+        ltypes.append(h[3] if len(h) > 3 else "")
+        frho[i] = rd.values(nrho)
+        if fs:
+            for j in range(n):
+                rhor[i, j] = rd.values(nr)
+        else:
+            rhor[i] = rd.values(nr)
+    z2r = np.zeros((n * (n + 1) // 2, nr))
+    for p in range(len(z2r)):
+        z2r[p] = rd.values(nr)
+    return Setfl(list(elements), zs, masses, lats, ltypes, nrho, drho, nr, dr, cutoff, frho, rhor, z2r, bool(fs), comments)
+
+
+def read_setfl(path, fs: bool = False) -> Setfl:
+    with open(path) as fh:
+        return parse_setfl(fh.read(), fs=fs)
+
+
+def write_setfl(setfl: Setfl, path=None) -> str:
+    """The text of ``setfl`` (values as ``%.16e``, five per line, so that parse_setfl gives back the same doubles); also
+    written to ``path`` when given."""
+    def table(v):
+        v = np.asarray(v, np.float64).reshape(-1)
+        return ["".join(f" {x:.16e}" for x in v[k:k + 5]).strip() for k in range(0, len(v), 5)]
+
+    n = len(setfl.elements)
+    out = [str(c) for c in (list(setfl.comments) + ["", "", ""])[:3]]
+    out.append(" ".join([str(n), *setfl.elements]))
+    out.append(f"{setfl.nrho} {setfl.drho:.16e} {setfl.nr} {setfl.dr:.16e} {setfl.cutoff:.16e}")
+    for i in range(n):
+        lt = setfl.lattices[i] if setfl.lattices[i] else "fcc"
+        out.append(f"{setfl.atomic_numbers[i]} {setfl.masses[i]:.16e} {setfl.lattice_constants[i]:.16e} {lt}")
+        out += table(setfl.frho[i])
+        if setfl.fs:
+            for j in range(n):
+                out += table(setfl.rhor[i][j])
+        else:
+            out += table(setfl.rhor[i])
+    for p in range(len(setfl.z2r)):
+        out += table(setfl.z2r[p])
+    text = "\n".join(out) + "\n"
+    if path is not None:
+        with open(path, "w") as fh:
+            fh.write(text)
+    return text
+
+
+def funcfl_to_setfl(f: Funcfl, element: str | None = None) -> Setfl:
+    """One funcfl file as a one-element setfl on the file's own grid: F and rho as they are, r * phi = 27.2 * 0.529 * Z^2."""
+    from .structures import SYMBOLS
+
+    el = element or SYMBOLS[f.atomic_number]
+    return Setfl([el], [f.atomic_number], [f.mass], [f.lattice_constant], [f.lattice or "fcc"], f.nrho, f.drho, f.nr, f.dr,
+                 f.cutoff, f.frho[None, :].copy(), f.rhor[None, :].copy(), (HARTREE_BOHR * f.zr ** 2)[None, :],
+                 False, (f.comment, "converted from funcfl", ""))
+
+
+def _check_names(names, what):
+    if not names:
+        raise ValueError(f"{what}: pair_coeff names no element")
+    if len(names) > 8:
+        raise ValueError(f"{what}: {len(names)} types (at most 8 are supported)")
+    if any(str(x).upper() == "NULL" for x in names):
+        raise ValueError(f"{what}: NULL types (pair_style hybrid) are not supported")
+
+
+def tables_from_setfl(setfl: Setfl, elements) -> EamTables:
+    """LAMMPS ``pair_coeff * * file el_1 ... el_n``: type t is element ``elements[t]`` of the file."""
+    names = [str(x) for x in elements]
+    what = "eam/fs" if setfl.fs else "eam/alloy"
+    _check_names(names, what)
+    idx = []
+    for x in names:
+        if x not in setfl.elements:
+            raise ValueError(f"{what}: element {x!r} is not in the potential file (it has {setfl.elements})")
+        idx.append(setfl.elements.index(x))
+    n = len(idx)
+    frho = np.stack([setfl.frho[a] for a in idx])
+    if setfl.fs:
+        rhor = np.stack([setfl.rhor[a][b] for a in idx for b in idx])
+    else:
+        rhor = np.stack([setfl.rhor[a] for a in idx])
+    z2r = np.stack([setfl.z2r[pair_index(idx[a], idx[b])] for a in range(n) for b in range(a + 1)])
+    return EamTables(names, setfl.fs, setfl.nrho, setfl.drho, setfl.nr, setfl.dr, setfl.cutoff, frho, rhor, z2r)
+
+
+def _lagrange(f, delta_file, n_file, x):
+    """LAMMPS file2array's 4-point Lagrange resampling of a 1-based table f[1..n_file] (numpy f[0..n_file-1]) at x."""
+    p = np.asarray(x, np.float64) / delta_file + 1.0
+    k = p.astype(np.int64)
+    k = np.maximum(np.minimum(k, n_file - 2), 2)
+    p = np.minimum(p - k, 2.0)
+    sixth = 1.0 / 6.0
+    c1 = -sixth * p * (p - 1.0) * (p - 2.0)
+    c2 = 0.5 * (p * p - 1.0) * (p - 2.0)
+    c3 = -0.5 * p * (p + 1.0) * (p - 2.0)
+    c4 = sixth * p * (p * p - 1.0)
+    f = np.asarray(f, np.float64)
+    return c1 * f[k - 2] + c2 * f[k - 1] + c3 * f[k] + c4 * f[k + 1]
+
+
+def tables_from_funcfl(files) -> EamTables:
+    """LAMMPS ``pair_style eam`` with ``pair_coeff t t file_t`` for every type t (``files``: one :class:`Funcfl` per type):
+    ``file2array`` for several files -- the largest dr / drho and r / rho ranges, every table resampled onto that grid with the
+    4-point Lagrange formula, r * phi_ab = 27.2 * 0.529 Z_a(r) Z_b(r), cutoff = the largest file cutoff.  The element of a type
+    is its file's atomic number."""
+    from .structures import SYMBOLS
+
+    files = list(files)
+    if not files:
+        raise ValueError("eam: no funcfl file")
+    if len(files) > 8:
+        raise ValueError(f"eam: {len(files)} types (at most 8 are supported)")
+    dr = max(f.dr for f in files)
+    drho = max(f.drho for f in files)
+    rmax = max((f.nr - 1) * f.dr for f in files)
+    rhomax = max((f.nrho - 1) * f.drho for f in files)
+    nr = int(rmax / dr + 0.5)
+    nrho = int(rhomax / drho + 0.5)
+    if nr < 5 or nrho < 5:
+        raise ValueError("eam: common grid too small")
+    r = np.arange(nr) * dr
+    rho = np.arange(nrho) * drho
+    frho = np.stack([_lagrange(f.frho, f.drho, f.nrho, rho) for f in files])
+    rhor = np.stack([_lagrange(f.rhor, f.dr, f.nr, r) for f in files])
+    zr = [_lagrange(f.zr, f.dr, f.nr, r) for f in files]
+    n = len(files)
+    z2r = np.stack([HARTREE_BOHR * zr[a] * zr[b] for a in range(n) for b in range(a + 1)])
+    return EamTables([SYMBOLS[f.atomic_number] for f in files], False, nrho, drho, nr, dr, max(f.cutoff for f in files),
+                     frho, rhor, z2r)
