@@ -25,6 +25,7 @@
  *   vssr_gmm_create / vssr_gmm_score_rows / vssr_gmm_score_batch
  *                                   <- GMMUncertainty.estimate_log_prob / negative_log_likelihood
  *                                      (mcmc/uncertainty/uncertainty.py:238-463)
+ *   vssr_gmm_fit_*                  <- gmm.GaussianMixture.fit / GMMUncertainty.fit_gmm (EM on the device)
  *
  * Conventions
  *   - All arrays are caller-allocated and borrowed only for the duration of the call.
@@ -392,6 +393,80 @@ int vssr_gmm_score_rows(vssr_handle *g, int64_t n_rows, const double *x, double 
  * after a relaxation); VSSR_E_BADARG when D != feat_dim or the handles live on different devices. */
 int vssr_gmm_score_batch(vssr_handle *g, vssr_handle *painn, int32_t model, int32_t rows, int32_t order, double *nll_rows,
                          double *system);
+
+/* ---- Fitting the Gaussian mixture on the device (fp64 EM; reference mcmc.uncertainty.gmm.GaussianMixture, a copy of sklearn's with a
+ *      blocked matrix product; GMMUncertainty.fit_gmm, mcmc/uncertainty/uncertainty.py:295-315) ------------------------------------ */
+/* Rows x_n [D] (fp64, resident on the device as [N][Dp], Dp = 16 ceil(D / 16), zero pad columns).  One EM iteration:
+ *   E:  logp_nk and NLL_n as vssr_gmm_score_rows with the fp64 constant log 2 pi;  r_nk = exp(logp_nk + log w_k + NLL_n);
+ *       lower bound = mean_n(-NLL_n), reduced in a fixed order (per-workgroup partials, then one tree)
+ *   M:  n_k = sum_n r_nk + 10 eps;  mu_k = sum_n r_nk x_n / n_k;  w_k = n_k / sum_k n_k
+ *       full:       S_k = sum_n r_nk (x_n - mu_k)(x_n - mu_k)^T / n_k + reg_covar I   (centred form, v_mfma_f64_16x16x4_f64, row slabs
+ *                   summed in slab order)
+ *       tied:       S = (X^T X - sum_k n_k mu_k mu_k^T) / sum_k n_k + reg_covar I
+ *       diag:       s_kd = sum_n r_nk x_nd^2 / n_k - 2 mu_kd mu_kd + mu_kd^2 + reg_covar;   spherical: mean_d s_kd
+ *       P_k = (chol(S_k)^-1)^T (diag / spherical: 1 / sqrt(s)), log det P_k, c_k = mu_k P_k, written into the scoring layout
+ *   stop when |lower bound - previous| < tol, or after max_iter iterations; n_init restarts keep the best final lower bound.
+ * No floating-point atomics: two runs of the same fit on the same rows give the same bits. */
+enum { VSSR_GMM_COV_FULL = 0, VSSR_GMM_COV_TIED = 1, VSSR_GMM_COV_DIAG = 2, VSSR_GMM_COV_SPHERICAL = 3 };
+/* GIVEN: the start comes from vssr_gmm_fit_set_init (all of means / weights / precisions, or labels, or both: explicit values win as in
+ * sklearn's _initialize).  KMEANS: Lloyd iterations on the device from K distinct rows drawn with Philox4x32-10 keyed by `seed`;
+ * RANDOM_FROM_DATA: K distinct rows drawn the same way get responsibility 1 for one component each.  The draws do not reproduce numpy's
+ * streams.  Explicit values from set_init override what either produces. */
+enum { VSSR_GMM_INIT_GIVEN = 0, VSSR_GMM_INIT_KMEANS = 1, VSSR_GMM_INIT_RANDOM_FROM_DATA = 2 };
+typedef struct {
+    uint32_t struct_size;    /* sizeof(vssr_gmm_fit_config) */
+    int32_t device;          /* HIP device ordinal; the device is first touched by the first append / run */
+    int32_t n_components;    /* K, 1 .. 256 */
+    int32_t dim;             /* D, 1 .. 256 */
+    int32_t covariance_type; /* VSSR_GMM_COV_* */
+    int32_t max_iter;        /* >= 1 */
+    int32_t n_init;          /* >= 1 */
+    int32_t init;            /* VSSR_GMM_INIT_* */
+    double tol;              /* >= 0 */
+    double reg_covar;        /* >= 0 */
+    uint64_t seed;
+} vssr_gmm_fit_config;
+typedef struct {
+    int32_t n_iter;          /* iterations of the best restart */
+    int32_t converged;       /* 1 = that restart stopped on tol */
+    int32_t best_init;       /* index of the best restart */
+    int32_t n_lower_bounds;  /* entries written to lower_bounds (min(n_iter, lower_bounds_cap)) */
+    double lower_bound;      /* lower bound of the last iteration of the best restart */
+    double *lower_bounds;    /* caller buffer [lower_bounds_cap] for that restart's trace; may be NULL */
+    int32_t lower_bounds_cap;
+} vssr_gmm_fit_result;
+/* Handle kind 6 (freed by vssr_destroy); every entry point other than vssr_gmm_fit_*, vssr_destroy and vssr_last_error refuses it.
+ * Refused with VSSR_E_BADARG without touching a device: K or D outside 1 .. 256, an unknown covariance type or init, tol < 0,
+ * reg_covar < 0, max_iter < 1, n_init < 1, non-finite tol / reg_covar. */
+int vssr_gmm_fit_create(const vssr_gmm_fit_config *cfg, vssr_handle **out);
+/* Append caller rows x [n_rows][D] (fp64) to the resident set.  VSSR_E_BADARG (before a device is touched) for a null pointer,
+ * n_rows < 1 or a non-finite entry; VSSR_E_DEVICE when no device is available. */
+int vssr_gmm_fit_append_rows(vssr_handle *h, int64_t n_rows, const double *x);
+/* Append the resident embedding of a PaiNN handle's last run (ensemble member `model`), device to device, widened to fp64.
+ * rows: 0 = one row per atom, 1 = one mean row per structure.  Errors as vssr_gmm_score_batch: VSSR_E_STATE without a completed run
+ * (or with a partial graph), VSSR_E_BADARG when D != feat_dim, the devices differ, or a row is not finite. */
+int vssr_gmm_fit_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model, int32_t rows);
+/* Drop the resident rows and the labels given to set_init (explicit parameters are kept). */
+int vssr_gmm_fit_clear(vssr_handle *h);
+/* Starting values; every pointer may be NULL (= not given; a call replaces all four).  means [K][D]; weights [K] (finite, >= 0, one positive; that
+ * they sum to 1 is the caller's check); precisions in sklearn's shape for the
+ * covariance type (full [K][D][D], tied [D][D], diag [K][D], spherical [K]) -- PRECISION matrices, factorised here with a lower
+ * Cholesky as gmm.py:657-664 does; labels [N] in -1 .. K-1 for the N rows resident at the time of the call (one-hot
+ * responsibilities, -1 = no component; what sklearn does with its k-means result).  VSSR_E_BADARG for non-finite values, a precision
+ * that is not positive definite, or a label out of range. */
+int vssr_gmm_fit_set_init(vssr_handle *h, const double *means, const double *weights, const double *precisions,
+                          const int32_t *labels);
+/* Run the fit (sklearn's BaseMixture.fit loop).  VSSR_E_BADARG (no device touched) when N < 2, K > N, or the start is
+ * incomplete (INIT_GIVEN without labels and without all three parameter arrays; labels of another length).  VSSR_E_STATE with the
+ * reference's "ill-defined empirical covariance" text when a covariance has a non-positive pivot (flag set by the kernel, no device
+ * assert).  One 8-byte read-back per iteration. */
+int vssr_gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res);
+/* Fitted parameters in sklearn's shapes for the handle's covariance type: weights [K], means [K][D], covariances and prec_chol
+ * (full [K][D][D], tied [D][D], diag [K][D], spherical [K]).  Any may be NULL.  VSSR_E_STATE before a successful run. */
+int vssr_gmm_fit_params(vssr_handle *h, double *weights, double *means, double *covariances, double *prec_chol);
+/* A scoring handle (kind 5) of the fitted mixture on the same device, built from the device arrays (no host copy); log_2pi as in
+ * vssr_gmm_config.  VSSR_E_STATE before a successful run. */
+int vssr_gmm_fit_scorer(vssr_handle *h, double log_2pi, vssr_handle **gmm);
 
 #ifdef __cplusplus
 }

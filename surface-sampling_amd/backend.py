@@ -32,6 +32,8 @@ EXPORTS = (
     "vssr_device_context", "vssr_batch_stress", "vssr_batch_energy_f64", "vssr_batch_device_results_f64",
     "vssr_batch_relax_counts", "vssr_sw_create", "vssr_sw_create_from_text", "vssr_sw_eval_batch",
     "vssr_gmm_create", "vssr_gmm_score_rows", "vssr_gmm_score_batch", "vssr_eam_create_alloy",
+    "vssr_gmm_fit_create", "vssr_gmm_fit_append_rows", "vssr_gmm_fit_append_batch", "vssr_gmm_fit_clear",
+    "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
 )
 
 
@@ -93,6 +95,21 @@ class GmmConfig(C.Structure):
                 ("means", C.POINTER(C.c_double)), ("prec_chol", C.POINTER(C.c_double)), ("weights", C.POINTER(C.c_double)),
                 ("log_2pi", C.c_double)]
 
+
+class GmmFitConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_components", C.c_int32), ("dim", C.c_int32),
+                ("covariance_type", C.c_int32), ("max_iter", C.c_int32), ("n_init", C.c_int32), ("init", C.c_int32),
+                ("tol", C.c_double), ("reg_covar", C.c_double), ("seed", C.c_uint64)]
+
+
+class GmmFitResult(C.Structure):
+    _fields_ = [("n_iter", C.c_int32), ("converged", C.c_int32), ("best_init", C.c_int32), ("n_lower_bounds", C.c_int32),
+                ("lower_bound", C.c_double), ("lower_bounds", C.POINTER(C.c_double)), ("lower_bounds_cap", C.c_int32)]
+
+
+GMM_COV_TYPES = {"full": 0, "tied": 1, "diag": 2, "spherical": 3}
+GMM_INITS = {"given": 0, "kmeans": 1, "random_from_data": 2}
+GMM_ILL_DEFINED = "ill-defined empirical covariance"   # (in the message of the reference's ValueError)
 
 # order / rows codes of vssr_gmm_score_batch
 GMM_ORDERS = {"atomic": 0, "system_sum": 1, "system_mean": 2, "system_max": 3, "system_min": 4, "system_mean_squared": 5,
@@ -230,6 +247,22 @@ def load_library():
     L.vssr_gmm_score_rows.argtypes = [vp, C.c_int64, dp, dp, dp]
     L.vssr_gmm_score_batch.restype = C.c_int
     L.vssr_gmm_score_batch.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
+    L.vssr_gmm_fit_create.restype = C.c_int
+    L.vssr_gmm_fit_create.argtypes = [C.POINTER(GmmFitConfig), C.POINTER(vp)]
+    L.vssr_gmm_fit_append_rows.restype = C.c_int
+    L.vssr_gmm_fit_append_rows.argtypes = [vp, C.c_int64, dp]
+    L.vssr_gmm_fit_append_batch.restype = C.c_int
+    L.vssr_gmm_fit_append_batch.argtypes = [vp, vp, C.c_int32, C.c_int32]
+    L.vssr_gmm_fit_clear.restype = C.c_int
+    L.vssr_gmm_fit_clear.argtypes = [vp]
+    L.vssr_gmm_fit_set_init.restype = C.c_int
+    L.vssr_gmm_fit_set_init.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.vssr_gmm_fit_run.restype = C.c_int
+    L.vssr_gmm_fit_run.argtypes = [vp, C.POINTER(GmmFitResult)]
+    L.vssr_gmm_fit_params.restype = C.c_int
+    L.vssr_gmm_fit_params.argtypes = [vp, dp, dp, dp, dp]
+    L.vssr_gmm_fit_scorer.restype = C.c_int
+    L.vssr_gmm_fit_scorer.argtypes = [vp, C.c_double, C.POINTER(vp)]
     if L.vssr_abi_version() != 1:
         raise BackendError("libvssr_eval.so ABI version mismatch")
     _lib = L
@@ -347,6 +380,12 @@ class _Handle:
         buf = np.zeros(n.value, np.float32)
         self._check(self._lib.vssr_batch_embedding(self._h, m, _ptr(buf, C.c_float), n.value, C.byref(n)))
         return buf.reshape((self.n_models, self._n_atoms, -1) if model is None else (self._n_atoms, -1))
+
+    def embedding_dim(self):
+        """Feature width F of the resident embedding (needs a completed run, as ``embedding``)."""
+        n = C.c_int64(0)
+        self._check(self._lib.vssr_batch_embedding(self._h, 0, None, 0, C.byref(n)))
+        return int(n.value // max(self._n_atoms, 1))
 
     def saturated(self):
         """bool [B]: chains whose last evaluation left the range of the fp16-split arithmetic (a value beyond +-65504 was
@@ -741,3 +780,112 @@ class GMMEngine(_Handle):
         self._check(self._lib.vssr_gmm_score_batch(self._h, painn_engine._h, int(model), GMM_ROWS[rows], GMM_ORDERS[order],
                                                    _ptr(nll, C.c_double), _ptr(sysv, C.c_double)))
         return nll, sysv
+
+    @classmethod
+    def _adopt(cls, handle, n_components, dim, device):
+        """An engine around a scoring handle the library built itself (vssr_gmm_fit_scorer)."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self)
+        self._h = handle
+        self._means = self._prec = self._weights = None
+        self.n_components, self.dim, self.device = int(n_components), int(dim), int(device)
+        return self
+
+
+def gmm_cov_shape(covariance_type, K, D):
+    """sklearn's shape of covariances_ / precisions_cholesky_ for a covariance type."""
+    return {"full": (K, D, D), "tied": (D, D), "diag": (K, D), "spherical": (K,)}[covariance_type]
+
+
+class GMMFitEngine(_Handle):
+    """Expectation-maximisation fit of a Gaussian mixture on one GPU (vssr_gmm_fit_*, ``csrc/gmm_fit.hip``): fp64 throughout,
+    no floating-point atomics (a fit repeats bit for bit).
+
+    The loop is sklearn's ``BaseMixture.fit`` (``tol`` on the change of the lower bound, ``max_iter``, ``n_init`` restarts keeping
+    the best lower bound).  ``init``: "given" (``set_init``: labels, or means + weights + precisions), "kmeans" (k-means++ seeding
+    and Lloyd iterations on the device) or "random_from_data".  Random draws come from Philox4x32-10 keyed by ``seed``: they
+    do not reproduce numpy's or sklearn's streams.  Rows are appended from the host (``append_rows``) or taken device to device
+    from a ``PainnEngine``'s resident embedding (``append_batch``).  The device is first touched by the first append or fit."""
+
+    def __init__(self, n_components, dim, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1, init="given",
+                 seed=0, device=0):
+        super().__init__()
+        if covariance_type not in GMM_COV_TYPES:
+            raise ValueError(f"covariance_type must be one of {sorted(GMM_COV_TYPES)}, got {covariance_type!r}")
+        if init not in GMM_INITS:
+            raise ValueError(f"init must be one of {sorted(GMM_INITS)}, got {init!r}")
+        cfg = GmmFitConfig(C.sizeof(GmmFitConfig), int(device), int(n_components), int(dim), GMM_COV_TYPES[covariance_type],
+                           int(max_iter), int(n_init), GMM_INITS[init], float(tol), float(reg_covar), int(seed) & (2 ** 64 - 1))
+        rc = self._lib.vssr_gmm_fit_create(C.byref(cfg), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_gmm_fit_create failed ({rc}): {msg.decode() if msg else '?'}")
+        self.n_components, self.dim, self.device = int(n_components), int(dim), int(device)
+        self.covariance_type, self.max_iter = covariance_type, int(max_iter)
+        self.n_rows = 0
+
+    def append_rows(self, x):
+        """Append rows ``x [n, D]`` (any float dtype; kept in fp64 on the device)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}], got {x.shape}")
+        self._check(self._lib.vssr_gmm_fit_append_rows(self._h, x.shape[0], _ptr(x, C.c_double)))
+        self.n_rows += x.shape[0]
+
+    def append_batch(self, painn_engine, model=0, rows="atoms"):
+        """Append the resident embedding of ``painn_engine``'s last run (ensemble member ``model``), device to device:
+        ``rows="atoms"`` one row per atom, ``"mean"`` one mean row per structure."""
+        if rows not in GMM_ROWS:
+            raise ValueError(f"rows must be one of {sorted(GMM_ROWS)}, got {rows!r}")
+        self._check(self._lib.vssr_gmm_fit_append_batch(self._h, painn_engine._h, int(model), GMM_ROWS[rows]))
+        self.n_rows += painn_engine._n_atoms if rows == "atoms" else painn_engine._n_cfg
+
+    def clear(self):
+        self._check(self._lib.vssr_gmm_fit_clear(self._h))
+        self.n_rows = 0
+
+    def set_init(self, means=None, weights=None, precisions=None, labels=None):
+        """Starting values (each optional; a call replaces all four): ``means [K, D]``, ``weights [K]``, ``precisions`` (precision
+        MATRICES in sklearn's shape for the covariance type), ``labels [N]`` in -1 .. K-1 for the resident rows."""
+        K, D = self.n_components, self.dim
+        conv = lambda a, shape: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        m, w = conv(means, (K, D)), conv(weights, (K,))
+        p = conv(precisions, gmm_cov_shape(self.covariance_type, K, D))
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+            if lab.shape[0] != self.n_rows:
+                raise ValueError(f"{lab.shape[0]} labels for {self.n_rows} resident rows")
+        self._check(self._lib.vssr_gmm_fit_set_init(self._h, _ptr(m, C.c_double), _ptr(w, C.c_double), _ptr(p, C.c_double),
+                                                    _ptr(lab, C.c_int32)))
+
+    def fit(self):
+        """Run the fit; returns ``{"n_iter", "converged", "lower_bound", "best_init", "lower_bounds"}``.  A collapsed component
+        raises ``ValueError`` with the reference's message."""
+        trace = np.zeros(self.max_iter, np.float64)
+        res = GmmFitResult(0, 0, 0, 0, 0.0, _ptr(trace, C.c_double), self.max_iter)
+        rc = self._lib.vssr_gmm_fit_run(self._h, C.byref(res))
+        if rc != 0:
+            msg = (self._lib.vssr_last_error(self._h) or b"?").decode()
+            if GMM_ILL_DEFINED in msg:
+                raise ValueError(msg)
+            raise BackendError(f"vssr error {rc}: {msg}")
+        return {"n_iter": int(res.n_iter), "converged": bool(res.converged), "lower_bound": float(res.lower_bound),
+                "best_init": int(res.best_init), "lower_bounds": trace[:res.n_lower_bounds].copy()}
+
+    def params(self):
+        """``{"weights_", "means_", "covariances_", "precisions_cholesky_"}`` in sklearn's shapes."""
+        K, D = self.n_components, self.dim
+        shape = gmm_cov_shape(self.covariance_type, K, D)
+        w, m, cov, pc = np.zeros(K), np.zeros((K, D)), np.zeros(shape), np.zeros(shape)
+        self._check(self._lib.vssr_gmm_fit_params(self._h, _ptr(w, C.c_double), _ptr(m, C.c_double), _ptr(cov, C.c_double),
+                                                  _ptr(pc, C.c_double)))
+        return {"weights_": w, "means_": m, "covariances_": cov, "precisions_cholesky_": pc}
+
+    def scorer(self, log_2pi=1.8378770351409912):
+        """A ``GMMEngine`` of the fitted mixture on the same GPU, built from the device arrays."""
+        h = C.c_void_p(None)
+        self._check(self._lib.vssr_gmm_fit_scorer(self._h, float(log_2pi), C.byref(h)))
+        return GMMEngine._adopt(h, self.n_components, self.dim, self.device)

@@ -272,10 +272,12 @@ static int sync_and_check(vssr_handle *h) {
     return set_err(h, VSSR_E_CAPACITY, "neighbor list capacity could not be satisfied");
 }
 
-// a Gaussian-mixture handle (kind 5) serves vssr_gmm_*, vssr_destroy and vssr_last_error only: every other entry point refuses it
+// a Gaussian-mixture handle (kind 5) serves vssr_gmm_*, vssr_destroy and vssr_last_error only: every other entry point refuses it;
+// likewise a fit handle (kind 6) and vssr_gmm_fit_*
 #define VSSR_REFUSE_GMM(h)                                                                                               \
     do {                                                                                                                 \
         if ((h)->kind == 5) return set_err((h), VSSR_E_BADARG, "%s: a Gaussian-mixture handle serves the vssr_gmm_* calls only", __func__); \
+        if ((h)->kind == 6) return set_err((h), VSSR_E_BADARG, "%s: a Gaussian-mixture fit handle serves the vssr_gmm_fit_* calls only", __func__); \
     } while (0)
 
 }  // namespace vssr
@@ -529,6 +531,11 @@ int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr
 
 void vssr_destroy(vssr_handle *h) {
     if (!h) return;
+    if (h->kind == 6 && !h->fit->device_ready) {   // a fit handle that never reached a device owns host memory only
+        delete h->fit;
+        delete h;
+        return;
+    }
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->prof.destroy();
@@ -539,6 +546,10 @@ void vssr_destroy(vssr_handle *h) {
                       &h->d_forces_std, &h->d_e_atoms, &h->d_ters_e, &h->d_ters_ea, &h->d_ters_f, &h->d_sat, &h->d_sat_out, &h->d_stress, &h->d_traj_pos, &h->d_traj_f, &h->d_traj_e, &h->d_traj_n, &h->d_chain_class, &h->d_class_list, &h->d_upd_save, &h->d_gpart, &h->d_energy64, &h->d_cmp, &h->d_cm, &h->d_bundle_sub, &h->d_bundle_subb,
                       &h->d_gmm_P, &h->d_gmm_c, &h->d_gmm_kc, &h->d_gmm_mask, &h->d_gmm_x, &h->d_gmm_lp, &h->d_gmm_nll, &h->d_gmm_sys, &h->d_gmm_start};
     for (DevBuf *b : bufs) b->release();
+    if (h->fit) {
+        h->fit->release();
+        delete h->fit;
+    }
     if (h->h_counters) (void)hipHostFree(h->h_counters);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1379,6 +1390,151 @@ int vssr_gmm_score_batch(vssr_handle *g, vssr_handle *painn, int32_t model, int3
         const void *src = rows == 0 ? g->d_gmm_sys.p : g->d_gmm_nll.p;   // one mean row per structure: its own NLL
         VSSR_HIP(g, hipMemcpy(system, src, sizeof(double) * B, hipMemcpyDeviceToHost));
     }
+    return VSSR_OK;
+}
+
+// ---- Gaussian-mixture fit (gmm_fit.hip) ---------------------------------------------------------------------------------------------
+#define VSSR_FIT_HANDLE(h)                                                                          \
+    do {                                                                                            \
+        if (!(h)) return VSSR_E_BADARG;                                                             \
+        if ((h)->kind != 6) return set_err((h), VSSR_E_BADARG, "not a GMM fit handle");            \
+    } while (0)
+
+// first use of the device by a fit handle
+static int fit_device(vssr_handle *h) {
+    if (h->fit->device_ready) {
+        VSSR_HIP(h, hipSetDevice(h->device));
+        return VSSR_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return set_err(h, VSSR_E_DEVICE, "no HIP device available (this backend has no CPU fallback)");
+    if (h->device < 0 || h->device >= ndev) return set_err(h, VSSR_E_BADARG, "device %d out of range", h->device);
+    int rc = common_init(h, h->device);
+    if (rc) return rc;
+    h->fit->device_ready = true;
+    return VSSR_OK;
+}
+
+int vssr_gmm_fit_create(const vssr_gmm_fit_config *cfg, vssr_handle **out) {
+    if (!cfg || !out) return set_err(nullptr, VSSR_E_BADARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(vssr_gmm_fit_config))
+        return set_err(nullptr, VSSR_E_BADARG, "vssr_gmm_fit_config size mismatch (%u vs %zu)", cfg->struct_size, sizeof(vssr_gmm_fit_config));
+    int rc = gmm_fit_check_config(cfg);
+    if (rc) return rc;
+    if (cfg->device < 0) return set_err(nullptr, VSSR_E_BADARG, "device %d out of range", cfg->device);
+    vssr_handle *h = new vssr_handle();
+    h->kind = 6;
+    h->device = cfg->device;
+    h->gmm_K = cfg->n_components;
+    h->gmm_D = cfg->dim;
+    h->gmm_Dp = 16 * ((cfg->dim + 15) / 16);
+    h->gmm_log2pi = 1.8378770664093453;   // log(2 pi) in fp64, as gmm.py; the float32 constant is a scoring quirk of GMMUncertainty
+    h->fit = new GmmFit();
+    GmmFit *f = h->fit;
+    f->cov_type = cfg->covariance_type; f->init = cfg->init; f->max_iter = cfg->max_iter; f->n_init = cfg->n_init;
+    f->tol = cfg->tol; f->reg_covar = cfg->reg_covar; f->seed = cfg->seed;
+    *out = h;
+    return VSSR_OK;
+}
+
+int vssr_gmm_fit_append_rows(vssr_handle *h, int64_t n_rows, const double *x) {
+    VSSR_FIT_HANDLE(h);
+    if (n_rows < 1 || !x) return set_err(h, VSSR_E_BADARG, "GMM fit: null or empty rows");
+    if (n_rows > (int64_t)INT32_MAX - 64) return set_err(h, VSSR_E_BADARG, "GMM fit: n_rows %lld out of range", (long long)n_rows);
+    const size_t tot = (size_t)n_rows * h->gmm_D;
+    for (size_t i = 0; i < tot; ++i)
+        if (!std::isfinite(x[i])) return set_err(h, VSSR_E_BADARG, "GMM fit: row %zu holds a non-finite value", i / h->gmm_D);
+    int rc = fit_device(h);
+    if (rc) return rc;
+    return gmm_fit_append_host(h, n_rows, x);
+}
+
+int vssr_gmm_fit_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model, int32_t rows) {
+    VSSR_FIT_HANDLE(h);
+    if (!painn) return set_err(h, VSSR_E_BADARG, "null PaiNN handle");
+    if (painn->kind != 1) return set_err(h, VSSR_E_BADARG, "the second handle is not a PaiNN ensemble");
+    if (rows != 0 && rows != 1) return set_err(h, VSSR_E_BADARG, "rows must be 0 (atoms) or 1 (structure means), got %d", rows);
+    if (model < 0 || model >= painn->n_models)
+        return set_err(h, VSSR_E_BADARG, "model index %d out of range (%d models)", model, painn->n_models);
+    if (h->device != painn->device)
+        return set_err(h, VSSR_E_BADARG, "the GMM fit handle is on device %d, the PaiNN handle on device %d", h->device, painn->device);
+    if (h->gmm_D != painn->feat_dim)
+        return set_err(h, VSSR_E_BADARG, "GMM dimension %d differs from the PaiNN feat_dim %d", h->gmm_D, painn->feat_dim);
+    if (!painn->ran) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
+    if (painn->graph_partial)
+        return set_err(h, VSSR_E_STATE, "the resident activations cover only the chains of the last relaxation iteration: run the batch once (vssr_batch_run) first");
+    int rc = fit_device(h);
+    if (rc) return rc;
+    rc = sync_and_check(painn);
+    if (rc) return set_err(h, rc, "PaiNN run failed: %s", painn->err.c_str());
+    const int B = painn->n_cfg, N = painn->n_atoms;
+    const hipStream_t st = painn->stream;
+    const float *emb = painn->sv.s_in[painn->num_conv] + (size_t)model * N * painn->feat_dim;
+    if (rows == 0) return gmm_fit_append_f32(h, st, N, emb);
+    if (h->d_gmm_start.ensure(sizeof(int) * (B + 1))) return set_err(h, VSSR_E_NOMEM, "device allocation failed (GMM offsets)");
+    VSSR_HIP(h, hipMemcpyAsync(h->d_gmm_start.p, painn->h_cfg_start.data(), sizeof(int) * (B + 1), hipMemcpyHostToDevice, st));
+    rc = gmm_mean_rows(h, st, B, h->d_gmm_start.as<int>(), emb);
+    if (rc) return rc;
+    return gmm_fit_append_f64p(h, st, B, h->d_gmm_x.as<double>());
+}
+
+int vssr_gmm_fit_clear(vssr_handle *h) {
+    VSSR_FIT_HANDLE(h);
+    h->fit->n = 0;
+    h->fit->fitted = false;
+    h->fit->i_labels.clear();
+    h->fit->has_labels = false;
+    return VSSR_OK;
+}
+
+int vssr_gmm_fit_set_init(vssr_handle *h, const double *means, const double *weights, const double *precisions,
+                          const int32_t *labels) {
+    VSSR_FIT_HANDLE(h);
+    return gmm_fit_set_init(h, means, weights, precisions, labels);
+}
+
+int vssr_gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res) {
+    VSSR_FIT_HANDLE(h);
+    GmmFit *f = h->fit;
+    if (f->n < 2) return set_err(h, VSSR_E_BADARG, "GMM fit: at least 2 rows are needed (%lld resident)", (long long)f->n);
+    if (h->gmm_K > f->n) return set_err(h, VSSR_E_BADARG, "GMM fit: n_components %d exceeds the %lld resident rows", h->gmm_K, (long long)f->n);
+    const bool all_given = f->has_means && f->has_weights && f->has_prec;
+    if (f->init == VSSR_GMM_INIT_GIVEN && !all_given && !f->has_labels)
+        return set_err(h, VSSR_E_BADARG, "GMM fit: init = given needs labels, or means, weights and precisions (vssr_gmm_fit_set_init)");
+    if (f->has_labels && (int64_t)f->i_labels.size() != f->n)
+        return set_err(h, VSSR_E_BADARG, "GMM fit: %zu labels for %lld resident rows", f->i_labels.size(), (long long)f->n);
+    int rc = fit_device(h);
+    if (rc) return rc;
+    return gmm_fit_run(h, res);
+}
+
+int vssr_gmm_fit_params(vssr_handle *h, double *weights, double *means, double *covariances, double *prec_chol) {
+    VSSR_FIT_HANDLE(h);
+    if (!h->fit->fitted) return set_err(h, VSSR_E_STATE, "GMM fit: no completed fit");
+    VSSR_HIP(h, hipSetDevice(h->device));
+    return gmm_fit_params(h, weights, means, covariances, prec_chol);
+}
+
+int vssr_gmm_fit_scorer(vssr_handle *h, double log_2pi, vssr_handle **gmm) {
+    VSSR_FIT_HANDLE(h);
+    if (!gmm) return set_err(h, VSSR_E_BADARG, "null argument");
+    *gmm = nullptr;
+    if (!std::isfinite(log_2pi)) return set_err(h, VSSR_E_BADARG, "GMM: log_2pi is not finite");
+    if (!h->fit->fitted) return set_err(h, VSSR_E_STATE, "GMM fit: no completed fit");
+    vssr_handle *g = new vssr_handle();
+    g->kind = 5;
+    g->gmm_K = h->gmm_K; g->gmm_D = h->gmm_D; g->gmm_Dp = h->gmm_Dp;
+    g->gmm_log2pi = log_2pi;
+    int rc = common_init(g, h->device);
+    if (!rc) rc = gmm_fit_copy_scorer(h, g);
+    if (rc) {
+        set_err(h, rc, "GMM fit: building the scoring handle failed: %s", g->err.c_str());
+        vssr_destroy(g);
+        return rc;
+    }
+    *gmm = g;
     return VSSR_OK;
 }
 

@@ -229,10 +229,38 @@ struct Profiler {
     void destroy();
 };
 
+// State of a Gaussian-mixture fit (handle kind 6, gmm_fit.hip).  The mixture being fitted lives in the handle's scoring layout
+// (gmm_K / gmm_D / gmm_Dp / d_gmm_P / d_gmm_c / d_gmm_kc / d_gmm_mask): the E step is gmm_score_f64 on the resident rows.
+struct GmmFit {
+    int cov_type = 0;   // VSSR_GMM_COV_*
+    int init = 0;       // VSSR_GMM_INIT_*
+    int max_iter = 100, n_init = 1;
+    double tol = 1e-3, reg_covar = 1e-6;
+    uint64_t seed = 0;
+    bool device_ready = false, fitted = false;
+    int64_t n = 0, cap = 0;        // resident rows / capacity of x
+    double *x = nullptr;           // [cap][Dp] fp64, zero pad columns
+    // explicit initial values (vssr_gmm_fit_set_init), host side
+    std::vector<double> i_means, i_weights, i_prec;
+    std::vector<int> i_labels;
+    bool has_means = false, has_weights = false, has_prec = false, has_labels = false;
+    DevBuf resp, labels, lbpart, status, flags;
+    DevBuf part_s, part_q, part_n, nk, means, avg_x2, w, cov, part_cov, chol_w, chol_y, centers, assign_part;
+    DevBuf b_w, b_means, b_cov, b_P, b_c, b_kc, b_mask;   // best restart so far (n_init > 1)
+    void release() {
+        if (x) (void)hipFree(x);
+        x = nullptr;
+        DevBuf *bufs[] = {&resp, &labels, &lbpart, &status, &flags, &part_s, &part_q, &part_n, &nk, &means, &avg_x2, &w, &cov,
+                          &part_cov, &chol_w, &chol_y, &centers, &assign_part, &b_w, &b_means, &b_cov, &b_P, &b_c, &b_kc, &b_mask};
+        for (DevBuf *b : bufs) b->release();
+    }
+};
+
 }  // namespace vssr
 
 struct vssr_handle {
-    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber, 5 = Gaussian mixture (gmm.hip)
+    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber, 5 = Gaussian mixture (gmm.hip),
+                   // 6 = Gaussian-mixture fit (gmm_fit.hip)
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in ters_params
     int eam_nel = 0, eam_fs = 0;   // EAM with typed tables (vssr_eam_create_alloy): elements, 1 = eam/fs densities; 0 = one funcfl
     int device = 0;
@@ -354,6 +382,7 @@ struct vssr_handle {
     vssr::DevBuf d_gmm_kc;    // double [2][K]       log det P_k, log w_k
     vssr::DevBuf d_gmm_mask;  // uint8 [K][Dp/16][Dp/16]  1 = the 16 x 16 block of P_k holds a non-zero entry
     vssr::DevBuf d_gmm_x, d_gmm_lp, d_gmm_nll, d_gmm_sys, d_gmm_start;   // per-call workspaces
+    vssr::GmmFit *fit = nullptr;   // kind 6 only
 };
 
 namespace vssr {
@@ -394,6 +423,15 @@ int gmm_score_f32(vssr_handle *g, hipStream_t st, int64_t n, const float *x_dev)
 int gmm_mean_rows(vssr_handle *g, hipStream_t st, int B, const int *start, const float *emb);
 // per-structure reductions of g->d_gmm_nll (order 1 .. 6 as vssr_gmm_score_batch) into g->d_gmm_sys [B]
 int gmm_reduce(vssr_handle *g, hipStream_t st, int B, const int *start, int order);
+// Gaussian-mixture fit (gmm_fit.hip): EM on the rows resident in h->fit->x; the device is initialised by the caller (vssr_api.hip)
+int gmm_fit_check_config(const vssr_gmm_fit_config *cfg);
+int gmm_fit_append_host(vssr_handle *h, int64_t n_rows, const double *x);
+int gmm_fit_append_f32(vssr_handle *h, hipStream_t st, int64_t n_rows, const float *emb_dev);   // device rows [n][D] fp32
+int gmm_fit_append_f64p(vssr_handle *h, hipStream_t st, int64_t n_rows, const double *x_dev);   // device rows [n][Dp] fp64
+int gmm_fit_set_init(vssr_handle *h, const double *means, const double *weights, const double *precisions, const int32_t *labels);
+int gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res);
+int gmm_fit_params(vssr_handle *h, double *weights, double *means, double *covariances, double *prec_chol);
+int gmm_fit_copy_scorer(vssr_handle *h, vssr_handle *g);   // the fitted mixture into the scoring buffers of a kind-5 handle
 // the fp64 analytic potentials (Tersoff, EAM, SW): same result buffers (d_ters_e / _ea / _f), same drivers
 inline bool is_f64_kind(const vssr_handle *h) { return h->kind == 2 || h->kind == 3 || h->kind == 4; }
 inline int f64_run(vssr_handle *h, uint32_t want) {

@@ -325,7 +325,7 @@ class GMMUncertainty(Uncertainty):
                  order: str = "atomic", covariance_type: str = "full", tol: float = 1e-3, max_iter: int = 100000,
                  n_init: int = 1, init_params: str = "kmeans", verbose: int = 0, device: str = "cuda", calibrate: bool = False,
                  cp_alpha: float | None = None, min_uncertainty: float | None = None, gmm_path: str | None = None,
-                 gm_model=None, *args, **kwargs):
+                 gm_model=None, fit_device=None, *args, **kwargs):
         super().__init__(order=order, calibrate=calibrate, cp_alpha=cp_alpha, min_uncertainty=min_uncertainty, *args, **kwargs)
         self.train_key = train_embed_key
         self.test_key = test_embed_key
@@ -337,6 +337,8 @@ class GMMUncertainty(Uncertainty):
         self.init_params = init_params
         self.verbose = verbose
         self.device = device
+        self.fit_device = fit_device   # None: fit_gmm runs scikit-learn on the host; "cuda" / "cuda:n": EM on that GPU (gmm_fit.hip)
+        self._pending = None           # (GaussianMixture, GMMFitEngine) collecting resident rows (append_resident)
         self._engines = {}
         self.gm_model = None
         self.gmm_path = gmm_path
@@ -349,9 +351,51 @@ class GMMUncertainty(Uncertainty):
         else:
             print(f"gm_model {gmm_path} does not exist")
 
-    # -- fitting (host) --
+    # -- fitting on the device (fit_device) --
+    def _device_estimator(self):
+        if self.fit_device is None or _device_index(self.fit_device) is None:
+            raise ValueError("fitting on the device needs GMMUncertainty(fit_device='cuda' / 'cuda:n')")
+        return GaussianMixture(n_components=self.n, covariance_type=self.covar_type, tol=self.tol, max_iter=self.max_iter,
+                               n_init=self.n_init, init_params=self.init_params, verbose=self.verbose, device=self.fit_device,
+                               random_state=getattr(self, "random_state", None))
+
+    def _adopt_fit(self, gm) -> None:
+        self.gm_model = gm
+        if self.gmm_path is not None and not os.path.exists(self.gmm_path):
+            gm.save(self.gmm_path)
+            print(f"Saved fitted GMM model to {self.gmm_path}")
+        self._set_gmm_params()
+
+    def append_resident(self, painn_engine, model: int = 0, rows: str = "atoms") -> None:
+        """Add the embedding resident on ``painn_engine``'s GPU after its last run to the rows of the next ``fit_appended``,
+        device to device (vssr_gmm_fit_append_batch); call once per PaiNN batch."""
+        if self._pending is None:
+            gm = self._device_estimator()
+            self._pending = (gm, gm.new_engine(painn_engine.embedding_dim()))
+        self._pending[1].append_batch(painn_engine, model=model, rows=rows)
+
+    def fit_appended(self) -> None:
+        """Fit on everything ``append_resident`` collected; the rows never leave the device."""
+        if self._pending is None:
+            raise Exception("GMMUncertainty: no resident rows appended")
+        gm, eng = self._pending
+        self._pending = None
+        self._adopt_fit(gm.fit_engine(eng))
+
+    def fit_resident(self, painn_engine, model: int = 0, rows: str = "atoms") -> None:
+        """``append_resident`` of one PaiNN batch and ``fit_appended``."""
+        self._pending = None
+        self.append_resident(painn_engine, model=model, rows=rows)
+        self.fit_appended()
+
+    # -- fitting (host, or the device with fit_device) --
     def fit_gmm(self, Xtrain) -> None:
-        """Fit the mixture on the host with sklearn's ``GaussianMixture`` (EM stays on the host)."""
+        """Fit the mixture: with ``fit_device=None`` on the host with sklearn's ``GaussianMixture``; with ``fit_device="cuda"`` /
+        ``"cuda:n"`` on that GPU (``uncertainty.GaussianMixture``)."""
+        if self.fit_device is not None:
+            self.Xtrain = Xtrain
+            self._adopt_fit(self._device_estimator().fit(self._rows(Xtrain)))
+            return
         try:
             from sklearn.mixture import GaussianMixture
         except ImportError as e:
@@ -400,6 +444,10 @@ class GMMUncertainty(Uncertainty):
         if key not in self._engines:
             from . import backend
 
+            gm = self.gm_model
+            if isinstance(gm, GaussianMixture) and gm._fit_engine is not None and gm._fit_engine.device == idx:
+                self._engines[key] = gm.scorer(float(self.log2pi))   # from the device arrays of the fit (vssr_gmm_fit_scorer)
+                return self._engines[key]
             self._engines[key] = backend.GMMEngine(self.means, self.prec_chol_full, self.weights, device=idx,
                                                    log_2pi=float(self.log2pi))
         return self._engines[key]
@@ -496,6 +544,162 @@ class GMMUncertainty(Uncertainty):
         if self.calibrate:
             inputs["qhat"] = self.CP.qhat
         return "gmm", inputs
+
+
+# ---- the estimator, fitted on the device ---------------------------------------------------------------------------------------------
+class GaussianMixture:
+    """Gaussian mixture fitted by expectation-maximisation on the GPU (``backend.GMMFitEngine``, ``csrc/gmm_fit.hip``): the
+    reference's ``mcmc.uncertainty.gmm.GaussianMixture`` (a copy of sklearn's) with its constructor arguments and fitted
+    attributes (``weights_``, ``means_``, ``covariances_``, ``precisions_cholesky_``, ``precisions_``, ``converged_``, ``n_iter_``,
+    ``lower_bound_``, ``lower_bounds_``).
+
+    What is and is not reproduced: the EM loop, the stopping rule, ``n_init`` and the precedence of ``weights_init`` /
+    ``means_init`` / ``precisions_init`` are sklearn's; all arithmetic is fp64 with fixed summation orders (two fits of the same
+    rows agree bit for bit).  The random draws of ``init_params="kmeans"`` (k-means++ seeding, then Lloyd iterations on the
+    device) and ``"random_from_data"`` come from the project's counter-based generator (Philox4x32-10, ``mc.py``) keyed by
+    ``random_state``: they cannot and need not reproduce numpy's or sklearn's streams, so a fit started that way matches sklearn
+    in quality, not in numbers.  ``init_params="random"`` and ``"k-means++"`` are not built here (fit on the host with sklearn for
+    those); ``warm_start`` is not supported.  ``fit(X, labels=...)`` starts from one-hot responsibilities of integer labels
+    (what sklearn does with its k-means result) and is deterministic on both sides.  ``random_state=None`` draws a fresh seed.
+    ``device``: "cuda" / "cuda:n" / int."""
+
+    def __init__(self, n_components=1, *, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1,
+                 init_params="kmeans", weights_init=None, means_init=None, precisions_init=None, random_state=None,
+                 warm_start=False, verbose=0, verbose_interval=10, device="cuda"):
+        self.n_components, self.covariance_type, self.tol, self.reg_covar = n_components, covariance_type, tol, reg_covar
+        self.max_iter, self.n_init, self.init_params = max_iter, n_init, init_params
+        self.weights_init, self.means_init, self.precisions_init = weights_init, means_init, precisions_init
+        self.random_state, self.warm_start, self.verbose, self.verbose_interval = random_state, warm_start, verbose, verbose_interval
+        self.device = device
+        self._fit_engine = None
+        self._scorers = {}
+
+    # -- fitting --
+    def _check_parameters(self):
+        if self.covariance_type not in ("spherical", "tied", "diag", "full"):
+            raise ValueError(f"Invalid value for 'covariance_type': {self.covariance_type} 'covariance_type' should be in "
+                             "['spherical', 'tied', 'diag', 'full']")
+        if self.warm_start:
+            raise NotImplementedError("warm_start is not supported by the device fit")
+        if self.init_params in ("random", "k-means++"):
+            raise NotImplementedError(f"init_params={self.init_params!r} is not built on the device: use 'kmeans', "
+                                      "'random_from_data' or labels=, or fit on the host (sklearn.mixture.GaussianMixture)")
+        if self.init_params not in ("kmeans", "random_from_data"):
+            raise ValueError(f"unknown init_params {self.init_params!r}")
+
+    def new_engine(self, n_features: int, labels_given: bool = False):
+        """A ``backend.GMMFitEngine`` configured from this estimator (rows still to be appended)."""
+        from . import backend
+
+        self._check_parameters()
+        idx = _device_index(self.device)
+        if idx is None:
+            raise ValueError("GaussianMixture fits on a GPU: device must be 'cuda' / 'cuda:n'")
+        seed = int.from_bytes(os.urandom(8), "little") if self.random_state is None else int(self.random_state)
+        return backend.GMMFitEngine(self.n_components, n_features, covariance_type=self.covariance_type, tol=self.tol,
+                                    reg_covar=self.reg_covar, max_iter=self.max_iter, n_init=self.n_init,
+                                    init="given" if labels_given else self.init_params, seed=seed, device=idx)
+
+    def fit_engine(self, eng, labels=None):
+        """Fit on the rows resident in ``eng`` (``new_engine``; rows appended from the host or from PaiNN engines)."""
+        eng.set_init(means=self.means_init, weights=self.weights_init, precisions=self.precisions_init, labels=labels)
+        r = eng.fit()
+        p = eng.params()
+        self.weights_, self.means_ = p["weights_"], p["means_"]
+        self.covariances_, self.precisions_cholesky_ = p["covariances_"], p["precisions_cholesky_"]
+        self.converged_, self.n_iter_, self.lower_bound_ = r["converged"], r["n_iter"], r["lower_bound"]
+        self.lower_bounds_ = list(r["lower_bounds"])
+        if not self.converged_:
+            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase "
+                          "max_iter, tol, or check for degenerate data.")
+        self._fit_engine, self._scorers = eng, {}
+        return self
+
+    def fit(self, X, y=None, labels=None):
+        X = GMMUncertainty._rows(X)
+        eng = self.new_engine(X.shape[1], labels_given=labels is not None)
+        eng.append_rows(X)
+        return self.fit_engine(eng, labels=labels)
+
+    def fit_predict(self, X, y=None):
+        return self.fit(X).predict(X)
+
+    @property
+    def precisions_(self):
+        pc = np.asarray(self.precisions_cholesky_)
+        if self.covariance_type == "full":
+            return np.einsum("kij,klj->kil", pc, pc)
+        if self.covariance_type == "tied":
+            return pc @ pc.T
+        return pc ** 2
+
+    # -- scoring (fp64 log 2 pi, as sklearn) --
+    def scorer(self, log_2pi: float = LOG2PI_F64):
+        """The ``backend.GMMEngine`` of the fitted mixture: from the device arrays after a fit (vssr_gmm_fit_scorer)."""
+        key = float(log_2pi)
+        if key not in self._scorers:
+            from . import backend
+
+            if self._fit_engine is not None:
+                self._scorers[key] = self._fit_engine.scorer(key)
+            else:
+                K, D = np.asarray(self.means_).shape
+                self._scorers[key] = backend.GMMEngine(self.means_, full_precision_cholesky(self.precisions_cholesky_,
+                                                       self.covariance_type, K, D), self.weights_,
+                                                       device=_device_index(self.device), log_2pi=key)
+        return self._scorers[key]
+
+    def _estimate_log_prob(self, X):
+        return self.scorer().score_rows(GMMUncertainty._rows(X), log_prob=True)[1]
+
+    def score_samples(self, X):
+        return -self.scorer().score_rows(GMMUncertainty._rows(X))
+
+    def score(self, X, y=None):
+        return float(np.mean(self.score_samples(X)))
+
+    def predict_proba(self, X):
+        nll, lp = self.scorer().score_rows(GMMUncertainty._rows(X), log_prob=True)
+        return np.exp(lp + np.log(self.weights_) + nll[:, None])
+
+    def predict(self, X):
+        return (self._estimate_log_prob(X) + np.log(self.weights_)).argmax(axis=1)
+
+    def _n_parameters(self) -> int:
+        K, D = np.asarray(self.means_).shape
+        cov = {"full": K * D * (D + 1) / 2.0, "diag": K * D, "tied": D * (D + 1) / 2.0, "spherical": K}[self.covariance_type]
+        return int(cov + D * K + K - 1)
+
+    def bic(self, X):
+        n = GMMUncertainty._rows(X).shape[0]
+        return -2 * self.score(X) * n + self._n_parameters() * np.log(n)
+
+    def aic(self, X):
+        return -2 * self.score(X) * GMMUncertainty._rows(X).shape[0] + 2 * self._n_parameters()
+
+    # -- persistence: a dict of arrays, the form load_pickle reads --
+    FITTED = ("weights_", "means_", "covariances_", "precisions_cholesky_", "converged_", "n_iter_", "lower_bound_", "lower_bounds_")
+
+    def as_dict(self) -> dict:
+        d = {"covariance_type": self.covariance_type, "n_components": self.n_components}
+        for k in self.FITTED:
+            if hasattr(self, k):
+                v = getattr(self, k)
+                d[k] = np.asarray(v) if k != "covariance_type" else v
+        return d
+
+    def save(self, filename):
+        with open(filename, "wb") as fh:
+            pickle.dump(self.as_dict(), fh)
+
+    @classmethod
+    def from_dict(cls, d, device="cuda"):
+        gm = cls(n_components=int(d.get("n_components", len(d["weights_"]))), covariance_type=d.get("covariance_type", "full"),
+                 device=device)
+        for k in cls.FITTED:
+            if k in d:
+                setattr(gm, k, d[k])
+        return gm
 
 
 UNC_DICT = {"ensemble": EnsembleUncertainty, "gmm": GMMUncertainty}
