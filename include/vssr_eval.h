@@ -468,6 +468,63 @@ int vssr_gmm_fit_params(vssr_handle *h, double *weights, double *means, double *
  * vssr_gmm_config.  VSSR_E_STATE before a successful run. */
 int vssr_gmm_fit_scorer(vssr_handle *h, double log_2pi, vssr_handle **gmm);
 
+/* ---- Clustering latent embeddings on the device (reference mcmc/utils/clustering.py: perform_clustering :21-85,
+ *      get_cluster_centers :160-188; scripts/clustering.py) ------------------------------------------------------------------------- */
+/* Rows x_n [D] (fp64, resident as [N][Dp] like the rows of the mixture fit).  All arithmetic fp64, fixed summation orders, no
+ * floating-point atomics: two runs on the same rows give the same bits.
+ *   PCA (clustering.py:50-51, sklearn PCA(n_components, whiten).fit(X).transform(X)):  mean_ = column means;  C = sum_n (x_n - mean)
+ *       (x_n - mean)^T / (N - 1) on v_mfma_f64_16x16x4_f64 (the row-slab kernel of the mixture fit, unit responsibilities);  C = V diag(l)
+ *       V^T by cyclic Jacobi rotations in one workgroup (round-robin ordering);  components_ = the n_components eigenvectors of the
+ *       largest l, each with its largest-magnitude entry positive (the first one on ties; sklearn's svd_flip on V^T);
+ *       explained_variance_ = l;  ratio = l / sum of all l;  X_r = (X - mean) components_^T, divided by sqrt(l) when whitening.
+ *   Ward linkage (clustering.py:60, :174, scipy linkage(P, "ward")) of points P [N][cluster_dims] without a distance matrix: clusters are
+ *       (centroid, size); d(A, B) = sqrt(2 |A| |B| / (|A| + |B|)) |c_A - c_B|.  Per round every live cluster finds its nearest live
+ *       cluster (the lowest position in the live list wins a tie), all reciprocal pairs merge (centroid = size-weighted mean), the live
+ *       list is compacted in order.  Ward is reducible, so the tree equals that of one global minimum at a time.  The N - 1 merge
+ *       records are then sorted by height (stable) and renumbered to scipy's Z: row r creates cluster N + r, the smaller id first.
+ * optimal_ordering=True of the reference (a reordering of children for the dendrogram plot) is not built. */
+typedef struct {
+    uint32_t struct_size;  /* sizeof(vssr_cluster_config) */
+    int32_t device;        /* HIP device ordinal; the device is first touched by the first append / set_points */
+    int32_t dim;           /* D, 1 .. 256 */
+    int32_t n_components;  /* 1 .. D (and <= N when vssr_cluster_pca runs) */
+    int32_t whiten;        /* 0 / 1 */
+    int32_t cluster_dims;  /* 1 .. 32: leading columns of X_r that are clustered (the reference: 3), or the width of set_points */
+} vssr_cluster_config;
+typedef struct {
+    int64_t n_rows;        /* rows the PCA was fitted on */
+    int32_t n_sweeps;      /* Jacobi sweeps */
+    int32_t converged;     /* 1 = every off-diagonal entry fell below eps |C|_F / D before the sweep limit */
+} vssr_cluster_pca_result;
+/* Handle kind 7 (freed by vssr_destroy); every entry point other than vssr_cluster_*, vssr_destroy and vssr_last_error refuses it, and
+ * the vssr_cluster_* calls refuse every other kind.  Refused with VSSR_E_BADARG without touching a device: dim outside 1 .. 256,
+ * n_components outside 1 .. dim, cluster_dims outside 1 .. 32, whiten other than 0 / 1, a negative device. */
+int vssr_cluster_create(const vssr_cluster_config *cfg, vssr_handle **out);
+/* Append caller rows x [n_rows][D] (fp64); several appends accumulate.  VSSR_E_BADARG (before a device is touched) for a null
+ * pointer, n_rows < 1 or a non-finite entry. */
+int vssr_cluster_append_rows(vssr_handle *h, int64_t n_rows, const double *x);
+/* Append one mean row per structure of a PaiNN handle's last run (ensemble member `model`), device to device -- the reference's
+ * get_embeddings_single(flatten=True, flatten_axis=0).  Errors as vssr_gmm_fit_append_batch. */
+int vssr_cluster_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model);
+/* Drop the resident rows, the PCA and the points. */
+int vssr_cluster_clear(vssr_handle *h);
+/* Fit the PCA on the resident rows and project them; the first cluster_dims columns of X_r become the points of the linkage.
+ * VSSR_E_BADARG (no device touched) when N < 2, n_components > N or cluster_dims > n_components.  result may be NULL. */
+int vssr_cluster_pca(vssr_handle *h, vssr_cluster_pca_result *result);
+/* mean_ [D], components_ [n_components][D], explained_variance_ and explained_variance_ratio_ [n_components]; any may be NULL.
+ * VSSR_E_STATE before vssr_cluster_pca. */
+int vssr_cluster_pca_params(vssr_handle *h, double *mean, double *components, double *explained_variance, double *ratio);
+/* Rows first .. first + n_rows - 1 of X_r into xr [n_rows][n_components].  VSSR_E_STATE before vssr_cluster_pca, VSSR_E_BADARG for a
+ * range outside the fitted rows. */
+int vssr_cluster_projected(vssr_handle *h, int64_t first, int64_t n_rows, double *xr);
+/* Skip the PCA: cluster caller points p [n][cluster_dims] (clustering.py:174, get_cluster_centers).  Replaces the resident points.
+ * VSSR_E_BADARG (before a device is touched) for a null pointer, n < 2 or a non-finite entry. */
+int vssr_cluster_set_points(vssr_handle *h, int64_t n, const double *p);
+/* Ward linkage of the resident points: Z [N - 1][4] in scipy's convention (ids as doubles, height, size); n_rounds (may be NULL)
+ * receives the rounds taken (at most N - 1: every round merges at least one pair, duplicated points included).  One 8-byte read-back
+ * per round.  VSSR_E_STATE without points. */
+int vssr_cluster_linkage(vssr_handle *h, double *Z, int32_t *n_rounds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,8 @@ EXPORTS = (
     "vssr_gmm_create", "vssr_gmm_score_rows", "vssr_gmm_score_batch", "vssr_eam_create_alloy",
     "vssr_gmm_fit_create", "vssr_gmm_fit_append_rows", "vssr_gmm_fit_append_batch", "vssr_gmm_fit_clear",
     "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
+    "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
+    "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
 )
 
 
@@ -105,6 +107,15 @@ class GmmFitConfig(C.Structure):
 class GmmFitResult(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("converged", C.c_int32), ("best_init", C.c_int32), ("n_lower_bounds", C.c_int32),
                 ("lower_bound", C.c_double), ("lower_bounds", C.POINTER(C.c_double)), ("lower_bounds_cap", C.c_int32)]
+
+
+class ClusterConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("dim", C.c_int32), ("n_components", C.c_int32),
+                ("whiten", C.c_int32), ("cluster_dims", C.c_int32)]
+
+
+class ClusterPcaResult(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_sweeps", C.c_int32), ("converged", C.c_int32)]
 
 
 GMM_COV_TYPES = {"full": 0, "tied": 1, "diag": 2, "spherical": 3}
@@ -263,6 +274,24 @@ def load_library():
     L.vssr_gmm_fit_params.argtypes = [vp, dp, dp, dp, dp]
     L.vssr_gmm_fit_scorer.restype = C.c_int
     L.vssr_gmm_fit_scorer.argtypes = [vp, C.c_double, C.POINTER(vp)]
+    L.vssr_cluster_create.restype = C.c_int
+    L.vssr_cluster_create.argtypes = [C.POINTER(ClusterConfig), C.POINTER(vp)]
+    L.vssr_cluster_append_rows.restype = C.c_int
+    L.vssr_cluster_append_rows.argtypes = [vp, C.c_int64, dp]
+    L.vssr_cluster_append_batch.restype = C.c_int
+    L.vssr_cluster_append_batch.argtypes = [vp, vp, C.c_int32]
+    L.vssr_cluster_clear.restype = C.c_int
+    L.vssr_cluster_clear.argtypes = [vp]
+    L.vssr_cluster_pca.restype = C.c_int
+    L.vssr_cluster_pca.argtypes = [vp, C.POINTER(ClusterPcaResult)]
+    L.vssr_cluster_pca_params.restype = C.c_int
+    L.vssr_cluster_pca_params.argtypes = [vp, dp, dp, dp, dp]
+    L.vssr_cluster_projected.restype = C.c_int
+    L.vssr_cluster_projected.argtypes = [vp, C.c_int64, C.c_int64, dp]
+    L.vssr_cluster_set_points.restype = C.c_int
+    L.vssr_cluster_set_points.argtypes = [vp, C.c_int64, dp]
+    L.vssr_cluster_linkage.restype = C.c_int
+    L.vssr_cluster_linkage.argtypes = [vp, dp, C.POINTER(C.c_int32)]
     if L.vssr_abi_version() != 1:
         raise BackendError("libvssr_eval.so ABI version mismatch")
     _lib = L
@@ -889,3 +918,81 @@ class GMMFitEngine(_Handle):
         h = C.c_void_p(None)
         self._check(self._lib.vssr_gmm_fit_scorer(self._h, float(log_2pi), C.byref(h)))
         return GMMEngine._adopt(h, self.n_components, self.dim, self.device)
+
+
+class ClusterEngine(_Handle):
+    """Clustering of latent embeddings on one GPU (vssr_cluster_*, ``csrc/cluster.hip``): the PCA of the reference's
+    ``perform_clustering`` (``sklearn.decomposition.PCA(n_components, whiten)``) and Ward linkage of the leading ``cluster_dims``
+    projected columns without a distance matrix, fp64 throughout, no floating-point atomics (a run repeats bit for bit).
+
+    Rows are appended from the host (``append_rows``) or device to device from a ``PainnEngine``'s last run, one mean row per
+    structure (``append_resident``); several appends accumulate.  ``set_points`` skips the PCA (``get_cluster_centers``).  The tree
+    comes back as scipy's ``Z``; cutting it is ``clustering.fcluster``.  The device is first touched by the first append."""
+
+    def __init__(self, dim, n_components=32, whiten=True, cluster_dims=3, device=0):
+        super().__init__()
+        cfg = ClusterConfig(C.sizeof(ClusterConfig), int(device), int(dim), int(n_components), int(bool(whiten)), int(cluster_dims))
+        rc = self._lib.vssr_cluster_create(C.byref(cfg), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_cluster_create failed ({rc}): {msg.decode() if msg else '?'}")
+        self.dim, self.n_components, self.cluster_dims, self.device = int(dim), int(n_components), int(cluster_dims), int(device)
+        self.n_rows = 0
+        self.n_points = 0
+
+    def append_rows(self, x):
+        """Append rows ``x [n, D]`` (any float dtype; kept in fp64 on the device)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}], got {x.shape}")
+        self._check(self._lib.vssr_cluster_append_rows(self._h, x.shape[0], _ptr(x, C.c_double)))
+        self.n_rows += x.shape[0]
+
+    def append_resident(self, painn_engine, model=0):
+        """Append one mean row per structure of ``painn_engine``'s last run (ensemble member ``model``), device to device."""
+        self._check(self._lib.vssr_cluster_append_batch(self._h, painn_engine._h, int(model)))
+        self.n_rows += painn_engine._n_cfg
+
+    def clear(self):
+        self._check(self._lib.vssr_cluster_clear(self._h))
+        self.n_rows = 0
+        self.n_points = 0
+
+    def pca(self):
+        """Fit the PCA on the resident rows and project them; returns ``{"n_rows", "n_sweeps", "converged"}``."""
+        res = ClusterPcaResult(0, 0, 0)
+        self._check(self._lib.vssr_cluster_pca(self._h, C.byref(res)))
+        self.n_points = int(res.n_rows)
+        return {"n_rows": int(res.n_rows), "n_sweeps": int(res.n_sweeps), "converged": bool(res.converged)}
+
+    def pca_params(self):
+        """``{"mean_", "components_", "explained_variance_", "explained_variance_ratio_"}`` in sklearn's shapes."""
+        D, nc = self.dim, self.n_components
+        mean, comp, ev, ratio = np.zeros(D), np.zeros((nc, D)), np.zeros(nc), np.zeros(nc)
+        self._check(self._lib.vssr_cluster_pca_params(self._h, _ptr(mean, C.c_double), _ptr(comp, C.c_double), _ptr(ev, C.c_double),
+                                                      _ptr(ratio, C.c_double)))
+        return {"mean_": mean, "components_": comp, "explained_variance_": ev, "explained_variance_ratio_": ratio}
+
+    def projected(self, first=0, n_rows=None):
+        """Rows ``first .. first + n_rows`` of ``X_r`` as ``[n_rows, n_components]``."""
+        n_rows = self.n_points - first if n_rows is None else int(n_rows)
+        xr = np.zeros((max(n_rows, 0), self.n_components))
+        self._check(self._lib.vssr_cluster_projected(self._h, int(first), n_rows, _ptr(xr, C.c_double)))
+        return xr
+
+    def set_points(self, points):
+        """Cluster ``points [n, cluster_dims]`` directly (no PCA)."""
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.cluster_dims:
+            raise ValueError(f"points must be [n, {self.cluster_dims}], got {p.shape}")
+        self._check(self._lib.vssr_cluster_set_points(self._h, p.shape[0], _ptr(p, C.c_double)))
+        self.n_points = p.shape[0]
+
+    def linkage(self):
+        """Ward linkage of the resident points: ``(Z [n - 1, 4], rounds)``, ``Z`` in scipy's convention."""
+        Z = np.zeros((max(self.n_points - 1, 1), 4))
+        rounds = C.c_int32(0)
+        self._check(self._lib.vssr_cluster_linkage(self._h, _ptr(Z, C.c_double), C.byref(rounds)))
+        return Z[: self.n_points - 1], int(rounds.value)

@@ -658,6 +658,19 @@ static int fit_m_step(vssr_handle *h, hipStream_t st, const double *resp, const 
     return VSSR_OK;
 }
 
+// Centred scatter of rows that are not a mixture's (cluster.hip: the covariance of a PCA): cov [Dp][Dp] = sum_n (x_n - mean)(x_n - mean)^T
+// / denom[0], through the row-slab kernel with unit responsibilities and the same slab-ordered finish (no reg, pad rows / columns zero).
+// mean [Dp] and denom [1] live on the device; part is the caller's workspace.
+int gmm_fit_centered_cov(vssr_handle *h, hipStream_t st, const double *X, int n, int D, int Dp, const double *mean, const double *denom,
+                         DevBuf &part, double *cov) {
+    const FitGeom g = fit_geom(n, 1, Dp, 1);
+    if (part.ensure(sizeof(double) * (size_t)g.S_c * Dp * Dp)) return set_err(h, VSSR_E_NOMEM, "device allocation failed (covariance partials)");
+    hipLaunchKernelGGL(k_fit_cov, dim3(g.S_c, 1, g.ZT), dim3(256), 0, st, X, n, Dp, (const double *)nullptr, 1, mean, g.rps_c, part.as<double>());
+    hipLaunchKernelGGL(k_fit_cov_finish, dim3(1, Dp), dim3(256), 0, st, part.as<double>(), g.S_c, D, Dp, 1, 0, denom, mean, 0.0, cov);
+    VSSR_HIP(h, hipGetLastError());
+    return VSSR_OK;
+}
+
 // one-hot responsibilities of labels are only needed by the full covariance kernel: written as a dense [n][K] array
 __global__ void __launch_bounds__(256)
 k_fit_onehot(const int *__restrict__ labels, int n, int K, double *__restrict__ resp) {

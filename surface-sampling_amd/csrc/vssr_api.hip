@@ -273,11 +273,12 @@ static int sync_and_check(vssr_handle *h) {
 }
 
 // a Gaussian-mixture handle (kind 5) serves vssr_gmm_*, vssr_destroy and vssr_last_error only: every other entry point refuses it;
-// likewise a fit handle (kind 6) and vssr_gmm_fit_*
+// likewise a fit handle (kind 6) and vssr_gmm_fit_*, a clustering handle (kind 7) and vssr_cluster_*
 #define VSSR_REFUSE_GMM(h)                                                                                               \
     do {                                                                                                                 \
         if ((h)->kind == 5) return set_err((h), VSSR_E_BADARG, "%s: a Gaussian-mixture handle serves the vssr_gmm_* calls only", __func__); \
         if ((h)->kind == 6) return set_err((h), VSSR_E_BADARG, "%s: a Gaussian-mixture fit handle serves the vssr_gmm_fit_* calls only", __func__); \
+        if ((h)->kind == 7) return set_err((h), VSSR_E_BADARG, "%s: a clustering handle serves the vssr_cluster_* calls only", __func__); \
     } while (0)
 
 }  // namespace vssr
@@ -531,8 +532,9 @@ int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr
 
 void vssr_destroy(vssr_handle *h) {
     if (!h) return;
-    if (h->kind == 6 && !h->fit->device_ready) {   // a fit handle that never reached a device owns host memory only
+    if ((h->kind == 6 || h->kind == 7) && !h->fit->device_ready) {   // a fit / clustering handle that never reached a device owns host memory only
         delete h->fit;
+        delete h->clu;
         delete h;
         return;
     }
@@ -549,6 +551,10 @@ void vssr_destroy(vssr_handle *h) {
     if (h->fit) {
         h->fit->release();
         delete h->fit;
+    }
+    if (h->clu) {
+        h->clu->release();
+        delete h->clu;
     }
     if (h->h_counters) (void)hipHostFree(h->h_counters);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1451,8 +1457,8 @@ int vssr_gmm_fit_append_rows(vssr_handle *h, int64_t n_rows, const double *x) {
     return gmm_fit_append_host(h, n_rows, x);
 }
 
-int vssr_gmm_fit_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model, int32_t rows) {
-    VSSR_FIT_HANDLE(h);
+// rows of a PaiNN handle's resident embedding into the resident set of a fit (kind 6) or clustering (kind 7) handle
+static int fit_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model, int32_t rows) {
     if (!painn) return set_err(h, VSSR_E_BADARG, "null PaiNN handle");
     if (painn->kind != 1) return set_err(h, VSSR_E_BADARG, "the second handle is not a PaiNN ensemble");
     if (rows != 0 && rows != 1) return set_err(h, VSSR_E_BADARG, "rows must be 0 (atoms) or 1 (structure means), got %d", rows);
@@ -1478,6 +1484,11 @@ int vssr_gmm_fit_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model,
     rc = gmm_mean_rows(h, st, B, h->d_gmm_start.as<int>(), emb);
     if (rc) return rc;
     return gmm_fit_append_f64p(h, st, B, h->d_gmm_x.as<double>());
+}
+
+int vssr_gmm_fit_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model, int32_t rows) {
+    VSSR_FIT_HANDLE(h);
+    return fit_append_batch(h, painn, model, rows);
 }
 
 int vssr_gmm_fit_clear(vssr_handle *h) {
@@ -1536,6 +1547,120 @@ int vssr_gmm_fit_scorer(vssr_handle *h, double log_2pi, vssr_handle **gmm) {
     }
     *gmm = g;
     return VSSR_OK;
+}
+
+// ---- clustering of latent embeddings (cluster.hip) ----------------------------------------------------------------------------------
+#define VSSR_CLUSTER_HANDLE(h)                                                                      \
+    do {                                                                                            \
+        if (!(h)) return VSSR_E_BADARG;                                                             \
+        if ((h)->kind != 7) return set_err((h), VSSR_E_BADARG, "not a clustering handle");         \
+    } while (0)
+
+int vssr_cluster_create(const vssr_cluster_config *cfg, vssr_handle **out) {
+    if (!cfg || !out) return set_err(nullptr, VSSR_E_BADARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(vssr_cluster_config))
+        return set_err(nullptr, VSSR_E_BADARG, "vssr_cluster_config size mismatch (%u vs %zu)", cfg->struct_size, sizeof(vssr_cluster_config));
+    if (cfg->dim < 1 || cfg->dim > 256) return set_err(nullptr, VSSR_E_BADARG, "clustering: dim must be in 1..256 (got %d)", cfg->dim);
+    if (cfg->n_components < 1 || cfg->n_components > cfg->dim)
+        return set_err(nullptr, VSSR_E_BADARG, "clustering: n_components must be in 1..dim = %d (got %d)", cfg->dim, cfg->n_components);
+    if (cfg->cluster_dims < 1 || cfg->cluster_dims > 32)
+        return set_err(nullptr, VSSR_E_BADARG, "clustering: cluster_dims must be in 1..32 (got %d)", cfg->cluster_dims);
+    if (cfg->whiten != 0 && cfg->whiten != 1) return set_err(nullptr, VSSR_E_BADARG, "clustering: whiten must be 0 or 1 (got %d)", cfg->whiten);
+    if (cfg->device < 0) return set_err(nullptr, VSSR_E_BADARG, "device %d out of range", cfg->device);
+    vssr_handle *h = new vssr_handle();
+    h->kind = 7;
+    h->device = cfg->device;
+    h->gmm_K = 1;
+    h->gmm_D = cfg->dim;
+    h->gmm_Dp = 16 * ((cfg->dim + 15) / 16);
+    h->fit = new GmmFit();
+    h->clu = new Cluster();
+    h->clu->n_components = cfg->n_components;
+    h->clu->whiten = cfg->whiten;
+    h->clu->d_clu = cfg->cluster_dims;
+    h->clu->d_pad = cluster_pad_dims(cfg->cluster_dims);
+    *out = h;
+    return VSSR_OK;
+}
+
+int vssr_cluster_append_rows(vssr_handle *h, int64_t n_rows, const double *x) {
+    VSSR_CLUSTER_HANDLE(h);
+    if (n_rows < 1 || !x) return set_err(h, VSSR_E_BADARG, "clustering: null or empty rows");
+    if (n_rows > (int64_t)INT32_MAX - 64) return set_err(h, VSSR_E_BADARG, "clustering: n_rows %lld out of range", (long long)n_rows);
+    const size_t tot = (size_t)n_rows * h->gmm_D;
+    for (size_t i = 0; i < tot; ++i)
+        if (!std::isfinite(x[i])) return set_err(h, VSSR_E_BADARG, "clustering: row %zu holds a non-finite value", i / h->gmm_D);
+    int rc = fit_device(h);
+    if (rc) return rc;
+    h->clu->pca_done = false;
+    return gmm_fit_append_host(h, n_rows, x);
+}
+
+int vssr_cluster_append_batch(vssr_handle *h, vssr_handle *painn, int32_t model) {
+    VSSR_CLUSTER_HANDLE(h);
+    h->clu->pca_done = false;
+    return fit_append_batch(h, painn, model, 1);
+}
+
+int vssr_cluster_clear(vssr_handle *h) {
+    VSSR_CLUSTER_HANDLE(h);
+    h->fit->n = 0;
+    h->clu->pca_done = false;
+    h->clu->n_pts = 0;
+    return VSSR_OK;
+}
+
+int vssr_cluster_pca(vssr_handle *h, vssr_cluster_pca_result *result) {
+    VSSR_CLUSTER_HANDLE(h);
+    const int64_t n = h->fit->n;
+    if (n < 2) return set_err(h, VSSR_E_BADARG, "clustering: the PCA needs at least 2 rows (%lld resident)", (long long)n);
+    if (h->clu->n_components > n)
+        return set_err(h, VSSR_E_BADARG, "clustering: n_components = %d must be between 0 and min(n_samples, n_features) = %lld",
+                       h->clu->n_components, (long long)std::min<int64_t>(n, h->gmm_D));
+    if (h->clu->d_clu > h->clu->n_components)
+        return set_err(h, VSSR_E_BADARG, "clustering: cluster_dims %d exceeds n_components %d", h->clu->d_clu, h->clu->n_components);
+    int rc = fit_device(h);
+    if (rc) return rc;
+    return cluster_pca(h, result);
+}
+
+int vssr_cluster_pca_params(vssr_handle *h, double *mean, double *components, double *explained_variance, double *ratio) {
+    VSSR_CLUSTER_HANDLE(h);
+    if (!h->clu->pca_done) return set_err(h, VSSR_E_STATE, "clustering: no completed PCA");
+    VSSR_HIP(h, hipSetDevice(h->device));
+    return cluster_pca_params(h, mean, components, explained_variance, ratio);
+}
+
+int vssr_cluster_projected(vssr_handle *h, int64_t first, int64_t n_rows, double *xr) {
+    VSSR_CLUSTER_HANDLE(h);
+    if (!h->clu->pca_done) return set_err(h, VSSR_E_STATE, "clustering: no completed PCA");
+    if (!xr || first < 0 || n_rows < 0 || first + n_rows > h->fit->n)
+        return set_err(h, VSSR_E_BADARG, "clustering: rows %lld .. %lld outside the %lld fitted rows", (long long)first,
+                       (long long)(first + n_rows), (long long)h->fit->n);
+    if (n_rows == 0) return VSSR_OK;
+    VSSR_HIP(h, hipSetDevice(h->device));
+    return cluster_projected(h, first, n_rows, xr);
+}
+
+int vssr_cluster_set_points(vssr_handle *h, int64_t n, const double *p) {
+    VSSR_CLUSTER_HANDLE(h);
+    if (n < 2 || !p) return set_err(h, VSSR_E_BADARG, "clustering: at least 2 points are needed");
+    if (n > (int64_t)INT32_MAX - 64) return set_err(h, VSSR_E_BADARG, "clustering: %lld points out of range", (long long)n);
+    const size_t tot = (size_t)n * h->clu->d_clu;
+    for (size_t i = 0; i < tot; ++i)
+        if (!std::isfinite(p[i])) return set_err(h, VSSR_E_BADARG, "clustering: point %zu holds a non-finite value", i / h->clu->d_clu);
+    int rc = fit_device(h);
+    if (rc) return rc;
+    return cluster_set_points(h, n, p);
+}
+
+int vssr_cluster_linkage(vssr_handle *h, double *Z, int32_t *n_rounds) {
+    VSSR_CLUSTER_HANDLE(h);
+    if (!Z) return set_err(h, VSSR_E_BADARG, "null argument");
+    if (h->clu->n_pts < 2) return set_err(h, VSSR_E_STATE, "clustering: no points (run vssr_cluster_pca or vssr_cluster_set_points first)");
+    VSSR_HIP(h, hipSetDevice(h->device));
+    return cluster_linkage(h, Z, n_rounds);
 }
 
 }  // extern "C"

@@ -256,11 +256,28 @@ struct GmmFit {
     }
 };
 
+// State of a latent-space clustering (handle kind 7, cluster.hip).  The rows live in the handle's GmmFit (x / n / cap: the append paths
+// of the mixture fit serve both kinds); everything below is the PCA and the Ward linkage.
+struct Cluster {
+    int n_components = 0, whiten = 1, d_clu = 3, d_pad = 3;   // d_pad: d_clu rounded up to 1, 2, 3, 4, 8, 16 or 32 (zero coordinates)
+    bool pca_done = false;
+    int64_t n_pts = 0;             // points resident for the linkage (from the PCA or from vssr_cluster_set_points)
+    DevBuf mean, denom, part_sum, part_cov, cov, evec, eval, comp, comp_t, ev, ratio, jac, xr;   // PCA
+    DevBuf pts;                    // [n_pts][d_pad] fp64
+    DevBuf cen[2], siz[2], cid[2]; // live clusters, double buffered: centroids [m][d_pad], sizes [m], ids [m]
+    DevBuf nn, flag, blk, rec, counters;
+    void release() {
+        DevBuf *bufs[] = {&mean, &denom, &part_sum, &part_cov, &cov, &evec, &eval, &comp, &comp_t, &ev, &ratio, &jac, &xr, &pts,
+                          &cen[0], &cen[1], &siz[0], &siz[1], &cid[0], &cid[1], &nn, &flag, &blk, &rec, &counters};
+        for (DevBuf *b : bufs) b->release();
+    }
+};
+
 }  // namespace vssr
 
 struct vssr_handle {
     int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber, 5 = Gaussian mixture (gmm.hip),
-                   // 6 = Gaussian-mixture fit (gmm_fit.hip)
+                   // 6 = Gaussian-mixture fit (gmm_fit.hip), 7 = latent-space clustering (cluster.hip)
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in ters_params
     int eam_nel = 0, eam_fs = 0;   // EAM with typed tables (vssr_eam_create_alloy): elements, 1 = eam/fs densities; 0 = one funcfl
     int device = 0;
@@ -382,7 +399,8 @@ struct vssr_handle {
     vssr::DevBuf d_gmm_kc;    // double [2][K]       log det P_k, log w_k
     vssr::DevBuf d_gmm_mask;  // uint8 [K][Dp/16][Dp/16]  1 = the 16 x 16 block of P_k holds a non-zero entry
     vssr::DevBuf d_gmm_x, d_gmm_lp, d_gmm_nll, d_gmm_sys, d_gmm_start;   // per-call workspaces
-    vssr::GmmFit *fit = nullptr;   // kind 6 only
+    vssr::GmmFit *fit = nullptr;   // kinds 6 and 7 (7: the resident rows only)
+    vssr::Cluster *clu = nullptr;  // kind 7 only
 };
 
 namespace vssr {
@@ -432,6 +450,16 @@ int gmm_fit_set_init(vssr_handle *h, const double *means, const double *weights,
 int gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res);
 int gmm_fit_params(vssr_handle *h, double *weights, double *means, double *covariances, double *prec_chol);
 int gmm_fit_copy_scorer(vssr_handle *h, vssr_handle *g);   // the fitted mixture into the scoring buffers of a kind-5 handle
+// cov [Dp][Dp] = sum_n (x_n - mean)(x_n - mean)^T / denom[0] on the fit's row-slab MFMA kernel (mean [Dp], denom [1]: device)
+int gmm_fit_centered_cov(vssr_handle *h, hipStream_t st, const double *X, int n, int D, int Dp, const double *mean, const double *denom,
+                         DevBuf &part, double *cov);
+// Latent-space clustering (cluster.hip): PCA of the rows resident in h->fit->x, Ward linkage of the resident points
+int cluster_pca(vssr_handle *h, vssr_cluster_pca_result *res);
+int cluster_pca_params(vssr_handle *h, double *mean, double *components, double *explained_variance, double *ratio);
+int cluster_projected(vssr_handle *h, int64_t first, int64_t n_rows, double *xr);
+int cluster_set_points(vssr_handle *h, int64_t n, const double *pts);
+int cluster_linkage(vssr_handle *h, double *Z, int32_t *n_rounds);
+int cluster_pad_dims(int d);   // stored width of a point: 1, 2, 3, 4, 8, 16 or 32 coordinates
 // the fp64 analytic potentials (Tersoff, EAM, SW): same result buffers (d_ters_e / _ea / _f), same drivers
 inline bool is_f64_kind(const vssr_handle *h) { return h->kind == 2 || h->kind == 3 || h->kind == 4; }
 inline int f64_run(vssr_handle *h, uint32_t want) {

@@ -65,6 +65,37 @@ def install_uncertainty(keep=(), package: str = "mcmc.uncertainty") -> dict:
     return done
 
 
+# reference clustering names (mcmc.utils.clustering) -> attribute of surface_sampling_amd.clustering: scripts/clustering.py clusters the
+# embedding rows with perform_clustering and keeps one structure per cluster with select_data_and_save
+CLUSTERING_REPLACEMENTS = ("perform_clustering", "select_data_and_save", "get_cluster_centers", "find_closest_points_indices")
+
+
+def install_clustering(keep=(), package: str = "mcmc.utils") -> dict:
+    """Replace the clustering functions of ``mcmc.utils.clustering`` (and of ``mcmc.utils`` where it re-exports them); nothing happens
+    when the reference's package is not importable.  Returns {name: replacement} of what was replaced."""
+    from . import clustering as ours
+
+    try:
+        mod = importlib.import_module(package + ".clustering")
+    except ImportError:
+        return {}
+    targets = [mod]
+    try:
+        targets.append(importlib.import_module(package))
+    except ImportError:
+        pass
+    done = {}
+    for name in CLUSTERING_REPLACEMENTS:
+        if name in keep:
+            continue
+        repl = getattr(ours, name)
+        for t in targets:
+            if t is mod or hasattr(t, name):
+                setattr(t, name, repl)
+        done[name] = repl
+    return done
+
+
 def install(keep=(), package: str = "mcmc.calculators") -> dict:
     """Patch the reference's calculator namespace; returns {name: replacement} of what was replaced."""
     from . import calculators as ours
@@ -109,6 +140,7 @@ def main(argv=None) -> int:
     if not done:
         raise SystemExit("mcmc.calculators exposes none of the classes this backend replaces")
     install_uncertainty(keep)
+    install_clustering(keep)
     script = argv[0]
     sys.argv = argv                      # the script parses its own arguments
     runpy.run_path(script, run_name="__main__")
