@@ -275,7 +275,15 @@ int vssr_batch_saturated(vssr_handle *h, uint8_t *flags, int32_t *n_flagged);
  * reverse pass leaves dE/d r for every directed edge on the device, and sigma_ab = (1/V) sum_edges (dE/d r_a) r_b.
  * stress, stress_std (may be NULL): [B][6] fp64, Voigt order xx yy zz yz xz xy, eV / A^3, ASE's sign convention; ensemble
  * mean and population standard deviation over the models.  V = |det cell| (also for slabs with a vacuum axis, as ASE).
- * PaiNN handles only (VSSR_E_STATE otherwise, after an energies-only run, or after a relaxation that left a partial graph). */
+ * Tersoff, EAM (funcfl, eam/alloy, eam/fs, mixed) and Stillinger-Weber handles are served the same way, in fp64: the "stress" the
+ * reference's LAMMPSRun fills from pxx .. pxy (mcmc/calculators/lammpsrun.py:456-465).  Tersoff / SW: from the per-slot gradients
+ * dE_i / d r_ij of the last evaluation; EAM: the pair derivative of every edge is recomputed from the F'(rho) it left.  One model:
+ * stress_std is all zeros.  The kernels run only inside this call; an evaluation that is not asked for stress costs nothing extra.
+ * VSSR_E_STATE: before any run, for a handle of another kind, after a run that was not asked for forces, or after a relaxation that
+ * left a partial graph -- a lock-step relaxation during which chains converged early, and the chain-resident CG minimiser
+ * (vssr_batch_relax_cg on Tersoff chains of <= 256 atoms), which leaves no batch-wide gradients: run the batch once
+ * (vssr_batch_run), then ask.  After a lock-step relaxation that ended with its batch-wide evaluation the stress is that of the
+ * relaxed geometry. */
 int vssr_batch_stress(vssr_handle *h, double *stress, double *stress_std);
 /* The handle's HIP device ordinal, its stream (hipStream_t: every kernel of the handle is enqueued there) and the device
  * address of the neighbor-capacity overflow flag of the last run (int32, non-zero = the run's results are void and

@@ -426,8 +426,11 @@ class _Handle:
 
     def stress(self):
         """``(stress [B, 6], stress_std [B, 6])`` float64, Voigt order xx yy zz yz xz xy in eV / A^3 (ASE's convention): the
-        virial of the LAST evaluation of every chain, from the edge gradients its reverse pass left on the device
-        (vssr_batch_stress; the run must have produced forces)."""
+        virial of the LAST evaluation of every chain, from what that evaluation left on the device (vssr_batch_stress; the run
+        must have produced forces).  PaiNN: the edge gradients of the reverse pass, mean and spread over the models.  Tersoff,
+        SW and EAM engines: fp64, one model, ``stress_std`` all zeros.  After a relaxation that left a partial graph (the
+        chain-resident CG of ``relax_cg_f64``, a lock-step relaxation whose chains converged early) the call raises: ``run()``
+        once first."""
         st, sd = np.zeros((self._n_cfg, 6)), np.zeros((self._n_cfg, 6))
         self._check(self._lib.vssr_batch_stress(self._h, _ptr(st, C.c_double), _ptr(sd, C.c_double)))
         return st, sd

@@ -925,9 +925,14 @@ class NFFPourbaix(EnsembleNFFSurface):
 class _AnalyticSurfCalc(_Base):
     """Shared front end of the analytic potentials that the reference evaluates through LAMMPS (Tersoff, EAM): fp64
     ``energy`` / ``per_atom_energies`` / ``forces`` from the device, ``surface_energy`` = potential energy
-    (reference ``calculators.py:707-719,766-777``), batched evaluation and lock-step relaxation for ``mc.ChainEnsemble``."""
+    (reference ``calculators.py:707-719,766-777``), batched evaluation and lock-step relaxation for ``mc.ChainEnsemble``.
+    ``stress`` (Voigt 6-vector, eV / A^3, ASE's sign: what ``ase.Atoms.get_stress`` asks for and the reference's ``lammpsrun``
+    fills from ``pxx .. pxy``) is the device virial of the same evaluation (``vssr_batch_stress``), computed only when a call
+    asks for it."""
 
-    implemented_properties = ("energy", "relaxed_energy", "forces", "per_atom_energies", "surface_energy")
+    # what a calculate() without ``properties`` produces (its default argument); "stress" is served on request only
+    _default_properties = ("energy", "relaxed_energy", "forces", "per_atom_energies", "surface_energy")
+    implemented_properties = (*_default_properties, "stress")
     species: list = []
 
     def _init_common(self, device, all_periodic, logger):
@@ -983,14 +988,19 @@ class _AnalyticSurfCalc(_Base):
             atoms = self.atoms
         return self.get_potential_energy(atoms=atoms)
 
-    def calculate(self, atoms=None, properties=implemented_properties, system_changes=all_changes):
+    def calculate(self, atoms=None, properties=_default_properties, system_changes=all_changes):
         if atoms is None:
             atoms = self.atoms
         _Base.calculate(self, atoms, properties, system_changes)
-        e, ea, f = self._get_engine().evaluate_f64([self._pack(atoms)])
+        eng = self._get_engine()
+        e, ea, f = eng.evaluate_f64([self._pack(atoms)])
         self.results["energy"] = float(e[0])
         self.results["per_atom_energies"] = ea
         self.results["forces"] = f
+        # the virial of THIS evaluation, or none: an entry an earlier call left behind must not answer a later get_stress()
+        self.results.pop("stress", None)
+        if "stress" in properties:
+            self.results["stress"] = eng.stress()[0][0]
         if "relaxed_energy" in properties:   # reference calculators.py:688-691
             _, e_rel, ea_rel = self.run_lammps_opt(atoms)
             self.results["relaxed_energy"] = e_rel
@@ -1038,13 +1048,14 @@ class _AnalyticSurfCalc(_Base):
     MAX_FORCE_THRESHOLD = 1000.0
 
     def relax_batch(self, atoms_list, fixed_indices=None, relax_steps: int | None = None, fmax: float = 0.01,
-                    optimizer=None, **kwargs):
+                    optimizer=None, want_stress: bool = False, **kwargs):
         """Relax B slabs in ONE lock-step call -- what ``mc.ChainEnsemble(relax=True)`` needs from a calculator.  Default
         ``optimizer`` "LAMMPS" / "CG": the reference's GaN minimiser (``optimize_slab(optimizer="LAMMPS")`` ->
         ``run_lammps_opt``, ``mcmc/dynamics.py:107-116``) for all slabs at once (``vssr_batch_relax_cg``); "FIRE" / "BFGS"
         use the ASE-style optimizers with ``fmax``.  ``relax_steps`` defaults to ``self.relax_steps`` (the reference takes it
         from ``calc.relax_steps``).  Returns per slab ``(relaxed, None, energy, energy_oob, results)`` like
-        ``EnsembleNFFSurface.relax_batch``; results carry ``per_atom_energies`` of the relaxed slab."""
+        ``EnsembleNFFSurface.relax_batch``; results carry ``per_atom_energies`` of the relaxed slab, with ``want_stress`` also its
+        ``stress``."""
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "LAMMPS")
         steps = int(self.relax_steps if relax_steps is None else relax_steps)
@@ -1066,6 +1077,9 @@ class _AnalyticSurfCalc(_Base):
         else:
             e, ea, f, pos, nst, conv = eng.relax_f64(packs, fixed=fixed, max_steps=steps, fmax=fmax, optimizer=optimizer)
             extra = [{"n_steps": int(nst[b]), "converged": bool(conv[b])} for b in range(len(packs))]
+        # (both relaxation calls end with one plain evaluation of the relaxed geometries -- also after the chain-resident CG, which
+        # leaves no batch-wide gradients: the virial is that of the relaxed slabs)
+        stress = eng.stress()[0] if want_stress else None
         out, o = [], 0
         for b, (atoms, p) in enumerate(zip(atoms_list, packs)):
             n = len(p[0])
@@ -1076,17 +1090,23 @@ class _AnalyticSurfCalc(_Base):
             oob = bool(not np.isfinite(energy) or not np.isfinite(max_force) or abs(energy) > self.ENERGY_THRESHOLD
                        or max_force > self.MAX_FORCE_THRESHOLD)
             r = {"energy": energy, "per_atom_energies": ea[o:o + n].copy(), "forces": f[o:o + n].copy(), **extra[b]}
+            if stress is not None:
+                r["stress"] = stress[b].copy()
             out.append((relaxed, None, self.ENERGY_THRESHOLD if oob else energy, oob, r))
             o += n
         return out
 
-    def calculate_batch(self, atoms_list) -> list[dict]:
+    def calculate_batch(self, atoms_list, want_stress: bool = False) -> list[dict]:
         packs = [self._pack(a) for a in atoms_list]
-        e, ea, f = self._get_engine().evaluate_f64(packs)
+        eng = self._get_engine()
+        e, ea, f = eng.evaluate_f64(packs)
+        stress = eng.stress()[0] if want_stress else None
         out, o = [], 0
         for b, p in enumerate(packs):
             n = len(p[0])
             out.append({"energy": float(e[b]), "per_atom_energies": ea[o:o + n].copy(), "forces": f[o:o + n].copy()})
+            if stress is not None:
+                out[-1]["stress"] = stress[b].copy()
             o += n
         return out
 
@@ -1309,9 +1329,11 @@ class EAMSurfCalc(_AnalyticSurfCalc):
 
     Atoms map to types by symbol: ``specorder`` (ASE's keyword) when given, else the elements ``pair_coeff`` names; an atom of
     another element is refused.  ``pair_coeff`` file names are matched against ``files`` (path or base name), else opened as
-    given.  Boundary conditions follow the atoms' ``pbc`` (ASE lammpsrun derives ``boundary`` from it)."""
+    given.  Boundary conditions follow the atoms' ``pbc`` (ASE lammpsrun derives ``boundary`` from it).  ``free_energy`` (= ``energy``)
+    and ``energies`` (= ``per_atom_energies``) are the names the reference's class lists (``lammpsrun.py:125``), filled on request."""
 
     name = "eam_mi355x"
+    implemented_properties = (*_AnalyticSurfCalc.implemented_properties, "free_energy", "energies")
 
     def __init__(self, files=None, potential=None, device="cuda", all_periodic=False, logger=None, keep_tmp_files=False,
                  keep_alive=False, tmp_dir=None, **kwargs):
@@ -1331,6 +1353,13 @@ class EAMSurfCalc(_AnalyticSurfCalc):
             self.species = []
         self._init_common(device, all_periodic, logger)
         super().__init__(**kwargs)
+
+    def calculate(self, atoms=None, properties=_AnalyticSurfCalc._default_properties, system_changes=all_changes):
+        super().calculate(atoms, properties, system_changes)
+        for name, source in (("free_energy", "energy"), ("energies", "per_atom_energies")):
+            self.results.pop(name, None)
+            if name in properties:
+                self.results[name] = self.results[source]
 
     def _file_text(self, name):
         from . import eam as eam_io

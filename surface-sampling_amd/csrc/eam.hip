@@ -10,7 +10,7 @@
 // One thread owns one centre and walks its CSR row (padded multigraph of nbr.hip, cutoff = the file's cutoff):
 // pass 1 densities and F'(rho_i); pass 2 energies and the force sum_slots [(F'_i + F'_j) rho'(r) + phi'(r)] r_hat --
 // every pair is seen from both ends, so there is no scatter and no atomics.
-#include "vssr_internal.h"
+#include "virial_dev.h"
 
 namespace vssr {
 
@@ -226,6 +226,115 @@ __global__ void k_eam_force_typed(int N, vssr_eam_grid g, EamTyped T, const int 
     forces[3 * i] = f0; forces[3 * i + 1] = f1; forces[3 * i + 2] = f2;
 }
 
+// ---- virial stress (vssr_batch_stress) ---------------------------------------------------------------------------------------
+// There are no per-slot gradients to read: every directed edge recomputes psip = dE / d r of its pair exactly as the force kernels do,
+// from the F'(rho) of the last run (fp: the linear continuation of F beyond the table is inside it), and W_ab = 1/2 sum over the
+// directed edges of psip r_a r_b / d -- every pair is seen from both ends.  Lane layout and reduction: virial_dev.h.
+__global__ void __launch_bounds__(VIR_THREADS)
+k_eam_stress(vssr_eam_grid g, const double *__restrict__ rhor, const double *__restrict__ z2r, const int *__restrict__ cfg_start,
+             const double *__restrict__ cell, const double *__restrict__ wpos, const int *__restrict__ row_start,
+             const float4 *__restrict__ edge, const int *__restrict__ edge_S, const int *__restrict__ counters,
+             const double *__restrict__ fp, double *__restrict__ stress, double *__restrict__ stress_std) {
+    __shared__ double red[6][VIR_THREADS];
+    const int b = blockIdx.x, q = threadIdx.x % VIR_LANES;
+    if (counters[2]) return;   // (uniform)
+    const double *C = cell + 9 * (size_t)b;
+    double w[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = cfg_start[b] + threadIdx.x / VIR_LANES; i < cfg_start[b + 1]; i += VIR_THREADS / VIR_LANES) {
+        const double fpi = fp[i];
+        for (int e = row_start[i] + q; e < row_start[i + 1]; e += VIR_LANES) {
+            const int j = __float_as_int(edge[e].w);
+            if (j < 0) continue;
+            double r[3];
+            eam_edge(wpos, C, i, j, edge_S[e], r);
+            const double d = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            if (d >= g.cutoff) continue;
+            double rh, drh, z, dz;
+            eam_eval(rhor, g.nr, d, 1.0 / g.dr, false, rh, drh);
+            eam_eval(z2r, g.nr, d, 1.0 / g.dr, false, z, dz);
+            const double recip = 1.0 / d;
+            const double phi = z * recip;
+            const double phip = dz * recip - phi * recip;
+            const double psip = (fpi + fp[j]) * drh + phip;
+            const double s = psip * recip;
+            virial_add(w, s * r[0], s * r[1], s * r[2], r[0], r[1], r[2]);
+        }
+    }
+    virial_reduce_store(red, w, 0.5, b, cell, stress, stress_std);
+}
+
+__global__ void __launch_bounds__(VIR_THREADS)
+k_eam_stress_typed(vssr_eam_grid g, EamTyped T, const int *__restrict__ type, const int *__restrict__ cfg_start,
+                   const double *__restrict__ cell, const double *__restrict__ wpos, const int *__restrict__ row_start,
+                   const float4 *__restrict__ edge, const int *__restrict__ edge_S, const int *__restrict__ counters,
+                   const double *__restrict__ fp, double *__restrict__ stress, double *__restrict__ stress_std) {
+    __shared__ double red[6][VIR_THREADS];
+    const int b = blockIdx.x, q = threadIdx.x % VIR_LANES;
+    if (counters[2]) return;   // (uniform)
+    const double *C = cell + 9 * (size_t)b;
+    double w[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = cfg_start[b] + threadIdx.x / VIR_LANES; i < cfg_start[b + 1]; i += VIR_THREADS / VIR_LANES) {
+        const int ti = type[i];
+        const double fpi = fp[i];
+        for (int e = row_start[i] + q; e < row_start[i + 1]; e += VIR_LANES) {
+            const int j = __float_as_int(edge[e].w);
+            if (j < 0) continue;
+            double r[3];
+            eam_edge(wpos, C, i, j, edge_S[e], r);
+            const double d = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            if (d >= g.cutoff) continue;
+            const int tj = type[j];
+            double rh, drh_ji, z, dz;
+            eam_eval(T.rho_tab(tj, ti), g.nr, d, 1.0 / g.dr, false, rh, drh_ji);   // rho of j at i
+            eam_eval(T.z2r_tab(ti, tj), g.nr, d, 1.0 / g.dr, false, z, dz);
+            double dE;
+            if (ti == tj) {
+                dE = (fpi + fp[j]) * drh_ji;
+            } else {
+                double rh2, drh_ij;
+                eam_eval(T.rho_tab(ti, tj), g.nr, d, 1.0 / g.dr, false, rh2, drh_ij);   // rho of i at j
+                dE = fpi * drh_ji + fp[j] * drh_ij;
+            }
+            const double recip = 1.0 / d;
+            const double phi = z * recip;
+            const double phip = dz * recip - phi * recip;
+            const double psip = dE + phip;
+            const double s = psip * recip;
+            virial_add(w, s * r[0], s * r[1], s * r[2], r[0], r[1], r[2]);
+        }
+    }
+    virial_reduce_store(red, w, 0.5, b, cell, stress, stress_std);
+}
+
+// the typed tables of a handle of several elements (layout: see EamTyped)
+static EamTyped eam_typed_view(const vssr_handle *h) {
+    const int n = h->eam_nel;
+    const double *frho = h->ters_params.as<double>();
+    return EamTyped{frho, frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n,
+                    frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n + 7 * (size_t)(h->eam_grid.nr + 1) * (h->eam_fs ? n * n : n),
+                    n, h->eam_fs, 7 * (size_t)(h->eam_grid.nrho + 1), 7 * (size_t)(h->eam_grid.nr + 1)};
+}
+
+int eam_stress(vssr_handle *h) {
+    if (h->d_stress.ensure(sizeof(double) * 12 * (size_t)h->n_cfg)) return set_err(h, VSSR_E_NOMEM, "out of device memory (stress)");
+    double *out = h->d_stress.as<double>(), *out_std = out + 6 * (size_t)h->n_cfg;
+    const double *fp = h->d_gbar.as<double>() + h->n_atoms;   // e_embed | fp (eam_run)
+    if (h->eam_nel > 0) {
+        hipLaunchKernelGGL(k_eam_stress_typed, dim3(h->n_cfg), dim3(VIR_THREADS), 0, h->stream, h->eam_grid, eam_typed_view(h),
+                           h->d_Z.as<int>(), h->d_cfg_start.as<int>(), h->d_cell.as<double>(), h->d_wpos.as<double>(),
+                           h->d_row_start.as<int>(), h->d_edge.as<float4>(), h->d_edge_S.as<int>(), h->d_counters.as<int>(), fp, out,
+                           out_std);
+    } else {
+        const double *rhor = h->ters_params.as<double>() + 7 * (size_t)(h->eam_grid.nrho + 1);
+        const double *z2r = rhor + 7 * (size_t)(h->eam_grid.nr + 1);
+        hipLaunchKernelGGL(k_eam_stress, dim3(h->n_cfg), dim3(VIR_THREADS), 0, h->stream, h->eam_grid, rhor, z2r, h->d_cfg_start.as<int>(),
+                           h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
+                           h->d_edge_S.as<int>(), h->d_counters.as<int>(), fp, out, out_std);
+    }
+    VSSR_HIP(h, hipGetLastError());
+    return VSSR_OK;
+}
+
 int eam_run(vssr_handle *h, uint32_t want) {
     (void)want;
     const int N = h->n_atoms;
@@ -243,10 +352,7 @@ int eam_run(vssr_handle *h, uint32_t want) {
     dim3 blk(64), grd((N + 63) / 64);
     const ActiveView av{h->active_mask, h->d_atom_cfg.as<int>()};
     if (h->eam_nel > 0) {
-        const int n = h->eam_nel;
-        const EamTyped T{frho, frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n,
-                         frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n + 7 * (size_t)(h->eam_grid.nr + 1) * (h->eam_fs ? n * n : n),
-                         n, h->eam_fs, 7 * (size_t)(h->eam_grid.nrho + 1), 7 * (size_t)(h->eam_grid.nr + 1)};
+        const EamTyped T = eam_typed_view(h);
         hipLaunchKernelGGL(k_eam_density_typed, grd, blk, 0, st, N, h->eam_grid, T, h->d_Z.as<int>(), h->d_atom_cfg.as<int>(),
                            h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
                            h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, av);

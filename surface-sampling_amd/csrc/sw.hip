@@ -48,6 +48,8 @@ k_sw_energy(const int *__restrict__ cfg_start, const double *__restrict__ e_atom
     tersoff_chain_energy(b, red, cfg_start, e_atom, energy);
 }
 
+int sw_stress(vssr_handle *h) { return slot_stress(h, h->d_gbar.as<double>() + 2 * h->slot_cap); }   // eo | ej | G (sw_run)
+
 int sw_run(vssr_handle *h, uint32_t want) {
     (void)want;
     const int N = h->n_atoms;

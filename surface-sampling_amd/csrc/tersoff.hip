@@ -23,6 +23,7 @@
 //   pass 2 (slot n as k): G_n += sum_m pref_m dzeta_mn/dr_n
 // so every G is produced by one lane (stored by pass 1, completed by pass 2), without atomics.
 #include "tersoff_dev.h"
+#include "virial_dev.h"
 
 namespace vssr {
 
@@ -68,6 +69,43 @@ k_tersoff_energy(const int *__restrict__ cfg_start, const double *__restrict__ e
     if (active && !active[b]) return;
     tersoff_chain_energy(b, red, cfg_start, e_atom, energy);
 }
+
+// Virial stress of every chain from the per-slot gradients G_slot = dE_i / d r_ij the last evaluation left behind (either form of the
+// site kernel writes every slot of its rows, padding slots as zeros): W_ab = sum over the chain's slots of G_a r_b with r rebuilt in
+// fp64 as the site kernels build it (virial_dev.h).  Serves the Stillinger-Weber handles too (sw.hip leaves the same array).
+__global__ void __launch_bounds__(VIR_THREADS)
+k_slot_stress(const int *__restrict__ cfg_start, const int *__restrict__ row_start, const float4 *__restrict__ edge,
+              const int *__restrict__ edge_S, const int *__restrict__ counters, const double *__restrict__ cell,
+              const double *__restrict__ wpos, const double *__restrict__ gslot, double *__restrict__ stress,
+              double *__restrict__ stress_std) {
+    __shared__ double red[6][VIR_THREADS];
+    const int b = blockIdx.x, q = threadIdx.x % VIR_LANES;
+    if (counters[2]) return;   // (uniform)
+    const double *C = cell + 9 * (size_t)b;
+    double w[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = cfg_start[b] + threadIdx.x / VIR_LANES; i < cfg_start[b + 1]; i += VIR_THREADS / VIR_LANES)
+        for (int e = row_start[i] + q; e < row_start[i + 1]; e += VIR_LANES) {
+            const int j = __float_as_int(edge[e].w);
+            if (j < 0) continue;   // padding slot
+            double r[3];
+            edge_vec(wpos, C, i, j, edge_S[e], r);
+            virial_add(w, gslot[3 * (size_t)e], gslot[3 * (size_t)e + 1], gslot[3 * (size_t)e + 2], r[0], r[1], r[2]);
+        }
+    virial_reduce_store(red, w, 1.0, b, cell, stress, stress_std);
+}
+
+// vssr_batch_stress on a Tersoff or Stillinger-Weber handle: enqueues k_slot_stress (gslot: where the handle's run keeps G in d_gbar)
+int slot_stress(vssr_handle *h, const double *gslot) {
+    if (h->d_stress.ensure(sizeof(double) * 12 * (size_t)h->n_cfg)) return set_err(h, VSSR_E_NOMEM, "out of device memory (stress)");
+    double *out = h->d_stress.as<double>();
+    hipLaunchKernelGGL(k_slot_stress, dim3(h->n_cfg), dim3(VIR_THREADS), 0, h->stream, h->d_cfg_start.as<int>(), h->d_row_start.as<int>(),
+                       h->d_edge.as<float4>(), h->d_edge_S.as<int>(), h->d_counters.as<int>(), h->d_cell.as<double>(),
+                       h->d_wpos.as<double>(), gslot, out, out + 6 * (size_t)h->n_cfg);
+    VSSR_HIP(h, hipGetLastError());
+    return VSSR_OK;
+}
+
+int tersoff_stress(vssr_handle *h) { return slot_stress(h, h->d_gbar.as<double>() + h->slot_cap); }   // eps | G (tersoff_run)
 
 int tersoff_run(vssr_handle *h, uint32_t want) {
     (void)want;

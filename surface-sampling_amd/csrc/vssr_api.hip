@@ -1176,15 +1176,15 @@ int vssr_batch_embedding(vssr_handle *h, int32_t model, float *dst, int64_t cap,
 int vssr_batch_stress(vssr_handle *h, double *stress, double *stress_std) {
     if (!h) return VSSR_E_BADARG;
     VSSR_REFUSE_GMM(h);
-    if (!h->ran || h->kind != 1) return set_err(h, VSSR_E_STATE, "no completed PaiNN run");
+    if (!h->ran || !(h->kind == 1 || is_f64_kind(h))) return set_err(h, VSSR_E_STATE, "no completed PaiNN, Tersoff, EAM or Stillinger-Weber run");
     if (!(h->last_want & VSSR_WANT_FORCES))
         return set_err(h, VSSR_E_STATE, "stress needs the edge gradients of a run that produced forces; the last run was asked for energies only");
-    if (h->graph_partial)
+    if (h->graph_partial)   // (after the chain-resident CG minimiser too: it numbers its rows per chain and leaves no batch-wide gradients)
         return set_err(h, VSSR_E_STATE, "the resident graph covers only the chains of the last relaxation iteration: run the batch once (vssr_batch_run) first");
     VSSR_HIP(h, hipSetDevice(h->device));
     int rc = sync_and_check(h);   // (a capacity overflow is repaired here: the gradients below are those of the repeated run)
     if (rc) return rc;
-    rc = painn_stress(h);
+    rc = is_f64_kind(h) ? f64_stress(h) : painn_stress(h);   // fp64 potentials: one model, the spread is written as zeros
     if (rc) return rc;
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
     const size_t n = 6 * (size_t)h->n_cfg;

@@ -465,6 +465,13 @@ inline bool is_f64_kind(const vssr_handle *h) { return h->kind == 2 || h->kind =
 inline int f64_run(vssr_handle *h, uint32_t want) {
     return h->kind == 2 ? tersoff_run(h, want) : h->kind == 3 ? eam_run(h, want) : sw_run(h, want);
 }
+// vssr_batch_stress on these handles: enqueue the virial kernel over what the last run left on the device (d_stress, as painn_stress);
+// nothing of it runs unless asked for.  slot_stress (tersoff.hip): the kernel Tersoff and SW share, gslot = the handle's G array
+int slot_stress(vssr_handle *h, const double *gslot);
+int tersoff_stress(vssr_handle *h);
+int eam_stress(vssr_handle *h);
+int sw_stress(vssr_handle *h);
+inline int f64_stress(vssr_handle *h) { return h->kind == 2 ? tersoff_stress(h) : h->kind == 3 ? eam_stress(h) : sw_stress(h); }
 void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1][7]*/);
 // lock-step FIRE relaxation (relax.hip)
 // method 0: FIRE (fp), 1: BFGS (bp)
