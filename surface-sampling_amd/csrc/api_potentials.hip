@@ -1,0 +1,303 @@
+// api_potentials.hip — the fp64 analytic potentials: Tersoff, EAM and Stillinger-Weber creates, the two LAMMPS text parsers,
+// and the *_eval_batch entry points.
+#include <cmath>
+
+#include "vssr_internal.h"
+#include "sw_dev.h"
+
+using namespace vssr;
+
+// the potential's tables into pot_params; the two messages: out of memory, failed copy
+static int upload_params(vssr_handle *h, const void *src, size_t bytes, const char *nomem, const char *failed) {
+    if (h->pot_params.ensure(bytes)) return set_err(h, VSSR_E_NOMEM, "%s", nomem);
+    if (hipMemcpy(h->pot_params.p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return set_err(h, VSSR_E_DEVICE, "%s", failed);
+    return VSSR_OK;
+}
+
+extern "C" {
+
+int vssr_tersoff_create(int32_t device, int32_t n_types, const double *params, vssr_handle **out) {
+    if (!params || !out || n_types < 1 || n_types > 8) return set_err(nullptr, VSSR_E_BADARG, "bad tersoff arguments");
+    *out = nullptr;
+    return create_handle(Kind::TERSOFF, device, out, [=](vssr_handle *h) {
+        h->n_types = n_types;
+        h->n_embed = n_types;
+        const size_t np = (size_t)n_types * n_types * n_types;
+        double cutmax = 0;
+        for (size_t t = 0; t < np; ++t) {
+            const double *p = params + 14 * t;
+            if (!(p[0] == 1.0 || p[0] == 3.0) || !(p[11] > 0) || !(p[4] != 0)) return set_err(h, VSSR_E_BADARG, "bad tersoff entry %zu", t);
+            if (p[10] + p[11] > cutmax) cutmax = p[10] + p[11];
+        }
+        h->pot_cutoff = cutmax;
+        return upload_params(h, params, sizeof(double) * 14 * np, "tersoff params", "tersoff params upload failed");
+    });
+}
+
+// whitespace-separated tokens of a LAMMPS potential file; `#` starts a comment
+static std::vector<std::string> potential_tokens(const char *param_text) {
+    std::vector<std::string> tok;
+    std::string line, text(param_text);
+    size_t pos = 0;
+    while (pos <= text.size()) {
+        size_t nl = text.find('\n', pos);
+        if (nl == std::string::npos) nl = text.size();
+        line = text.substr(pos, nl - pos);
+        pos = nl + 1;
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        size_t i = 0;
+        while (i < line.size()) {
+            while (i < line.size() && isspace((unsigned char)line[i])) ++i;
+            size_t j = i;
+            while (j < line.size() && !isspace((unsigned char)line[j])) ++j;
+            if (j > i) tok.push_back(line.substr(i, j - i));
+            i = j;
+        }
+    }
+    return tok;
+}
+
+int vssr_tersoff_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
+                                  vssr_handle **out) {
+    if (!param_text || !species || !out || n_species < 1 || n_species > 8)
+        return set_err(nullptr, VSSR_E_BADARG, "bad tersoff arguments");
+    *out = nullptr;
+    const std::vector<std::string> tok = potential_tokens(param_text);
+    if (tok.empty() || tok.size() % 17) return set_err(nullptr, VSSR_E_BADARG, "tersoff file: token count is not a multiple of 17");
+    auto index_of = [&](const std::string &s) {
+        for (int t = 0; t < n_species; ++t)
+            if (species[t] && s == species[t]) return t;
+        return -1;
+    };
+    const size_t np = (size_t)n_species * n_species * n_species;
+    std::vector<double> params(14 * np, 0.0);
+    std::vector<char> seen(np, 0);
+    for (size_t o = 0; o < tok.size(); o += 17) {
+        const int a = index_of(tok[o]), b = index_of(tok[o + 1]), c = index_of(tok[o + 2]);
+        if (a < 0 || b < 0 || c < 0) continue;   // entry of another element
+        const size_t e = ((size_t)a * n_species + b) * n_species + c;
+        for (int k = 0; k < 14; ++k) {
+            char *end = nullptr;
+            params[14 * e + k] = strtod(tok[o + 3 + k].c_str(), &end);
+            if (!end || *end) return set_err(nullptr, VSSR_E_BADARG, "tersoff file: bad number '%s'", tok[o + 3 + k].c_str());
+        }
+        seen[e] = 1;
+    }
+    for (size_t e = 0; e < np; ++e)
+        if (!seen[e]) return set_err(nullptr, VSSR_E_BADARG, "tersoff file lacks entries for some species triplets");
+    return vssr_tersoff_create(device, n_species, params.data(), out);
+}
+
+int vssr_eam_create(int32_t device, const vssr_eam_grid *grid, const double *frho, const double *zr, const double *rhor,
+                    vssr_handle **out) {
+    if (!grid || !frho || !zr || !rhor || !out) return set_err(nullptr, VSSR_E_BADARG, "null EAM argument");
+    *out = nullptr;
+    if (grid->nrho < 5 || grid->nr < 5 || !(grid->drho > 0) || !(grid->dr > 0) || !(grid->cutoff > 0))
+        return set_err(nullptr, VSSR_E_BADARG, "bad EAM grid");
+    return create_handle(Kind::EAM, device, out, [=](vssr_handle *h) {
+        for (int k = 0; k < grid->nrho; ++k)
+            if (!std::isfinite(frho[k])) return set_err(h, VSSR_E_BADARG, "non-finite EAM table entry");
+        for (int k = 0; k < grid->nr; ++k)
+            if (!std::isfinite(zr[k]) || !std::isfinite(rhor[k])) return set_err(h, VSSR_E_BADARG, "non-finite EAM table entry");
+        h->n_types = 1;
+        h->n_embed = 1;
+        h->eam_grid = *grid;
+        // spline tables: frho [nrho + 1][7] | rhor [nr + 1][7] | z2r [nr + 1][7]   (LAMMPS file2array + array2spline for one file)
+        const size_t nF = 7 * (size_t)(grid->nrho + 1), nR = 7 * (size_t)(grid->nr + 1);
+        std::vector<double> tab(nF + 2 * nR), z2r(grid->nr);
+        for (int k = 0; k < grid->nr; ++k) z2r[k] = 27.2 * 0.529 * zr[k] * zr[k];
+        eam_build_spline(frho, grid->nrho, grid->drho, tab.data());
+        eam_build_spline(rhor, grid->nr, grid->dr, tab.data() + nF);
+        eam_build_spline(z2r.data(), grid->nr, grid->dr, tab.data() + nF + nR);
+        return upload_params(h, tab.data(), sizeof(double) * tab.size(), "EAM tables", "EAM table upload failed");
+    });
+}
+
+int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
+                          const double *rhor, const double *z2r, vssr_handle **out) {
+    if (!grid || !frho || !rhor || !z2r || !out) return set_err(nullptr, VSSR_E_BADARG, "null EAM argument");
+    *out = nullptr;
+    if (n_elem < 1 || n_elem > 8) return set_err(nullptr, VSSR_E_BADARG, "EAM: %d elements (1 .. 8 are supported)", n_elem);
+    if (grid->nrho < 5 || grid->nr < 5 || !(grid->drho > 0) || !(grid->dr > 0) || !(grid->cutoff > 0) ||
+        !std::isfinite(grid->drho) || !std::isfinite(grid->dr) || !std::isfinite(grid->cutoff))
+        return set_err(nullptr, VSSR_E_BADARG, "bad EAM grid");
+    const int nR = fs ? n_elem * n_elem : n_elem, nP = n_elem * (n_elem + 1) / 2;
+    const size_t cF = (size_t)n_elem * grid->nrho, cR = (size_t)nR * grid->nr, cP = (size_t)nP * grid->nr;
+    for (size_t k = 0; k < cF; ++k)
+        if (!std::isfinite(frho[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (F)");
+    for (size_t k = 0; k < cR; ++k)
+        if (!std::isfinite(rhor[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (rho)");
+    for (size_t k = 0; k < cP; ++k)
+        if (!std::isfinite(z2r[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (r phi)");
+    return create_handle(Kind::EAM, device, out, [=](vssr_handle *h) {
+        h->n_types = n_elem;
+        h->n_embed = n_elem;   // vssr_batch_upload refuses types outside [0, n_elem)
+        h->eam_nel = n_elem;
+        h->eam_fs = fs ? 1 : 0;
+        h->eam_grid = *grid;
+        // spline tables (eam.hip EamTyped): F [n][nrho + 1][7] | rho [nR][nr + 1][7] | r phi [nP][nr + 1][7]
+        const size_t sF = 7 * (size_t)(grid->nrho + 1), sR = 7 * (size_t)(grid->nr + 1);
+        std::vector<double> tab(sF * n_elem + sR * (nR + nP));
+        for (int t = 0; t < n_elem; ++t) eam_build_spline(frho + (size_t)t * grid->nrho, grid->nrho, grid->drho, tab.data() + sF * t);
+        double *R = tab.data() + sF * n_elem;
+        for (int t = 0; t < nR; ++t) eam_build_spline(rhor + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * t);
+        for (int t = 0; t < nP; ++t) eam_build_spline(z2r + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * (nR + t));
+        return upload_params(h, tab.data(), sizeof(double) * tab.size(), "EAM tables", "EAM table upload failed");
+    });
+}
+
+// ---- Stillinger-Weber ------------------------------------------------------------------------------------------------------
+static const char *const kSwField[11] = {"eps", "sig", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"};
+
+// Checks an [i][j][k] table of 11 LAMMPS columns and derives the kernels' entries (sw_dev.h SwP).  Refused: non-finite numbers,
+// eps / sig / a <= 0, negative lambda / gamma / A / B / p / q / tol (pair_sw.cpp refuses those as well), and (i, j, k) / (i, k, j)
+// pairs that differ in eps, lambda or costheta0 (the LAMMPS energy would depend on the order of its neighbor list).
+static int sw_derive(int nt, const double *params, const char *const *species, std::vector<SwP> &out, double &cutmax) {
+    const size_t np = (size_t)nt * nt * nt;
+    auto name = [&](size_t e, char *buf, size_t n) {
+        const int a = (int)(e / ((size_t)nt * nt)), b = (int)(e / nt % nt), c = (int)(e % nt);
+        if (species) snprintf(buf, n, "%s %s %s", species[a], species[b], species[c]);
+        else snprintf(buf, n, "(%d,%d,%d)", a, b, c);
+    };
+    char nm[96];
+    out.assign(np, SwP{});
+    cutmax = 0.0;
+    for (size_t e = 0; e < np; ++e) {
+        const double *p = params + 11 * e;
+        for (int k = 0; k < 11; ++k) {
+            const bool pos = k == 0 || k == 1 || k == 2;   // eps, sig, a
+            const bool any = k == 5;                       // costheta0: any finite value
+            if (!std::isfinite(p[k]) || (pos && !(p[k] > 0)) || (!pos && !any && !(p[k] >= 0))) {
+                name(e, nm, sizeof nm);
+                return set_err(nullptr, VSSR_E_BADARG, "sw entry %s: bad %s = %g (%s)", nm, kSwField[k], p[k],
+                               pos ? "must be > 0" : any ? "must be finite" : "must be >= 0");
+            }
+        }
+        const double eps = p[0], sig = p[1], a = p[2], lam = p[3], gam = p[4], A = p[6], B = p[7], pp = p[8], qq = p[9];
+        SwP &d = out[e];
+        d.cut = a * sig; d.sig = sig; d.gs = gam * sig;
+        d.c5 = A * eps * B * pow(sig, pp); d.c6 = A * eps * pow(sig, qq);
+        d.p = pp; d.q = qq; d.le = lam * eps; d.c0 = p[5]; d.pad0 = 0.0; d.pad1 = 0.0;
+        if (!std::isfinite(d.c5) || !std::isfinite(d.c6)) {
+            name(e, nm, sizeof nm);
+            return set_err(nullptr, VSSR_E_BADARG, "sw entry %s: A eps B sig^p / A eps sig^q overflow", nm);
+        }
+        cutmax = std::max(cutmax, d.cut);
+    }
+    for (int i = 0; i < nt; ++i)
+        for (int j = 0; j < nt; ++j)
+            for (int k = j + 1; k < nt; ++k) {
+                const double *x = params + 11 * (((size_t)i * nt + j) * nt + k), *y = params + 11 * (((size_t)i * nt + k) * nt + j);
+                for (int f : {0, 3, 5})
+                    if (x[f] != y[f]) {
+                        name(((size_t)i * nt + j) * nt + k, nm, sizeof nm);
+                        char nm2[96];
+                        name(((size_t)i * nt + k) * nt + j, nm2, sizeof nm2);
+                        return set_err(nullptr, VSSR_E_BADARG,
+                                       "sw entries %s and %s differ in %s (%g vs %g): the three-body term would depend on neighbor order",
+                                       nm, nm2, kSwField[f], x[f], y[f]);
+                    }
+            }
+    return VSSR_OK;
+}
+
+static int sw_create_checked(int32_t device, int32_t n_types, const double *params, const char *const *species, vssr_handle **out) {
+    if (!params || !out || n_types < 1 || n_types > 8) return set_err(nullptr, VSSR_E_BADARG, "bad sw arguments (1 .. 8 types)");
+    *out = nullptr;
+    std::vector<SwP> tab;
+    double cutmax = 0.0;
+    int rc = sw_derive(n_types, params, species, tab, cutmax);
+    if (rc) return rc;
+    return create_handle(Kind::SW, device, out, [&](vssr_handle *h) {
+        h->n_types = n_types;
+        h->n_embed = n_types;
+        h->pot_cutoff = cutmax;
+        return upload_params(h, tab.data(), sizeof(SwP) * tab.size(), "sw params", "sw params upload failed");
+    });
+}
+
+int vssr_sw_create(int32_t device, int32_t n_types, const double *params, vssr_handle **out) {
+    return sw_create_checked(device, n_types, params, nullptr, out);
+}
+
+int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
+                             vssr_handle **out) {
+    if (!param_text || !species || !out || n_species < 1 || n_species > 8)
+        return set_err(nullptr, VSSR_E_BADARG, "bad sw arguments (1 .. 8 species)");
+    *out = nullptr;
+    for (int t = 0; t < n_species; ++t)
+        if (!species[t] || !species[t][0]) return set_err(nullptr, VSSR_E_BADARG, "sw: species %d has no name", t);
+    const std::vector<std::string> tok = potential_tokens(param_text);
+    if (tok.empty() || tok.size() % 14)
+        return set_err(nullptr, VSSR_E_BADARG, "sw file: %zu tokens, not a multiple of 14 (e1 e2 e3 + 11 numbers)", tok.size());
+    auto index_of = [&](const std::string &s) {
+        for (int t = 0; t < n_species; ++t)
+            if (s == species[t]) return t;
+        return -1;
+    };
+    const size_t np = (size_t)n_species * n_species * n_species;
+    std::vector<double> params(11 * np, 0.0);
+    std::vector<char> seen(np, 0);
+    for (size_t o = 0; o < tok.size(); o += 14) {
+        const int a = index_of(tok[o]), b = index_of(tok[o + 1]), c = index_of(tok[o + 2]);
+        if (a < 0 || b < 0 || c < 0) continue;   // entry of another element
+        const size_t e = ((size_t)a * n_species + b) * n_species + c;
+        for (int k = 0; k < 11; ++k) {
+            char *end = nullptr;
+            params[11 * e + k] = strtod(tok[o + 3 + k].c_str(), &end);
+            if (!end || *end || end == tok[o + 3 + k].c_str())
+                return set_err(nullptr, VSSR_E_BADARG, "sw file: entry %s %s %s: bad number '%s' for %s", tok[o].c_str(),
+                               tok[o + 1].c_str(), tok[o + 2].c_str(), tok[o + 3 + k].c_str(), kSwField[k]);
+        }
+        seen[e] = 1;
+    }
+    for (size_t e = 0; e < np; ++e)
+        if (!seen[e])
+            return set_err(nullptr, VSSR_E_BADARG, "sw file lacks the entry %s %s %s", species[e / ((size_t)n_species * n_species)],
+                           species[e / n_species % n_species], species[e % n_species]);
+    return sw_create_checked(device, n_species, params.data(), species, out);
+}
+
+}  // extern "C"
+
+// ---- evaluation with fp64 results: one body behind the three exported names ------------------------------------------------------
+static int analytic_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                               const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                               double *energy_atoms_f64, double *forces_f64) {
+    // (a refusal names the Tersoff entry point whichever of the three was called: the message is kept as it always was)
+    if (int rc = check_kind(h, KINDS_EVAL, "vssr_tersoff_eval_batch")) return rc;
+    if (!is_analytic(h)) return set_err(h, VSSR_E_STATE, "not a Tersoff / EAM / SW handle");
+    vssr_out dummy;
+    memset(&dummy, 0, sizeof dummy);
+    int rc = vssr_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out ? out : &dummy);
+    if (rc) return rc;
+    if (energy_f64) VSSR_HIP(h, hipMemcpy(energy_f64, h->d_pot_e.p, sizeof(double) * h->n_cfg, hipMemcpyDeviceToHost));
+    if (energy_atoms_f64)
+        VSSR_HIP(h, hipMemcpy(energy_atoms_f64, h->d_pot_ea.p, sizeof(double) * h->n_atoms, hipMemcpyDeviceToHost));
+    if (forces_f64)
+        VSSR_HIP(h, hipMemcpy(forces_f64, h->d_pot_f.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
+    return VSSR_OK;
+}
+
+extern "C" {
+
+int vssr_tersoff_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type,
+                            const double *pos, const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out,
+                            double *energy_f64, double *energy_atoms_f64, double *forces_f64) {
+    return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
+}
+
+int vssr_eam_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                        const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                        double *energy_atoms_f64, double *forces_f64) {
+    return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
+}
+
+int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                       const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                       double *energy_atoms_f64, double *forces_f64) {
+    return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
+}
+
+}  // extern "C"

@@ -203,7 +203,7 @@ __global__ void k_cm_report(int B, const CgState *__restrict__ st, int *__restri
 // of the site terms as well as the batch-wide kernels do at 12 waves per CU once every CU has work for many rounds.
 // VSSR_CG_FUSED: 0 = always the lock-step driver, 1 = the chain-resident kernel whenever it applies, unset = by batch size.
 bool chain_min_supported(const vssr_handle *h) {
-    if (h->kind != 2 || h->max_cfg_atoms > CM_MAX_ATOMS) return false;
+    if (h->kind != Kind::TERSOFF || h->max_cfg_atoms > CM_MAX_ATOMS) return false;
     const char *e = getenv("VSSR_CG_FUSED");   // (read per call)
     if (e) return atoi(e) != 0;
     // the automatic choice covers the regime that was measured: chains of <= 64 atoms (one site tile per workgroup).  A 200-atom
@@ -212,7 +212,7 @@ bool chain_min_supported(const vssr_handle *h) {
     return h->n_cfg <= 3072 && h->max_cfg_atoms <= 64;
 }
 
-// Same contract as relax_cg (relax.hip): afterwards the batch holds the minimised positions, d_ters_e / _ea / _f the static results of
+// Same contract as relax_cg (relax.hip): afterwards the batch holds the minimised positions, d_pot_e / _ea / _f the static results of
 // those geometries, d_relax_steps [B][3] = (iterations, evaluations, stop reason) per chain.
 int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want) {
     (void)want;
@@ -222,8 +222,8 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         h->d_counters.ensure(sizeof(int) * 4) || h->d_fire.ensure(sizeof(CgState) * (size_t)B) || h->d_vel.ensure(sizeof(double) * 9 * (size_t)N) ||
         h->d_cm.ensure(sizeof(int) * ((size_t)B + 8) + 1024) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
         h->d_wrap.ensure(sizeof(int) * 3 * (size_t)N) || h->d_deg.ensure(sizeof(int) * (size_t)N) ||
-        h->d_row_start.ensure(sizeof(int) * ((size_t)N + B + 1)) || h->d_ters_e.ensure(sizeof(double) * (size_t)B) ||
-        h->d_ters_ea.ensure(sizeof(double) * (size_t)N) || h->d_ters_f.ensure(sizeof(double) * 3 * (size_t)N))
+        h->d_row_start.ensure(sizeof(int) * ((size_t)N + B + 1)) || h->d_pot_e.ensure(sizeof(double) * (size_t)B) ||
+        h->d_pot_ea.ensure(sizeof(double) * (size_t)N) || h->d_pot_f.ensure(sizeof(double) * 3 * (size_t)N))
         return set_err(h, VSSR_E_NOMEM, "chain-resident minimiser: out of device memory");
     const uint8_t *fixed = nullptr;
     if (fixed_host) {
@@ -237,7 +237,7 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
     h->relax_lockstep = 0;
     h->relax_chain_evals = 0;
     h->relax_compactions = 0;
-    const double rc = h->ters_cutmax;
+    const double rc = h->pot_cutoff;
     // slots per atom of the per-chain pools: the handle's capacity, or what an earlier chain-resident relaxation had to grow to.  The
     // grown value stays with THIS driver (cm_cap_per_atom): the batch-wide runs size their buffers from cap_per_atom and repair an
     // overflow exactly, they must not inherit up to 64x from a pool that doubles (advisor r5)
@@ -258,7 +258,7 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         ChainMinArgs A{};
         A.n_types = h->n_types;
         A.fast = (h->n_types * h->n_types * h->n_types <= TS_MAXP) ? 1 : 0;
-        A.P = h->ters_params.as<TersP>();
+        A.P = h->pot_params.as<TersP>();
         A.type = h->d_Z.as<int>(); A.atom_cfg = h->d_atom_cfg.as<int>(); A.cfg_start = h->d_cfg_start.as<int>(); A.nimg = h->d_nimg.as<int>();
         A.cell = h->d_cell.as<double>(); A.invcell = h->d_invcell.as<double>();
         A.pbc = h->d_pbc.as<uint8_t>(); A.fixed = fixed;
@@ -267,12 +267,12 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         A.edge_S = h->d_edge_S.as<int>(); A.rev = h->d_rev.as<int>(); A.edge = h->d_edge.as<float4>();
         A.hits = hits_buf; A.hits_stride = hits_stride; A.cap_per_atom = cap; A.rc2 = rc * rc;
         A.eps = h->d_gbar.as<double>(); A.gslot = A.eps + h->slot_cap;
-        A.e_atom = h->d_ters_ea.as<double>(); A.forces = h->d_ters_f.as<double>(); A.energy = h->d_ters_e.as<double>();
+        A.e_atom = h->d_pot_ea.as<double>(); A.forces = h->d_pot_f.as<double>(); A.energy = h->d_pot_e.as<double>();
         A.max_iter = cp->max_iter; A.max_eval = cp->max_eval; A.etol = cp->etol; A.ftol = cp->ftol; A.dmax = cp->dmax;
         A.x0 = h->d_vel.as<double>(); A.hh = A.x0 + 3 * (size_t)N; A.gg = A.x0 + 6 * (size_t)N;
         A.st = h->d_fire.as<CgState>(); A.active = h->d_active.as<unsigned char>(); A.flags = flags; A.n_evals = n_evals;
         A.max_launch = (long long)cp->max_eval + 72;   // the lock-step driver's launch budget (relax.hip), per chain here
-        h->prof.begin(KC_TERSOFF, st);
+        h->prof.begin(KC_ANALYTIC, st);
         VSSR_HIP(h, hipMemcpyAsync(d_args, &A, sizeof(A), hipMemcpyHostToDevice, st));   // (pageable source: copied before the call returns)
         hipLaunchKernelGGL(k_cg_chain, dim3(B), dim3(CM_THREADS), 0, st, d_args);
         h->prof.end(st);

@@ -362,7 +362,7 @@ static void ward_round(hipStream_t st, Cluster *c, int cur, int m, int n) {
 int cluster_pad_dims(int d) { return d <= 4 ? d : d <= 8 ? 8 : d <= 16 ? 16 : 32; }
 
 int cluster_pca(vssr_handle *h, vssr_cluster_pca_result *res) {
-    Cluster *c = h->clu;
+    Cluster *c = h->clu.get();
     const int D = h->gmm_D, Dp = h->gmm_Dp, n = (int)h->fit->n, nc = c->n_components;
     const size_t d = sizeof(double);
     hipStream_t st = h->stream;
@@ -376,17 +376,17 @@ int cluster_pca(vssr_handle *h, vssr_cluster_pca_result *res) {
         c->comp_t.ensure(d * (size_t)nc * Dp) || c->ev.ensure(d * nc) || c->ratio.ensure(d * nc) || c->counters.ensure(sizeof(int) * 8) ||
         c->xr.ensure(d * (size_t)n * nc) || c->pts.ensure(d * (size_t)n * c->d_pad))
         return set_err(h, VSSR_E_NOMEM, "device allocation failed (PCA workspaces: %d rows, D = %d)", n, D);
-    hipLaunchKernelGGL(k_clu_colsum, dim3(S2), dim3(256), 0, st, h->fit->x, n, Dp, rps, c->part_sum.as<double>());
+    hipLaunchKernelGGL(k_clu_colsum, dim3(S2), dim3(256), 0, st, h->fit->x(), n, Dp, rps, c->part_sum.as<double>());
     hipLaunchKernelGGL(k_clu_mean, dim3(1), dim3(256), 0, st, c->part_sum.as<double>(), S2, n, Dp, c->mean.as<double>(), c->denom.as<double>());
     VSSR_HIP(h, hipGetLastError());
-    int rc = gmm_fit_centered_cov(h, st, h->fit->x, n, D, Dp, c->mean.as<double>(), c->denom.as<double>(), c->part_cov, c->cov.as<double>());
+    int rc = gmm_fit_centered_cov(h, st, h->fit->x(), n, D, Dp, c->mean.as<double>(), c->denom.as<double>(), c->part_cov, c->cov.as<double>());
     if (rc) return rc;
     int *info = c->counters.as<int>() + 4;
     hipLaunchKernelGGL(k_clu_eigh, dim3(1), dim3(EIGH_THREADS), 0, st, c->cov.as<double>(), c->jac.as<double>(), c->evec.as<double>(), D, Dp, info);
     hipLaunchKernelGGL(k_clu_components, dim3(1), dim3(256), 0, st, c->jac.as<double>(), c->evec.as<double>(), D, Dp, nc, c->comp.as<double>(),
                        c->comp_t.as<double>(), c->ev.as<double>(), c->ratio.as<double>());
     const int64_t tot = (int64_t)n * nc;
-    hipLaunchKernelGGL(k_clu_project, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->fit->x, (int64_t)n, D, Dp, c->mean.as<double>(),
+    hipLaunchKernelGGL(k_clu_project, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->fit->x(), (int64_t)n, D, Dp, c->mean.as<double>(),
                        c->comp_t.as<double>(), nc, c->ev.as<double>(), c->whiten, c->xr.as<double>(), c->pts.as<double>(), c->d_clu, c->d_pad);
     VSSR_HIP(h, hipGetLastError());
     int hinfo[2] = {0, 0};
@@ -399,7 +399,7 @@ int cluster_pca(vssr_handle *h, vssr_cluster_pca_result *res) {
 }
 
 int cluster_pca_params(vssr_handle *h, double *mean, double *components, double *explained_variance, double *ratio) {
-    Cluster *c = h->clu;
+    Cluster *c = h->clu.get();
     const int D = h->gmm_D, Dp = h->gmm_Dp, nc = c->n_components;
     const size_t d = sizeof(double);
     if (mean) VSSR_HIP(h, hipMemcpy(mean, c->mean.p, d * D, hipMemcpyDeviceToHost));
@@ -410,14 +410,14 @@ int cluster_pca_params(vssr_handle *h, double *mean, double *components, double 
 }
 
 int cluster_projected(vssr_handle *h, int64_t first, int64_t n_rows, double *xr) {
-    Cluster *c = h->clu;
+    Cluster *c = h->clu.get();
     const size_t row = sizeof(double) * c->n_components;
     VSSR_HIP(h, hipMemcpy(xr, c->xr.as<char>() + (size_t)first * row, (size_t)n_rows * row, hipMemcpyDeviceToHost));
     return VSSR_OK;
 }
 
 int cluster_set_points(vssr_handle *h, int64_t n, const double *pts) {
-    Cluster *c = h->clu;
+    Cluster *c = h->clu.get();
     const size_t d = sizeof(double);
     c->n_pts = 0;
     if (c->pts.ensure(d * (size_t)n * c->d_pad)) return set_err(h, VSSR_E_NOMEM, "device allocation failed (%lld points)", (long long)n);
@@ -432,7 +432,7 @@ int cluster_set_points(vssr_handle *h, int64_t n, const double *pts) {
 }
 
 int cluster_linkage(vssr_handle *h, double *Z, int32_t *n_rounds) {
-    Cluster *c = h->clu;
+    Cluster *c = h->clu.get();
     const int n = (int)c->n_pts, dp = c->d_pad;
     const size_t d = sizeof(double);
     hipStream_t st = h->stream;

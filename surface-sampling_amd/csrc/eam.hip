@@ -309,7 +309,7 @@ k_eam_stress_typed(vssr_eam_grid g, EamTyped T, const int *__restrict__ type, co
 // the typed tables of a handle of several elements (layout: see EamTyped)
 static EamTyped eam_typed_view(const vssr_handle *h) {
     const int n = h->eam_nel;
-    const double *frho = h->ters_params.as<double>();
+    const double *frho = h->pot_params.as<double>();
     return EamTyped{frho, frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n,
                     frho + 7 * (size_t)(h->eam_grid.nrho + 1) * n + 7 * (size_t)(h->eam_grid.nr + 1) * (h->eam_fs ? n * n : n),
                     n, h->eam_fs, 7 * (size_t)(h->eam_grid.nrho + 1), 7 * (size_t)(h->eam_grid.nr + 1)};
@@ -325,7 +325,7 @@ int eam_stress(vssr_handle *h) {
                            h->d_row_start.as<int>(), h->d_edge.as<float4>(), h->d_edge_S.as<int>(), h->d_counters.as<int>(), fp, out,
                            out_std);
     } else {
-        const double *rhor = h->ters_params.as<double>() + 7 * (size_t)(h->eam_grid.nrho + 1);
+        const double *rhor = h->pot_params.as<double>() + 7 * (size_t)(h->eam_grid.nrho + 1);
         const double *z2r = rhor + 7 * (size_t)(h->eam_grid.nr + 1);
         hipLaunchKernelGGL(k_eam_stress, dim3(h->n_cfg), dim3(VIR_THREADS), 0, h->stream, h->eam_grid, rhor, z2r, h->d_cfg_start.as<int>(),
                            h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
@@ -341,14 +341,14 @@ int eam_run(vssr_handle *h, uint32_t want) {
     hipStream_t st = h->stream;
     int rc = build_neighbors(h, h->eam_grid.cutoff);
     if (rc) return rc;
-    if (h->d_ters_e.ensure(sizeof(double) * h->n_cfg) || h->d_ters_ea.ensure(sizeof(double) * N) ||
-        h->d_ters_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 2 * (size_t)N))
+    if (h->d_pot_e.ensure(sizeof(double) * h->n_cfg) || h->d_pot_ea.ensure(sizeof(double) * N) ||
+        h->d_pot_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 2 * (size_t)N))
         return set_err(h, VSSR_E_NOMEM, "EAM buffers: out of device memory");
     double *e_embed = h->d_gbar.as<double>(), *fp = e_embed + N;
-    const double *frho = h->ters_params.as<double>();
+    const double *frho = h->pot_params.as<double>();
     const double *rhor = frho + 7 * (size_t)(h->eam_grid.nrho + 1);
     const double *z2r = rhor + 7 * (size_t)(h->eam_grid.nr + 1);
-    h->prof.begin(KC_TERSOFF, st);
+    h->prof.begin(KC_ANALYTIC, st);
     dim3 blk(64), grd((N + 63) / 64);
     const ActiveView av{h->active_mask, h->d_atom_cfg.as<int>()};
     if (h->eam_nel > 0) {
@@ -358,10 +358,10 @@ int eam_run(vssr_handle *h, uint32_t want) {
                            h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, av);
         hipLaunchKernelGGL(k_eam_force_typed, grd, blk, 0, st, N, h->eam_grid, T, h->d_Z.as<int>(), h->d_atom_cfg.as<int>(),
                            h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
-                           h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, h->d_ters_ea.as<double>(),
-                           h->d_ters_f.as<double>(), av);
+                           h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, h->d_pot_ea.as<double>(),
+                           h->d_pot_f.as<double>(), av);
         hipLaunchKernelGGL(k_eam_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(),
-                           h->d_ters_ea.as<double>(), h->d_ters_e.as<double>(), h->active_mask);
+                           h->d_pot_ea.as<double>(), h->d_pot_e.as<double>(), h->active_mask);
         h->prof.end(st);
         VSSR_HIP(h, hipGetLastError());
         return VSSR_OK;
@@ -371,10 +371,10 @@ int eam_run(vssr_handle *h, uint32_t want) {
                        h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, av);
     hipLaunchKernelGGL(k_eam_force, grd, blk, 0, st, N, h->eam_grid, rhor, z2r, h->d_atom_cfg.as<int>(),
                        h->d_cell.as<double>(), h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(),
-                       h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, h->d_ters_ea.as<double>(),
-                       h->d_ters_f.as<double>(), av);
+                       h->d_edge_S.as<int>(), h->d_counters.as<int>(), e_embed, fp, h->d_pot_ea.as<double>(),
+                       h->d_pot_f.as<double>(), av);
     hipLaunchKernelGGL(k_eam_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(),
-                       h->d_ters_ea.as<double>(), h->d_ters_e.as<double>(), h->active_mask);
+                       h->d_pot_ea.as<double>(), h->d_pot_e.as<double>(), h->active_mask);
     h->prof.end(st);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;

@@ -451,30 +451,31 @@ int gmm_fit_check_config(const vssr_gmm_fit_config *cfg) {
 
 // room for `extra` more rows; resident rows are kept
 static int fit_reserve(vssr_handle *h, int64_t extra) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int64_t need = f->n + extra;
     if (need > (int64_t)INT32_MAX - 64) return set_err(h, VSSR_E_BADARG, "GMM fit: %lld rows exceed the supported count", (long long)need);
     if (need <= f->cap) return VSSR_OK;
     const int64_t cap = need + need / 2 + 64;
-    double *p = nullptr;
-    if (hipMalloc((void **)&p, sizeof(double) * (size_t)cap * h->gmm_Dp) != hipSuccess)
+    DevBuf grown;   // sized exactly
+    const size_t bytes = sizeof(double) * (size_t)cap * h->gmm_Dp;
+    if (hipMalloc(&grown.p, bytes) != hipSuccess)
         return set_err(h, VSSR_E_NOMEM, "device allocation failed (GMM fit rows, %lld)", (long long)cap);
+    grown.bytes = bytes;
     if (f->n) {
         VSSR_HIP(h, hipStreamSynchronize(h->stream));
-        VSSR_HIP(h, hipMemcpy(p, f->x, sizeof(double) * (size_t)f->n * h->gmm_Dp, hipMemcpyDeviceToDevice));
+        VSSR_HIP(h, hipMemcpy(grown.p, f->x(), sizeof(double) * (size_t)f->n * h->gmm_Dp, hipMemcpyDeviceToDevice));
     }
-    if (f->x) (void)hipFree(f->x);
-    f->x = p;
+    f->rows.swap(grown);   // the old rows go with `grown`
     f->cap = cap;
     return VSSR_OK;
 }
 
 int gmm_fit_append_host(vssr_handle *h, int64_t n_rows, const double *x) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int D = h->gmm_D, Dp = h->gmm_Dp;
     int rc = fit_reserve(h, n_rows);
     if (rc) return rc;
-    double *dst = f->x + (size_t)f->n * Dp;
+    double *dst = f->x() + (size_t)f->n * Dp;
     if (Dp == D) {
         VSSR_HIP(h, hipMemcpy(dst, x, sizeof(double) * (size_t)n_rows * D, hipMemcpyHostToDevice));
     } else {
@@ -495,7 +496,7 @@ static int fit_flag_after(vssr_handle *h, hipStream_t st, const char *what) {
 }
 
 int gmm_fit_append_f32(vssr_handle *h, hipStream_t st, int64_t n_rows, const float *emb_dev) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int D = h->gmm_D, Dp = h->gmm_Dp;
     int rc = fit_reserve(h, n_rows);
     if (rc) return rc;
@@ -503,7 +504,7 @@ int gmm_fit_append_f32(vssr_handle *h, hipStream_t st, int64_t n_rows, const flo
     VSSR_HIP(h, hipMemsetAsync(f->flags.p, 0, sizeof(int), st));
     const int64_t tot = n_rows * Dp;
     hipLaunchKernelGGL(k_fit_widen, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, emb_dev, n_rows, D, Dp,
-                       f->x + (size_t)f->n * Dp, f->flags.as<int>());
+                       f->x() + (size_t)f->n * Dp, f->flags.as<int>());
     VSSR_HIP(h, hipGetLastError());
     rc = fit_flag_after(h, st, "the embedding");
     if (rc) return rc;
@@ -513,7 +514,7 @@ int gmm_fit_append_f32(vssr_handle *h, hipStream_t st, int64_t n_rows, const flo
 }
 
 int gmm_fit_append_f64p(vssr_handle *h, hipStream_t st, int64_t n_rows, const double *x_dev) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int Dp = h->gmm_Dp;
     int rc = fit_reserve(h, n_rows);
     if (rc) return rc;
@@ -522,7 +523,7 @@ int gmm_fit_append_f64p(vssr_handle *h, hipStream_t st, int64_t n_rows, const do
     const int64_t tot = n_rows * Dp;
     hipLaunchKernelGGL(k_fit_check_f64, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x_dev, tot, f->flags.as<int>());
     VSSR_HIP(h, hipGetLastError());
-    VSSR_HIP(h, hipMemcpyAsync(f->x + (size_t)f->n * Dp, x_dev, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
+    VSSR_HIP(h, hipMemcpyAsync(f->x() + (size_t)f->n * Dp, x_dev, sizeof(double) * (size_t)tot, hipMemcpyDeviceToDevice, st));
     rc = fit_flag_after(h, st, "the embedding");
     if (rc) return rc;
     f->n += n_rows;
@@ -549,7 +550,7 @@ static bool host_cholesky_lower(double *a, int D) {
 }
 
 int gmm_fit_set_init(vssr_handle *h, const double *means, const double *weights, const double *precisions, const int32_t *labels) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, D = h->gmm_D;
     std::vector<double> m, w, p;
     std::vector<int> lab;
@@ -626,12 +627,12 @@ static FitGeom fit_geom(int n, int K, int Dp, int cov_components) {
 
 // M step from responsibilities (resp) or one-hot labels; init = true: w_k = n_k / N (gmm.py:644-647)
 static int fit_m_step(vssr_handle *h, hipStream_t st, const double *resp, const int *labels, bool init) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, D = h->gmm_D, Dp = h->gmm_Dp, n = (int)f->n, ct = f->cov_type;
     const bool vec = ct == VSSR_GMM_COV_DIAG || ct == VSSR_GMM_COV_SPHERICAL;
     const int Kc = ct == VSSR_GMM_COV_TIED ? 1 : K;
     const FitGeom g = fit_geom(n, K, Dp, Kc);
-    hipLaunchKernelGGL(k_fit_moments, dim3(g.S_m, K), dim3(256), 0, st, f->x, n, Dp, resp, labels, K, g.rps_m, vec ? 1 : 0,
+    hipLaunchKernelGGL(k_fit_moments, dim3(g.S_m, K), dim3(256), 0, st, f->x(), n, Dp, resp, labels, K, g.rps_m, vec ? 1 : 0,
                        f->part_s.as<double>(), f->part_q.as<double>(), f->part_n.as<double>());
     hipLaunchKernelGGL(k_fit_means, dim3(K), dim3(256), 0, st, f->part_s.as<double>(), f->part_q.as<double>(), f->part_n.as<double>(),
                        g.S_m, K, Dp, vec ? 1 : 0, f->nk.as<double>(), f->means.as<double>(), f->avg_x2.as<double>());
@@ -646,7 +647,7 @@ static int fit_m_step(vssr_handle *h, hipStream_t st, const double *resp, const 
     } else {
         const bool tied = ct == VSSR_GMM_COV_TIED;
         // tied: X^T X does not change between iterations, but it is cheap next to the E step of K components and keeps one path
-        hipLaunchKernelGGL(k_fit_cov, dim3(g.S_c, Kc, g.ZT), dim3(256), 0, st, f->x, n, Dp, tied ? nullptr : resp, K,
+        hipLaunchKernelGGL(k_fit_cov, dim3(g.S_c, Kc, g.ZT), dim3(256), 0, st, f->x(), n, Dp, tied ? nullptr : resp, K,
                            tied ? nullptr : f->means.as<double>(), g.rps_c, f->part_cov.as<double>());
         hipLaunchKernelGGL(k_fit_cov_finish, dim3(Kc, Dp), dim3(256), 0, st, f->part_cov.as<double>(), g.S_c, D, Dp, K, tied ? 1 : 0,
                            f->nk.as<double>(), f->means.as<double>(), f->reg_covar, f->cov.as<double>());
@@ -681,7 +682,7 @@ k_fit_onehot(const int *__restrict__ labels, int n, int K, double *__restrict__ 
 }
 
 static int fit_read_status(vssr_handle *h, hipStream_t st, const double *value, double *out) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     hipLaunchKernelGGL(k_fit_status, dim3(1), dim3(64), 0, st, f->flags.as<int>() + 1, h->gmm_K, value, f->status.as<double>() + 1);
     VSSR_HIP(h, hipGetLastError());
     VSSR_HIP(h, hipMemcpyAsync(out, f->status.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -703,7 +704,7 @@ static void fit_draw_rows(const GmmFit *f, int restart, uint32_t *draw, int n, i
 // k-means on the device: k-means++ seeding (D^2 sampling, one candidate per centre), then Lloyd iterations until the inertia stops
 // changing (bitwise: every reduction has a fixed order) or 300 iterations; labels end up in f->labels
 static int fit_kmeans(vssr_handle *h, hipStream_t st, int restart) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, D = h->gmm_D, Dp = h->gmm_Dp, n = (int)f->n;
     const FitGeom g = fit_geom(n, K, Dp, 1);
     double *cen = f->centers.as<double>(), *mind2 = f->centers.as<double>() + (size_t)K * Dp, *part = f->assign_part.as<double>();
@@ -711,9 +712,9 @@ static int fit_kmeans(vssr_handle *h, hipStream_t st, int restart) {
     uint32_t draw = 0;
     std::vector<double> hp(g.n_blk), hm(256);
     int first = std::min(n - 1, (int)(fit_uniform(f->seed, (uint32_t)restart, draw++) * n));
-    hipLaunchKernelGGL(k_fit_copy_row, dim3(1), dim3(256), 0, st, f->x, first, Dp, cen);
+    hipLaunchKernelGGL(k_fit_copy_row, dim3(1), dim3(256), 0, st, f->x(), first, Dp, cen);
     for (int c = 1; c < K; ++c) {
-        hipLaunchKernelGGL(k_fit_dist, dim3(g.n_blk), dim3(256), 0, st, f->x, n, D, Dp, cen, c - 1, c, c == 1 ? 1 : 0, mind2, (int *)nullptr, part);
+        hipLaunchKernelGGL(k_fit_dist, dim3(g.n_blk), dim3(256), 0, st, f->x(), n, D, Dp, cen, c - 1, c, c == 1 ? 1 : 0, mind2, (int *)nullptr, part);
         VSSR_HIP(h, hipGetLastError());
         VSSR_HIP(h, hipMemcpyAsync(hp.data(), part, sizeof(double) * g.n_blk, hipMemcpyDeviceToHost, st));
         VSSR_HIP(h, hipStreamSynchronize(st));
@@ -728,11 +729,11 @@ static int fit_kmeans(vssr_handle *h, hipStream_t st, int restart) {
         int pick = 0;
         while (pick < cnt - 1 && run + hm[pick] <= target) run += hm[pick++];
         while (pick < cnt - 1 && !(hm[pick] > 0.0)) ++pick;   // (never a row that already is a centre, when another is left)
-        hipLaunchKernelGGL(k_fit_copy_row, dim3(1), dim3(256), 0, st, f->x, r0 + pick, Dp, cen + (size_t)c * Dp);
+        hipLaunchKernelGGL(k_fit_copy_row, dim3(1), dim3(256), 0, st, f->x(), r0 + pick, Dp, cen + (size_t)c * Dp);
     }
     double prev = -1.0;
     for (int it = 0; it < 300; ++it) {
-        hipLaunchKernelGGL(k_fit_dist, dim3(g.n_blk), dim3(256), 0, st, f->x, n, D, Dp, cen, 0, K, 1, mind2, lab, part);
+        hipLaunchKernelGGL(k_fit_dist, dim3(g.n_blk), dim3(256), 0, st, f->x(), n, D, Dp, cen, 0, K, 1, mind2, lab, part);
         hipLaunchKernelGGL(k_fit_sum, dim3(1), dim3(256), 0, st, part, g.n_blk, 1.0, f->status.as<double>());
         VSSR_HIP(h, hipGetLastError());
         double inertia = 0.0;
@@ -740,7 +741,7 @@ static int fit_kmeans(vssr_handle *h, hipStream_t st, int restart) {
         VSSR_HIP(h, hipStreamSynchronize(st));
         if (inertia == prev) break;
         prev = inertia;
-        hipLaunchKernelGGL(k_fit_moments, dim3(g.S_m, K), dim3(256), 0, st, f->x, n, Dp, (const double *)nullptr, lab, K, g.rps_m, 0,
+        hipLaunchKernelGGL(k_fit_moments, dim3(g.S_m, K), dim3(256), 0, st, f->x(), n, Dp, (const double *)nullptr, lab, K, g.rps_m, 0,
                            f->part_s.as<double>(), f->part_q.as<double>(), f->part_n.as<double>());
         hipLaunchKernelGGL(k_fit_means, dim3(K), dim3(256), 0, st, f->part_s.as<double>(), f->part_q.as<double>(), f->part_n.as<double>(),
                            g.S_m, K, Dp, 0, f->nk.as<double>(), cen, f->avg_x2.as<double>());
@@ -750,7 +751,7 @@ static int fit_kmeans(vssr_handle *h, hipStream_t st, int restart) {
 }
 
 static int fit_alloc(vssr_handle *h) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, Dp = h->gmm_Dp, n = (int)f->n, NB = Dp / 16;
     const int Kc = f->cov_type == VSSR_GMM_COV_TIED ? 1 : K;
     const bool mat = f->cov_type == VSSR_GMM_COV_FULL || f->cov_type == VSSR_GMM_COV_TIED;
@@ -773,7 +774,7 @@ static int fit_alloc(vssr_handle *h) {
 }
 
 static int fit_copy_best(vssr_handle *h, hipStream_t st, bool save) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, Dp = h->gmm_Dp, NB = Dp / 16;
     const int Kc = f->cov_type == VSSR_GMM_COV_TIED ? 1 : K;
     const bool mat = f->cov_type == VSSR_GMM_COV_FULL || f->cov_type == VSSR_GMM_COV_TIED;
@@ -789,7 +790,7 @@ static int fit_copy_best(vssr_handle *h, hipStream_t st, bool save) {
 
 // starting mixture of restart `restart` in the scoring buffers
 static int fit_initialise(vssr_handle *h, hipStream_t st, int restart) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, D = h->gmm_D, Dp = h->gmm_Dp, n = (int)f->n;
     const bool all_given = f->has_means && f->has_weights && f->has_prec;
     VSSR_HIP(h, hipMemsetAsync(f->flags.p, 0, sizeof(int) * 257, st));
@@ -839,7 +840,7 @@ static int fit_initialise(vssr_handle *h, hipStream_t st, int restart) {
 }
 
 int gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, n = (int)f->n;
     hipStream_t st = h->stream;
     f->fitted = false;
@@ -857,7 +858,7 @@ int gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res) {
         trace.clear();
         for (it = 1; it <= f->max_iter; ++it) {
             const double prev = lb;
-            rc = gmm_score_f64(h, st, n, f->x);
+            rc = gmm_score_f64(h, st, n, f->x());
             if (rc) return rc;
             hipLaunchKernelGGL(k_fit_resp, dim3(n_blk), dim3(256), 0, st, h->d_gmm_lp.as<double>(), h->d_gmm_kc.as<double>(),
                                h->d_gmm_nll.as<double>(), n, K, f->resp.as<double>(), f->lbpart.as<double>());
@@ -898,7 +899,7 @@ int gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res) {
 }
 
 int gmm_fit_params(vssr_handle *h, double *weights, double *means, double *covariances, double *prec_chol) {
-    GmmFit *f = h->fit;
+    GmmFit *f = h->fit.get();
     const int K = h->gmm_K, D = h->gmm_D, Dp = h->gmm_Dp, ct = f->cov_type;
     const size_t d = sizeof(double);
     if (weights) VSSR_HIP(h, hipMemcpy(weights, f->w.p, d * K, hipMemcpyDeviceToHost));

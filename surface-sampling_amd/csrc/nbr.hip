@@ -466,7 +466,7 @@ int build_neighbors(vssr_handle *h, double cutoff) {
     // beat one wave per centre in the search at every chain size (260-atom chains: 4 full chunks of 64 + one with 4 lanes; 48-atom
     // chains: 48 of 64 lanes, once), the reverse-slot search likes 32 lanes on PaiNN rows (~41 slots) and 16 on the 8-slot rows of
     // the analytic potentials.  (The 32- and 64-lane search forms gave the same list bit for bit and are not built any more.)
-    const int lpc_rev = h->kind != 1 ? 16 : 32;
+    const int lpc_rev = h->kind != Kind::PAINN ? 16 : 32;
     dim3 wblk(256);
     auto grid_for = [&](int lpc) { return dim3((n + 256 / lpc - 1) / (256 / lpc)); };
 #define NBR_ARGS(FILLING) n, h->d_wpos.as<double>(), h->d_atom_cfg.as<int>(), h->d_cfg_start.as<int>(), h->d_cell.as<double>(),          \
@@ -491,7 +491,7 @@ int build_neighbors(vssr_handle *h, double cutoff) {
     if (lpc_rev == 16) hipLaunchKernelGGL(k_rev<16>, grid_for(16), wblk, 0, st, REV_ARGS);
     else hipLaunchKernelGGL(k_rev<32>, grid_for(32), wblk, 0, st, REV_ARGS);
 #undef REV_ARGS
-    if (h->kind == 1 && !h->painn_general) {   // PaiNN 128 / 20: per-slot geometry tables shared by all layers / models / slices
+    if (h->kind == Kind::PAINN && !h->painn_general) {   // PaiNN 128 / 20: per-slot geometry tables shared by all layers / models / slices
                                                 // (the general path computes its radial functions on the fly)
         // layer-0 factorisation with at most 4 species: its T blocks are accumulated by k_edge_geom (h->l0T_by_geom); with more species
         // a separate kernel builds them from the fp32 table and the per-slot unit vectors, which are only written for it

@@ -226,7 +226,7 @@ void build_wd16(const float *Wd, const float *bd, unsigned *dst) {
 // two filter sections into one tile: tile row i = 4 q + j carries feature 2 q + (j & 1) of section 2 T + (j >> 1), so that lane
 // (slot, fq) -- which owns tile rows 4 fq .. 4 fq + 3 -- still finds the a, b and c filter values of ITS features in its own
 // accumulator registers (tile 0 = [a | b], tile 1 = [c | -]).  Every chain takes the path its own atom count selects
-// (vssr_api.hip classify_chains), whatever it is batched with.
+// (vssr_batch_upload, api_batch.hip), whatever it is batched with.
 #ifndef STAGE_BATCH
 #define STAGE_BATCH 4   // slice staging: loads in flight per thread before the first LDS store
 #endif

@@ -506,7 +506,7 @@ int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr
     const int POLL = 4;
     int rc = VSSR_OK;
     auto evaluate = [&]() {
-        return is_f64_kind(h) ? f64_run(h, want | VSSR_WANT_FORCES) : painn_run(h, want | VSSR_WANT_FORCES);
+        return evaluator(h).run(h, want | VSSR_WANT_FORCES);
     };
     h->relax_lockstep = 0;
     h->relax_chain_evals = 0;
@@ -519,16 +519,16 @@ int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr
         {   // (last iteration: every unconverged chain has taken relax_steps steps -- the kernel only tests convergence, like the
             // final check of ASE's run loop)
             VSSR_HIP(h, hipMemsetAsync(n_active_d, 0, sizeof(int), st));
-            if (is_f64_kind(h)) {   // Tersoff / EAM / SW forces are fp64 on the device: the optimizer state works on an fp32 copy
+            if (is_analytic(h)) {   // Tersoff / EAM / SW forces are fp64 on the device: the optimizer state works on an fp32 copy
                 if (h->d_forces.ensure(sizeof(float) * 3 * N)) { rc = set_err(h, VSSR_E_NOMEM, "force buffer"); break; }
                 hipLaunchKernelGGL(k_narrow_forces, dim3((3 * N + 255) / 256), dim3(256), 0, st, 3 * N,
-                                   h->d_ters_f.as<double>(), h->d_forces.as<float>());
+                                   h->d_pot_f.as<double>(), h->d_forces.as<float>());
             }
             const float *forces = h->d_forces.as<float>();
             if (nrec) {
-                const bool f64 = is_f64_kind(h);
+                const bool f64 = is_analytic(h);
                 const float *e32 = f64 ? nullptr : h->d_energy.as<float>();
-                const double *e64 = f64 ? h->d_ters_e.as<double>() : nullptr;
+                const double *e64 = f64 ? h->d_pot_e.as<double>() : nullptr;
                 if (method == 0)
                     hipLaunchKernelGGL(k_traj_record<FireState>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
                                        h->d_fire.as<FireState>(), active, rec_iv, nrec, B, N, fixed, h->d_pos.as<double>(), forces, e32, e64,
@@ -702,7 +702,7 @@ __global__ void k_cg_report(int B, const CgState *__restrict__ st, int *__restri
 int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want) {
     const int B = h->n_cfg, N = h->n_atoms;
     hipStream_t st = h->stream;
-    if (!is_f64_kind(h))
+    if (!is_analytic(h))
         return set_err(h, VSSR_E_STATE, "conjugate gradients need an fp64 potential (Tersoff / EAM / SW handle); use BFGS or FIRE");
     if (h->d_fixed.ensure((size_t)N) || h->d_relax_steps.ensure(sizeof(int) * 3 * B) || h->d_active.ensure((size_t)B) ||
         h->d_counters.ensure(sizeof(int) * 4) || h->d_fire.ensure(sizeof(CgState) * B) || h->d_vel.ensure(sizeof(double) * 9 * N))
@@ -824,7 +824,7 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
     h->relax_chain_evals = 0;
     while (!rc && !finished) {
         for (; it < max_launch && !rc; ++it) {
-            rc = f64_run(h, want | VSSR_WANT_FORCES);
+            rc = evaluator(h).run(h, want | VSSR_WANT_FORCES);
             if (rc) break;
             ++h->relax_lockstep;
             h->relax_chain_evals += B_cur;
@@ -833,7 +833,7 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
             const bool poll_it = (it + 1) % POLL == 0;
             if (poll_it) VSSR_HIP(h, hipMemsetAsync(n_active_d, 0, sizeof(int), st));
             hipLaunchKernelGGL(k_cg_step, dim3(B_cur), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                               h->d_ters_e.as<double>(), h->d_ters_f.as<double>(), fixed, cp->max_iter, cp->max_eval, cp->etol,
+                               h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), fixed, cp->max_iter, cp->max_eval, cp->etol,
                                cp->ftol, cp->dmax, h->d_pos.as<double>(), h->d_vel.as<double>(), h->d_vel.as<double>() + 3 * (size_t)N,
                                h->d_vel.as<double>() + 6 * (size_t)N, h->d_fire.as<CgState>(), active, n_active_d);
             if (poll_it) {
@@ -871,7 +871,7 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
     rc = restore();
     if (rc) return rc;
     // results of the final positions for every chain (finished chains were switched off at different times)
-    rc = f64_run(h, want | VSSR_WANT_FORCES);
+    rc = evaluator(h).run(h, want | VSSR_WANT_FORCES);
     if (rc) return rc;
     ++h->relax_lockstep;
     h->relax_chain_evals += B;

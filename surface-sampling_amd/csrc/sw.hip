@@ -54,24 +54,24 @@ int sw_run(vssr_handle *h, uint32_t want) {
     (void)want;
     const int N = h->n_atoms;
     hipStream_t st = h->stream;
-    int rc = build_neighbors(h, h->ters_cutmax);
+    int rc = build_neighbors(h, h->pot_cutoff);
     if (rc) return rc;
-    if (h->d_ters_e.ensure(sizeof(double) * h->n_cfg) || h->d_ters_ea.ensure(sizeof(double) * N) ||
-        h->d_ters_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 5 * (size_t)h->slot_cap))
+    if (h->d_pot_e.ensure(sizeof(double) * h->n_cfg) || h->d_pot_ea.ensure(sizeof(double) * N) ||
+        h->d_pot_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 5 * (size_t)h->slot_cap))
         return set_err(h, VSSR_E_NOMEM, "sw buffers: out of device memory");
     double *eo = h->d_gbar.as<double>();
     double *ej = eo + h->slot_cap;
     double *gslot = ej + h->slot_cap;
-    h->prof.begin(KC_TERSOFF, st);
+    h->prof.begin(KC_ANALYTIC, st);
     const ActiveView av{h->active_mask, h->d_atom_cfg.as<int>()};
     hipLaunchKernelGGL(k_sw_site, dim3((N + SW_CENTRES - 1) / SW_CENTRES), dim3(SW_CENTRES * SW_LANES), 0, st, N, h->n_types,
-                       h->ters_params.as<SwP>(), h->d_Z.as<int>(), h->d_atom_cfg.as<int>(), h->d_cell.as<double>(),
+                       h->pot_params.as<SwP>(), h->d_Z.as<int>(), h->d_atom_cfg.as<int>(), h->d_cell.as<double>(),
                        h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(), h->d_edge_S.as<int>(),
                        h->d_counters.as<int>(), eo, ej, gslot, av);
     hipLaunchKernelGGL(k_sw_gather, dim3((N + 63) / 64), dim3(64), 0, st, N, h->d_row_start.as<int>(), h->d_rev.as<int>(),
-                       h->d_counters.as<int>(), eo, ej, gslot, h->d_ters_ea.as<double>(), h->d_ters_f.as<double>(), av);
-    hipLaunchKernelGGL(k_sw_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_ters_ea.as<double>(),
-                       h->d_ters_e.as<double>(), h->active_mask);
+                       h->d_counters.as<int>(), eo, ej, gslot, h->d_pot_ea.as<double>(), h->d_pot_f.as<double>(), av);
+    hipLaunchKernelGGL(k_sw_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_pot_ea.as<double>(),
+                       h->d_pot_e.as<double>(), h->active_mask);
     h->prof.end(st);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;

@@ -111,14 +111,14 @@ int tersoff_run(vssr_handle *h, uint32_t want) {
     (void)want;
     const int N = h->n_atoms;
     hipStream_t st = h->stream;
-    int rc = build_neighbors(h, h->ters_cutmax);
+    int rc = build_neighbors(h, h->pot_cutoff);
     if (rc) return rc;
-    if (h->d_ters_e.ensure(sizeof(double) * h->n_cfg) || h->d_ters_ea.ensure(sizeof(double) * N) ||
-        h->d_ters_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 4 * (size_t)h->slot_cap))
+    if (h->d_pot_e.ensure(sizeof(double) * h->n_cfg) || h->d_pot_ea.ensure(sizeof(double) * N) ||
+        h->d_pot_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 4 * (size_t)h->slot_cap))
         return set_err(h, VSSR_E_NOMEM, "tersoff buffers: out of device memory");
     double *eps = h->d_gbar.as<double>();
     double *gslot = eps + h->slot_cap;
-    h->prof.begin(KC_TERSOFF, st);
+    h->prof.begin(KC_ANALYTIC, st);
     dim3 blk(64), grd((N + 63) / 64);
     const ActiveView av{h->active_mask, h->d_atom_cfg.as<int>()};
     // rows of <= TS_MAXD slots: four lanes per centre from LDS; longer rows (and potentials of more than 4 species): one thread per
@@ -126,17 +126,17 @@ int tersoff_run(vssr_handle *h, uint32_t want) {
     const bool fast = h->n_types * h->n_types * h->n_types <= TS_MAXP;
     if (fast)
         hipLaunchKernelGGL(k_tersoff_site4, dim3((N + TS_CENTRES - 1) / TS_CENTRES), dim3(TS_CENTRES * TS_LANES), 0, st, N, h->n_types,
-                           h->ters_params.as<TersP>(), h->d_Z.as<int>(), h->d_atom_cfg.as<int>(), h->d_cell.as<double>(),
+                           h->pot_params.as<TersP>(), h->d_Z.as<int>(), h->d_atom_cfg.as<int>(), h->d_cell.as<double>(),
                            h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(), h->d_edge_S.as<int>(),
                            h->d_counters.as<int>(), eps, gslot, av);
-    hipLaunchKernelGGL(k_tersoff_site, grd, blk, 0, st, N, h->n_types, h->ters_params.as<TersP>(), h->d_Z.as<int>(),
+    hipLaunchKernelGGL(k_tersoff_site, grd, blk, 0, st, N, h->n_types, h->pot_params.as<TersP>(), h->d_Z.as<int>(),
                        h->d_atom_cfg.as<int>(), h->d_cell.as<double>(), h->d_wpos.as<double>(),
                        h->d_row_start.as<int>(), h->d_edge.as<float4>(), h->d_edge_S.as<int>(),
                        h->d_counters.as<int>(), eps, gslot, av, fast ? TS_MAXD : -1);
     hipLaunchKernelGGL(k_tersoff_gather, grd, blk, 0, st, N, h->d_row_start.as<int>(), h->d_rev.as<int>(),
-                       h->d_counters.as<int>(), eps, gslot, h->d_ters_ea.as<double>(), h->d_ters_f.as<double>(), av);
+                       h->d_counters.as<int>(), eps, gslot, h->d_pot_ea.as<double>(), h->d_pot_f.as<double>(), av);
     hipLaunchKernelGGL(k_tersoff_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(),
-                       h->d_ters_ea.as<double>(), h->d_ters_e.as<double>(), h->active_mask);
+                       h->d_pot_ea.as<double>(), h->d_pot_e.as<double>(), h->active_mask);
     h->prof.end(st);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;

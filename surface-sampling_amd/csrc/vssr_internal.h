@@ -7,7 +7,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/vssr_eval.h"
@@ -174,14 +176,16 @@ struct StateView {  // activations of all models: index [m][atom][...]
 };
 
 // ---- host-side helpers ----------------------------------------------------------------------
-struct DevBuf {
+struct DevBuf {   // owns its device allocation
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t need) {  // grow-only; contents are NOT preserved
         if (need <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
+        release();
         size_t want = need + need / 4 + 256;
         if (hipMalloc(&p, want) != hipSuccess) return -1;
         bytes = want;
@@ -192,8 +196,28 @@ struct DevBuf {
         p = nullptr;
         bytes = 0;
     }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
     template <class T>
     T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// The handle's stream and its pinned counters: created by open_device, released with the handle.  Both convert to the raw
+// pointer, so call sites read as they would with one.
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream &) = delete;
+    OwnedStream &operator=(const OwnedStream &) = delete;
+    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct PinnedInts {
+    int *p = nullptr;
+    PinnedInts() = default;
+    PinnedInts(const PinnedInts &) = delete;
+    PinnedInts &operator=(const PinnedInts &) = delete;
+    ~PinnedInts() { if (p) (void)hipHostFree(p); }
+    operator int *() const { return p; }
 };
 
 enum KernelClass {
@@ -207,7 +231,7 @@ enum KernelClass {
     KC_EDGE_BWD,
     KC_MSG_MLP_BWD,
     KC_FINALIZE,
-    KC_TERSOFF,
+    KC_ANALYTIC,   // the fp64 analytic potentials (reported as "tersoff")
     KC_L0_FWD,
     KC_L0_BWD,
     KC_COUNT
@@ -226,10 +250,13 @@ struct Profiler {
     void end(hipStream_t s);
     void collect();  // stream must be synchronised
     void reset();
-    void destroy();
+    Profiler() = default;
+    Profiler(const Profiler &) = delete;
+    Profiler &operator=(const Profiler &) = delete;
+    ~Profiler();     // stream must be synchronised; no HIP call when no event was ever created
 };
 
-// State of a Gaussian-mixture fit (handle kind 6, gmm_fit.hip).  The mixture being fitted lives in the handle's scoring layout
+// State of a Gaussian-mixture fit (Kind::GMM_FIT, gmm_fit.hip).  The mixture being fitted lives in the handle's scoring layout
 // (gmm_K / gmm_D / gmm_Dp / d_gmm_P / d_gmm_c / d_gmm_kc / d_gmm_mask): the E step is gmm_score_f64 on the resident rows.
 struct GmmFit {
     int cov_type = 0;   // VSSR_GMM_COV_*
@@ -238,8 +265,9 @@ struct GmmFit {
     double tol = 1e-3, reg_covar = 1e-6;
     uint64_t seed = 0;
     bool device_ready = false, fitted = false;
-    int64_t n = 0, cap = 0;        // resident rows / capacity of x
-    double *x = nullptr;           // [cap][Dp] fp64, zero pad columns
+    int64_t n = 0, cap = 0;        // resident rows / capacity of rows
+    DevBuf rows;                   // [cap][Dp] fp64, zero pad columns (sized exactly and grown with its contents: fit_reserve, gmm_fit.hip)
+    double *x() const { return rows.as<double>(); }
     // explicit initial values (vssr_gmm_fit_set_init), host side
     std::vector<double> i_means, i_weights, i_prec;
     std::vector<int> i_labels;
@@ -247,16 +275,9 @@ struct GmmFit {
     DevBuf resp, labels, lbpart, status, flags;
     DevBuf part_s, part_q, part_n, nk, means, avg_x2, w, cov, part_cov, chol_w, chol_y, centers, assign_part;
     DevBuf b_w, b_means, b_cov, b_P, b_c, b_kc, b_mask;   // best restart so far (n_init > 1)
-    void release() {
-        if (x) (void)hipFree(x);
-        x = nullptr;
-        DevBuf *bufs[] = {&resp, &labels, &lbpart, &status, &flags, &part_s, &part_q, &part_n, &nk, &means, &avg_x2, &w, &cov,
-                          &part_cov, &chol_w, &chol_y, &centers, &assign_part, &b_w, &b_means, &b_cov, &b_P, &b_c, &b_kc, &b_mask};
-        for (DevBuf *b : bufs) b->release();
-    }
 };
 
-// State of a latent-space clustering (handle kind 7, cluster.hip).  The rows live in the handle's GmmFit (x / n / cap: the append paths
+// State of a latent-space clustering (Kind::CLUSTER, cluster.hip).  The rows live in the handle's GmmFit (x / n / cap: the append paths
 // of the mixture fit serve both kinds); everything below is the PCA and the Ward linkage.
 struct Cluster {
     int n_components = 0, whiten = 1, d_clu = 3, d_pad = 3;   // d_pad: d_clu rounded up to 1, 2, 3, 4, 8, 16 or 32 (zero coordinates)
@@ -266,22 +287,33 @@ struct Cluster {
     DevBuf pts;                    // [n_pts][d_pad] fp64
     DevBuf cen[2], siz[2], cid[2]; // live clusters, double buffered: centroids [m][d_pad], sizes [m], ids [m]
     DevBuf nn, flag, blk, rec, counters;
-    void release() {
-        DevBuf *bufs[] = {&mean, &denom, &part_sum, &part_cov, &cov, &evec, &eval, &comp, &comp_t, &ev, &ratio, &jac, &xr, &pts,
-                          &cen[0], &cen[1], &siz[0], &siz[1], &cid[0], &cid[1], &nn, &flag, &blk, &rec, &counters};
-        for (DevBuf *b : bufs) b->release();
-    }
 };
+
+// What a handle is.  The numbers are part of the documentation, so they stay.
+enum class Kind : int {
+    NONE = 0,
+    PAINN = 1,     // PaiNN ensemble (painn.hip, painn_gen.hip)
+    TERSOFF = 2,   // tersoff.hip
+    EAM = 3,       // funcfl, eam/alloy and eam/fs tables (eam.hip)
+    SW = 4,        // Stillinger-Weber (sw.hip)
+    GMM = 5,       // Gaussian-mixture scoring (gmm.hip)
+    GMM_FIT = 6,   // Gaussian-mixture fit (gmm_fit.hip)
+    CLUSTER = 7,   // latent-space clustering (cluster.hip)
+    COUNT
+};
+constexpr unsigned kind_bit(Kind k) { return 1u << (int)k; }
+// kinds that evaluate a resident batch: the vssr_batch_* / vssr_eval* / relaxation / introspection entry points serve these
+constexpr unsigned KINDS_EVAL = kind_bit(Kind::PAINN) | kind_bit(Kind::TERSOFF) | kind_bit(Kind::EAM) | kind_bit(Kind::SW);
 
 }  // namespace vssr
 
+// Members are destroyed in reverse order: every device buffer after the stream's declaration goes before the stream does.
 struct vssr_handle {
-    int kind = 0;  // 1 = PaiNN ensemble, 2 = Tersoff, 3 = EAM (funcfl), 4 = Stillinger-Weber, 5 = Gaussian mixture (gmm.hip),
-                   // 6 = Gaussian-mixture fit (gmm_fit.hip), 7 = latent-space clustering (cluster.hip)
-    vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in ters_params
+    vssr::Kind kind = vssr::Kind::NONE;
+    vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in pot_params
     int eam_nel = 0, eam_fs = 0;   // EAM with typed tables (vssr_eam_create_alloy): elements, 1 = eam/fs densities; 0 = one funcfl
     int device = 0;
-    hipStream_t stream = nullptr;
+    vssr::OwnedStream stream;    // null until the handle reaches a device (open_device)
     std::string err;
     vssr::Profiler prof;
 
@@ -315,10 +347,10 @@ struct vssr_handle {
     vssr::DevBuf model_table;    // ModelW[n_models]
     vssr::DevBuf offset_per_z;   // double[n_embed]
 
-    // tersoff / Stillinger-Weber
+    // the fp64 analytic potentials (Tersoff, EAM, Stillinger-Weber)
     int n_types = 0;
-    double ters_cutmax = 0;
-    vssr::DevBuf ters_params;    // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h)
+    double pot_cutoff = 0;       // Tersoff, SW: largest cutoff of the table (EAM: eam_grid.cutoff)
+    vssr::DevBuf pot_params;     // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h); EAM: spline tables (eam.hip)
 
     // resident batch
     bool batch_valid = false, ran = false;
@@ -364,7 +396,7 @@ struct vssr_handle {
     bool cap_tight = false;       // regrow to the exact need only (tests: forces repeated overflows)
     uint32_t last_want = 0;                       // outputs produced by the last run
     int64_t slot_cap = 0;
-    int *h_counters = nullptr;   // pinned: [0] total slots, [1] total real edges, [2] overflow flag
+    vssr::PinnedInts h_counters; // pinned: [0] total slots, [1] total real edges, [2] overflow flag
 
     // state
     vssr::DevBuf d_state;        // one arena for all activations
@@ -385,13 +417,13 @@ struct vssr_handle {
     // results (device)
     vssr::DevBuf d_energy, d_energy_std, d_energy_models, d_forces, d_forces_std, d_e_atoms;
     vssr::DevBuf d_energy64;   // double [B] E | [B] sigma_E | [B][M] per model: the results before narrowing to float32
-    vssr::DevBuf d_ters_e, d_ters_ea, d_ters_f;  // fp64 Tersoff results
+    vssr::DevBuf d_pot_e, d_pot_ea, d_pot_f;   // fp64 results of the analytic potentials: energies [B], per atom [N], forces [N][3]
     vssr::DevBuf d_sat, d_sat_out;   // [n_cfg] unsigned: saturation flags raised during a run / reported for the last evaluation of every chain
     std::vector<unsigned> h_sat;     // host copy of d_sat_out taken by vssr_batch_download (vssr_batch_saturated serves it: no second
     bool h_sat_valid = false;        // synchronisation / copy per download, advisor r3); void after every run
     vssr::DevBuf d_stress;           // [2][n_cfg][6] double: virial stress (mean, std over models) of the last evaluation (vssr_batch_stress)
 
-    // Gaussian mixture (kind 5, gmm.hip): K components of dimension D, zero-padded to Dp = 16 ceil(D / 16)
+    // Gaussian mixture (Kind::GMM, gmm.hip): K components of dimension D, zero-padded to Dp = 16 ceil(D / 16)
     int gmm_K = 0, gmm_D = 0, gmm_Dp = 0;
     double gmm_log2pi = 0.0;
     vssr::DevBuf d_gmm_P;     // double [K][Dp][Dp]  precision Cholesky factors
@@ -399,13 +431,13 @@ struct vssr_handle {
     vssr::DevBuf d_gmm_kc;    // double [2][K]       log det P_k, log w_k
     vssr::DevBuf d_gmm_mask;  // uint8 [K][Dp/16][Dp/16]  1 = the 16 x 16 block of P_k holds a non-zero entry
     vssr::DevBuf d_gmm_x, d_gmm_lp, d_gmm_nll, d_gmm_sys, d_gmm_start;   // per-call workspaces
-    vssr::GmmFit *fit = nullptr;   // kinds 6 and 7 (7: the resident rows only)
-    vssr::Cluster *clu = nullptr;  // kind 7 only
+    std::unique_ptr<vssr::GmmFit> fit;    // GMM_FIT and CLUSTER (CLUSTER: the resident rows only)
+    std::unique_ptr<vssr::Cluster> clu;   // CLUSTER only
 };
 
 namespace vssr {
 
-int set_err(vssr_handle *h, int code, const char *fmt, ...);
+int set_err(vssr_handle *h, int code, const char *fmt, ...);   // h == nullptr: the per-thread error of the create functions
 #define VSSR_HIP(h, expr)                                                                    \
     do {                                                                                     \
         hipError_t _e = (expr);                                                              \
@@ -413,6 +445,35 @@ int set_err(vssr_handle *h, int code, const char *fmt, ...);
             return vssr::set_err(h, VSSR_E_DEVICE, "%s failed: %s (%s:%d)", #expr,          \
                                  hipGetErrorString(_e), __FILE__, __LINE__);                 \
     } while (0)
+
+// ---- handle lifecycle and what the api_*.hip files share (api_handle.hip) ----
+// Entry-point guard: VSSR_E_BADARG for a null handle or one whose kind is not in `served` (kind_bit set), with the message the
+// entry point's family gives ("<func>: a ... handle serves the ... calls only" / "not a ... handle"); VSSR_OK otherwise.
+int check_kind(vssr_handle *h, unsigned served, const char *func);
+// The device part of a create, in two steps: device count and range; then current device, stream, pinned counters.  Errors go to h->err.
+int device_in_range(vssr_handle *h, int device);
+int open_device(vssr_handle *h, int device);
+void publish_create_error(const vssr_handle *h);   // a non-empty h->err into the per-thread error vssr_last_error(NULL) reads
+// One create path: a new handle of `kind` on `device`, then init(h); on failure the error is published, the handle destroyed
+// and the code returned.  Arguments that can be refused without a device are checked by the caller first.  range_check = false:
+// vssr_gmm_create has always left a bad device to hipSetDevice (VSSR_E_DEVICE), and keeps doing so.
+template <class Init>
+int create_handle(Kind kind, int device, vssr_handle **out, Init init, bool range_check = true) {
+    vssr_handle *h = new vssr_handle();
+    h->kind = kind;
+    int rc = range_check ? device_in_range(h, device) : VSSR_OK;
+    if (!rc) rc = open_device(h, device);
+    if (!rc) rc = init(h);
+    if (rc) {
+        publish_create_error(h);
+        vssr_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return VSSR_OK;
+}
+int run_any(vssr_handle *h, uint32_t want);
+int sync_and_check(vssr_handle *h);   // synchronise; if the neighbor capacity overflowed, grow and rerun
 
 // neighbor list (nbr.hip)
 int build_neighbors(vssr_handle *h, double cutoff);
@@ -430,7 +491,7 @@ int painn_gen_run(vssr_handle *h, uint32_t want);
 int tersoff_run(vssr_handle *h, uint32_t want);
 // EAM (eam.hip)
 int eam_run(vssr_handle *h, uint32_t want);
-// Stillinger-Weber (sw.hip; profiled under KC_TERSOFF)
+// Stillinger-Weber (sw.hip)
 int sw_run(vssr_handle *h, uint32_t want);
 // Gaussian-mixture scoring (gmm.hip).  Rows: caller fp64 rows [n][Dp] (padded), or fp32 rows with leading dimension ldx = Dp;
 // writes g->d_gmm_lp [n][K] (logp_k) and g->d_gmm_nll [n] on stream st
@@ -441,7 +502,7 @@ int gmm_score_f32(vssr_handle *g, hipStream_t st, int64_t n, const float *x_dev)
 int gmm_mean_rows(vssr_handle *g, hipStream_t st, int B, const int *start, const float *emb);
 // per-structure reductions of g->d_gmm_nll (order 1 .. 6 as vssr_gmm_score_batch) into g->d_gmm_sys [B]
 int gmm_reduce(vssr_handle *g, hipStream_t st, int B, const int *start, int order);
-// Gaussian-mixture fit (gmm_fit.hip): EM on the rows resident in h->fit->x; the device is initialised by the caller (vssr_api.hip)
+// Gaussian-mixture fit (gmm_fit.hip): EM on the rows resident in h->fit->rows; the device is initialised by the caller (api_gmm.hip)
 int gmm_fit_check_config(const vssr_gmm_fit_config *cfg);
 int gmm_fit_append_host(vssr_handle *h, int64_t n_rows, const double *x);
 int gmm_fit_append_f32(vssr_handle *h, hipStream_t st, int64_t n_rows, const float *emb_dev);   // device rows [n][D] fp32
@@ -449,29 +510,33 @@ int gmm_fit_append_f64p(vssr_handle *h, hipStream_t st, int64_t n_rows, const do
 int gmm_fit_set_init(vssr_handle *h, const double *means, const double *weights, const double *precisions, const int32_t *labels);
 int gmm_fit_run(vssr_handle *h, vssr_gmm_fit_result *res);
 int gmm_fit_params(vssr_handle *h, double *weights, double *means, double *covariances, double *prec_chol);
-int gmm_fit_copy_scorer(vssr_handle *h, vssr_handle *g);   // the fitted mixture into the scoring buffers of a kind-5 handle
+int gmm_fit_copy_scorer(vssr_handle *h, vssr_handle *g);   // the fitted mixture into the scoring buffers of a Kind::GMM handle
 // cov [Dp][Dp] = sum_n (x_n - mean)(x_n - mean)^T / denom[0] on the fit's row-slab MFMA kernel (mean [Dp], denom [1]: device)
 int gmm_fit_centered_cov(vssr_handle *h, hipStream_t st, const double *X, int n, int D, int Dp, const double *mean, const double *denom,
                          DevBuf &part, double *cov);
-// Latent-space clustering (cluster.hip): PCA of the rows resident in h->fit->x, Ward linkage of the resident points
+// Latent-space clustering (cluster.hip): PCA of the rows resident in h->fit->rows, Ward linkage of the resident points
 int cluster_pca(vssr_handle *h, vssr_cluster_pca_result *res);
 int cluster_pca_params(vssr_handle *h, double *mean, double *components, double *explained_variance, double *ratio);
 int cluster_projected(vssr_handle *h, int64_t first, int64_t n_rows, double *xr);
 int cluster_set_points(vssr_handle *h, int64_t n, const double *pts);
 int cluster_linkage(vssr_handle *h, double *Z, int32_t *n_rounds);
 int cluster_pad_dims(int d);   // stored width of a point: 1, 2, 3, 4, 8, 16 or 32 coordinates
-// the fp64 analytic potentials (Tersoff, EAM, SW): same result buffers (d_ters_e / _ea / _f), same drivers
-inline bool is_f64_kind(const vssr_handle *h) { return h->kind == 2 || h->kind == 3 || h->kind == 4; }
-inline int f64_run(vssr_handle *h, uint32_t want) {
-    return h->kind == 2 ? tersoff_run(h, want) : h->kind == 3 ? eam_run(h, want) : sw_run(h, want);
-}
-// vssr_batch_stress on these handles: enqueue the virial kernel over what the last run left on the device (d_stress, as painn_stress);
-// nothing of it runs unless asked for.  slot_stress (tersoff.hip): the kernel Tersoff and SW share, gslot = the handle's G array
+// vssr_batch_stress on the analytic potentials: enqueue the virial kernel over what the last run left on the device (d_stress, as
+// painn_stress); nothing of it runs unless asked for.  slot_stress (tersoff.hip): the kernel Tersoff and SW share, gslot = the handle's G array
 int slot_stress(vssr_handle *h, const double *gslot);
 int tersoff_stress(vssr_handle *h);
 int eam_stress(vssr_handle *h);
 int sw_stress(vssr_handle *h);
-inline int f64_stress(vssr_handle *h) { return h->kind == 2 ? tersoff_stress(h) : h->kind == 3 ? eam_stress(h) : sw_stress(h); }
+// What differs between the kinds that evaluate a batch, one row per Kind (api_handle.hip); run == nullptr: the kind evaluates nothing.
+// f64: an analytic potential -- results in d_pot_e / _ea / _f (fp64, one "model"), driven by relax_cg / chain_min as well.
+struct Evaluator {
+    bool f64;
+    int (*run)(vssr_handle *h, uint32_t want);
+    int (*stress)(vssr_handle *h);
+    double (*cutoff)(const vssr_handle *h);
+};
+const Evaluator &evaluator(const vssr_handle *h);
+inline bool is_analytic(const vssr_handle *h) { return evaluator(h).f64; }
 void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1][7]*/);
 // lock-step FIRE relaxation (relax.hip)
 // method 0: FIRE (fp), 1: BFGS (bp)
