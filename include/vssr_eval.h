@@ -22,6 +22,9 @@
  *   vssr_sw_create / vssr_sw_eval_batch
  *                                   <- the same with pair_style sw, or pair_style kim with the
  *                                      Stillinger-Weber Si model (tutorials/Si_111_5x5)
+ *   vssr_pair_create / vssr_pair_eval_batch
+ *                                   <- the same with pair_style lj/cut, morse, buck, born, coul/dsf
+ *                                      and hybrid / hybrid/overlay of them
  *   vssr_gmm_create / vssr_gmm_score_rows / vssr_gmm_score_batch
  *                                   <- GMMUncertainty.estimate_log_prob / negative_log_likelihood
  *                                      (mcmc/uncertainty/uncertainty.py:238-463)
@@ -365,6 +368,38 @@ int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_s
 int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                        const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                        double *energy_atoms_f64, double *forces_f64);
+
+/* ---- Pair potentials with damped-shifted-force Coulomb (pair_style lj/cut, morse, buck, born, coul/dsf; hybrid and
+ * hybrid/overlay of these) ------------------------------------------------------------------------------------------------------- */
+/* LAMMPS units metal: eV, A, charges in e, qqrd2e = 14.399645.  E(r) for r < rc, coefficients in LAMMPS order:
+ *   VSSR_PAIR_LJ_CUT    4 eps [(sig/r)^12 - (sig/r)^6]                         c = eps sig
+ *   VSSR_PAIR_MORSE     D0 [exp(-2 alpha (r - r0)) - 2 exp(-alpha (r - r0))]   c = D0 alpha r0
+ *   VSSR_PAIR_BUCK      A exp(-r/rho) - C/r^6                                  c = A rho C
+ *   VSSR_PAIR_BORN      A exp((sig - r)/rho) - C/r^6 + D/r^8                   c = A rho sig C D
+ *   VSSR_PAIR_COUL_DSF  qqrd2e q_a q_b [erfc(alpha r)/r - erfc(alpha rc)/rc + B (r - rc)]      c = alpha
+ *                       B = erfc(alpha rc)/rc^2 + 2 alpha/sqrt(pi) exp(-alpha^2 rc^2)/rc  (energy and force vanish at rc)
+ * shift != 0 (pair_modify shift yes) subtracts E(rc) from the four non-Coulomb styles; coul/dsf ignores it.  Every atom whose type
+ * has a coul/dsf term gets the self energy -(erfc(alpha rc)/(2 rc) + alpha/sqrt(pi)) qqrd2e q_i^2 in its pe/atom; pair energies
+ * are split half / half. */
+enum { VSSR_PAIR_NONE = 0, VSSR_PAIR_LJ_CUT = 1, VSSR_PAIR_MORSE = 2, VSSR_PAIR_BUCK = 3, VSSR_PAIR_BORN = 4, VSSR_PAIR_COUL_DSF = 5 };
+typedef struct vssr_pair_term {
+    int32_t type_a, type_b, style;
+    double c[5], rc;
+    int32_t shift;
+} vssr_pair_term;
+/* Handle kind 8.  terms: n_terms entries; a term on (a, b) serves (b, a) as well (give each unordered pair's term once), and the
+ * terms of a pair add up.  charge: [n_types] per-type charges, or NULL.  Refused with VSSR_E_BADARG before any device is touched:
+ * n_types outside 1 .. 8, a type outside [0, n_types), an unknown style, more than 3 terms on a pair, a non-finite coefficient,
+ * rc <= 0, lj/cut sig <= 0, buck / born rho <= 0, coul/dsf alpha < 0, coul/dsf without charges or with a non-finite charge, and
+ * coul/dsf terms that differ in alpha or rc (the self energy of a type would not be defined).  Cutoff of the neighbor list: the
+ * largest rc.  vssr_batch_upload refuses with VSSR_E_CAPACITY a periodic cell so thin for that cutoff that an axis would need more
+ * than 100 images on either side (the neighbor search's limit); nothing is truncated. */
+int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                     vssr_handle **out);
+/* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
+int vssr_pair_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                         const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                         double *energy_atoms_f64, double *forces_f64);
 
 /* ---- Gaussian-mixture uncertainty of PaiNN latent embeddings (reference mcmc.uncertainty.GMMUncertainty,
  *      mcmc/uncertainty/uncertainty.py:238-463; scripts/clustering.py --clustering_metric gmm) ---------------------------------- */

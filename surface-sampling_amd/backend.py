@@ -36,6 +36,7 @@ EXPORTS = (
     "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
+    "vssr_pair_create", "vssr_pair_eval_batch",
 )
 
 
@@ -67,6 +68,12 @@ class FireParams(C.Structure):
 
 class EamGrid(C.Structure):
     _fields_ = [("nrho", C.c_int32), ("nr", C.c_int32), ("drho", C.c_double), ("dr", C.c_double), ("cutoff", C.c_double)]
+
+
+class PairTerm(C.Structure):
+    """vssr_pair_term: 0-based types, style code (``pair.STYLES``), coefficients in LAMMPS order, cutoff, shift flag."""
+    _fields_ = [("type_a", C.c_int32), ("type_b", C.c_int32), ("style", C.c_int32), ("c", C.c_double * 5), ("rc", C.c_double),
+                ("shift", C.c_int32)]
 
 
 class CgParams(C.Structure):
@@ -226,6 +233,10 @@ def load_library():
     L.vssr_sw_create_from_text.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.vssr_sw_eval_batch.restype = C.c_int
     L.vssr_sw_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
+    L.vssr_pair_create.restype = C.c_int
+    L.vssr_pair_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(vp)]
+    L.vssr_pair_eval_batch.restype = C.c_int
+    L.vssr_pair_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_batch_relax_fire.restype = C.c_int
     L.vssr_batch_relax_fire.argtypes = [vp, C.POINTER(FireParams), u8p, C.c_uint32, dp, ip, u8p]
     L.vssr_batch_relax_bfgs.restype = C.c_int
@@ -602,7 +613,7 @@ class PainnEngine(_Handle):
 
 
 class _AnalyticEngine(_Handle):
-    """Shared fp64 interface of the analytic potentials (Tersoff, EAM, Stillinger-Weber): types instead of atomic numbers."""
+    """Shared fp64 interface of the analytic potentials (Tersoff, EAM, Stillinger-Weber, pair): types instead of atomic numbers."""
 
     has_device_results = False    # fp64 results: sharding uses the host result path
 
@@ -724,6 +735,41 @@ class SWEngine(_AnalyticEngine):
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"vssr_sw_create failed ({rc}): {msg.decode() if msg else '?'}")
+
+
+class PairEngine(_AnalyticEngine):
+    """Pair potentials with damped-shifted-force Coulomb (LAMMPS ``pair_style lj/cut``, ``morse``, ``buck``, ``born``, ``coul/dsf``
+    and ``hybrid`` / ``hybrid/overlay`` of them) evaluator, fp64 on device.  Relaxes with FIRE / BFGS and the lock-step CG driver."""
+
+    def __init__(self, terms, charges=None, n_types=None, device=0):
+        """``terms``: a ``pair.PairModel`` (then ``charges`` / ``n_types`` come from it), or a list of ``(type_a, type_b, style, c,
+        rc, shift)`` with 0-based types, a style code or name of ``pair.STYLES`` and up to five coefficients in LAMMPS order;
+        ``charges``: per-type charges [n_types] (needed by coul/dsf)."""
+        super().__init__()
+        from . import pair as pair_io
+
+        if isinstance(terms, pair_io.PairModel):
+            terms, charges, n_types = terms.terms, terms.charges, terms.n_types
+        terms = list(terms)
+        if n_types is None:
+            raise ValueError("n_types is required with a plain term list")
+        arr = (PairTerm * max(len(terms), 1))()
+        for k, (a, b, style, c, rc, shift) in enumerate(terms):
+            c = [float(x) for x in c]
+            if len(c) > 5:
+                raise ValueError("a pair term has at most five coefficients")
+            arr[k] = PairTerm(int(a), int(b), int(pair_io.STYLES.get(style, style)), (C.c_double * 5)(*(c + [0.0] * (5 - len(c)))),
+                              float(rc), int(shift))
+        q = None
+        if charges is not None:
+            q = np.ascontiguousarray(charges, dtype=np.float64)
+            if q.size != int(n_types):
+                raise ValueError("charges must hold one value per type")
+        self.n_types = int(n_types)
+        rc = self._lib.vssr_pair_create(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_pair_create failed ({rc}): {msg.decode() if msg else '?'}")
 
 
 class EAMEngine(_AnalyticEngine):

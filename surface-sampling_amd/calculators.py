@@ -29,7 +29,7 @@ from collections import Counter
 
 import numpy as np
 
-from . import backend, checkpoint, structures, sw as sw_io, tersoff as tersoff_io
+from . import backend, checkpoint, pair as pair_io, structures, sw as sw_io, tersoff as tersoff_io
 
 EV_TO_KCAL_MOL = 23.0605   # nff/utils/constants.py
 HARTREE_TO_EV = 27.2114    # nff/utils/constants.py (reference import: calculators.py:21)
@@ -1240,6 +1240,30 @@ class SWSurfCalc(_AnalyticSurfCalc):
         return backend.SWEngine(self.params, device=_device_index(self.device))
 
 
+class PairSurfCalc(_AnalyticSurfCalc):
+    """Pair potentials with damped-shifted-force Coulomb on MI355X: LAMMPS ``pair_style lj/cut``, ``morse``, ``buck``, ``born``,
+    ``coul/dsf`` and ``hybrid`` / ``hybrid/overlay`` of them, given as the LAMMPS commands a template would carry (``pair_style``,
+    ``pair_coeff``, ``pair_modify shift | mix``, ``set type N charge q``; ``pair.parse``).  ``per_atom_energies`` follow LAMMPS
+    ``pe/atom`` (pair energies half / half, the coul/dsf self term on its atom).  Relaxations use the lock-step CG / FIRE / BFGS
+    drivers.  ``all_periodic=False`` keeps the atoms' own ``pbc``."""
+
+    name = "pair_mi355x"
+
+    def __init__(self, commands=None, text=None, species=None, device="cuda", all_periodic=False, logger=None, **kwargs):
+        """commands: list of LAMMPS command lines, or ``text``: the same as one string; species: symbols in LAMMPS type order."""
+        if (commands is None) == (text is None):
+            raise ValueError("give the pair commands either as commands=[...] or as text=...")
+        if not species:
+            raise ValueError("species (LAMMPS type order) are required")
+        self.species = list(species)
+        self.pair_model = pair_io.parse(text if commands is None else list(commands), len(self.species))
+        self._init_common(device, all_periodic, logger)
+        super().__init__(**kwargs)
+
+    def _make_engine(self):
+        return backend.PairEngine(self.pair_model, device=_device_index(self.device))
+
+
 EAM_STYLES = ("eam", "eam/alloy", "eam/fs")
 
 
@@ -1422,7 +1446,10 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
       model (``sw.MODELS``: the Si(111) 5x5 tutorial's ``SW_StillingerWeber_1985_Si__MO_405512056662_005``; no
       ``potential_file`` needed, the species come from ``atoms``) are evaluated on the device, anything else raises.  For the SW
       styles the energy template's ``boundary`` applies (``p`` periodic; ``f``, ``s``, ``m`` open) and pe/atom follows LAMMPS
-      ``pair_style sw`` (a KIM model's own per-particle split is not reproduced; totals do not depend on it).  When the opt
+      ``pair_style sw`` (a KIM model's own per-particle split is not reproduced; totals do not depend on it).  ``lj/cut``,
+      ``morse``, ``buck``, ``born``, ``coul/dsf`` and ``hybrid`` / ``hybrid/overlay`` of them take their ``pair_coeff`` /
+      ``pair_modify`` / ``set type N charge q`` lines and the ``boundary`` from the energy template (``pair.parse``; no
+      ``potential_file``).  When the opt
       template names another potential the backend lacks (the Si tutorial's SRS model), relaxations raise; single points work.
 
     The potential file is looked up like LAMMPS does (as given, in the run directory, in the working directory, in
@@ -1440,6 +1467,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self.relax_refused = None     # SW styles: the opt template's potential when the backend lacks it
         self.kim_model = None
         self.tables = None            # EAM with several elements (eam/alloy, eam/fs, funcfl files per species)
+        self.pair_model = None        # the pair styles: what pair.parse read from the energy template
         self._cfg_key = None
         self._init_common(device, True, logger)
         self.run_dir = os.getcwd()        # the reference's default (calculators.py:502)
@@ -1520,6 +1548,9 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             self._configure_sw(cfg_path, cfg, tmpls, args, src)
             return
         style = args[0]
+        if style in pair_io.PAIR_STYLES:
+            self._configure_pair(run_dir, cfg_path, cfg)
+            return
         pf = cfg["potential_file"]
         pots = [self._find_potential(x, run_dir) for x in (pf if isinstance(pf, (list, tuple)) else [pf])]
         pot = pots[0]
@@ -1567,7 +1598,39 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             self.funcfl = self.params = None
         else:
             raise backend.BackendError(f"pair_style {style!r} is not provided by this backend "
-                                       "(tersoff, eam, eam/alloy, eam/fs and sw are)")
+                                       "(tersoff, eam, eam/alloy, eam/fs, sw, lj/cut, morse, buck, born, coul/dsf and "
+                                       "hybrid / hybrid/overlay of the last five are)")
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
+        self._cfg_key = key
+
+    def _configure_pair(self, run_dir, cfg_path, cfg):
+        """``pair_style lj/cut | morse | buck | born | coul/dsf | hybrid | hybrid/overlay``: the pair commands (``pair.parse``) and the
+        ``boundary`` come from the energy template (the opt template when there is no other), the species from ``atoms``; no
+        ``potential_file``.  Commands that cannot be read raise ``BackendError``."""
+        name = next(t for t in ("lammps_energy_template.txt", "lammps_opt_template.txt") if os.path.isfile(os.path.join(run_dir, t)))
+        path = os.path.join(run_dir, name)
+        with open(path, encoding="utf-8") as fh:
+            text = fh.read()
+        key = (cfg_path, os.path.getmtime(cfg_path), path, os.path.getmtime(path), "pair")
+        if key == self._cfg_key:
+            return
+        species = list(cfg["atoms"])
+        try:
+            model = pair_io.parse(text, len(species))
+            b = re.search(r"^\s*boundary\s+([^#\n]+)", text, re.M)
+            boundary = self._boundary_pbc(b.group(1).split() if b else None)
+        except ValueError as e:
+            raise backend.BackendError(f"{path}: the pair commands cannot be read: {e}") from None
+        self.pair_model = model
+        self.params = self.funcfl = self.tables = None
+        self.species = species
+        self.bulk_index = int(cfg.get("bulk_index", 0))
+        self.pair_style = "pair"
+        self.kim_model = None
+        self.boundary = boundary
+        self.relax_refused = None
         if self._engine is not None:
             self._engine.close()
             self._engine = None
@@ -1611,7 +1674,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self._cfg_key = key
 
     def _fixed_pbc(self):
-        if self.pair_style in ("sw", "kim") and self.boundary is not None:
+        if self.pair_style in ("sw", "kim", "pair") and self.boundary is not None:
             return self.boundary
         return super()._fixed_pbc()
 
@@ -1625,6 +1688,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
     def _make_engine(self):
         if self.pair_style in ("sw", "kim"):
             return backend.SWEngine(self.params, device=_device_index(self.device))
+        if self.pair_style == "pair":
+            return backend.PairEngine(self.pair_model, device=_device_index(self.device))
         if self.pair_style == "tersoff":
             return backend.TersoffEngine(self.params, device=_device_index(self.device))
         return backend.EAMEngine(self.funcfl if self.tables is None else self.tables, device=_device_index(self.device))

@@ -62,7 +62,14 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
         cell_host_setup(cell + 9 * b, pbc + 3 * b, rc, inv.data() + 9 * b, nimg.data() + 3 * b, ok);
         if (!ok) return set_err(h, VSSR_E_BADARG, "configuration %d: periodic but singular cell", b);
         for (int k = 0; k < 3; ++k)
-            if (nimg[3 * b + k] > 100) return set_err(h, VSSR_E_BADARG, "configuration %d: cell too thin for the cutoff", b);
+            if (nimg[3 * b + k] > 100) {
+                // (a pair handle's cutoff is the caller's choice: its refusal says what was exceeded, with the capacity code)
+                if (h->kind == Kind::PAIR)
+                    return set_err(h, VSSR_E_CAPACITY, "configuration %d: the %g A cutoff needs %d periodic images along axis %d, the neighbor "
+                                   "search scans at most 100 on either side (nothing is truncated: shorten the cutoff or repeat the cell)",
+                                   b, rc, nimg[3 * b + k], k);
+                return set_err(h, VSSR_E_BADARG, "configuration %d: cell too thin for the cutoff", b);
+            }
         const long long imgs = (2LL * nimg[3 * b] + 1) * (2 * nimg[3 * b + 1] + 1) * (2 * nimg[3 * b + 2] + 1);
         if (b == 0 || imgs > h->max_images) h->max_images = (int)(imgs > 1000000 ? 1000000 : imgs);
     }

@@ -1,9 +1,10 @@
-// api_potentials.hip — the fp64 analytic potentials: Tersoff, EAM and Stillinger-Weber creates, the two LAMMPS text parsers,
+// api_potentials.hip — the fp64 analytic potentials: Tersoff, EAM, Stillinger-Weber and pair creates, the two LAMMPS text parsers,
 // and the *_eval_batch entry points.
 #include <cmath>
 
 #include "vssr_internal.h"
 #include "sw_dev.h"
+#include "pair_dev.h"
 
 using namespace vssr;
 
@@ -259,13 +260,123 @@ int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_s
     return sw_create_checked(device, n_species, params.data(), species, out);
 }
 
+// ---- pair potentials --------------------------------------------------------------------------------------------------------
+static const char *const kPairStyle[6] = {"none", "lj/cut", "morse", "buck", "born", "coul/dsf"};
+
+// Checks one caller term and derives the kernel's entry (pair_dev.h PairTerm); qq = q_a q_b.
+static int pair_derive(const vssr_pair_term &t, int idx, double qq, PairTerm &d) {
+    static const int n_coef[6] = {0, 2, 3, 3, 5, 1};
+    const char *nm = kPairStyle[t.style];
+    for (int k = 0; k < n_coef[t.style]; ++k)
+        if (!std::isfinite(t.c[k])) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (%s %d %d): coefficient %d is not finite", idx, nm, t.type_a, t.type_b, k);
+    if (!std::isfinite(t.rc) || !(t.rc > 0)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (%s %d %d): bad cutoff %g (must be > 0)", idx, nm, t.type_a, t.type_b, t.rc);
+    d = PairTerm{};
+    d.style = t.style;
+    d.rc = t.rc;
+    const double rc = t.rc;
+    double e_rc = 0.0;
+    switch (t.style) {
+    case VSSR_PAIR_LJ_CUT: {
+        if (!(t.c[1] > 0)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (lj/cut %d %d): bad sigma %g (must be > 0)", idx, t.type_a, t.type_b, t.c[1]);
+        d.c[0] = t.c[0]; d.c[1] = t.c[1];
+        const double s6 = pow(t.c[1] / rc, 6.0);
+        e_rc = 4.0 * t.c[0] * s6 * (s6 - 1.0);
+        break;
+    }
+    case VSSR_PAIR_MORSE: {
+        d.c[0] = t.c[0]; d.c[1] = t.c[1]; d.c[2] = t.c[2];
+        const double x = exp(-t.c[1] * (rc - t.c[2]));
+        e_rc = t.c[0] * (x * x - 2.0 * x);
+        break;
+    }
+    case VSSR_PAIR_BUCK:
+    case VSSR_PAIR_BORN: {
+        if (!(t.c[1] > 0)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (%s %d %d): bad rho %g (must be > 0)", idx, nm, t.type_a, t.type_b, t.c[1]);
+        d.c[0] = t.c[0]; d.c[1] = 1.0 / t.c[1];
+        if (t.style == VSSR_PAIR_BUCK) {
+            d.c[2] = t.c[2];
+            e_rc = t.c[0] * exp(-rc * d.c[1]) - t.c[2] / pow(rc, 6.0);
+        } else {
+            d.c[2] = t.c[2]; d.c[3] = t.c[3]; d.c[4] = t.c[4];
+            e_rc = t.c[0] * exp((t.c[2] - rc) * d.c[1]) - t.c[3] / pow(rc, 6.0) + t.c[4] / pow(rc, 8.0);
+        }
+        break;
+    }
+    default: {   // coul/dsf
+        const double a = t.c[0];
+        if (!(a >= 0)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (coul/dsf %d %d): bad alpha %g (must be >= 0)", idx, t.type_a, t.type_b, a);
+        const double ec = erfc(a * rc);
+        d.c[0] = a;
+        d.c[1] = ec / rc;
+        d.c[2] = ec / (rc * rc) + PAIR_2_SQRTPI * a * exp(-a * a * rc * rc) / rc;
+        d.c[3] = PAIR_QQRD2E * qq;
+        break;
+    }
+    }
+    if (t.style != VSSR_PAIR_COUL_DSF && t.shift) {
+        if (!std::isfinite(e_rc)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (%s %d %d): E(rc) is not finite", idx, nm, t.type_a, t.type_b);
+        d.eshift = e_rc;
+    }
+    return VSSR_OK;
+}
+
+int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                     vssr_handle **out) {
+    if (!terms || !out || n_terms < 1) return set_err(nullptr, VSSR_E_BADARG, "bad pair arguments");
+    *out = nullptr;
+    if (n_types < 1 || n_types > PAIR_MAX_TYPES) return set_err(nullptr, VSSR_E_BADARG, "pair: %d types (1 .. 8 are supported)", n_types);
+    if (charge)
+        for (int t = 0; t < n_types; ++t)
+            if (!std::isfinite(charge[t])) return set_err(nullptr, VSSR_E_BADARG, "pair: the charge of type %d is not finite", t);
+    std::vector<PairTable> tab(1);
+    memset(tab.data(), 0, sizeof(PairTable));
+    PairTable &T = tab[0];
+    int count[PAIR_MAX_TYPES][PAIR_MAX_TYPES] = {};
+    double cutmax = 0.0, dsf_alpha = 0.0, dsf_rc = 0.0;
+    bool dsf = false, dsf_type[PAIR_MAX_TYPES] = {};
+    for (int n = 0; n < n_terms; ++n) {
+        const vssr_pair_term &t = terms[n];
+        if (t.type_a < 0 || t.type_a >= n_types || t.type_b < 0 || t.type_b >= n_types)
+            return set_err(nullptr, VSSR_E_BADARG, "pair term %d: types %d %d outside [0,%d)", n, t.type_a, t.type_b, n_types);
+        if (t.style < VSSR_PAIR_LJ_CUT || t.style > VSSR_PAIR_COUL_DSF) return set_err(nullptr, VSSR_E_BADARG, "pair term %d: unknown style %d", n, t.style);
+        if (t.style == VSSR_PAIR_COUL_DSF && !charge)
+            return set_err(nullptr, VSSR_E_BADARG, "pair term %d: coul/dsf needs per-type charges (charge is NULL)", n);
+        PairTerm d;
+        if (int rc = pair_derive(t, n, charge ? charge[t.type_a] * charge[t.type_b] : 0.0, d)) return rc;
+        if (t.style == VSSR_PAIR_COUL_DSF) {
+            if (dsf && (t.c[0] != dsf_alpha || t.rc != dsf_rc))
+                return set_err(nullptr, VSSR_E_BADARG, "pair term %d: coul/dsf terms differ in alpha or rc (%g %g vs %g %g)", n, t.c[0], t.rc, dsf_alpha, dsf_rc);
+            dsf = true; dsf_alpha = t.c[0]; dsf_rc = t.rc;
+            dsf_type[t.type_a] = dsf_type[t.type_b] = true;
+        }
+        const int a = t.type_a, b = t.type_b;
+        if (count[a][b] >= PAIR_MAX_TERMS)
+            return set_err(nullptr, VSSR_E_BADARG, "pair term %d: more than %d terms on the type pair %d %d", n, PAIR_MAX_TERMS, a, b);
+        T.term[(a * PAIR_MAX_TYPES + b) * PAIR_MAX_TERMS + count[a][b]] = d;
+        if (a != b) T.term[(b * PAIR_MAX_TYPES + a) * PAIR_MAX_TERMS + count[a][b]] = d;
+        count[a][b] += 1;
+        count[b][a] = count[a][b];
+        cutmax = std::max(cutmax, t.rc);
+    }
+    if (dsf)
+        for (int t = 0; t < n_types; ++t)
+            if (dsf_type[t])
+                T.self_e[t] = -(erfc(dsf_alpha * dsf_rc) / (2.0 * dsf_rc) + 0.5 * PAIR_2_SQRTPI * dsf_alpha) * PAIR_QQRD2E * charge[t] * charge[t];
+    return create_handle(Kind::PAIR, device, out, [&](vssr_handle *h) {
+        h->n_types = n_types;
+        h->n_embed = n_types;
+        h->pot_cutoff = cutmax;
+        return upload_params(h, tab.data(), sizeof(PairTable), "pair table", "pair table upload failed");
+    });
+}
+
 }  // extern "C"
 
-// ---- evaluation with fp64 results: one body behind the three exported names ------------------------------------------------------
+// ---- evaluation with fp64 results: one body behind the four exported names ------------------------------------------------------
 static int analytic_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                                const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                                double *energy_atoms_f64, double *forces_f64) {
-    // (a refusal names the Tersoff entry point whichever of the three was called: the message is kept as it always was)
+    // (a refusal names the Tersoff entry point whichever of the four was called: the message is kept as it always was)
     if (int rc = check_kind(h, KINDS_EVAL, "vssr_tersoff_eval_batch")) return rc;
     if (!is_analytic(h)) return set_err(h, VSSR_E_STATE, "not a Tersoff / EAM / SW handle");
     vssr_out dummy;
@@ -297,6 +408,12 @@ int vssr_eam_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, c
 int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                        const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                        double *energy_atoms_f64, double *forces_f64) {
+    return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
+}
+
+int vssr_pair_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                         const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                         double *energy_atoms_f64, double *forces_f64) {
     return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
 }
 

@@ -203,6 +203,7 @@ __global__ void k_cm_report(int B, const CgState *__restrict__ st, int *__restri
 // of the site terms as well as the batch-wide kernels do at 12 waves per CU once every CU has work for many rounds.
 // VSSR_CG_FUSED: 0 = always the lock-step driver, 1 = the chain-resident kernel whenever it applies, unset = by batch size.
 bool chain_min_supported(const vssr_handle *h) {
+    // (the kernel holds the Tersoff site terms: every other kind -- SW, EAM, pair -- takes the lock-step driver, whatever the knob says)
     if (h->kind != Kind::TERSOFF || h->max_cfg_atoms > CM_MAX_ATOMS) return false;
     const char *e = getenv("VSSR_CG_FUSED");   // (read per call)
     if (e) return atoi(e) != 0;

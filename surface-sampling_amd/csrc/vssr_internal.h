@@ -299,11 +299,13 @@ enum class Kind : int {
     GMM = 5,       // Gaussian-mixture scoring (gmm.hip)
     GMM_FIT = 6,   // Gaussian-mixture fit (gmm_fit.hip)
     CLUSTER = 7,   // latent-space clustering (cluster.hip)
+    PAIR = 8,      // pair potentials + damped-shifted-force Coulomb (pair.hip)
     COUNT
 };
 constexpr unsigned kind_bit(Kind k) { return 1u << (int)k; }
 // kinds that evaluate a resident batch: the vssr_batch_* / vssr_eval* / relaxation / introspection entry points serve these
-constexpr unsigned KINDS_EVAL = kind_bit(Kind::PAINN) | kind_bit(Kind::TERSOFF) | kind_bit(Kind::EAM) | kind_bit(Kind::SW);
+constexpr unsigned KINDS_EVAL = kind_bit(Kind::PAINN) | kind_bit(Kind::TERSOFF) | kind_bit(Kind::EAM) | kind_bit(Kind::SW) |
+                                kind_bit(Kind::PAIR);
 
 }  // namespace vssr
 
@@ -347,10 +349,10 @@ struct vssr_handle {
     vssr::DevBuf model_table;    // ModelW[n_models]
     vssr::DevBuf offset_per_z;   // double[n_embed]
 
-    // the fp64 analytic potentials (Tersoff, EAM, Stillinger-Weber)
+    // the fp64 analytic potentials (Tersoff, EAM, Stillinger-Weber, pair)
     int n_types = 0;
-    double pot_cutoff = 0;       // Tersoff, SW: largest cutoff of the table (EAM: eam_grid.cutoff)
-    vssr::DevBuf pot_params;     // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h); EAM: spline tables (eam.hip)
+    double pot_cutoff = 0;       // Tersoff, SW, pair: largest cutoff of the table (EAM: eam_grid.cutoff)
+    vssr::DevBuf pot_params;     // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h); EAM: spline tables (eam.hip); pair: PairTable (pair_dev.h)
 
     // resident batch
     bool batch_valid = false, ran = false;
@@ -493,6 +495,8 @@ int tersoff_run(vssr_handle *h, uint32_t want);
 int eam_run(vssr_handle *h, uint32_t want);
 // Stillinger-Weber (sw.hip)
 int sw_run(vssr_handle *h, uint32_t want);
+// pair potentials (pair.hip)
+int pair_run(vssr_handle *h, uint32_t want);
 // Gaussian-mixture scoring (gmm.hip).  Rows: caller fp64 rows [n][Dp] (padded), or fp32 rows with leading dimension ldx = Dp;
 // writes g->d_gmm_lp [n][K] (logp_k) and g->d_gmm_nll [n] on stream st
 int gmm_upload(vssr_handle *g, const double *means, const double *prec_chol, const double *weights);
@@ -527,6 +531,7 @@ int slot_stress(vssr_handle *h, const double *gslot);
 int tersoff_stress(vssr_handle *h);
 int eam_stress(vssr_handle *h);
 int sw_stress(vssr_handle *h);
+int pair_stress(vssr_handle *h);   // runs the site kernel's gradient form first: a plain evaluation keeps no per-slot gradients
 // What differs between the kinds that evaluate a batch, one row per Kind (api_handle.hip); run == nullptr: the kind evaluates nothing.
 // f64: an analytic potential -- results in d_pot_e / _ea / _f (fp64, one "model"), driven by relax_cg / chain_min as well.
 struct Evaluator {

@@ -1,0 +1,224 @@
+"""CPU: the pair-command parser (surface_sampling_amd/pair.py), the numpy restatement of the pair styles (tests/pair_oracle.py)
+against closed forms and its own central differences, the Madelung check of the damped-shifted Coulomb sum, and the ABI's export
+list.  No LAMMPS binary is compared anywhere: the formulas are those of the LAMMPS documentation."""
+import json
+import math
+
+import numpy as np
+import pytest
+
+import pair_oracle as po
+from surface_sampling_amd import backend, pair
+from surface_sampling_amd import calculators as calcs
+
+
+# -- parser ------------------------------------------------------------------------------------------------------------------------
+def _by_pair(model):
+    out = {}
+    for t in model.terms:
+        out.setdefault((t.type_a, t.type_b), []).append(t)
+    return out
+
+
+def test_wildcards_and_override_order():
+    m = pair.parse(["pair_style morse 5.0",
+                    "pair_coeff * * 0.1 1.0 2.0",          # every pair
+                    "pair_coeff 2* 3 0.2 1.1 2.1 4.5",     # 2 3 and 3 3, own cutoff
+                    "pair_coeff *2 2 0.3 1.2 2.2",         # 1 2 and 2 2
+                    "pair_coeff 1*2 3 0.4 1.3 2.3",        # 1 3 and 2 3 (overrides the 2* line)
+                    "pair_coeff 1 1 0.5 1.4 2.4  # comment"], 3)
+    P = _by_pair(m)
+    assert sorted(P) == [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)] and all(len(v) == 1 for v in P.values())
+    assert P[(0, 0)][0].c[:3] == (0.5, 1.4, 2.4) and P[(0, 0)][0].rc == 5.0
+    assert P[(0, 1)][0].c[:3] == (0.3, 1.2, 2.2) and P[(1, 1)][0].c[:3] == (0.3, 1.2, 2.2)
+    assert P[(0, 2)][0].c[:3] == (0.4, 1.3, 2.3) and P[(1, 2)][0].c[:3] == (0.4, 1.3, 2.3) and P[(1, 2)][0].rc == 5.0
+    assert P[(2, 2)][0].c[:3] == (0.2, 1.1, 2.1) and P[(2, 2)][0].rc == 4.5
+    assert all(t.style == pair.STYLES["morse"] and t.shift == 0 for t in m.terms) and m.charges is None and m.cutoff == 5.0
+    assert pair.type_range("*", 4) == (1, 4) and pair.type_range("2*", 4) == (2, 4) and pair.type_range("*3", 4) == (1, 3)
+    assert pair.type_range("2*3", 4) == (2, 3) and pair.type_range("4", 4) == (4, 4)
+
+
+def test_both_mixing_rules_fill_unset_lj_pairs_only():
+    lines = ["pair_style lj/cut 6.0", "pair_coeff 1 1 0.01 3.0", "pair_coeff 2 2 0.04 4.0 8.0"]
+    g = _by_pair(pair.parse(lines, 2))[(0, 1)][0]
+    assert g.c[0] == pytest.approx(0.02) and g.c[1] == pytest.approx(math.sqrt(12.0)) and g.rc == pytest.approx(math.sqrt(48.0))
+    a = _by_pair(pair.parse(lines + ["pair_modify mix arithmetic shift yes"], 2))[(0, 1)][0]
+    assert a.c[0] == pytest.approx(0.02) and a.c[1] == pytest.approx(3.5) and a.rc == pytest.approx(7.0) and a.shift == 1
+    e = _by_pair(pair.parse(lines + ["pair_coeff 1 2 0.5 2.0"], 2))[(0, 1)][0]
+    assert e.c[:2] == (0.5, 2.0) and e.rc == 6.0                                # an explicit line wins over mixing
+    for style, coeffs in (("morse", "0.1 1.0 2.0"), ("buck", "100.0 0.3 10.0"), ("born", "1.0 0.3 2.0 1.0 1.0")):
+        with pytest.raises(ValueError, match="All pair coeffs are not set"):
+            pair.parse([f"pair_style {style} 5.0", f"pair_coeff 1 1 {coeffs}", f"pair_coeff 2 2 {coeffs}"], 2)
+
+
+def test_hybrid_assigns_one_substyle_per_pair_and_overlay_adds():
+    h = pair.parse(["pair_style hybrid lj/cut 6.0 morse 5.0 buck 7.0",
+                    "pair_coeff 1 1 lj/cut 0.01 3.0", "pair_coeff 2 2 lj/cut 0.02 3.2",   # 1 2 is mixed (both diagonals lj/cut)
+                    "pair_coeff 1 3 morse 0.1 1.5 2.5", "pair_coeff 2 3 none", "pair_coeff 3 3 morse 0.3 1.2 2.2",
+                    "pair_coeff 3 3 buck 800.0 0.3 20.0"], 3)                              # reassigns 3 3
+    P = _by_pair(h)
+    assert sorted(P) == [(0, 0), (0, 1), (0, 2), (1, 1), (2, 2)]                            # 2 3 is none
+    assert [P[k][0].style for k in sorted(P)] == [1, 1, 2, 1, 3] and all(len(v) == 1 for v in P.values())
+    assert P[(2, 2)][0].rc == 7.0 and P[(0, 2)][0].rc == 5.0 and h.cutoff == 7.0
+    with pytest.raises(ValueError, match="All pair coeffs are not set: 2 3"):
+        pair.parse(["pair_style hybrid lj/cut 6.0 morse 5.0", "pair_coeff 1*2 1*2 lj/cut 0.01 3.0", "pair_coeff 1 3 morse 0.1 1.5 2.5",
+                    "pair_coeff 3 3 morse 0.1 1.5 2.5"], 3)
+    o = pair.parse(po.ROCKSALT_COMMANDS, 2)
+    P = _by_pair(o)
+    assert sorted(P) == [(0, 0), (0, 1), (1, 1)] and all([t.style for t in v] == [4, 5] for v in P.values())
+    assert P[(0, 1)][1].c[0] == 0.2 and P[(0, 1)][1].rc == 12.0 and P[(0, 1)][0].rc == 8.0
+    assert o.charges.tolist() == [1.0, -1.0] and o.cutoff == 12.0
+    wild = pair.parse(["pair_style coul/dsf 0.25 9.0", "pair_coeff * *", "set type * charge 0.5", "set type 2 charge -1.5"], 2)
+    assert wild.charges.tolist() == [0.5, -1.5] and len(wild.terms) == 3
+
+
+@pytest.mark.parametrize("lines, match", [
+    (["pair_style hybrid lj/cut 6.0 eam", "pair_coeff * * lj/cut 0.01 3.0"], "eam"),
+    (["pair_style hybrid/overlay tersoff lj/cut 6.0"], "tersoff"),
+    (["pair_style sw"], "sw"),
+    (["pair_style lj/cut", "pair_coeff * * 0.01 3.0"], "global cutoff"),
+    (["pair_style lj/cut 6.0", "pair_coeff * * {} {} {}"], "not a number"),
+    (["pair_style lj/cut 6.0", "pair_coeff * * 0.01"], "2 coefficient"),
+    (["pair_style lj/cut 6.0", "pair_coeff 2 1 0.01 3.0"], "I <= J"),
+    (["pair_style lj/cut 6.0", "pair_coeff 1 4 0.01 3.0"], "outside 1 .. 3"),
+    (["pair_coeff 1 1 0.01 3.0"], "before pair_style"),
+    (["pair_style hybrid lj/cut 6.0 morse 5.0", "pair_coeff * * buck 1 2 3"], "not in the pair_style line"),
+    (["pair_style lj/cut 6.0", "pair_coeff * * 0.01 3.0", "pair_modify tail yes"], "pair_modify"),
+    (["pair_style coul/dsf 0.2 9.0", "pair_coeff * *", "set atom 3 charge 1.0"], "per type"),
+    (["units metal"], "no pair_style"),
+])
+def test_parser_refusals(lines, match):
+    with pytest.raises(ValueError, match=match):
+        pair.parse(lines, 3)
+
+
+def _run_dir(path, body, atoms=("Na", "Cl")):
+    path.mkdir()
+    (path / "lammps_config.json").write_text(json.dumps({"atoms": list(atoms), "bulk_index": 0}))
+    (path / "lammps_energy_template.txt").write_text("units metal\nboundary p p f\nread_data {}\n" + body + "\nrun 0\n")
+    return path
+
+
+def test_lammps_surf_calc_reads_pair_templates_and_raises_backend_errors(tmp_path):
+    ok = calcs.LAMMPSSurfCalc()
+    ok.set(run_dir=_run_dir(tmp_path / "ok", "\n".join(po.ROCKSALT_COMMANDS)))
+    ok._configure()
+    assert ok.pair_style == "pair" and ok.species == ["Na", "Cl"] and ok.boundary.tolist() == [1, 1, 0]
+    want = pair.parse(po.ROCKSALT_COMMANDS, 2)
+    assert ok.pair_model.terms == want.terms and ok.pair_model.charges.tolist() == [1.0, -1.0]
+    assert ok._fixed_pbc().tolist() == [1, 1, 0]
+    for k, body in enumerate(("pair_style lj/cut\npair_coeff * * {} {} {}", "pair_style hybrid lj/cut 6.0 eam\npair_coeff * * eam Cu_u3.eam",
+                              "pair_style buck 8.0\npair_coeff 1 1 100.0 0.3 1.0\npair_coeff 2 2 100.0 0.3 1.0")):
+        bad = calcs.LAMMPSSurfCalc()
+        bad.set(run_dir=_run_dir(tmp_path / f"bad{k}", body))
+        with pytest.raises(backend.BackendError, match="cannot be read"):
+            bad._configure()
+    c = calcs.PairSurfCalc(commands=po.ROCKSALT_COMMANDS, species=["Na", "Cl"])
+    assert c.pair_model.cutoff == 12.0 and {"energy", "forces", "stress", "per_atom_energies", "surface_energy",
+                                            "relaxed_energy"} <= set(c.implemented_properties)
+    t = calcs.PairSurfCalc(text="\n".join(po.ROCKSALT_COMMANDS), species=["Na", "Cl"])
+    assert t.pair_model.terms == c.pair_model.terms
+    with pytest.raises(ValueError):
+        calcs.PairSurfCalc(species=["Na", "Cl"])
+
+
+def test_exports_list_the_pair_entry_points():
+    assert {"vssr_pair_create", "vssr_pair_eval_batch"} <= set(backend.EXPORTS)
+    lib = backend.load_library()
+    assert lib.vssr_pair_create is not None and lib.vssr_pair_eval_batch is not None
+
+
+# -- the restatement against closed forms --------------------------------------------------------------------------------------------
+OPEN = [0, 0, 0]
+BOX = np.eye(3) * 20.0
+
+
+def _dimer(terms, r, charges=None, types=(0, 0)):
+    X = np.array([[5.0, 5.0, 5.0], [5.0 + r, 5.0, 5.0]])
+    return po.pair(terms, charges, np.array(types), X, BOX, OPEN)
+
+
+def test_dimers_reproduce_the_closed_forms():
+    eps, sig = 0.0104, 3.4
+    E, ea, F = _dimer([(0, 0, "lj/cut", (eps, sig), 10.0, 0)], 2.0 ** (1.0 / 6.0) * sig)
+    assert E == pytest.approx(-eps, rel=1e-14) and ea.tolist() == pytest.approx([-eps / 2] * 2) and np.abs(F).max() < 1e-14
+    D0, al, r0 = 0.35, 1.6, 2.3
+    E, _, F = _dimer([(0, 0, "morse", (D0, al, r0), 8.0, 0)], r0)
+    assert E == pytest.approx(-D0, rel=1e-15) and np.abs(F).max() < 1e-15
+    # hand-computed at r = 2.5: buck A = 1000, rho = 0.3, C = 30; born A = 0.5, rho = 0.3, sig = 2.8, C = 30, D = 50
+    r = 2.5
+    buck = 1000.0 * math.exp(-r / 0.3) - 30.0 / r ** 6
+    assert buck == pytest.approx(0.240369476 - 0.12288, abs=1e-8)
+    E, _, F = _dimer([(0, 0, "buck", (1000.0, 0.3, 30.0), 8.0, 0)], r)
+    assert E == pytest.approx(buck, rel=1e-15)
+    assert F[0, 0] == pytest.approx(-(1000.0 / 0.3 * math.exp(-r / 0.3) - 6 * 30.0 / r ** 7), rel=1e-14) and F[1, 0] == -F[0, 0]
+    born = 0.5 * math.exp((2.8 - r) / 0.3) - 30.0 / r ** 6 + 50.0 / r ** 8
+    assert born == pytest.approx(1.359140914 - 0.12288 + 0.032768, abs=1e-8)
+    E, _, _ = _dimer([(0, 0, "born", (0.5, 0.3, 2.8, 30.0, 50.0), 8.0, 0)], r)
+    assert E == pytest.approx(born, rel=1e-15)
+
+
+@pytest.mark.parametrize("style, c", [("lj/cut", (0.0104, 3.4)), ("morse", (0.35, 1.6, 2.3)), ("buck", (1000.0, 0.3, 30.0)),
+                                      ("born", (0.5, 0.3, 2.8, 30.0, 50.0))])
+def test_shifted_energy_vanishes_at_the_cutoff(style, c):
+    rc = 6.0
+    below = rc * (1 - 2.0 ** -50)
+    E0, _, _ = _dimer([(0, 0, style, c, rc, 0)], below)
+    E1, _, _ = _dimer([(0, 0, style, c, rc, 1)], below)
+    assert abs(E0) > 1e-6 and abs(E1) <= 1e-14
+    assert _dimer([(0, 0, style, c, rc, 1)], rc)[0] == 0.0                       # r < rc is strict
+
+
+def test_dsf_energy_and_force_vanish_at_the_cutoff_and_the_self_term_is_there():
+    al, rc, q = 0.2, 12.0, np.array([1.0, -1.0])
+    terms = [(0, 1, "coul/dsf", (al,), rc, 0), (0, 0, "coul/dsf", (al,), rc, 0), (1, 1, "coul/dsf", (al,), rc, 0)]
+    self_e = -(math.erfc(al * rc) / (2 * rc) + al / math.sqrt(math.pi)) * po.QQRD2E
+    below = rc * (1 - 2.0 ** -50)
+    E, ea, F = _dimer(terms, below, q, (0, 1))
+    assert abs(E - 2 * self_e) <= 1e-13 and np.abs(F).max() <= 1e-13 and ea.tolist() == pytest.approx([self_e] * 2, abs=1e-13)
+    e, de = po.term_energy("coul/dsf", (al,), rc, np.array([3.0]), qq=-1.0)
+    B = math.erfc(al * rc) / rc ** 2 + 2 * al / math.sqrt(math.pi) * math.exp(-(al * rc) ** 2) / rc
+    assert e[0] == pytest.approx(-po.QQRD2E * (math.erfc(0.6) / 3 - math.erfc(al * rc) / rc + B * (3 - rc)), rel=1e-15)
+    E, _, F = _dimer(terms, 3.0, q, (0, 1))
+    assert E == pytest.approx(e[0] + 2 * self_e, rel=1e-14) and F[0, 0] == pytest.approx(de[0], rel=1e-14)
+
+
+def test_oracle_forces_are_the_central_differences_of_its_energies():
+    """12 atoms of three types in a skewed periodic cell, every style present (hybrid/overlay of lj/cut, morse, buck, born and
+    coul/dsf, shifted).  Central difference at h = 1e-5 A: truncation ~ h^2 |E'''| / 6 ~ 1e-9, rounding ~ 2^-52 |E| / h ~ 1e-9 eV/A
+    for |E| ~ 30 eV: 1e-7 eV/A bounds both with a factor of fifty."""
+    rng = np.random.default_rng(12)
+    cell = np.array([[7.0, 0.0, 0.0], [1.0, 6.5, 0.0], [0.5, -0.8, 7.5]])
+    frac = np.array([[x, y, z] for x in (0.1, 0.6) for y in (0.15, 0.65) for z in (0.1, 0.45, 0.8)])
+    X = frac @ cell + rng.normal(0, 0.15, (12, 3))
+    T = np.arange(12) % 3
+    m = pair.parse(["pair_style hybrid/overlay lj/cut 6.0 morse 5.0 buck 7.0 born 6.5 coul/dsf 0.25 9.0",
+                    "pair_coeff 1 1 lj/cut 0.02 2.6", "pair_coeff 2 2 lj/cut 0.03 2.8", "pair_coeff 1 2 morse 0.2 1.4 2.6",
+                    "pair_coeff 1 3 buck 900.0 0.29 25.0", "pair_coeff 2 3 born 0.4 0.3 2.7 20.0 30.0", "pair_coeff 3 3 lj/cut 0.01 3.0",
+                    "pair_coeff * * coul/dsf", "pair_modify shift yes",
+                    "set type 1 charge 0.8", "set type 2 charge 0.4", "set type 3 charge -1.2"], 3)
+    terms, q = po.model_of(m)
+    assert {t[2] for t in terms} == {1, 2, 3, 4, 5}
+    E, ea, F = po.pair(terms, q, T, X, cell, [1, 1, 1])
+    assert ea.sum() == pytest.approx(E, rel=1e-14) and np.abs(F.sum(axis=0)).max() < 1e-12
+    h = 1e-5
+    for a in range(12):
+        for k in range(3):
+            Xp, Xm = X.copy(), X.copy()
+            Xp[a, k] += h; Xm[a, k] -= h
+            fd = -(po.pair(terms, q, T, Xp, cell, [1, 1, 1])[0] - po.pair(terms, q, T, Xm, cell, [1, 1, 1])[0]) / (2 * h)
+            assert abs(fd - F[a, k]) <= 1e-7, (a, k, fd, F[a, k])
+
+
+def test_madelung_energy_of_rocksalt_from_the_dsf_sum():
+    """8-atom rocksalt cube, a = 5.64 A, q = +-1, alpha = 0.2 / A, rc = 12 A, against -1.7475646 qqrd2e 2 / a per ion pair
+    (-8.923514 eV).  The damped-shifted sum is an approximation of the Ewald sum whose error is not derivable in advance; measured
+    once with this restatement: E / 4 = -8.915072852 eV, deviation +8.441281e-3 eV per ion pair (9.46e-4 relative).  The bound is
+    twice that; the margin covers a change of summation order only."""
+    m = pair.parse(["pair_style coul/dsf 0.2 12.0", "pair_coeff * *", "set type 1 charge 1.0", "set type 2 charge -1.0"], 2)
+    T, X, C = po.rocksalt(5.64)
+    E, ea, F = po.pair(*po.model_of(m), T, X, C, [1, 1, 1])
+    ref = -po.MADELUNG_NACL * po.QQRD2E * 2 / 5.64
+    print(f"DSF rocksalt: E / 4 = {E / 4:.9f} eV, Madelung {ref:.9f} eV, deviation {E / 4 - ref:+.6e} eV")
+    assert abs(E / 4 - ref) <= 2 * 8.441281e-3
+    assert np.abs(F).max() < 1e-12 and np.ptp(ea) < 1e-12
