@@ -127,16 +127,21 @@ int run_any(vssr_handle *h, uint32_t want) {
     return evaluator(h).run(h, want);
 }
 
+// The neighbor build overflowed (h_counters[2]): slot_cap becomes what the build counted plus an eighth (cap_tight: the exact need)
+int grow_slot_cap(vssr_handle *h) {
+    if (h->h_counters[0] <= 0) return set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots");
+    h->slot_cap = (int64_t)h->h_counters[0] + (h->cap_tight ? 0 : (int64_t)h->h_counters[0] / 8) + 64;
+    return VSSR_OK;
+}
+
 int sync_and_check(vssr_handle *h) {
     const uint32_t want = h->last_want;   // a rerun after a capacity overflow produces what the original run was asked for
     for (int attempt = 0; attempt < 4; ++attempt) {
         VSSR_HIP(h, hipStreamSynchronize(h->stream));
         h->prof.collect();
         if (!h->ran || !h->h_counters[2]) return VSSR_OK;
-        if (h->h_counters[0] <= 0)
-            return set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots");
-        h->slot_cap = (int64_t)h->h_counters[0] + (h->cap_tight ? 0 : (int64_t)h->h_counters[0] / 8) + 64;
-        int rc = run_any(h, want);
+        int rc = grow_slot_cap(h);
+        if (!rc) rc = run_any(h, want);
         if (rc) return rc;
     }
     return set_err(h, VSSR_E_CAPACITY, "neighbor list capacity could not be satisfied");

@@ -137,7 +137,7 @@ int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr
         h->eam_nel = n_elem;
         h->eam_fs = fs ? 1 : 0;
         h->eam_grid = *grid;
-        // spline tables (eam.hip EamTyped): F [n][nrho + 1][7] | rho [nR][nr + 1][7] | r phi [nP][nr + 1][7]
+        // spline tables (eam_dev.h EamTyped): F [n][nrho + 1][7] | rho [nR][nr + 1][7] | r phi [nP][nr + 1][7]
         const size_t sF = 7 * (size_t)(grid->nrho + 1), sR = 7 * (size_t)(grid->nr + 1);
         std::vector<double> tab(sF * n_elem + sR * (nR + nP));
         for (int t = 0; t < n_elem; ++t) eam_build_spline(frho + (size_t)t * grid->nrho, grid->nrho, grid->drho, tab.data() + sF * t);

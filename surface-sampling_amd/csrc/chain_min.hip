@@ -154,7 +154,7 @@ k_cg_chain(const ChainMinArgs *__restrict__ Ap) {
         for (int i = a0 + tid; i < a1; i += CM_THREADS) tersoff_gather_atom(i, rs, A.rev, A.eps, A.gslot, A.e_atom, A.forces);
         __syncthreads();
         CMP(7)
-        tersoff_chain_energy(b, red, A.cfg_start, A.e_atom, A.energy);
+        chain_energy(b, red, A.cfg_start, A.e_atom, A.energy);
         __syncthreads();
         CMP(8)
         evals += 1;
@@ -249,7 +249,7 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         if (slots > 2147483000LL) return set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots");
         if (h->slot_cap < slots) h->slot_cap = slots;
         if (h->d_edge.ensure(sizeof(float4) * h->slot_cap) || h->d_edge_S.ensure(sizeof(int) * h->slot_cap) ||
-            h->d_rev.ensure(sizeof(int) * h->slot_cap) || h->d_gbar.ensure(sizeof(double) * 4 * (size_t)h->slot_cap))
+            h->d_rev.ensure(sizeof(int) * h->slot_cap) || h->d_gbar.ensure(sizeof(double) * TersoffSlots::doubles(h)))
             return set_err(h, VSSR_E_NOMEM, "neighbor buffers: out of device memory");
         unsigned long long *hits_buf = nullptr;
         const int hits_stride = (h->max_cfg_atoms + 63) & ~63;
@@ -267,7 +267,7 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         A.wpos = h->d_wpos.as<double>(); A.wrap = h->d_wrap.as<int>(); A.deg = h->d_deg.as<int>(); A.row_start = h->d_row_start.as<int>();
         A.edge_S = h->d_edge_S.as<int>(); A.rev = h->d_rev.as<int>(); A.edge = h->d_edge.as<float4>();
         A.hits = hits_buf; A.hits_stride = hits_stride; A.cap_per_atom = cap; A.rc2 = rc * rc;
-        A.eps = h->d_gbar.as<double>(); A.gslot = A.eps + h->slot_cap;
+        A.eps = slots_of(h).eps; A.gslot = slots_of(h).gslot;
         A.e_atom = h->d_pot_ea.as<double>(); A.forces = h->d_pot_f.as<double>(); A.energy = h->d_pot_e.as<double>();
         A.max_iter = cp->max_iter; A.max_eval = cp->max_eval; A.etol = cp->etol; A.ftol = cp->ftol; A.dmax = cp->dmax;
         A.x0 = h->d_vel.as<double>(); A.hh = A.x0 + 3 * (size_t)N; A.gg = A.x0 + 6 * (size_t)N;

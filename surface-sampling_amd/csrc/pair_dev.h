@@ -1,8 +1,8 @@
 // pair_dev.h — device bodies of the pair-potential kernel (pair.hip): the term table, one term's energy and derivative, the
-// 4-lane combine.  Semantics: LAMMPS pair_style lj/cut, morse, buck, born and coul/dsf, units metal (see pair.hip).
+// 4-lane combine, the site tile.  Semantics: LAMMPS pair_style lj/cut, morse, buck, born and coul/dsf, units metal (see pair.hip).
 #ifndef VSSR_PAIR_DEV_H
 #define VSSR_PAIR_DEV_H
-#include "tersoff_dev.h"   // edge_vec, tersoff_chain_energy
+#include "pot_dev.h"
 
 namespace vssr {
 
@@ -86,6 +86,77 @@ __device__ __forceinline__ double quad_sum_f64(double x) {
     x += quad_xchg_f64(x, false);
     x += quad_xchg_f64(x, true);
     return x;
+}
+
+// One tile of PAIR_CENTRES centres, PAIR_LANES lanes each: thread tid serves centre i = (tile's first atom) + (tid >> 2), `mine`: the
+// centre exists and is evaluated.  Every thread of the workgroup calls this (one barrier inside).  sh: the term table in LDS,
+// PAIR_MAX_TYPES^2 x PAIR_MAX_TERMS entries.  GRAD: write the per-slot gradients G_n = 1/2 E'(r_n) u_n into gslot and nothing else.
+template <bool GRAD>
+__device__ __forceinline__ void pair_site_tile(PairTerm *sh, int i, bool mine, int nt, const PairTable *__restrict__ P,
+                                               const int *__restrict__ type, const int *__restrict__ atom_cfg,
+                                               const double *__restrict__ cell, const double *__restrict__ wpos,
+                                               const int *__restrict__ row_start, const float4 *__restrict__ edge,
+                                               const int *__restrict__ edge_S, double *__restrict__ e_atom, double *__restrict__ forces,
+                                               double *__restrict__ gslot) {
+    const int tid = threadIdx.x, q = tid & (PAIR_LANES - 1);
+    // the terms of the nt x nt pairs in use, packed [a][b][k]; 16-byte pieces
+    {
+        constexpr int PIECES = sizeof(PairTerm) / sizeof(uint4);
+        const uint4 *src = reinterpret_cast<const uint4 *>(P->term);
+        uint4 *dst = reinterpret_cast<uint4 *>(sh);
+        for (int t = tid; t < nt * nt * PAIR_MAX_TERMS * PIECES; t += PAIR_CENTRES * PAIR_LANES) {
+            const int term = t / PIECES, piece = t % PIECES;
+            const int k = term % PAIR_MAX_TERMS, ab = term / PAIR_MAX_TERMS, a = ab / nt, b = ab % nt;
+            dst[t] = src[((a * PAIR_MAX_TYPES + b) * PAIR_MAX_TERMS + k) * PIECES + piece];
+        }
+    }
+    __syncthreads();
+    int e0 = 0, deg = 0, ti = 0;
+    const double *C = cell;
+    if (mine) {
+        e0 = row_start[i];
+        deg = row_start[i + 1] - e0;
+        ti = type[i];
+        C = cell + 9 * atom_cfg[i];
+    }
+    double es = 0.0, fx = 0.0, fy = 0.0, fz = 0.0;
+#pragma unroll 1
+    for (int n = q; n < deg; n += PAIR_LANES) {
+        const int j = __float_as_int(edge[e0 + n].w);
+        if (j < 0) continue;   // padding slot (k_slot_stress skips it as well)
+        double rv[3];
+        edge_vec(wpos, C, i, j, edge_S[e0 + n], rv);
+        const double r = sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
+        const PairTerm *T = sh + (ti * nt + type[j]) * PAIR_MAX_TERMS;
+        double e = 0.0, de = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < PAIR_MAX_TERMS; ++k) {
+            if (T[k].style == VSSR_PAIR_NONE) break;
+            if (!(r < T[k].rc)) continue;
+            double ek, dek;
+            pair_term(T[k], r, ek, dek);
+            e += ek;
+            de += dek;
+        }
+        const double w = de / r;
+        if (GRAD) {
+            double *g = gslot + 3 * (size_t)(e0 + n);
+            g[0] = 0.5 * w * rv[0]; g[1] = 0.5 * w * rv[1]; g[2] = 0.5 * w * rv[2];
+        } else {
+            es += e;
+            fx += w * rv[0]; fy += w * rv[1]; fz += w * rv[2];
+        }
+    }
+    if (GRAD) return;
+    // (every lane of the wave arrives here: lanes without a centre carry zeros into the quad sums)
+    es = quad_sum_f64(es);
+    fx = quad_sum_f64(fx);
+    fy = quad_sum_f64(fy);
+    fz = quad_sum_f64(fz);
+    if (mine && q == 0) {
+        e_atom[i] = 0.5 * es + P->self_e[ti];
+        forces[3 * i] = fx; forces[3 * i + 1] = fy; forces[3 * i + 2] = fz;
+    }
 }
 
 }  // namespace vssr

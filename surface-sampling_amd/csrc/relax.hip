@@ -554,8 +554,7 @@ int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr
         if (last || (it + 1) % POLL == 0) {
             VSSR_HIP(h, hipStreamSynchronize(st));
             if (h->h_counters[2]) {   // neighbor capacity overflow in one of the enqueued evaluations: grow, redo
-                if (h->h_counters[0] <= 0) { rc = set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots"); break; }
-                h->slot_cap = (int64_t)h->h_counters[0] + (h->cap_tight ? 0 : (int64_t)h->h_counters[0] / 8) + 64;
+                if ((rc = grow_slot_cap(h))) break;
                 // the step kernels behind the overflowed evaluations did not move anything and did not count steps: go back
                 // by one polling window (chains that did step in it are held to relax_steps by their own step counters)
                 it -= POLL;
@@ -813,8 +812,7 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
     // halvings of alpha (fp64), so the launch budget is max_eval plus one line search plus setup / reset evaluations
     const long long max_launch = (long long)cp->max_eval + 72;
     auto regrow = [&]() -> int {   // capacity overflow seen at a poll: grow; the step kernels behind it did nothing
-        if (h->h_counters[0] <= 0) return set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots");
-        h->slot_cap = (int64_t)h->h_counters[0] + (h->cap_tight ? 0 : (int64_t)h->h_counters[0] / 8) + 64;
+        if (int e = grow_slot_cap(h)) return e;
         if (++h->relax_regrows > 64) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
         return VSSR_OK;
     };

@@ -21,60 +21,45 @@
 namespace vssr {
 
 __global__ void __launch_bounds__(SW_CENTRES * SW_LANES)
-k_sw_site(int N, int nt, const SwP *__restrict__ P, const int *__restrict__ type, const int *__restrict__ atom_cfg,
-          const double *__restrict__ cell, const double *__restrict__ wpos, const int *__restrict__ row_start,
-          const float4 *__restrict__ edge, const int *__restrict__ edge_S, const int *__restrict__ counters,
-          double *__restrict__ eo, double *__restrict__ ej, double *__restrict__ gslot, ActiveView av) {
+k_sw_site(PotView V, const SwP *__restrict__ P, double *__restrict__ eo, double *__restrict__ ej, double *__restrict__ gslot) {
     __shared__ SwShared sh;
-    if (counters[2]) return;   // (uniform)
+    if (V.counters[2]) return;   // (uniform)
     const int i = blockIdx.x * SW_CENTRES + (threadIdx.x >> 2);
-    sw_site_tile(sh, i, i < N && av.atom(i), nt, P, type, atom_cfg, cell, wpos, row_start, edge, edge_S, eo, ej, gslot);
+    sw_site_tile(sh, i, i < V.n_atoms && V.act.atom(i), V.n_types, P, V.type, V.atom_cfg, V.cell, V.wpos, V.row_start, V.edge, V.edge_S, eo,
+                 ej, gslot);
 }
 
-__global__ void k_sw_gather(int N, const int *__restrict__ row_start, const int *__restrict__ rev, const int *__restrict__ counters,
-                            const double *__restrict__ eo, const double *__restrict__ ej, const double *__restrict__ gslot,
-                            double *__restrict__ e_atom, double *__restrict__ forces, ActiveView av) {
+__global__ void k_sw_gather(PotView V, const double *__restrict__ eo, const double *__restrict__ ej, const double *__restrict__ gslot,
+                            double *__restrict__ e_atom, double *__restrict__ forces) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= N || counters[2] || !av.atom(c)) return;
-    sw_gather_atom(c, row_start, rev, eo, ej, gslot, e_atom, forces);
+    if (!V.runs(c)) return;
+    sw_gather_atom(c, V.row_start, V.rev, eo, ej, gslot, e_atom, forces);
 }
 
-__global__ void __launch_bounds__(256)
-k_sw_energy(const int *__restrict__ cfg_start, const double *__restrict__ e_atom, double *__restrict__ energy,
-            const unsigned char *__restrict__ active) {
-    __shared__ double red[256];
-    const int b = blockIdx.x;
-    if (active && !active[b]) return;
-    tersoff_chain_energy(b, red, cfg_start, e_atom, energy);
+// d_gbar of a Stillinger-Weber handle between the site kernel, the gather and the virial kernel: eo [slots] | ej [slots] | G [slots][3]
+struct SwSlots {
+    double *eo, *ej, *gslot;
+    static size_t doubles(const vssr_handle *h) { return 5 * (size_t)h->slot_cap; }
+};
+static SwSlots slots_of(const vssr_handle *h) {
+    double *eo = h->d_gbar.as<double>();
+    return {eo, eo + h->slot_cap, eo + 2 * h->slot_cap};
 }
 
-int sw_stress(vssr_handle *h) { return slot_stress(h, h->d_gbar.as<double>() + 2 * h->slot_cap); }   // eo | ej | G (sw_run)
+int sw_stress(vssr_handle *h) { return slot_stress(h, slots_of(h).gslot); }
 
 int sw_run(vssr_handle *h, uint32_t want) {
     (void)want;
-    const int N = h->n_atoms;
-    hipStream_t st = h->stream;
-    int rc = build_neighbors(h, h->pot_cutoff);
+    int rc = analytic_begin(h, h->pot_cutoff, SwSlots::doubles, "sw");
     if (rc) return rc;
-    if (h->d_pot_e.ensure(sizeof(double) * h->n_cfg) || h->d_pot_ea.ensure(sizeof(double) * N) ||
-        h->d_pot_f.ensure(sizeof(double) * 3 * N) || h->d_gbar.ensure(sizeof(double) * 5 * (size_t)h->slot_cap))
-        return set_err(h, VSSR_E_NOMEM, "sw buffers: out of device memory");
-    double *eo = h->d_gbar.as<double>();
-    double *ej = eo + h->slot_cap;
-    double *gslot = ej + h->slot_cap;
-    h->prof.begin(KC_ANALYTIC, st);
-    const ActiveView av{h->active_mask, h->d_atom_cfg.as<int>()};
-    hipLaunchKernelGGL(k_sw_site, dim3((N + SW_CENTRES - 1) / SW_CENTRES), dim3(SW_CENTRES * SW_LANES), 0, st, N, h->n_types,
-                       h->pot_params.as<SwP>(), h->d_Z.as<int>(), h->d_atom_cfg.as<int>(), h->d_cell.as<double>(),
-                       h->d_wpos.as<double>(), h->d_row_start.as<int>(), h->d_edge.as<float4>(), h->d_edge_S.as<int>(),
-                       h->d_counters.as<int>(), eo, ej, gslot, av);
-    hipLaunchKernelGGL(k_sw_gather, dim3((N + 63) / 64), dim3(64), 0, st, N, h->d_row_start.as<int>(), h->d_rev.as<int>(),
-                       h->d_counters.as<int>(), eo, ej, gslot, h->d_pot_ea.as<double>(), h->d_pot_f.as<double>(), av);
-    hipLaunchKernelGGL(k_sw_energy, dim3(h->n_cfg), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_pot_ea.as<double>(),
-                       h->d_pot_e.as<double>(), h->active_mask);
-    h->prof.end(st);
-    VSSR_HIP(h, hipGetLastError());
-    return VSSR_OK;
+    const PotView V = pot_view(h);
+    const SwSlots S = slots_of(h);
+    const int N = V.n_atoms;
+    hipLaunchKernelGGL(k_sw_site, dim3((N + SW_CENTRES - 1) / SW_CENTRES), dim3(SW_CENTRES * SW_LANES), 0, h->stream, V,
+                       h->pot_params.as<SwP>(), S.eo, S.ej, S.gslot);
+    hipLaunchKernelGGL(k_sw_gather, dim3((N + 63) / 64), dim3(64), 0, h->stream, V, S.eo, S.ej, S.gslot, h->d_pot_ea.as<double>(),
+                       h->d_pot_f.as<double>());
+    return analytic_end(h, V);
 }
 
 }  // namespace vssr

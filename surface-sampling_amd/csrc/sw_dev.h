@@ -2,7 +2,7 @@
 // the gather.  Semantics: LAMMPS pair_style sw, units metal (see sw.hip).
 #ifndef VSSR_SW_DEV_H
 #define VSSR_SW_DEV_H
-#include "tersoff_dev.h"   // edge_vec, tersoff_chain_energy
+#include "pot_dev.h"
 
 namespace vssr {
 

@@ -2,7 +2,7 @@
 // implementation of the site energy / gradient arithmetic, so both drivers produce the same bits.
 #ifndef VSSR_TERSOFF_DEV_H
 #define VSSR_TERSOFF_DEV_H
-#include "vssr_internal.h"
+#include "pot_dev.h"
 
 namespace vssr {
 
@@ -104,13 +104,6 @@ __device__ inline void t_bij(double zeta, const TersP &p, double &b, double &db)
     double c1, c2;
     t_bij_limits(p.n, c1, c2);
     t_bij(zeta, p, c1, c2, b, db);
-}
-
-__device__ inline void edge_vec(const double *__restrict__ wpos, const double *C, int i, int j, int packedS,
-                                double r[3]) {
-    int s0 = (packedS & 255) - 128, s1 = ((packedS >> 8) & 255) - 128, s2 = ((packedS >> 16) & 255) - 128;
-    for (int x = 0; x < 3; ++x)
-        r[x] = wpos[3 * j + x] - wpos[3 * i + x] + s0 * C[x] + s1 * C[3 + x] + s2 * C[6 + x];
 }
 
 // one thread per centre i (rows longer than `longer_than` slots; -1: every row).  row_start: indexed [i], [i + 1]
@@ -445,19 +438,14 @@ __device__ __forceinline__ void tersoff_gather_atom(int c, const int *__restrict
     forces[3 * c] = f0; forces[3 * c + 1] = f1; forces[3 * c + 2] = f2;
 }
 
-// energy of chain b: 256 threads (strided partial sums, binary tree in LDS); red: 256 doubles
-__device__ __forceinline__ void tersoff_chain_energy(int b, double *red, const int *__restrict__ cfg_start, const double *__restrict__ e_atom,
-                                                     double *__restrict__ energy) {
-    const int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int i = cfg_start[b] + tid; i < cfg_start[b + 1]; i += blockDim.x) acc += e_atom[i];
-    red[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) energy[b] = red[0];
+// d_gbar of a Tersoff handle between the site kernels, the gather and the virial kernel: eps [slots] | G [slots][3]
+struct TersoffSlots {
+    double *eps, *gslot;
+    static size_t doubles(const vssr_handle *h) { return 4 * (size_t)h->slot_cap; }
+};
+inline TersoffSlots slots_of(const vssr_handle *h) {
+    double *eps = h->d_gbar.as<double>();
+    return {eps, eps + h->slot_cap};
 }
 
 }  // namespace vssr

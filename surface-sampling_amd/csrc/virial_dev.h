@@ -1,5 +1,5 @@
-// virial_dev.h — device bodies of the virial-stress kernels of the fp64 analytic potentials (k_slot_stress in tersoff.hip for the
-// Tersoff and Stillinger-Weber handles, k_eam_stress / k_eam_stress_typed in eam.hip): the lane layout and the reduction they share.
+// virial_dev.h — device bodies of the virial-stress kernels of the fp64 analytic potentials (k_slot_stress in pot_common.hip for the
+// Tersoff, Stillinger-Weber and pair handles, k_eam_stress in eam.hip): the lane layout and the reduction they share.
 //
 // Under a homogeneous strain every edge vector becomes (1 + eps) r, so W_ab = dE / d eps_ab is a sum over the chain's slots of
 // (dE / d r)_a r_b; sigma = sym(W) / |det cell| (ASE's sign: tensile positive; the volume of the cell also for slabs), Voigt order

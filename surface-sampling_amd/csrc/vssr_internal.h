@@ -476,6 +476,7 @@ int create_handle(Kind kind, int device, vssr_handle **out, Init init, bool rang
 }
 int run_any(vssr_handle *h, uint32_t want);
 int sync_and_check(vssr_handle *h);   // synchronise; if the neighbor capacity overflowed, grow and rerun
+int grow_slot_cap(vssr_handle *h);    // slot_cap for the rerun after an overflow, from the slots the build counted (h_counters[0])
 
 // neighbor list (nbr.hip)
 int build_neighbors(vssr_handle *h, double cutoff);
@@ -526,8 +527,7 @@ int cluster_set_points(vssr_handle *h, int64_t n, const double *pts);
 int cluster_linkage(vssr_handle *h, double *Z, int32_t *n_rounds);
 int cluster_pad_dims(int d);   // stored width of a point: 1, 2, 3, 4, 8, 16 or 32 coordinates
 // vssr_batch_stress on the analytic potentials: enqueue the virial kernel over what the last run left on the device (d_stress, as
-// painn_stress); nothing of it runs unless asked for.  slot_stress (tersoff.hip): the kernel Tersoff and SW share, gslot = the handle's G array
-int slot_stress(vssr_handle *h, const double *gslot);
+// painn_stress); nothing of it runs unless asked for.  (The pieces the analytic potentials share are declared in pot_dev.h.)
 int tersoff_stress(vssr_handle *h);
 int eam_stress(vssr_handle *h);
 int sw_stress(vssr_handle *h);

@@ -173,7 +173,7 @@ def test_edge_kernel_isa_keeps_loads_out_of_mfma_windows():
 def test_hot_kernels_have_no_register_spills():
     """VERDICT r2 item 1c, kept true: every matrix-pipe kernel of the edge and node files compiles without spilled VGPRs / SGPRs
     -- since round 4 without exception (the unfused MODE 0 reverse update kernel, used with readout widths other than 64, runs
-    the rolled GEMMs).  Also the Tersoff kernels: no spilled VECTOR registers and no scratch (the first one-thread-per-centre
+    the rolled GEMMs).  Also the kernels of the fp64 analytic potentials (Tersoff, the kernels they share, SW, pair, EAM): no spilled VECTOR registers and no scratch (the first one-thread-per-centre
     kernel ran for three rounds with 49 spilled registers because it was compiled for 1 024-thread workgroups; scalar spills go
     to vector lanes and are allowed there).  Reads the code-object metadata of a cross-compile (no GPU needed)."""
     import re
@@ -183,7 +183,8 @@ def test_hot_kernels_have_no_register_spills():
     csrc = os.path.join(ROOT, "surface-sampling_amd", "csrc")
     checked = 0
     for hip, extra, scalar_spills_ok in (("painn_node_mfma.hip", [], False), ("painn_edge_mfma.hip", ["-fno-slp-vectorize"], False),
-                                         ("painn_l0.hip", [], False), ("tersoff.hip", [], True)):
+                                         ("painn_l0.hip", [], False), ("tersoff.hip", [], True), ("pot_common.hip", [], True),
+                                         ("sw.hip", [], True), ("pair.hip", [], True), ("eam.hip", [], True)):
         with tempfile.TemporaryDirectory() as tmp:
             out = os.path.join(tmp, "k.s")
             subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", *extra,

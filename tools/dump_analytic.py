@@ -1,0 +1,144 @@
+"""Bit-equality record of the fp64 analytic potentials: evaluates a fixed set of small cases on the library VSSR_EVAL_LIB names (as
+every tool here) and prints one JSON object {case: {array: SHA-256 of its bytes}}.  Run it once per build and diff the outputs: a
+refactor of tersoff.hip / sw.hip / pair.hip / eam.hip / pot_common.hip / relax.hip must leave every digest as it was.
+
+Cases (the smallest that reach every kernel and branch of those files):
+  tersoff_gan       GaN.tersoff: the 3x3 slab + 12 Ga adatoms (48 atoms), the bare slab (36), a 43-atom dense box whose rows
+                    exceed the 16-slot tile -- three chains of unequal length, 127 atoms (no multiple of 64)
+  tersoff_5species  synthetic five-species entries: more than the LDS kernel holds, every row takes the one-thread form
+  sw_si111 / sw_3species   the Si(111) 5x5 slab (100 atoms); one dense three-species cell (long-row form)
+  eam_funcfl / eam_alloy / eam_fs   Cu(100) and Au(110) with adatoms: Cu_u3 funcfl handle, a Cu/Au eam/alloy and an eam/fs handle
+  pair_rocksalt     the 64-atom rocksalt cell with Born + coul/dsf
+each with energies, per-atom energies, forces and stress(); relax_*: chain-resident CG, lock-step CG (VSSR_CG_FUSED=0), FIRE and BFGS
+of the GaN batch with positions, energies and step counts; *_tight: the Tersoff and pair cases and relaxations again after
+debug_capacity(tight=1) with one slot per atom, so the first run overflows and the capacity is regrown (vssr_synchronize, the
+lock-step relaxation drivers).
+Usage: VSSR_EVAL_LIB=build/variants/lib_x.so python tools/dump_analytic.py > out.json"""
+import hashlib, json, os, sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+OUT = {}
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def record(case, **arrays):
+    OUT[case] = {k: sha(v) for k, v in arrays.items()}
+
+
+def single_point(case, eng, structs, tight=False):
+    if tight:
+        eng.debug_capacity(slots_per_atom=1, tight=1)
+    e, ea, f = eng.evaluate_f64(structs)
+    record(case, energy=e, e_atom=ea, forces=f, stress=eng.stress()[0])
+
+
+def with_adatoms(name, every):
+    """(positions, cell, pbc) of a golden slab with an adatom on every ``every``-th adsorption site."""
+    d = np.load(os.path.join(GOLDEN, name + ".npz"))
+    return np.concatenate([d["positions"], d["ads_coords"][::every]]), d["cell"], d["pbc"].astype(np.uint8)
+
+
+def gan_batch():
+    import sw_oracle as so
+
+    S = np.load(os.path.join(GOLDEN, "structures.npz"))
+    Z, X, Cl = S["GaN_3x3_pristine.numbers"], S["GaN_3x3_pristine.positions"], S["GaN_3x3_pristine.cell"]
+    pbc = S["GaN_3x3_pristine.pbc"].astype(np.uint8)
+    T = np.where(Z == 31, 0, 1).astype(np.int32)
+    ztop = X[:, 2].max()
+    ads = np.array([(i + 0.5) / 4 * Cl[0] + (j + 0.5) / 3 * Cl[1] for i in range(4) for j in range(3)])
+    ads[:, 2] = ztop + 1.8
+    rng = np.random.default_rng(12)
+    slab48 = (np.concatenate([T, np.zeros(12, np.int32)]), np.concatenate([X, ads]) + rng.normal(0, 0.05, (48, 3)), Cl, pbc)
+    return [slab48, (T, X + rng.normal(0, 0.05, X.shape), Cl, pbc), so.dense_box(n=43, box=6.5, min_dist=1.55, seed=3, nt=2)]
+
+
+def relaxations(eng, structs, tag, tight):
+    def fresh():
+        if tight:
+            eng.debug_capacity(slots_per_atom=1, tight=1)
+
+    fixed = np.concatenate([np.arange(len(s[0])) % 5 == 0 for s in structs]).astype(np.uint8)
+    for name, fused in (("cg_chain", "1"), ("cg_lockstep", "0")):
+        os.environ["VSSR_CG_FUSED"] = fused   # (read by the library at every call)
+        fresh()
+        e, ea, f, pos, it, ev, why = eng.relax_cg_f64(structs, fixed=fixed, max_iter=40, etol=0.0, ftol=1e-4)
+        record(f"relax_{name}{tag}", energy=e, e_atom=ea, forces=f, positions=pos, n_iter=it, n_eval=ev, stop=why,
+               regrows=np.int32(eng.debug_capacity()))
+    del os.environ["VSSR_CG_FUSED"]
+    for opt in ("FIRE", "BFGS"):
+        fresh()
+        e, ea, f, pos, steps, conv = eng.relax_f64(structs, fixed=fixed, max_steps=30, fmax=0.01, optimizer=opt)
+        record(f"relax_{opt.lower()}{tag}", energy=e, e_atom=ea, forces=f, positions=pos, n_steps=steps, converged=conv,
+               regrows=np.int32(eng.debug_capacity()))
+
+
+def main():
+    import eam_alloy_oracle as ao
+    import pair_oracle as po
+    import sw_oracle as so
+    from conftest import synthetic_tersoff
+    from surface_sampling_amd import backend, eam, pair
+
+    with open(os.path.join(GOLDEN, "GaN_tersoff_params.json")) as fh:
+        gan_params = np.array(json.load(fh)["params_ijk"], dtype=np.float64)
+    gan = gan_batch()
+    m = pair.parse(po.ROCKSALT_COMMANDS, 2)
+    Tr, Xr, Cr = po.rocksalt(5.64)
+    rep = np.array([[x, y, z] for x in range(2) for y in range(2) for z in range(2)], float) * 5.64
+    rock = (np.tile(Tr, 8), (Xr[None] + rep[:, None]).reshape(-1, 3) + np.random.default_rng(21).normal(0, 0.05, (64, 3)), Cr * 2,
+            np.ones(3, np.uint8))
+    for tag, tight in (("", False), ("_tight", True)):
+        eng = backend.TersoffEngine(gan_params, device=0)
+        single_point("tersoff_gan" + tag, eng, gan, tight)
+        relaxations(eng, gan, tag, tight)
+        eng.close()
+        eng = backend.PairEngine(m, device=0)
+        single_point("pair_rocksalt" + tag, eng, [rock], tight)
+        eng.close()
+    eng = backend.PairEngine(m, device=0)   # the lock-step drivers of a handle the chain-resident minimiser does not serve
+    eng.debug_capacity(slots_per_atom=1, tight=1)
+    e, ea, f, pos, it, ev, why = eng.relax_cg_f64([rock], max_iter=5, etol=0.0, ftol=1e-4)
+    record("relax_cg_pair_tight", energy=e, e_atom=ea, forces=f, positions=pos, n_iter=it, n_eval=ev, stop=why)
+    eng.close()
+
+    eng = backend.TersoffEngine(synthetic_tersoff(5, 2), device=0)
+    single_point("tersoff_5species", eng, [so.dense_box(n=30, box=8.0, min_dist=1.9, seed=5, nt=5)])
+    eng.close()
+
+    Z, X, Cl, pbc, _ = so.si_slab()
+    eng = backend.SWEngine(so.si_params(), device=0)
+    single_point("sw_si111", eng, [(np.zeros(len(Z), np.int32), X, Cl, pbc.astype(np.uint8))])
+    eng.close()
+    eng = backend.SWEngine(so.three_species()[1], device=0)
+    single_point("sw_3species", eng, [so.dense_box(nt=3, seed=3)])
+    eng.close()
+
+    cu, au = eam.read_funcfl(os.path.join(GOLDEN, "Cu_u3.eam")), eam.read_funcfl(os.path.join(GOLDEN, "Au_u3.eam"))
+    slabs = [with_adatoms("cu100", 3), with_adatoms("au110", 2)]
+    one = [(np.zeros(len(x), np.int32), x, c, p) for x, c, p in slabs]
+    two = [(ao.random_alloy(x, 0.4, 7 + k), x, c, p) for k, (x, c, p) in enumerate(slabs)]
+    eng = backend.EAMEngine(cu, device=0)
+    single_point("eam_funcfl", eng, one)
+    eng.close()
+    eng = backend.EAMEngine(eam.tables_from_setfl(ao.cuau_setfl(cu, au), ["Cu", "Au"]), device=0)
+    single_point("eam_alloy", eng, two)
+    eng.close()
+    eng = backend.EAMEngine(eam.tables_from_setfl(eam.parse_setfl(eam.write_setfl(ao.cuau_setfl(cu, au, (0.7, 1.3))), fs=True), ["Cu", "Au"]),
+                            device=0)
+    single_point("eam_fs", eng, two)
+    eng.close()
+    print(json.dumps(OUT, indent=1, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
