@@ -1,4 +1,4 @@
-"""Create / destroy routes of the seven handle kinds on the MI355X (csrc/api_handle.hip: one create path, owning buffers): every
+"""Create / destroy routes of the eight handle kinds on the MI355X (csrc/api_handle.hip: one create path, owning buffers): every
 kind is created, does one small piece of work, is closed, and is created again -- the second life gives the first one's bits.  A
 create that fails after the device was opened leaves its message and a usable process; closing never-used and already-closed
 handles works.  Nothing here faults the device: every failing call fails in host validation."""
@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cell_cases as cc
+import pair_oracle as po
 import sw_oracle as so
 from conftest import SI_T3, SI_T3_A0, diamond_cell
 from surface_sampling_amd import backend
@@ -30,6 +31,19 @@ def _analytic(make, a):
         eng.close()
         return [e, ea, f, st]
     return life
+
+
+def _pair():
+    """Born + coul/dsf on the 8-atom rocksalt cube (a 12 A cutoff over several images) and a copy with displaced atoms."""
+    from surface_sampling_amd import pair
+
+    T, X, cell = po.rocksalt(5.64)
+    X2 = X + 0.05 * np.random.default_rng(3).normal(size=X.shape)
+    eng = backend.PairEngine(pair.parse(po.ROCKSALT_COMMANDS, 2), device=0)
+    e, ea, f = eng.evaluate_f64([(T, X, cell, ONES), (T, X2, cell, ONES)])
+    st, _ = eng.stress()
+    eng.close()
+    return [e, ea, f, st]
 
 
 def _painn(golden):
@@ -98,13 +112,14 @@ def _lives(golden):
         "tersoff": _analytic(lambda: backend.TersoffEngine(SI_T3, device=0), SI_T3_A0),
         "eam": _analytic(lambda: backend.EAMEngine(cc.cu_funcfl(), device=0), 5.0),
         "sw": _analytic(lambda: backend.SWEngine(so.si_params(), device=0), 5.431),
+        "pair": _pair,
         "gmm": _gmm,
         "gmm_fit": _gmm_fit,
         "cluster": _cluster,
     }
 
 
-@pytest.mark.parametrize("kind", ["painn", "tersoff", "eam", "sw", "gmm", "gmm_fit", "cluster"])
+@pytest.mark.parametrize("kind", ["painn", "tersoff", "eam", "sw", "pair", "gmm", "gmm_fit", "cluster"])
 def test_second_life_repeats_the_first_bit_for_bit(golden, kind):
     life = _lives(golden)[kind]
     first, second = life(), life()

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+import pair_cases as pc
 import pair_oracle as po
 from surface_sampling_amd import backend, pair
 from surface_sampling_amd import calculators as calcs
@@ -222,3 +223,75 @@ def test_madelung_energy_of_rocksalt_from_the_dsf_sum():
     print(f"DSF rocksalt: E / 4 = {E / 4:.9f} eV, Madelung {ref:.9f} eV, deviation {E / 4 - ref:+.6e} eV")
     assert abs(E / 4 - ref) <= 2 * 8.441281e-3
     assert np.abs(F).max() < 1e-12 and np.ptp(ea) < 1e-12
+
+
+# -- rehearsals of the device tests' inputs (tests/pair_cases.py) ------------------------------------------------------------------------
+def test_row_shape_inputs_have_the_degrees_the_device_test_presumes():
+    m = pair.parse(pc.ROWS_MODEL, 2)
+    assert m.cutoff == pc.ROWS_RC and m.charges.tolist() == [0.7, -0.5] and len(m.terms) == 6
+    batch = pc.rows_batch()
+    assert [len(s[0]) for s in batch] == [31, 65, 63] and [s[3].tolist() for s in batch] == [[0, 0, 0], [1, 1, 1], [1, 1, 0]]
+    deg = pc.degrees(batch[0], pc.ROWS_RC)
+    assert deg.tolist() == pc.ROWS_DEGREES and {0, 1, 2, 3, 4, 5, 9} <= set(deg.tolist())
+    assert (batch[0][1] > 2.0).all() and (batch[0][1] < 28.0).all()            # inside the open box
+    assert pc.cutoff_margin(m, batch[0]) > 0.05 and all(pc.cutoff_margin(m, s) > 1e-6 for s in batch[1:])
+    assert all(pc.degrees(s, pc.ROWS_RC).min() >= 5 for s in batch[1:])
+    E, ea, F = po.pair(*po.model_of(m), *batch[0])
+    self_e = -(math.erfc(0.25 * 4.0) / (2 * 4.0) + 0.25 / math.sqrt(math.pi)) * po.QQRD2E * 0.7 ** 2
+    assert ea[0] == pytest.approx(self_e, rel=1e-15) and not F[0].any() and np.abs(F[1]).max() > 0.1
+
+
+@pytest.mark.parametrize("nt", [8, 5])
+def test_table_inputs_give_every_pair_its_own_terms_and_notice_swapped_labels(nt):
+    m = pair.parse(pc.table_lines(nt), nt)
+    P = _by_pair(m)
+    assert sorted(P) == [(a, b) for a in range(nt) for b in range(a, nt)]
+    triple = [(0, nt - 1), (nt - 1, nt - 1), (3, 4)]
+    for p, terms in P.items():
+        assert [t.style for t in terms] == [1, 2, 5] if p in triple else len(terms) == 1
+    assert all(len({t.rc for t in P[p]}) == 3 for p in triple)
+    assert {t.style for t in m.terms} == {1, 2, 3, 4, 5} and len({(t.style, t.c, t.rc) for t in m.terms if t.style != 5}) == len(m.terms) - 3
+    assert len(set(m.charges.tolist())) == nt
+    s = pc.table_chain(nt)
+    assert len(s[0]) == 40 and set(s[0].tolist()) == set(range(nt)) and s[3].tolist() == [1, 1, 0]
+    assert pc.cutoff_margin(m, s) > 0.005                                      # the strain derivative crosses no cutoff
+    terms, q = po.model_of(m)
+    E = po.pair(terms, q, *s)[0]
+    moved = [abs(po.pair(terms, q, *pc.swap_types(s, a, b))[0] - E) for a in range(nt) for b in range(a + 1, nt)]
+    print(f"nt = {nt}: E {E:.6f} eV, smallest |dE| of a label swap {min(moved):.3e} eV")
+    assert min(moved) > 1e-6
+
+
+@pytest.mark.parametrize("lines, rc, inside", [(pc.CUT_LJ, 6.0, -1.3317912758948642e-3), (pc.CUT_OVERLAY, 6.0, -1.6170257725862544e-2),
+                                               (pc.CUT_OVERLAY, 5.0, None), (pc.CUT_DSF, 6.0, None)])
+def test_cutoff_dimers_sit_exactly_at_and_one_ulp_off_the_cutoff(lines, rc, inside):
+    m = pair.parse(lines, 1)
+    structs, sep = pc.cutoff_dimers(rc)
+    assert sep.tolist() == [np.nextafter(rc, 0.0), rc, np.nextafter(rc, 100.0)]
+    for (T, X, C, pbc), d in zip(structs, sep):
+        dx = X[1] - X[0]
+        assert dx[0] == d and not dx[1:].any() and np.sqrt(dx[0] * dx[0] + 0.0 + 0.0) == d      # r as a kernel forms it
+    E = [po.pair(*po.model_of(m), *s)[0] for s in structs]
+    if inside is not None:
+        assert E[1] == 0.0 and E[2] == 0.0 and E[0] == pytest.approx(inside, rel=1e-12) and abs(E[0]) > 1e-3
+    elif rc == 5.0:
+        assert abs(E[1] - E[2]) < 1e-15 and abs(E[1]) > 1e-2 and abs(E[0] - E[1]) > 1e-3                  # the inner term alone switches
+    else:
+        assert E[0] == E[1] == E[2] and abs(E[0] - 2 * po.pair(*po.model_of(m), *structs[1])[1][0]) == 0.0
+
+
+def test_relaxation_inputs_fall_in_energy_and_end_away_from_every_cutoff():
+    from fire_oracle import fire_relax
+
+    m = pair.parse(pc.OVERLAY5, 3)
+    terms, q = po.model_of(m)
+    chains, mask = pc.relax_batch()
+    assert [len(c[0]) for c in chains] == [7, 16, 23] and mask.sum() == 6 and mask[[0, 1, 7, 8, 23, 24]].all()
+    for T, X, Cl, pbc in pc.relax_batch(pc.STRESS_SEEDS)[0]:
+        def fn(p):
+            E, _, F = po.pair(terms, q, T, p, Cl, pbc)
+            return E, F
+
+        pref, _, steps, conv = fire_relax(fn, X, fixed=np.arange(2), max_steps=12, fmax=1e-9)
+        assert steps == 12 and not conv and fn(pref)[0] < fn(X)[0] - 1.0
+        assert pc.cutoff_margin(m, (T, pref, Cl, pbc)) > 0.005

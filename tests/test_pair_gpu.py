@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pair_oracle as po
+from pair_cases import OVERLAY5, grid_chain as _grid_chain
 import strain_fd as sf
 
 pytestmark = pytest.mark.gpu
@@ -54,27 +55,9 @@ def _check(eng, model, structs, tag, stress=False):
     return e, ea, f
 
 
-def _grid_chain(n, seed, pbc, n_types=3, spacing=2.7, jitter=0.15):
-    """n atoms on a jittered grid in a skewed cell; open axes get 12 A of vacuum: (types, positions, cell, pbc)."""
-    rng = np.random.default_rng(seed)
-    nx = int(np.ceil(n ** (1 / 3)))
-    ny = int(np.ceil(np.sqrt(n / nx)))
-    nz = int(np.ceil(n / (nx * ny)))
-    pts = np.array([[x, y, z] for z in range(nz) for y in range(ny) for x in range(nx)], float)[:n]
-    lens = np.array([nx, ny, nz], float) * spacing + np.where(np.asarray(pbc, bool), 0.0, 12.0)
-    cell = np.diag(lens) + np.array([[0, 0, 0], [0.9, 0, 0], [0.4, -0.6, 0]]) * np.asarray(pbc, float)[:, None]
-    X = (pts + 0.25) * spacing + rng.normal(0, jitter, (n, 3))
-    return rng.permutation(np.arange(n) % n_types).astype(np.int32), X, cell, np.asarray(pbc, np.uint8)
-
-
 HYBRID = ["pair_style hybrid lj/cut 6.0 morse 5.0 buck 7.0",
           "pair_coeff 1 1 lj/cut 0.02 2.6", "pair_coeff 2 2 lj/cut 0.03 2.5 5.5", "pair_coeff 1 2 morse 0.2 1.4 2.6",
           "pair_coeff 1 3 buck 900.0 0.29 25.0", "pair_coeff 3 3 morse 0.15 1.2 2.9", "pair_coeff 2 3 none"]
-OVERLAY5 = ["pair_style hybrid/overlay lj/cut 6.0 morse 5.0 buck 7.0 born 6.5 coul/dsf 0.25 9.0",
-            "pair_coeff 1 1 lj/cut 0.02 2.6", "pair_coeff 2 2 lj/cut 0.03 2.8", "pair_coeff 1 2 morse 0.2 1.4 2.6",
-            "pair_coeff 1 3 buck 900.0 0.29 25.0", "pair_coeff 2 3 born 0.4 0.3 2.7 20.0 30.0", "pair_coeff 3 3 lj/cut 0.01 3.0",
-            "pair_coeff * * coul/dsf", "pair_modify shift yes",
-            "set type 1 charge 0.8", "set type 2 charge 0.4", "set type 3 charge -1.2"]
 
 
 # 1 --------------------------------------------------------------------------------------------------------------------------------
