@@ -245,7 +245,7 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
     h->relax_regrows = 0;
     h->last_want = want | VSSR_WANT_FORCES;
     // chains of <= 256 atoms on the Tersoff potential: one workgroup minimises one chain from start to stop (chain_min.hip); else
-    // the lock-step driver (relax.hip).  Same results bit for bit.
+    // the lock-step driver (relax_cg.hip).  Same results bit for bit.
     const bool resident = chain_min_supported(h);
     int rc = resident ? chain_min_cg(h, params, fixed, want) : relax_cg(h, params, fixed, want);
     if (rc) return rc;
@@ -273,8 +273,7 @@ int vssr_batch_relax_bfgs(vssr_handle *h, const vssr_bfgs_params *params, const 
     VSSR_HIP(h, hipSetDevice(h->device));
     h->relax_regrows = 0;
     h->last_want = want | VSSR_WANT_FORCES;
-    int rc = relax_run(h, 1, nullptr, params, fixed, want);
-    if (rc) return rc;
+    if (int rc = relax_bfgs(h, *params, fixed, want)) return rc;
     return relax_finish(h, pos_out, n_steps, converged);
 }
 
@@ -287,8 +286,7 @@ int vssr_batch_relax_fire(vssr_handle *h, const vssr_fire_params *params, const 
     VSSR_HIP(h, hipSetDevice(h->device));
     h->relax_regrows = 0;
     h->last_want = want | VSSR_WANT_FORCES;
-    int rc = relax_run(h, 0, params, nullptr, fixed, want);
-    if (rc) return rc;
+    if (int rc = relax_fire(h, *params, fixed, want)) return rc;
     return relax_finish(h, pos_out, n_steps, converged);
 }
 

@@ -1,5 +1,5 @@
-// cg_dev.h — device side of the LAMMPS-style conjugate-gradient minimiser (relax.hip), shared with the chain-resident minimiser
-// (chain_min.hip): fp64 block reductions and the per-chain state machine.
+// cg_dev.h — device side of the LAMMPS-style conjugate-gradient minimiser (relax_cg.hip), shared with the chain-resident minimiser
+// (chain_min.hip): fp64 block reductions (relax.hip uses them too), the per-chain state machine and its workspace.
 #ifndef VSSR_CG_DEV_H
 #define VSSR_CG_DEV_H
 #include "vssr_internal.h"
@@ -57,7 +57,7 @@ struct CgState {
 };
 
 // One step of chain b's state machine on the evaluation that has just been made (energy[b], forces of its atoms); every thread of
-// the (256-thread) workgroup calls it; red: >= 16 doubles of LDS.  The lock-step driver (k_cg_step, relax.hip) and the chain-resident
+// the (256-thread) workgroup calls it; red: >= 16 doubles of LDS.  The lock-step driver (k_cg_step, relax_cg.hip) and the chain-resident
 // minimiser (chain_min.hip) run this same code.
 __device__ __forceinline__ void cg_step_chain(int b, double *red, const int *__restrict__ cfg_start, const double *__restrict__ energy,
           const double *__restrict__ forces, const uint8_t *__restrict__ fixed, int max_iter, int max_eval, double etol,
@@ -182,6 +182,19 @@ __device__ __forceinline__ void cg_step_chain(int b, double *red, const int *__r
     start_linesearch();
 }
 
+// The minimiser's workspace on the handle's optimizer buffers (as FireWork / BfgsWork, relax.hip)
+struct CgWork {
+    CgState *st;
+    double *x0, *hh, *gg;   // [3 N] each: start point of the line search, search direction, previous gradient
+    static int ensure(vssr_handle *h, CgWork &out) {
+        const size_t N = h->n_atoms;
+        if (h->d_opt_state.ensure(sizeof(CgState) * h->n_cfg) || h->d_opt_vec.ensure(sizeof(double) * 9 * N))
+            return set_err(h, VSSR_E_NOMEM, "CG state: out of device memory");
+        double *x0 = h->d_opt_vec.as<double>();
+        out = {h->d_opt_state.as<CgState>(), x0, x0 + 3 * N, x0 + 6 * N};
+        return VSSR_OK;
+    }
+};
 
 }  // namespace vssr
 #endif

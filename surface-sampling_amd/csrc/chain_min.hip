@@ -1,6 +1,6 @@
 // chain_min.hip — the chain-resident minimiser: ONE workgroup runs the whole LAMMPS-style CG relaxation of ONE chain.
 //
-// Replaces, for small chains on the fp64 Tersoff potential, the lock-step driver of relax.hip (reference: `optimizer: "LAMMPS"`,
+// Replaces, for small chains on the fp64 Tersoff potential, the lock-step driver of relax_cg.hip (reference: `optimizer: "LAMMPS"`,
 // LAMMMPSCalc.run_lammps_opt, mcmc/calculators/calculators.py:600-619 -> `min_style cg` / `minimize 1e-5 1e-5 {relax_steps} 10000`,
 // tutorials/data/GaN_0001/GaN_0001_lammps_opt_template.txt; one relaxation per MC proposal, mcmc/system.py:450-470).
 //
@@ -213,31 +213,25 @@ bool chain_min_supported(const vssr_handle *h) {
     return h->n_cfg <= 3072 && h->max_cfg_atoms <= 64;
 }
 
-// Same contract as relax_cg (relax.hip): afterwards the batch holds the minimised positions, d_pot_e / _ea / _f the static results of
+// Same contract as relax_cg (relax_cg.hip): afterwards the batch holds the minimised positions, d_pot_e / _ea / _f the static results of
 // those geometries, d_relax_steps [B][3] = (iterations, evaluations, stop reason) per chain.
 int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want) {
     (void)want;
     const int B = h->n_cfg, N = h->n_atoms;
     hipStream_t st = h->stream;
-    if (h->d_fixed.ensure((size_t)N) || h->d_relax_steps.ensure(sizeof(int) * 3 * (size_t)B) || h->d_active.ensure((size_t)B) ||
-        h->d_counters.ensure(sizeof(int) * 4) || h->d_fire.ensure(sizeof(CgState) * (size_t)B) || h->d_vel.ensure(sizeof(double) * 9 * (size_t)N) ||
-        h->d_cm.ensure(sizeof(int) * ((size_t)B + 8) + 1024) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
+    const uint8_t *fixed = nullptr;
+    CgWork W;
+    if (int e = relax_begin(h, fixed_host, 3, fixed)) return e;
+    if (int e = CgWork::ensure(h, W)) return e;
+    if (h->d_cm.ensure(sizeof(int) * ((size_t)B + 8) + 1024) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
         h->d_wrap.ensure(sizeof(int) * 3 * (size_t)N) || h->d_deg.ensure(sizeof(int) * (size_t)N) ||
         h->d_row_start.ensure(sizeof(int) * ((size_t)N + B + 1)) || h->d_pot_e.ensure(sizeof(double) * (size_t)B) ||
         h->d_pot_ea.ensure(sizeof(double) * (size_t)N) || h->d_pot_f.ensure(sizeof(double) * 3 * (size_t)N))
         return set_err(h, VSSR_E_NOMEM, "chain-resident minimiser: out of device memory");
-    const uint8_t *fixed = nullptr;
-    if (fixed_host) {
-        VSSR_HIP(h, hipMemcpyAsync(h->d_fixed.p, fixed_host, (size_t)N, hipMemcpyHostToDevice, st));
-        fixed = h->d_fixed.as<uint8_t>();
-    }
     static_assert(sizeof(ChainMinArgs) <= 1024, "argument block");
     ChainMinArgs *d_args = reinterpret_cast<ChainMinArgs *>(h->d_cm.as<char>());   // [arguments (1 KB) | flags [8] | evaluations [B]]
     int *flags = reinterpret_cast<int *>(h->d_cm.as<char>() + 1024), *n_evals = flags + 8;
-    hipLaunchKernelGGL(k_cm_init, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<CgState>(), h->d_active.as<unsigned char>(), n_evals);
-    h->relax_lockstep = 0;
-    h->relax_chain_evals = 0;
-    h->relax_compactions = 0;
+    hipLaunchKernelGGL(k_cm_init, dim3((B + 127) / 128), dim3(128), 0, st, B, W.st, h->d_active.as<unsigned char>(), n_evals);
     const double rc = h->pot_cutoff;
     // slots per atom of the per-chain pools: the handle's capacity, or what an earlier chain-resident relaxation had to grow to.  The
     // grown value stays with THIS driver (cm_cap_per_atom): the batch-wide runs size their buffers from cap_per_atom and repair an
@@ -270,9 +264,9 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         A.eps = slots_of(h).eps; A.gslot = slots_of(h).gslot;
         A.e_atom = h->d_pot_ea.as<double>(); A.forces = h->d_pot_f.as<double>(); A.energy = h->d_pot_e.as<double>();
         A.max_iter = cp->max_iter; A.max_eval = cp->max_eval; A.etol = cp->etol; A.ftol = cp->ftol; A.dmax = cp->dmax;
-        A.x0 = h->d_vel.as<double>(); A.hh = A.x0 + 3 * (size_t)N; A.gg = A.x0 + 6 * (size_t)N;
-        A.st = h->d_fire.as<CgState>(); A.active = h->d_active.as<unsigned char>(); A.flags = flags; A.n_evals = n_evals;
-        A.max_launch = (long long)cp->max_eval + 72;   // the lock-step driver's launch budget (relax.hip), per chain here
+        A.x0 = W.x0; A.hh = W.hh; A.gg = W.gg;
+        A.st = W.st; A.active = h->d_active.as<unsigned char>(); A.flags = flags; A.n_evals = n_evals;
+        A.max_launch = (long long)cp->max_eval + 72;   // the lock-step driver's launch budget (relax_cg.hip), per chain here
         h->prof.begin(KC_ANALYTIC, st);
         VSSR_HIP(h, hipMemcpyAsync(d_args, &A, sizeof(A), hipMemcpyHostToDevice, st));   // (pageable source: copied before the call returns)
         hipLaunchKernelGGL(k_cg_chain, dim3(B), dim3(CM_THREADS), 0, st, d_args);
@@ -290,7 +284,7 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         ++h->relax_regrows;
     }
     h->cm_cap_per_atom = cap;
-    hipLaunchKernelGGL(k_cm_report, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<CgState>(), h->d_relax_steps.as<int>());
+    hipLaunchKernelGGL(k_cm_report, dim3((B + 127) / 128), dim3(128), 0, st, B, W.st, h->d_relax_steps.as<int>());
     std::vector<int> ne(B);
     VSSR_HIP(h, hipMemcpyAsync(ne.data(), n_evals, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
     VSSR_HIP(h, hipStreamSynchronize(st));

@@ -24,6 +24,9 @@
 // No 3N x 3N storage and no large eigensolve for any number of free atoms; the m x m problem (m <= 2 relax_steps) is
 // solved by cyclic Jacobi rotations in LDS, fp64.  Pinned against the reference's stored BFGS traces through
 // tests/bfgs_oracle.py (dense restatement of ASE's algorithm) -- tests/test_bfgs.py.
+//
+// Both run in one driver frame, relax_lockstep<FireWork | BfgsWork>; its prologue and regrow also serve the CG driver (relax_cg.hip).
+#include <algorithm>
 #include "cg_dev.h"
 
 namespace vssr {
@@ -440,51 +443,96 @@ k_traj_record(const int *__restrict__ cfg_start, const int *__restrict__ counter
     }
 }
 
+// ---- shared by the relaxation drivers (relax_lockstep below, relax_cg.hip; relax_begin also chain_min.hip) ------------------
+// Per-relaxation buffers, the FixAtoms mask on the device (`fixed`: null without a mask), the work counters at zero.
+int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed) {
+    const size_t B = h->n_cfg, N = h->n_atoms;
+    if (h->d_fixed.ensure(N) || h->d_relax_steps.ensure(sizeof(int) * steps_ints_per_chain * B) || h->d_relax_conv.ensure(B) ||
+        h->d_active.ensure(B) || h->d_counters.ensure(sizeof(int) * 4))
+        return set_err(h, VSSR_E_NOMEM, "relaxation state: out of device memory");
+    if (fixed_host) VSSR_HIP(h, hipMemcpyAsync(h->d_fixed.p, fixed_host, N, hipMemcpyHostToDevice, h->stream));
+    fixed = fixed_host ? h->d_fixed.as<uint8_t>() : nullptr;
+    h->relax_lockstep = h->relax_chain_evals = h->relax_compactions = 0;
+    return VSSR_OK;
+}
+
+// Neighbor capacity overflow seen at a poll: grow (at most `cap` times per relaxation) and give the polling window back: the step
+// kernels behind the overflowed evaluations moved nothing and counted nothing; chains that did step are held by their own counters.
+int relax_regrow(vssr_handle *h, int cap, long long &it, int window) {
+    if (int rc = grow_slot_cap(h)) return rc;
+    if (++h->relax_regrows > cap) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
+    it = std::max(it - window, -1LL);
+    return VSSR_OK;
+}
+
+// ---- the two optimizers of the frame: a typed workspace on the handle's d_opt_state / d_opt_vec (as CgWork, cg_dev.h) that
+// knows its two launches.  init sizes the buffers, hands out the pointers and resets every chain ---------------------------
+struct FireWork {
+    using Params = vssr_fire_params; using State = FireState;
+    FireState *st;
+    double *vel;   // [3 N]
+    int init(vssr_handle *h, const Params &p) {
+        if (h->d_opt_vec.ensure(sizeof(double) * 3 * h->n_atoms) || h->d_opt_state.ensure(sizeof(FireState) * h->n_cfg))
+            return set_err(h, VSSR_E_NOMEM, "FIRE state: out of device memory");
+        st = h->d_opt_state.as<FireState>(); vel = h->d_opt_vec.as<double>();
+        hipLaunchKernelGGL(k_fire_init, dim3((h->n_cfg + 127) / 128), dim3(128), 0, h->stream, h->n_cfg, (double)p.dt, (double)p.astart, st,
+                           h->d_active.as<unsigned char>());
+        return VSSR_OK;
+    }
+    void step(vssr_handle *h, const Params &p, const uint8_t *fixed) const {
+        hipLaunchKernelGGL(k_fire_step, dim3(h->n_cfg), dim3(256), 0, h->stream, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
+                           h->d_forces.as<float>(), fixed, (double)p.fmax, (double)p.maxstep, (double)p.dtmax, (double)p.finc, (double)p.fdec,
+                           (double)p.astart, (double)p.fa, p.nmin, p.max_steps, h->d_pos.as<double>(), vel, st,
+                           h->d_active.as<unsigned char>(), h->d_counters.as<int>() + 3);
+    }
+};
+struct BfgsWork {
+    using Params = vssr_bfgs_params; using State = BfgsState;
+    BfgsState *st;
+    double *r0, *f0, *work, *Q, *B;   // [3 N] each, [mmax][3 N], [n_cfg][mmax][mmax]
+    int mmax;
+    size_t lds_bytes() const { return sizeof(double) * ((size_t)2 * mmax * (mmax | 1) + 5 * (size_t)mmax + 8); }
+    int init(vssr_handle *h, const Params &p) {
+        // Two basis vectors per Hessian update; the rotated matrices of the eigen-decomposition (2 x mmax^2 doubles) live in
+        // LDS, which holds 46 updates.  A longer relaxation keeps stepping with the Hessian of its first 46 updates (the
+        // step kernel skips the update when the basis is full): identical to ASE up to step 46, a frozen quasi-Newton
+        // method beyond (the reference's configurations use 20 steps).
+        const size_t nB = h->n_cfg, N = h->n_atoms;
+        mmax = 2 * p.max_steps + 2;
+        while (lds_bytes() > 160 * 1024 - 4096) mmax -= 2;   // (the kernel also holds 2 KB of static reduction scratch)
+        if (h->d_opt_state.ensure(sizeof(BfgsState) * nB) || h->d_opt_vec.ensure(sizeof(double) * 9 * N) ||
+            h->d_bfgs_q.ensure(sizeof(double) * 3 * N * mmax) || h->d_bfgs_b.ensure(sizeof(double) * nB * mmax * mmax))
+            return set_err(h, VSSR_E_NOMEM, "BFGS state: out of device memory");
+        VSSR_HIP(h, hipFuncSetAttribute((const void *)k_bfgs_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes()));
+        st = h->d_opt_state.as<BfgsState>();
+        r0 = h->d_opt_vec.as<double>(); f0 = r0 + 3 * N; work = r0 + 6 * N; Q = h->d_bfgs_q.as<double>(); B = h->d_bfgs_b.as<double>();
+        hipLaunchKernelGGL(k_bfgs_init, dim3((h->n_cfg + 127) / 128), dim3(128), 0, h->stream, h->n_cfg, st, h->d_active.as<unsigned char>());
+        return VSSR_OK;
+    }
+    void step(vssr_handle *h, const Params &p, const uint8_t *fixed) const {
+        hipLaunchKernelGGL(k_bfgs_step, dim3(h->n_cfg), dim3(256), lds_bytes(), h->stream, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
+                           h->d_forces.as<float>(), fixed, (double)p.fmax, (double)p.alpha, (double)p.maxstep, mmax, p.max_steps,
+                           h->d_pos.as<double>(), r0, f0, Q, B, work, st, h->d_active.as<unsigned char>(), h->d_counters.as<int>() + 3);
+    }
+};
+
 // ---- host driver ----------------------------------------------------------------------------------------------------------
 // Iteration i: evaluate energies / forces of the chains still active, then (device side) test convergence and step.  The host
 // only enqueues; every POLL iterations it reads the number of chains that took a step and the neighbor-capacity flag.  If
 // the capacity overflowed, the step kernels of the affected iterations did nothing (they test the flag): the buffers are
 // regrown and the loop continues from the same positions.  Iterations enqueued after every chain has converged find no
 // active chain and cost only their (empty) launches.
-static size_t bfgs_lds_bytes(int mmax) { return sizeof(double) * ((size_t)2 * mmax * (mmax | 1) + 5 * (size_t)mmax + 8); }
-
-int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr_bfgs_params *bp,
-              const uint8_t *fixed_host, uint32_t want) {
+template <class Work>
+int relax_lockstep(vssr_handle *h, const typename Work::Params &p, const uint8_t *fixed_host, uint32_t want) {
     const int B = h->n_cfg, N = h->n_atoms;
     hipStream_t st = h->stream;
-    const int max_steps = method == 1 ? bp->max_steps : fp->max_steps;
-    const double fmax_tol = method == 1 ? bp->fmax : fp->fmax;
-    int mmax = 0;
-    if (h->d_fixed.ensure((size_t)N) || h->d_relax_steps.ensure(sizeof(int) * B) || h->d_relax_conv.ensure((size_t)B) ||
-        h->d_active.ensure((size_t)B) || h->d_counters.ensure(sizeof(int) * 4))
-        return set_err(h, VSSR_E_NOMEM, "relaxation state: out of device memory");
-    if (method == 0) {
-        if (h->d_vel.ensure(sizeof(double) * 3 * N) || h->d_fire.ensure(sizeof(FireState) * B))
-            return set_err(h, VSSR_E_NOMEM, "FIRE state: out of device memory");
-    } else {
-        // Two basis vectors per Hessian update; the rotated matrices of the eigen-decomposition (2 x mmax^2 doubles) live in
-        // LDS, which holds 46 updates.  A longer relaxation keeps stepping with the Hessian of its first 46 updates (the
-        // step kernel skips the update when the basis is full): identical to ASE up to step 46, a frozen quasi-Newton
-        // method beyond (the reference's configurations use 20 steps).
-        mmax = 2 * max_steps + 2;
-        while (bfgs_lds_bytes(mmax) > 160 * 1024 - 4096) mmax -= 2;   // (the kernel also holds 2 KB of static reduction scratch)
-        if (h->d_fire.ensure(sizeof(BfgsState) * B) || h->d_vel.ensure(sizeof(double) * 3 * N * 3) ||
-            h->d_bfgs_q.ensure(sizeof(double) * 3 * (size_t)N * mmax) || h->d_bfgs_b.ensure(sizeof(double) * (size_t)B * mmax * mmax))
-            return set_err(h, VSSR_E_NOMEM, "BFGS state: out of device memory");
-        VSSR_HIP(h, hipFuncSetAttribute((const void *)k_bfgs_step, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)bfgs_lds_bytes(mmax)));
-    }
+    const int max_steps = p.max_steps;
     const uint8_t *fixed = nullptr;
-    if (fixed_host) {
-        VSSR_HIP(h, hipMemcpyAsync(h->d_fixed.p, fixed_host, (size_t)N, hipMemcpyHostToDevice, st));
-        fixed = h->d_fixed.as<uint8_t>();
-    }
+    Work w;
+    if (int e = relax_begin(h, fixed_host, 1, fixed)) return e;
+    if (int e = w.init(h, p)) return e;
+    int rc = VSSR_OK;
     unsigned char *active = h->d_active.as<unsigned char>();
-    if (method == 0)
-        hipLaunchKernelGGL(k_fire_init, dim3((B + 127) / 128), dim3(128), 0, st, B, (double)fp->dt, (double)fp->astart,
-                           h->d_fire.as<FireState>(), active);
-    else
-        hipLaunchKernelGGL(k_bfgs_init, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<BfgsState>(), active);
     // The evaluation kernels skip chains whose entry of `active` is 0 -- once the mask is handed to them.  While every chain is
     // still running the mask stays away (h->active_mask = nullptr): the masked forms of the kernels cost ~0.15 ms per evaluation
     // (tile / chain tests, the per-chain instead of the streaming gradient reduction), and with the reference's settings (fmax
@@ -503,65 +551,33 @@ int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr
         VSSR_HIP(h, hipMemsetAsync(h->d_traj_n.p, 0, sizeof(int) * B, st));
         h->traj_records = nrec; h->traj_B = B; h->traj_N = N;
     }
+    const bool f64 = is_analytic(h);   // Tersoff / EAM / SW / pair forces are fp64 on the device: the optimizer state works on an fp32 copy
     const int POLL = 4;
-    int rc = VSSR_OK;
-    auto evaluate = [&]() {
-        return evaluator(h).run(h, want | VSSR_WANT_FORCES);
-    };
-    h->relax_lockstep = 0;
-    h->relax_chain_evals = 0;
-    for (int it = 0; it <= max_steps && !rc; ++it) {
-        rc = evaluate();
-        if (rc) break;
+    for (long long it = 0; it <= max_steps && !rc; ++it) {
+        if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) break;
         ++h->relax_lockstep;
         h->relax_chain_evals += B;
+        // (last iteration: every unconverged chain has taken relax_steps steps -- the kernel only tests convergence, like the
+        // final check of ASE's run loop)
         const bool last = it == max_steps;
-        {   // (last iteration: every unconverged chain has taken relax_steps steps -- the kernel only tests convergence, like the
-            // final check of ASE's run loop)
-            VSSR_HIP(h, hipMemsetAsync(n_active_d, 0, sizeof(int), st));
-            if (is_analytic(h)) {   // Tersoff / EAM / SW forces are fp64 on the device: the optimizer state works on an fp32 copy
-                if (h->d_forces.ensure(sizeof(float) * 3 * N)) { rc = set_err(h, VSSR_E_NOMEM, "force buffer"); break; }
-                hipLaunchKernelGGL(k_narrow_forces, dim3((3 * N + 255) / 256), dim3(256), 0, st, 3 * N,
-                                   h->d_pot_f.as<double>(), h->d_forces.as<float>());
-            }
-            const float *forces = h->d_forces.as<float>();
-            if (nrec) {
-                const bool f64 = is_analytic(h);
-                const float *e32 = f64 ? nullptr : h->d_energy.as<float>();
-                const double *e64 = f64 ? h->d_pot_e.as<double>() : nullptr;
-                if (method == 0)
-                    hipLaunchKernelGGL(k_traj_record<FireState>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                       h->d_fire.as<FireState>(), active, rec_iv, nrec, B, N, fixed, h->d_pos.as<double>(), forces, e32, e64,
-                                       h->d_traj_pos.as<double>(), h->d_traj_f.as<float>(), h->d_traj_e.as<double>(), h->d_traj_n.as<int>());
-                else
-                    hipLaunchKernelGGL(k_traj_record<BfgsState>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                       h->d_fire.as<BfgsState>(), active, rec_iv, nrec, B, N, fixed, h->d_pos.as<double>(), forces, e32, e64,
-                                       h->d_traj_pos.as<double>(), h->d_traj_f.as<float>(), h->d_traj_e.as<double>(), h->d_traj_n.as<int>());
-            }
-            if (method == 0)
-                hipLaunchKernelGGL(k_fire_step, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                   forces, fixed, fmax_tol, (double)fp->maxstep, (double)fp->dtmax, (double)fp->finc,
-                                   (double)fp->fdec, (double)fp->astart, (double)fp->fa, fp->nmin, max_steps, h->d_pos.as<double>(),
-                                   h->d_vel.as<double>(), h->d_fire.as<FireState>(), active, n_active_d);
-            else
-                hipLaunchKernelGGL(k_bfgs_step, dim3(B), dim3(256), bfgs_lds_bytes(mmax), st, h->d_cfg_start.as<int>(),
-                                   h->d_counters.as<int>(), forces, fixed, fmax_tol, (double)bp->alpha, (double)bp->maxstep, mmax, max_steps,
-                                   h->d_pos.as<double>(), h->d_vel.as<double>(), h->d_vel.as<double>() + 3 * (size_t)N,
-                                   h->d_bfgs_q.as<double>(), h->d_bfgs_b.as<double>(),
-                                   h->d_vel.as<double>() + 6 * (size_t)N, h->d_fire.as<BfgsState>(), active, n_active_d);
-            VSSR_HIP(h, hipMemcpyAsync(h->h_counters + 3, n_active_d, sizeof(int), hipMemcpyDeviceToHost, st));
+        VSSR_HIP(h, hipMemsetAsync(n_active_d, 0, sizeof(int), st));
+        if (f64) {
+            if (h->d_forces.ensure(sizeof(float) * 3 * N)) { rc = set_err(h, VSSR_E_NOMEM, "force buffer"); break; }
+            hipLaunchKernelGGL(k_narrow_forces, dim3((3 * N + 255) / 256), dim3(256), 0, st, 3 * N, h->d_pot_f.as<double>(),
+                               h->d_forces.as<float>());
         }
+        const float *forces = h->d_forces.as<float>();
+        if (nrec)
+            hipLaunchKernelGGL(k_traj_record<typename Work::State>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(), w.st, active, rec_iv,
+                               nrec, B, N, fixed, h->d_pos.as<double>(), forces, f64 ? nullptr : h->d_energy.as<float>(),
+                               f64 ? h->d_pot_e.as<double>() : nullptr, h->d_traj_pos.as<double>(), h->d_traj_f.as<float>(),
+                               h->d_traj_e.as<double>(), h->d_traj_n.as<int>());
+        w.step(h, p, fixed);
+        VSSR_HIP(h, hipMemcpyAsync(h->h_counters + 3, n_active_d, sizeof(int), hipMemcpyDeviceToHost, st));
         if (last || (it + 1) % POLL == 0) {
             VSSR_HIP(h, hipStreamSynchronize(st));
-            if (h->h_counters[2]) {   // neighbor capacity overflow in one of the enqueued evaluations: grow, redo
-                if ((rc = grow_slot_cap(h))) break;
-                // the step kernels behind the overflowed evaluations did not move anything and did not count steps: go back
-                // by one polling window (chains that did step in it are held to relax_steps by their own step counters)
-                it -= POLL;
-                if (it < -1) it = -1;
-                if (++h->relax_regrows > (h->cap_tight ? 64 : 8)) { rc = set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied"); break; }
-                continue;
-            }
+            // neighbor capacity overflow in one of the enqueued evaluations: grow, redo
+            if (h->h_counters[2]) { rc = relax_regrow(h, h->cap_tight ? 64 : 8, it, POLL); continue; }
             if (!last && h->h_counters[3] == 0) break;   // no chain stepped in the last iteration: all converged, results final
             // (never at the final poll: the last evaluation above ran unmasked over every chain, the resident graph is complete)
             if (!last && !masked && h->h_counters[3] < B) { h->active_mask = active; masked = true; }
@@ -569,314 +585,15 @@ int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr
     }
     h->active_mask = nullptr;
     if (rc) return rc;
-    if (method == 0)
-        hipLaunchKernelGGL(k_relax_report<FireState>, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<FireState>(),
-                           h->d_relax_steps.as<int>(), h->d_relax_conv.as<uint8_t>());
-    else
-        hipLaunchKernelGGL(k_relax_report<BfgsState>, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<BfgsState>(),
-                           h->d_relax_steps.as<int>(), h->d_relax_conv.as<uint8_t>());
+    hipLaunchKernelGGL(k_relax_report<typename Work::State>, dim3((B + 127) / 128), dim3(128), 0, st, B, w.st, h->d_relax_steps.as<int>(),
+                       h->d_relax_conv.as<uint8_t>());
     VSSR_HIP(h, hipGetLastError());
     h->ran = true;
     h->graph_partial = masked;   // (with the mask in place the last evaluation covered only the chains still running: see vssr_batch_stats)
     return VSSR_OK;
 }
 
-// ---- LAMMPS min_style cg: the state machine lives in cg_dev.h (cg_step_chain) --------------------------------------------
-__global__ void k_cg_init(int B, CgState *__restrict__ st, unsigned char *__restrict__ active) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    CgState S = {};
-    S.phase = PH_START;
-    st[b] = S;
-    active[b] = 1;
-}
-
-__global__ void __launch_bounds__(256)
-k_cg_step(const int *__restrict__ cfg_start, const int *__restrict__ counters, const double *__restrict__ energy,
-          const double *__restrict__ forces, const uint8_t *__restrict__ fixed, int max_iter, int max_eval, double etol,
-          double ftol, double dmax, double *__restrict__ pos, double *__restrict__ x0all, double *__restrict__ hall,
-          double *__restrict__ gall, CgState *__restrict__ st, unsigned char *__restrict__ active, int *__restrict__ n_active) {
-    __shared__ double red[256];
-    if (counters[2]) return;
-    cg_step_chain(blockIdx.x, red, cfg_start, energy, forces, fixed, max_iter, max_eval, etol, ftol, dmax, pos, x0all, hall, gall, st, active,
-                  n_active);
-}
-
-// ---- live-chain compaction of the resident batch (fp64 analytic potentials) ---------------------------------------------------
-// The CG minimiser stops every chain by its own criteria; with the activity mask alone a finished chain still costs its share of
-// every later launch (grids are sized for the whole batch, its workgroups leave at once).  At a poll with at most 3/4 of the
-// resident chains still running the batch is PHYSICALLY compacted: the live chains' inputs (positions, types, cells) and optimizer
-// state are gathered into a smaller resident batch, the finished chains' final positions / states are parked in full-size
-// arrays, and every kernel of the path (neighbor build, potential, CG step) runs unchanged on the smaller batch -- a chain's
-// results do not depend on its batch, so the trajectories are the same bit for bit (tests/test_cg.py).  The original batch is
-// restored before the final static evaluation.
-struct CmpView {   // device pointers of one layout of the per-chain / per-atom arrays
-    int *cfg_start, *Z, *atom_cfg, *nimg;
-    double *pos, *cell, *inv, *x0, *hh, *gg;
-    uint8_t *pbc, *fixed;
-    CgState *st;
-};
-
-__global__ void __launch_bounds__(1024)
-k_cmp_plan(int B, const int *__restrict__ cfg_start, const unsigned char *__restrict__ active, const int *__restrict__ live,
-           int *__restrict__ live_new, int *__restrict__ src, int *__restrict__ start_new, int *__restrict__ totals) {
-    __shared__ int sc[1024], sa[1024];
-    const int t = threadIdx.x, per = (B + 1023) / 1024, c0 = min(B, t * per), c1 = min(B, c0 + per);
-    int nc = 0, na = 0;
-    for (int c = c0; c < c1; ++c)
-        if (active[c]) { nc += 1; na += cfg_start[c + 1] - cfg_start[c]; }
-    sc[t] = nc; sa[t] = na;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {   // inclusive scans
-        const int vc = t >= d ? sc[t - d] : 0, va = t >= d ? sa[t - d] : 0;
-        __syncthreads();
-        sc[t] += vc; sa[t] += va;
-        __syncthreads();
-    }
-    int oc = sc[t] - nc, oa = sa[t] - na;
-    for (int c = c0; c < c1; ++c)
-        if (active[c]) {
-            live_new[oc] = live ? live[c] : c;
-            src[oc] = c;
-            start_new[oc] = oa;
-            oc += 1;
-            oa += cfg_start[c + 1] - cfg_start[c];
-        }
-    if (t == 1023) { start_new[sc[t]] = sa[t]; totals[0] = sc[t]; totals[1] = sa[t]; }
-}
-
-// chains of the CURRENT batch whose results are final (active == nullptr: all of them): positions and optimizer state to their
-// places in the ORIGINAL batch
-__global__ void __launch_bounds__(128)
-k_cmp_flush(const int *__restrict__ cfg_start, const unsigned char *__restrict__ active, const int *__restrict__ live,
-            const int *__restrict__ start0, const double *__restrict__ pos, const CgState *__restrict__ st,
-            double *__restrict__ final_pos, CgState *__restrict__ final_st) {
-    const int c = blockIdx.x;
-    if (active && active[c]) return;
-    const int o = live ? live[c] : c, a0 = cfg_start[c], n = 3 * (cfg_start[c + 1] - a0);
-    const size_t d0 = 3 * (size_t)start0[o], s0 = 3 * (size_t)a0;
-    for (int k = threadIdx.x; k < n; k += blockDim.x) final_pos[d0 + k] = pos[s0 + k];
-    if (threadIdx.x == 0) final_st[o] = st[c];
-}
-
-__global__ void __launch_bounds__(128)
-k_cmp_gather(const int *__restrict__ src, const int *__restrict__ start_new, CmpView from, CmpView to, unsigned char *__restrict__ active_new) {
-    const int nc = blockIdx.x, c = src[nc], a0 = from.cfg_start[c], na = from.cfg_start[c + 1] - a0, b0 = start_new[nc];
-    for (int k = threadIdx.x; k < 3 * na; k += blockDim.x) {
-        to.pos[3 * (size_t)b0 + k] = from.pos[3 * (size_t)a0 + k];
-        to.x0[3 * (size_t)b0 + k] = from.x0[3 * (size_t)a0 + k];
-        to.hh[3 * (size_t)b0 + k] = from.hh[3 * (size_t)a0 + k];
-        to.gg[3 * (size_t)b0 + k] = from.gg[3 * (size_t)a0 + k];
-    }
-    for (int k = threadIdx.x; k < na; k += blockDim.x) {
-        to.Z[b0 + k] = from.Z[a0 + k];
-        to.atom_cfg[b0 + k] = nc;
-        if (from.fixed) to.fixed[b0 + k] = from.fixed[a0 + k];
-    }
-    if (threadIdx.x < 9) { to.cell[9 * (size_t)nc + threadIdx.x] = from.cell[9 * (size_t)c + threadIdx.x]; to.inv[9 * (size_t)nc + threadIdx.x] = from.inv[9 * (size_t)c + threadIdx.x]; }
-    if (threadIdx.x < 3) { to.nimg[3 * nc + threadIdx.x] = from.nimg[3 * c + threadIdx.x]; to.pbc[3 * nc + threadIdx.x] = from.pbc[3 * c + threadIdx.x]; }
-    if (threadIdx.x == 0) { to.st[nc] = from.st[c]; active_new[nc] = 1; }
-}
-
-// the gathered arrays back over the resident ones, one launch (13 small device-to-device copies cost more than the evaluation of a
-// small batch); live / start_new travel along
-__global__ void __launch_bounds__(256)
-k_cmp_copyback(int Bn, int Nn, CmpView to, CmpView from, int *__restrict__ live, const int *__restrict__ live_new,
-               const int *__restrict__ start_new) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
-    for (size_t k = t; k < 3 * (size_t)Nn; k += step) { to.pos[k] = from.pos[k]; to.x0[k] = from.x0[k]; to.hh[k] = from.hh[k]; to.gg[k] = from.gg[k]; }
-    for (size_t k = t; k < (size_t)Nn; k += step) { to.Z[k] = from.Z[k]; to.atom_cfg[k] = from.atom_cfg[k]; if (from.fixed && to.fixed) to.fixed[k] = from.fixed[k]; }
-    for (size_t k = t; k < 9 * (size_t)Bn; k += step) { to.cell[k] = from.cell[k]; to.inv[k] = from.inv[k]; }
-    for (size_t k = t; k < 3 * (size_t)Bn; k += step) { to.nimg[k] = from.nimg[k]; to.pbc[k] = from.pbc[k]; }
-    for (size_t k = t; k < (size_t)Bn; k += step) { to.st[k] = from.st[k]; live[k] = live_new[k]; }
-    for (size_t k = t; k <= (size_t)Bn; k += step) to.cfg_start[k] = start_new[k];
-}
-
-__global__ void k_cg_report(int B, const CgState *__restrict__ st, int *__restrict__ out /*[B][3]*/) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    out[3 * b] = st[b].niter; out[3 * b + 1] = st[b].neval; out[3 * b + 2] = st[b].reason;
-}
-
-int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want) {
-    const int B = h->n_cfg, N = h->n_atoms;
-    hipStream_t st = h->stream;
-    if (!is_analytic(h))
-        return set_err(h, VSSR_E_STATE, "conjugate gradients need an fp64 potential (Tersoff / EAM / SW handle); use BFGS or FIRE");
-    if (h->d_fixed.ensure((size_t)N) || h->d_relax_steps.ensure(sizeof(int) * 3 * B) || h->d_active.ensure((size_t)B) ||
-        h->d_counters.ensure(sizeof(int) * 4) || h->d_fire.ensure(sizeof(CgState) * B) || h->d_vel.ensure(sizeof(double) * 9 * N))
-        return set_err(h, VSSR_E_NOMEM, "CG state: out of device memory");
-    const uint8_t *fixed = nullptr;
-    if (fixed_host) {
-        VSSR_HIP(h, hipMemcpyAsync(h->d_fixed.p, fixed_host, (size_t)N, hipMemcpyHostToDevice, st));
-        fixed = h->d_fixed.as<uint8_t>();
-    }
-    unsigned char *active = h->d_active.as<unsigned char>();
-    hipLaunchKernelGGL(k_cg_init, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<CgState>(), active);
-    h->active_mask = active;
-    int *n_active_d = h->d_counters.as<int>() + 3;
-    const int POLL = 8;
-    int rc = VSSR_OK;
-    // ---- live-chain compaction (see k_cmp_plan): B_cur / N_cur = the resident batch the kernels see ------------------------
-    const char *cmp_env = getenv("VSSR_RELAX_COMPACT");   // (read per call: 0 switches the compaction off -- A/B runs, the equality test)
-    const bool cmp_enabled = !cmp_env || atoi(cmp_env) != 0;
-    const int cmp_min_atoms = cmp_env && atoi(cmp_env) > 1 ? atoi(cmp_env) : 65536;   // (VSSR_RELAX_COMPACT=n > 1: smallest resident batch, atoms)
-    int B_cur = B, N_cur = N;
-    bool compacted = false;
-    double *const x0v = h->d_vel.as<double>(), *const hv = x0v + 3 * (size_t)N, *const gv = x0v + 6 * (size_t)N;
-    // arena: [originals | parked finals | maps | gather targets]
-    struct Arena {
-        int *start0, *Z0, *cfg0, *nimg0, *live, *live_new, *src, *start_new, *totals;
-        double *cell0, *inv0, *final_pos;
-        uint8_t *pbc0, *fixed0;
-        CgState *final_st;
-        CmpView tmp;
-    } A{};
-    auto carve = [&]() -> int {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        const size_t Bz = (size_t)B, Nz = (size_t)N;
-        const size_t o_start0 = take(4 * (Bz + 1)), o_Z0 = take(4 * Nz), o_cfg0 = take(4 * Nz), o_nimg0 = take(12 * Bz), o_live = take(4 * Bz),
-                     o_live_new = take(4 * Bz), o_src = take(4 * Bz), o_start_new = take(4 * (Bz + 1)), o_tot = take(16),
-                     o_cell0 = take(72 * Bz), o_inv0 = take(72 * Bz), o_fpos = take(24 * Nz), o_pbc0 = take(3 * Bz), o_fixed0 = take(Nz),
-                     o_fst = take(sizeof(CgState) * Bz),
-                     t_start = take(4 * (Bz + 1)), t_Z = take(4 * Nz), t_cfg = take(4 * Nz), t_nimg = take(12 * Bz), t_pos = take(24 * Nz),
-                     t_cell = take(72 * Bz), t_inv = take(72 * Bz), t_x0 = take(24 * Nz), t_h = take(24 * Nz), t_g = take(24 * Nz),
-                     t_pbc = take(3 * Bz), t_fixed = take(Nz), t_st = take(sizeof(CgState) * Bz);
-        if (h->d_cmp.ensure(off)) return -1;
-        char *p = h->d_cmp.as<char>();
-        A.start0 = (int *)(p + o_start0); A.Z0 = (int *)(p + o_Z0); A.cfg0 = (int *)(p + o_cfg0); A.nimg0 = (int *)(p + o_nimg0);
-        A.live = (int *)(p + o_live); A.live_new = (int *)(p + o_live_new); A.src = (int *)(p + o_src);
-        A.start_new = (int *)(p + o_start_new); A.totals = (int *)(p + o_tot);
-        A.cell0 = (double *)(p + o_cell0); A.inv0 = (double *)(p + o_inv0); A.final_pos = (double *)(p + o_fpos);
-        A.pbc0 = (uint8_t *)(p + o_pbc0); A.fixed0 = (uint8_t *)(p + o_fixed0); A.final_st = (CgState *)(p + o_fst);
-        A.tmp = CmpView{(int *)(p + t_start), (int *)(p + t_Z), (int *)(p + t_cfg), (int *)(p + t_nimg), (double *)(p + t_pos),
-                        (double *)(p + t_cell), (double *)(p + t_inv), (double *)(p + t_x0), (double *)(p + t_h), (double *)(p + t_g),
-                        (uint8_t *)(p + t_pbc), (uint8_t *)(p + t_fixed), (CgState *)(p + t_st)};
-        return 0;
-    };
-    auto cur_view = [&]() {
-        return CmpView{h->d_cfg_start.as<int>(), h->d_Z.as<int>(), h->d_atom_cfg.as<int>(), h->d_nimg.as<int>(), h->d_pos.as<double>(),
-                       h->d_cell.as<double>(), h->d_invcell.as<double>(), x0v, hv, gv, h->d_pbc.as<uint8_t>(),
-                       const_cast<uint8_t *>(fixed), h->d_fire.as<CgState>()};
-    };
-#define CMP_COPY(dst, src_, bytes) VSSR_HIP(h, hipMemcpyAsync((dst), (src_), (bytes), hipMemcpyDeviceToDevice, st))
-    auto compact = [&]() -> int {
-        const CmpView cur = cur_view();
-        if (!compacted) {   // first time: keep the original batch
-            if (carve()) return set_err(h, VSSR_E_NOMEM, "compaction arena: out of device memory");
-            CMP_COPY(A.start0, cur.cfg_start, 4 * ((size_t)B + 1)); CMP_COPY(A.Z0, cur.Z, 4 * (size_t)N); CMP_COPY(A.cfg0, cur.atom_cfg, 4 * (size_t)N);
-            CMP_COPY(A.nimg0, cur.nimg, 12 * (size_t)B); CMP_COPY(A.cell0, cur.cell, 72 * (size_t)B); CMP_COPY(A.inv0, cur.inv, 72 * (size_t)B);
-            CMP_COPY(A.pbc0, cur.pbc, 3 * (size_t)B);
-            if (fixed) CMP_COPY(A.fixed0, fixed, (size_t)N);
-        }
-        const int *live = compacted ? A.live : nullptr;
-        hipLaunchKernelGGL(k_cmp_plan, dim3(1), dim3(1024), 0, st, B_cur, cur.cfg_start, active, live, A.live_new, A.src, A.start_new, A.totals);
-        hipLaunchKernelGGL(k_cmp_flush, dim3(B_cur), dim3(128), 0, st, cur.cfg_start, active, live, A.start0, cur.pos, cur.st, A.final_pos, A.final_st);
-        int tot[2] = {0, 0};
-        VSSR_HIP(h, hipMemcpyAsync(tot, A.totals, sizeof(tot), hipMemcpyDeviceToHost, st));
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        const int Bn = tot[0], Nn = tot[1];
-        if (Bn <= 0 || Bn > B_cur || Nn <= 0 || Nn > N_cur) return set_err(h, VSSR_E_STATE, "live-chain compaction: inconsistent plan");
-        hipLaunchKernelGGL(k_cmp_gather, dim3(Bn), dim3(128), 0, st, A.src, A.start_new, cur, A.tmp, active);
-        // (the gather reads the resident arrays and writes the arena; one more launch copies the arena over the resident arrays)
-        {
-            CmpView from = A.tmp;
-            if (!fixed) from.fixed = nullptr;
-            const int blocks = (int)std::min<size_t>(1024, (3 * (size_t)Nn + 255) / 256);
-            hipLaunchKernelGGL(k_cmp_copyback, dim3(blocks), dim3(256), 0, st, Bn, Nn, cur, from, A.live, A.live_new, A.start_new);
-        }
-        compacted = true;
-        B_cur = Bn; N_cur = Nn;
-        h->n_cfg = Bn; h->n_atoms = Nn;
-        ++h->relax_compactions;
-        return VSSR_OK;
-    };
-    auto restore = [&]() -> int {   // park what is still resident, then bring the original batch back (positions = the final ones)
-        if (!compacted) return VSSR_OK;
-        const CmpView cur = cur_view();
-        hipLaunchKernelGGL(k_cmp_flush, dim3(B_cur), dim3(128), 0, st, cur.cfg_start, (const unsigned char *)nullptr, A.live, A.start0, cur.pos, cur.st,
-                           A.final_pos, A.final_st);
-        CMP_COPY(cur.cfg_start, A.start0, 4 * ((size_t)B + 1)); CMP_COPY(cur.Z, A.Z0, 4 * (size_t)N); CMP_COPY(cur.atom_cfg, A.cfg0, 4 * (size_t)N);
-        CMP_COPY(cur.nimg, A.nimg0, 12 * (size_t)B); CMP_COPY(cur.cell, A.cell0, 72 * (size_t)B); CMP_COPY(cur.inv, A.inv0, 72 * (size_t)B);
-        CMP_COPY(cur.pbc, A.pbc0, 3 * (size_t)B); CMP_COPY(cur.pos, A.final_pos, 24 * (size_t)N); CMP_COPY(cur.st, A.final_st, sizeof(CgState) * (size_t)B);
-        if (fixed) CMP_COPY(cur.fixed, A.fixed0, (size_t)N);
-        compacted = false;
-        B_cur = B; N_cur = N;
-        h->n_cfg = B; h->n_atoms = N;
-        return VSSR_OK;
-    };
-#undef CMP_COPY
-    h->relax_compactions = 0;
-    // every launch is one evaluation; max_eval is tested between line searches, and a line search ends after at most ~60
-    // halvings of alpha (fp64), so the launch budget is max_eval plus one line search plus setup / reset evaluations
-    const long long max_launch = (long long)cp->max_eval + 72;
-    auto regrow = [&]() -> int {   // capacity overflow seen at a poll: grow; the step kernels behind it did nothing
-        if (int e = grow_slot_cap(h)) return e;
-        if (++h->relax_regrows > 64) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
-        return VSSR_OK;
-    };
-    long long it = 0;
-    bool finished = false;
-    h->relax_lockstep = 0;
-    h->relax_chain_evals = 0;
-    while (!rc && !finished) {
-        for (; it < max_launch && !rc; ++it) {
-            rc = evaluator(h).run(h, want | VSSR_WANT_FORCES);
-            if (rc) break;
-            ++h->relax_lockstep;
-            h->relax_chain_evals += B_cur;
-            // the count of chains still running is read at the polls only: it is cleared and copied back in those iterations (the
-            // step kernels in between add to a value nobody looks at) -- two dispatches less per evaluation, ~15 of them at 48 atoms
-            const bool poll_it = (it + 1) % POLL == 0;
-            if (poll_it) VSSR_HIP(h, hipMemsetAsync(n_active_d, 0, sizeof(int), st));
-            hipLaunchKernelGGL(k_cg_step, dim3(B_cur), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                               h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), fixed, cp->max_iter, cp->max_eval, cp->etol,
-                               cp->ftol, cp->dmax, h->d_pos.as<double>(), h->d_vel.as<double>(), h->d_vel.as<double>() + 3 * (size_t)N,
-                               h->d_vel.as<double>() + 6 * (size_t)N, h->d_fire.as<CgState>(), active, n_active_d);
-            if (poll_it) {
-                VSSR_HIP(h, hipMemcpyAsync(h->h_counters + 3, n_active_d, sizeof(int), hipMemcpyDeviceToHost, st));
-                VSSR_HIP(h, hipStreamSynchronize(st));
-                if (h->h_counters[2]) {
-                    rc = regrow();
-                    it -= POLL;   // the launches of this window are given back (those behind the overflow did nothing; a chain
-                                  // that did step is bounded by its own iteration / evaluation counters)
-                    continue;
-                }
-                if (h->h_counters[3] == 0) { finished = true; break; }   // every chain has finished
-                // at most 3/4 of the resident chains are still running: continue on a compacted batch.  Only where the kernels are
-                // throughput-bound: below ~one round of workgroups (256 CUs x 3 x 64 centres = 49 k atoms) a launch costs the same
-                // whatever the live share, and the compaction (four launches + a host read) would only add to it (measured, 256
-                // chains x 48 atoms: -3 %; profiles/r05/NOTES_tersoff.md)
-                if (cmp_enabled && N_cur >= cmp_min_atoms && (long long)h->h_counters[3] * 4 <= (long long)B_cur * 3) rc = compact();
-            }
-        }
-        if (rc || finished) break;
-        // the budget ran out between two polls: look at the last window as well
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (h->h_counters[2]) {
-            rc = regrow();
-            it -= POLL;
-            continue;
-        }
-        finished = true;
-    }
-    h->active_mask = nullptr;
-    if (rc) {   // (a compacted batch is not handed back half-way: the caller uploads again)
-        if (compacted) { h->n_cfg = B; h->n_atoms = N; h->batch_valid = false; }
-        return rc;
-    }
-    rc = restore();
-    if (rc) return rc;
-    // results of the final positions for every chain (finished chains were switched off at different times)
-    rc = evaluator(h).run(h, want | VSSR_WANT_FORCES);
-    if (rc) return rc;
-    ++h->relax_lockstep;
-    h->relax_chain_evals += B;
-    hipLaunchKernelGGL(k_cg_report, dim3((B + 127) / 128), dim3(128), 0, st, B, h->d_fire.as<CgState>(), h->d_relax_steps.as<int>());
-    VSSR_HIP(h, hipGetLastError());
-    h->ran = true;
-    return VSSR_OK;
-}
+int relax_fire(vssr_handle *h, const vssr_fire_params &p, const uint8_t *fixed, uint32_t want) { return relax_lockstep<FireWork>(h, p, fixed, want); }
+int relax_bfgs(vssr_handle *h, const vssr_bfgs_params &p, const uint8_t *fixed, uint32_t want) { return relax_lockstep<BfgsWork>(h, p, fixed, want); }
 
 }  // namespace vssr

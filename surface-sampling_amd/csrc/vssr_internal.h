@@ -377,13 +377,13 @@ struct vssr_handle {
     vssr::DevBuf d_l0A, d_l0At;          // [M][n_embed][2][24][F] and [M][n_embed][2][F][24], built at create
     vssr::DevBuf d_zmap, d_zlist;        // species index of Z (or -1), distinct Z of the resident batch
     vssr::DevBuf d_l0T, d_l0Q;
-    // lock-step relaxation (relax.hip)
-    vssr::DevBuf d_vel, d_fire, d_fixed, d_relax_steps, d_relax_conv, d_active, d_bfgs_q, d_bfgs_b;
-    const unsigned char *active_mask = nullptr;   // set by relax_run for the duration of a relaxation
+    // relaxations (relax.hip, relax_cg.hip, chain_min.hip); d_opt_state / d_opt_vec: handed out typed by FireWork / BfgsWork / CgWork only
+    vssr::DevBuf d_opt_state, d_opt_vec, d_bfgs_q, d_bfgs_b, d_fixed, d_relax_steps, d_relax_conv, d_active;
+    const unsigned char *active_mask = nullptr;   // set by the lock-step drivers for the duration of a relaxation
     int relax_regrows = 0;
     long long relax_lockstep = 0;   // lock-step evaluations of the batch launched by the last relaxation (vssr_batch_relax_counts)
     int relax_compactions = 0;      // live-chain compactions of the last CG relaxation
-    vssr::DevBuf d_cmp;            // arena of the live-chain compaction (relax.hip)
+    vssr::DevBuf d_cmp;            // arena of the live-chain compaction (Compactor, relax_cg.hip)
     vssr::DevBuf d_cm;             // flags + per-chain evaluation counters of the chain-resident minimiser (chain_min.hip)
     long long relax_chain_evals = 0;   // chain-evaluations those launches actually dispatched (live-chain compaction: < lockstep x B)
     // trajectory recording of the lock-step relaxations (relax.hip k_traj_record): every traj_interval optimizer steps
@@ -543,11 +543,12 @@ struct Evaluator {
 const Evaluator &evaluator(const vssr_handle *h);
 inline bool is_analytic(const vssr_handle *h) { return evaluator(h).f64; }
 void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1][7]*/);
-// lock-step FIRE relaxation (relax.hip)
-// method 0: FIRE (fp), 1: BFGS (bp)
-int relax_run(vssr_handle *h, int method, const vssr_fire_params *fp, const vssr_bfgs_params *bp,
-              const uint8_t *fixed_host, uint32_t want);
-// LAMMPS-style conjugate gradients for the fp64 potentials (relax.hip); results in d_relax_steps [B][3] = {iterations, evaluations, stop reason}
+// lock-step FIRE / BFGS relaxation (relax.hip, relax_lockstep<FireWork | BfgsWork>); results in d_relax_steps [B], d_relax_conv [B]; fixed_host may be null
+int relax_fire(vssr_handle *h, const vssr_fire_params &p, const uint8_t *fixed_host, uint32_t want);
+int relax_bfgs(vssr_handle *h, const vssr_bfgs_params &p, const uint8_t *fixed_host, uint32_t want);
+int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed);   // buffers, mask (-> fixed), counters
+int relax_regrow(vssr_handle *h, int cap, long long &it, int window);   // after an overflow seen at a poll: grow, give the poll window back
+// lock-step LAMMPS-style CG for the fp64 potentials (relax_cg.hip); results in d_relax_steps [B][3] = {iterations, evaluations, stop reason}
 int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want);
 // chain_min.hip: the same minimisation with one workgroup per chain (Tersoff handles, chains of <= 256 atoms; VSSR_CG_FUSED=0 disables)
 bool chain_min_supported(const vssr_handle *h);

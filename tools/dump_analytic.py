@@ -1,6 +1,7 @@
-"""Bit-equality record of the fp64 analytic potentials: evaluates a fixed set of small cases on the library VSSR_EVAL_LIB names (as
+"""Bit-equality record of the fp64 analytic potentials and the relaxation drivers: evaluates a fixed set of small cases on the library VSSR_EVAL_LIB names (as
 every tool here) and prints one JSON object {case: {array: SHA-256 of its bytes}}.  Run it once per build and diff the outputs: a
-refactor of tersoff.hip / sw.hip / pair.hip / eam.hip / pot_common.hip / relax.hip must leave every digest as it was.
+refactor of tersoff.hip / sw.hip / pair.hip / eam.hip / pot_common.hip / relax.hip / relax_cg.hip / chain_min.hip must leave every
+digest as it was.
 
 Cases (the smallest that reach every kernel and branch of those files):
   tersoff_gan       GaN.tersoff: the 3x3 slab + 12 Ga adatoms (48 atoms), the bare slab (36), a 43-atom dense box whose rows
@@ -12,7 +13,12 @@ Cases (the smallest that reach every kernel and branch of those files):
 each with energies, per-atom energies, forces and stress(); relax_*: chain-resident CG, lock-step CG (VSSR_CG_FUSED=0), FIRE and BFGS
 of the GaN batch with positions, energies and step counts; *_tight: the Tersoff and pair cases and relaxations again after
 debug_capacity(tight=1) with one slot per atom, so the first run overflows and the capacity is regrown (vssr_synchronize, the
-lock-step relaxation drivers).
+lock-step relaxation drivers).  Beyond those, on the GaN batch (whose chains stop at different polls):
+  relax_cg_compact  lock-step CG with the live-chain compaction forced (VSSR_RELAX_COMPACT=2, VSSR_CG_FUSED=0), with relax_counts in clear:
+                    fewer dispatched chain-evaluations than lock-step evaluations x chains = a compaction happened
+  traj_fire / traj_bfgs   FIRE and BFGS with record_interval=3: the trajectory records (n_records, positions, forces, energies)
+and one PaiNN (fp32) handle, the drivers' other force path:
+  painn_fire / painn_bfgs   two 60-atom SrTiO3 chains with different FixAtoms masks, 6 steps
 Usage: VSSR_EVAL_LIB=build/variants/lib_x.so python tools/dump_analytic.py > out.json"""
 import hashlib, json, os, sys
 
@@ -82,6 +88,44 @@ def relaxations(eng, structs, tag, tight):
                regrows=np.int32(eng.debug_capacity()))
 
 
+def relaxations_beyond(eng, structs):
+    """Forced compaction in the CG driver; trajectory records of FIRE / BFGS."""
+    fixed = np.concatenate([np.arange(len(s[0])) % 5 == 0 for s in structs]).astype(np.uint8)
+    os.environ.update(VSSR_CG_FUSED="0", VSSR_RELAX_COMPACT="2")
+    e, ea, f, pos, it, ev, why = eng.relax_cg_f64(structs, fixed=fixed, max_iter=40, etol=0.0, ftol=1e-4)
+    record("relax_cg_compact", energy=e, e_atom=ea, forces=f, positions=pos, n_iter=it, n_eval=ev, stop=why)
+    lockstep, dispatched = eng.last_relax_counts   # (in clear, not hashed: dispatched < lockstep x chains shows the compaction)
+    OUT["relax_cg_compact"]["relax_counts"] = {"lockstep": lockstep, "dispatched": dispatched, "chains": len(structs)}
+    del os.environ["VSSR_CG_FUSED"], os.environ["VSSR_RELAX_COMPACT"]
+    for opt in ("FIRE", "BFGS"):
+        eng.upload(structs)
+        out = eng.relax(opt, fixed=fixed, max_steps=30, fmax=0.01, want=1 | 2 | 16, record_interval=3)
+        t = out["traj"]
+        record(f"traj_{opt.lower()}", n_records=t["n_records"], pos=t["positions"], forces=t["forces"], energy=t["energies"],
+               positions=out["positions"], n_steps=out["n_steps"], converged=out["converged"])
+
+
+def painn_relaxations():
+    """The fp32 force path of the lock-step drivers: a PaiNN ensemble, two chains, different FixAtoms masks."""
+    from surface_sampling_amd import backend
+
+    blobs = [np.fromfile(os.path.join(GOLDEN, "weights", f"SrTiO3_painn_model0{m}.f32"), dtype="<f4") for m in (1, 2, 3)]
+    S = np.load(os.path.join(GOLDEN, "structures.npz"))
+    k = "SrTiO3_2x2_pristine"
+    Z, X, cell, pbc = S[f"{k}.numbers"], S[f"{k}.positions"], S[f"{k}.cell"], S[f"{k}.pbc"]
+    rng = np.random.default_rng(17)
+    chains = [(Z, X + rng.normal(0, 0.03, X.shape), cell, pbc) for _ in range(2)]
+    mask = np.concatenate([X[:, 2] < X[:, 2].min() + 2.0, np.arange(len(Z)) % 4 == 0]).astype(np.uint8)
+    eng = backend.PainnEngine(blobs, device=0)
+    for opt in ("FIRE", "BFGS"):
+        eng.upload(chains)
+        out = eng.relax(opt, fixed=mask, max_steps=6, fmax=0.01)
+        res = eng.download()
+        record(f"painn_{opt.lower()}", positions=out["positions"], n_steps=out["n_steps"], converged=out["converged"],
+               energy=res["energy"], forces=res["forces"], energy_std=res["energy_std"])
+    eng.close()
+
+
 def main():
     import eam_alloy_oracle as ao
     import pair_oracle as po
@@ -101,6 +145,8 @@ def main():
         eng = backend.TersoffEngine(gan_params, device=0)
         single_point("tersoff_gan" + tag, eng, gan, tight)
         relaxations(eng, gan, tag, tight)
+        if not tight:
+            relaxations_beyond(eng, gan)
         eng.close()
         eng = backend.PairEngine(m, device=0)
         single_point("pair_rocksalt" + tag, eng, [rock], tight)
@@ -137,6 +183,7 @@ def main():
                             device=0)
     single_point("eam_fs", eng, two)
     eng.close()
+    painn_relaxations()
     print(json.dumps(OUT, indent=1, sort_keys=True))
 
 
