@@ -210,7 +210,7 @@ int vssr_batch_traj_read(vssr_handle *h, int32_t cap_records, int32_t *n_records
  * 3 maxiter, 4 maxeval, 5 search direction not downhill, 6 zero force, 7 zero quadratic step, 8 zero alpha. */
 typedef struct {
     int32_t max_iter;  /* relax_steps (reference GaN: 100) */
-    int32_t max_eval;  /* 10000 */
+    int32_t max_eval;  /* 10000; >= 0, tested once per iteration behind the line search (0: stop after the first one, as LAMMPS) */
     double etol, ftol; /* 1e-5, 1e-5 */
     double dmax;       /* 0.1 */
 } vssr_cg_params;
@@ -259,6 +259,11 @@ int vssr_batch_device_results_f64(vssr_handle *h, const double **energy, const d
  * may be NULL.  Tersoff / EAM handles: energy = energy_models = the fp64 energy, energy_std = 0.  The Metropolis test of the
  * batched MC loop (mc.py) and relax_batch's returned energy take these values. */
 int vssr_batch_energy_f64(vssr_handle *h, double *energy, double *energy_std, double *energy_models);
+/* fp64 results of the LAST evaluation of the resident batch of an analytic (Tersoff / EAM / SW / pair) handle exactly as the device
+ * holds them (synchronises; no upload, no run): energy [B], energy_atoms [sum N], forces [sum N][3]; any pointer may be NULL.
+ * After vssr_batch_relax_fire / _bfgs / _cg: what the driver left, i.e. the static results of the relaxed geometries.  VSSR_E_STATE
+ * before any run, for a PaiNN handle, and for forces after a run that was asked for energies only. */
+int vssr_batch_results_f64(vssr_handle *h, double *energy, double *energy_atoms, double *forces);
 /* Latent-space embedding: the per-atom scalar features after the last update block, [sum N][feat_dim] fp32 per model --
  * what nff's Painn returns as results["embedding"] with requires_embedding=True and the reference's clustering /
  * uncertainty helpers read (get_embeddings_single, mcmc/calculators/calculators.py:67-93; scripts/clustering.py:239).

@@ -36,7 +36,7 @@ EXPORTS = (
     "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
-    "vssr_pair_create", "vssr_pair_eval_batch",
+    "vssr_pair_create", "vssr_pair_eval_batch", "vssr_batch_results_f64",
 )
 
 
@@ -81,8 +81,8 @@ class CgParams(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("max_eval", C.c_int32), ("etol", C.c_double), ("ftol", C.c_double), ("dmax", C.c_double)]
 
     @classmethod
-    def default(cls, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5):
-        return cls(int(max_iter), int(max_eval), float(etol), float(ftol), 0.1)
+    def default(cls, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5, dmax=0.1):
+        return cls(int(max_iter), int(max_eval), float(etol), float(ftol), float(dmax))
 
 
 CG_STOP_REASONS = {1: "energy tolerance", 2: "force tolerance", 3: "max iterations", 4: "max force evaluations",
@@ -249,6 +249,8 @@ def load_library():
     L.vssr_batch_relax_counts.argtypes = [vp, i64p, i64p]
     L.vssr_batch_energy_f64.restype = C.c_int
     L.vssr_batch_energy_f64.argtypes = [vp, dp, dp, dp]
+    L.vssr_batch_results_f64.restype = C.c_int
+    L.vssr_batch_results_f64.argtypes = [vp, dp, dp, dp]
     L.vssr_batch_traj_configure.restype = C.c_int
     L.vssr_batch_traj_configure.argtypes = [vp, C.c_int32]
     L.vssr_batch_traj_read.restype = C.c_int
@@ -630,14 +632,24 @@ class _AnalyticEngine(_Handle):
         e, ea, f = self.evaluate_arrays_f64(n_atoms, T, info["positions"], cell, pbc)
         return e, ea, f, info["positions"], info["n_steps"], info["converged"]
 
-    def relax_cg_f64(self, structs, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5):
+    def relax_cg_f64(self, structs, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5, dmax=0.1, rerun=True):
         """LAMMPS ``min_style cg`` / ``minimize etol ftol max_iter max_eval`` on the device (vssr_batch_relax_cg).  Returns
         (energy [B], e_atom [N], forces [N,3], positions [N,3], n_iter [B], n_eval [B], stop_reason [B])."""
-        return self.relax_cg_arrays_f64(*pack_batch(structs), fixed=fixed, max_iter=max_iter, max_eval=max_eval, etol=etol, ftol=ftol)
+        return self.relax_cg_arrays_f64(*pack_batch(structs), fixed=fixed, max_iter=max_iter, max_eval=max_eval, etol=etol, ftol=ftol,
+                                        dmax=dmax, rerun=rerun)
 
-    def relax_cg_arrays_f64(self, n_atoms, T, pos, cell, pbc, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5):
+    def results_f64(self):
+        """fp64 (energy [B], e_atom [N], forces [N,3]) of the resident batch as the last evaluation or relaxation left them on the
+        device (vssr_batch_results_f64: no upload, no run)."""
+        e, ea, f = np.zeros(self._n_cfg), np.zeros(self._n_atoms), np.zeros((self._n_atoms, 3))
+        self._check(self._lib.vssr_batch_results_f64(self._h, _ptr(e, C.c_double), _ptr(ea, C.c_double), _ptr(f, C.c_double)))
+        return e, ea, f
+
+    def relax_cg_arrays_f64(self, n_atoms, T, pos, cell, pbc, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5,
+                            dmax=0.1, rerun=True):
         """``relax_cg_f64`` on the ABI's packed arrays: the minimisation, then the static evaluation of the minimised geometries
-        (the reference's ``run_lammps_opt`` followed by ``run_lammps_energy``)."""
+        (the reference's ``run_lammps_opt`` followed by ``run_lammps_energy``).  ``dmax``: LAMMPS ``min_modify dmax``.
+        ``rerun=False`` returns the results the minimiser left on the device instead (no second upload, no second run)."""
         self.upload_arrays(n_atoms, T, pos, cell, pbc)
         N, B = self._n_atoms, self._n_cfg
         fx = None
@@ -645,14 +657,14 @@ class _AnalyticEngine(_Handle):
             fx = np.ascontiguousarray(fixed, dtype=np.uint8)
             if fx.size != N:
                 raise ValueError("fixed mask does not match the resident batch")
-        p = CgParams.default(max_iter, max_eval, etol, ftol)
+        p = CgParams.default(max_iter, max_eval, etol, ftol, dmax)
         out = np.zeros((N, 3), np.float64)
         it, ev, why = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
         self._check(self._lib.vssr_batch_relax_cg(self._h, C.byref(p), _ptr(fx, C.c_uint8),
                                                   WANT_ENERGY | WANT_FORCES | WANT_PER_ATOM, _ptr(out, C.c_double),
                                                   _ptr(it, C.c_int32), _ptr(ev, C.c_int32), _ptr(why, C.c_int32)))
         self.last_relax_counts = self.relax_counts()
-        e, ea, f = self.evaluate_arrays_f64(n_atoms, T, out, cell, pbc)
+        e, ea, f = self.evaluate_arrays_f64(n_atoms, T, out, cell, pbc) if rerun else self.results_f64()
         return e, ea, f, out, it, ev, why
 
     def evaluate_f64(self, structs, want=WANT_ENERGY | WANT_FORCES | WANT_PER_ATOM):

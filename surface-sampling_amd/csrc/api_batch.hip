@@ -239,7 +239,7 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
                         int32_t *n_iter, int32_t *n_eval, int32_t *stop_reason) {
     if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
     if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_cg before vssr_batch_upload");
-    if (!params || params->max_iter < 0 || params->max_eval < 1 || !(params->etol >= 0) || !(params->ftol >= 0) || !(params->dmax > 0))
+    if (!params || params->max_iter < 0 || params->max_eval < 0 || !(params->etol >= 0) || !(params->ftol >= 0) || !(params->dmax > 0))
         return set_err(h, VSSR_E_BADARG, "bad CG parameters");
     VSSR_HIP(h, hipSetDevice(h->device));
     h->relax_regrows = 0;
@@ -414,6 +414,22 @@ int vssr_batch_energy_f64(vssr_handle *h, double *energy, double *energy_std, do
     if (energy) VSSR_HIP(h, hipMemcpy(energy, src, sizeof(double) * B, hipMemcpyDeviceToHost));
     if (energy_std) VSSR_HIP(h, hipMemcpy(energy_std, src + B, sizeof(double) * B, hipMemcpyDeviceToHost));
     if (energy_models) VSSR_HIP(h, hipMemcpy(energy_models, src + 2 * B, sizeof(double) * B * M, hipMemcpyDeviceToHost));
+    return VSSR_OK;
+}
+
+int vssr_batch_results_f64(vssr_handle *h, double *energy, double *energy_atoms, double *forces) {
+    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
+    if (!is_analytic(h)) return set_err(h, VSSR_E_STATE, "vssr_batch_results_f64 needs an fp64 potential (Tersoff / EAM / SW / pair handle)");
+    if (!h->ran) return set_err(h, VSSR_E_STATE, "vssr_batch_results_f64 before a run");
+    VSSR_HIP(h, hipSetDevice(h->device));
+    if (forces && !(h->last_want & VSSR_WANT_FORCES))
+        return set_err(h, VSSR_E_STATE, "forces requested, but the last run was asked for energies only");
+    int rc = sync_and_check(h);
+    if (rc) return rc;
+    const size_t B = h->n_cfg, N = h->n_atoms;
+    if (energy) VSSR_HIP(h, hipMemcpy(energy, h->d_pot_e.p, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (energy_atoms) VSSR_HIP(h, hipMemcpy(energy_atoms, h->d_pot_ea.p, sizeof(double) * N, hipMemcpyDeviceToHost));
+    if (forces) VSSR_HIP(h, hipMemcpy(forces, h->d_pot_f.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     return VSSR_OK;
 }
 

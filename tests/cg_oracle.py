@@ -19,9 +19,24 @@ REASONS = {1: "energy tolerance", 2: "force tolerance", 3: "max iterations", 4: 
            8: "linesearch alpha is zero"}
 
 
-def cg_minimize(force_fn, pos, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5, dmax=0.1):
+BRANCHES = ("dmax_clamp", "alpha_one", "proj", "proj_accepted", "proj_rejected", "no_proj", "armijo_ok", "halve", "beta_zero",
+            "ndof_restart", "not_downhill_reset", "reset_to_start")
+
+
+def cg_minimize(force_fn, pos, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5, trace=None, dmax=0.1):
     """force_fn(pos) -> (energy, forces [N,3]).  Returns (pos, energy, n_iter, n_eval, stop_reason, energies of the
-    accepted points)."""
+    accepted points).  ``trace``: an optional ``collections.Counter`` that counts the branches taken (names: ``BRANCHES``):
+    ``dmax_clamp`` / ``alpha_one`` the two forms of alphamax, per line search; ``proj`` a secant projection evaluated,
+    ``proj_accepted`` / ``proj_rejected`` its energy test, ``no_proj`` a trial point without projection; ``armijo_ok`` the
+    backtracking test passed, ``halve`` alpha halved and the loop went on; ``beta_zero`` the Polak-Ribiere beta clipped at or
+    computed as 0, ``ndof_restart`` beta zeroed by the restart rule; ``not_downhill_reset`` h reset to g; ``reset_to_start`` a
+    failed line search went back to x0.  Counting changes no arithmetic and no return value."""
+    counter = trace   # (the name `trace` is reused below for the energies of the accepted points)
+
+    def hit(name):
+        if counter is not None:
+            counter[name] += 1
+
     x = np.array(pos, dtype=np.float64).reshape(-1)
     free = np.ones(len(x) // 3, bool)
     if fixed is not None and len(fixed):
@@ -53,6 +68,7 @@ def cg_minimize(force_fn, pos, fixed=None, max_iter=100, max_eval=10000, etol=1e
         if hmax == 0.0:
             return x.reshape(-1, 3), ecur, niter, neval, 6, trace
         alphamax = min(1.0, dmax / hmax)
+        hit("alpha_one" if alphamax == 1.0 else "dmax_clamp")
         x0, eorig = x.copy(), ecur
         alpha, alphaprev, fhprev, engprev = alphamax, 0.0, fdothall, eorig
         fail = 0
@@ -67,20 +83,28 @@ def cg_minimize(force_fn, pos, fixed=None, max_iter=100, max_eval=10000, etol=1e
             relerr = abs(1.0 - (0.5 * (alpha - alphaprev) * (fh + fhprev) + ecur) / engprev)
             alpha0 = alpha - (alpha - alphaprev) * fh / delfh
             if relerr <= 0.1 and 0.0 < alpha0 < alphamax:
+                hit("proj")
                 x = x0 + alpha0 * h
                 ecur, f = ef(x)
                 if ecur - eorig < 1e-8:
+                    hit("proj_accepted")
                     break
+                hit("proj_rejected")
+            else:
+                hit("no_proj")
             de_ideal = -0.4 * alpha * fdothall
             de = ecur - eorig
             if de <= de_ideal:
+                hit("armijo_ok")
                 break
             fhprev, engprev, alphaprev = fh, ecur, alpha
             alpha *= 0.5
             if alpha <= 0.0 or de_ideal >= -1e-8:
                 fail = 8
                 break
+            hit("halve")
         if fail:
+            hit("reset_to_start")
             x = x0
             ecur, f = ef(x)
             return x.reshape(-1, 3), ecur, niter, neval, fail, trace
@@ -94,10 +118,14 @@ def cg_minimize(force_fn, pos, fixed=None, max_iter=100, max_eval=10000, etol=1e
             return x.reshape(-1, 3), ecur, niter, neval, 2, trace
         beta = max(0.0, (d0 - d1) / gg)
         if (niter + 1) % ndof == 0:
+            hit("ndof_restart")
             beta = 0.0
+        if beta == 0.0:
+            hit("beta_zero")
         gg = d0
         g = f.copy()
         h = g + beta * h
         if g @ h <= 0.0:
+            hit("not_downhill_reset")
             h = g.copy()
     return x.reshape(-1, 3), ecur, niter, neval, 3, trace
