@@ -134,10 +134,12 @@ int vssr_abi_version(void);
  *                            the parity tests use it as an independent second path through the reverse update kernel)
  *   VSSR_DEBUG_KEEP=1        materialise buffers that only vssr_debug_read consumes (the last block's vector output)
  * Read by every vssr_batch_relax_cg call:
- *   VSSR_CG_FUSED=0|1        0: always the lock-step driver (one batch-wide evaluation per launch sequence); 1: the chain-resident
- *                            minimiser (one workgroup relaxes one chain from start to stop, csrc/chain_min.hip) whenever it applies
- *                            (Tersoff handles, chains of <= 256 atoms); unset: chain-resident for batches of <= 3 072 chains of <= 64
- *                            atoms.  Same results bit for bit either way
+ *   VSSR_CG_FUSED=0|1        0: always the lock-step driver (one batch-wide evaluation per launch sequence), whatever the kind of
+ *                            handle and its vssr_batch_relax_cg_driver setting; 1: a Tersoff handle takes the chain-resident minimiser
+ *                            (one workgroup relaxes one chain from start to stop, csrc/chain_min.hip) whenever it applies (chains of
+ *                            <= 256 atoms), SW / EAM / pair handles are not affected; unset: the handle's setting decides
+ *                            (vssr_batch_relax_cg_driver; its default takes the chain-resident minimiser for Tersoff batches of
+ *                            <= 3 072 chains of <= 64 atoms).  Same results bit for bit either way
  *   VSSR_RELAX_COMPACT=0     no live-chain compaction of the resident batch (default on for resident batches of >= 65 536 atoms: once
  *                            at most 3/4 of the chains are still minimising, the batch continues as a smaller one; same trajectories
  *                            bit for bit); n > 1: compact batches of >= n atoms (tests: 2 = always) */
@@ -205,8 +207,8 @@ int vssr_batch_traj_read(vssr_handle *h, int32_t cap_records, int32_t *n_records
  * GaN with it ("optimizer": "LAMMPS": mcmc/dynamics.py:107-116 -> LAMMMPSCalc.run_lammps_opt, mcmc/calculators/calculators.py:600-619,
  * template tutorials/data/GaN_0001/GaN_0001_lammps_opt_template.txt: `fix 2 bulk setforce 0 0 0`, `min_style cg`,
  * `minimize 1e-5 1e-5 {relax_steps} 10000`).  Polak-Ribiere conjugate gradients with LAMMPS' quadratic line search
- * (dmax 0.1 A per coordinate and line search), restated from LAMMPS min_cg.cpp / min_linesearch.cpp; Tersoff and EAM
- * handles only (fp64 energies drive the line search).  stop_reason [B] (may be NULL): 1 energy tolerance, 2 force tolerance,
+ * (dmax 0.1 A per coordinate and line search), restated from LAMMPS min_cg.cpp / min_linesearch.cpp; the analytic
+ * (Tersoff, EAM, SW, pair) handles only (fp64 energies drive the line search).  stop_reason [B] (may be NULL): 1 energy tolerance, 2 force tolerance,
  * 3 maxiter, 4 maxeval, 5 search direction not downhill, 6 zero force, 7 zero quadratic step, 8 zero alpha. */
 typedef struct {
     int32_t max_iter;  /* relax_steps (reference GaN: 100) */
@@ -214,17 +216,27 @@ typedef struct {
     double etol, ftol; /* 1e-5, 1e-5 */
     double dmax;       /* 0.1 */
 } vssr_cg_params;
-/* Two drivers, same results bit for bit (csrc/chain_min.hip, csrc/relax.hip; VSSR_CG_FUSED / VSSR_RELAX_COMPACT above): Tersoff batches
- * of <= 3 072 chains of <= 256 atoms are minimised by ONE workgroup per chain from the first evaluation to the stop criterion (no
- * lock step: the GaN chains of the reference stop after 21 .. 159 evaluations each); everything else in lock step, with the resident
- * batch compacted to the chains still minimising once it is large enough for that to pay.  The automatic choice takes the
- * chain-resident driver for batches of <= 3 072 chains of <= 64 atoms (the measured regime); VSSR_CG_FUSED=1 / 0 forces one.
+/* Two drivers, same results bit for bit (csrc/chain_min.hip, csrc/relax_cg.hip; VSSR_CG_FUSED / VSSR_RELAX_COMPACT above).  The
+ * chain-resident one minimises every chain with ONE workgroup from the first evaluation to the stop criterion (no lock step: the GaN
+ * chains of the reference stop after 21 .. 159 evaluations each); it serves Tersoff, Stillinger-Weber, EAM (funcfl, alloy, fs) and
+ * pair handles whose largest chain has <= 256 atoms.  The lock-step one evaluates the whole batch per step, with the resident batch
+ * compacted to the chains still minimising once it is large enough for that to pay.  Which one runs: vssr_batch_relax_cg_driver
+ * below.  The automatic choice takes the chain-resident driver for Tersoff batches of <= 3 072 chains of <= 64 atoms (the measured
+ * regime) and the lock-step driver for everything else; VSSR_CG_FUSED=0 forces lock step, VSSR_CG_FUSED=1 chain-resident on Tersoff.
  * State of the handle afterwards: positions, energies, per-atom energies and forces are those of the minimised geometries with
  * either driver.  The resident neighbor GRAPH differs: the lock-step driver leaves the batch-wide graph of the final evaluation
  * (vssr_batch_stats / vssr_batch_neighbors work at once), the chain-resident driver numbers its rows per chain and leaves no
  * batch-wide graph -- those two calls return VSSR_E_STATE until one vssr_batch_run has been made. */
 int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint8_t *fixed, uint32_t want,
                         double *pos_out, int32_t *n_iter, int32_t *n_eval, int32_t *stop_reason);
+/* The driver of vssr_batch_relax_cg for this handle.  AUTO (the default): the rule above.  LOCKSTEP / RESIDENT force one; RESIDENT
+ * applies where the chain-resident kernel does (Tersoff / SW / EAM / pair handle, largest chain of the resident batch <= 256 atoms),
+ * any other batch runs in lock step without an error.  VSSR_CG_FUSED, when set, goes first as described above.
+ * driver >= 0: set the handle's choice for later vssr_batch_relax_cg calls; driver < 0: leave it.
+ * last_used (may be NULL): the driver the last vssr_batch_relax_cg of this handle ran (0 = none yet, 1 lock-step, 2 chain-resident).
+ * VSSR_E_BADARG: a driver value above 2, or a PaiNN handle (it has no CG). */
+enum { VSSR_CG_DRIVER_AUTO = 0, VSSR_CG_DRIVER_LOCKSTEP = 1, VSSR_CG_DRIVER_RESIDENT = 2 };
+int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_used);
 
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
@@ -289,7 +301,7 @@ int vssr_batch_saturated(vssr_handle *h, uint8_t *flags, int32_t *n_flagged);
  * stress_std is all zeros.  The kernels run only inside this call; an evaluation that is not asked for stress costs nothing extra.
  * VSSR_E_STATE: before any run, for a handle of another kind, after a run that was not asked for forces, or after a relaxation that
  * left a partial graph -- a lock-step relaxation during which chains converged early, and the chain-resident CG minimiser
- * (vssr_batch_relax_cg on Tersoff chains of <= 256 atoms), which leaves no batch-wide gradients: run the batch once
+ * (vssr_batch_relax_cg on chains of <= 256 atoms, any analytic kind), which leaves no batch-wide gradients: run the batch once
  * (vssr_batch_run), then ask.  After a lock-step relaxation that ended with its batch-wide evaluation the stress is that of the
  * relaxed geometry. */
 int vssr_batch_stress(vssr_handle *h, double *stress, double *stress_std);

@@ -36,7 +36,7 @@ EXPORTS = (
     "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
-    "vssr_pair_create", "vssr_pair_eval_batch", "vssr_batch_results_f64",
+    "vssr_pair_create", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
 )
 
 
@@ -88,6 +88,18 @@ class CgParams(C.Structure):
 CG_STOP_REASONS = {1: "energy tolerance", 2: "force tolerance", 3: "max iterations", 4: "max force evaluations",
                    5: "search direction is not downhill", 6: "forces are zero", 7: "linesearch: zero quadratic step",
                    8: "linesearch alpha is zero"}
+
+
+# vssr_batch_relax_cg_driver: which driver vssr_batch_relax_cg takes ("auto": the library's rule)
+CG_DRIVERS = {"auto": 0, "lockstep": 1, "resident": 2}
+CG_DRIVER_NAMES = {0: None, 1: "lockstep", 2: "resident"}
+
+
+def cg_driver_code(driver) -> int:
+    """The VSSR_CG_DRIVER_* value of ``"auto"`` / ``"lockstep"`` / ``"resident"``; ``ValueError`` for anything else."""
+    if not isinstance(driver, str) or driver not in CG_DRIVERS:
+        raise ValueError(f"CG driver {driver!r}: one of {', '.join(repr(k) for k in CG_DRIVERS)}")
+    return CG_DRIVERS[driver]
 
 
 class BfgsParams(C.Structure):
@@ -221,6 +233,8 @@ def load_library():
     L.vssr_tersoff_create_from_text.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.vssr_batch_relax_cg.restype = C.c_int
     L.vssr_batch_relax_cg.argtypes = [vp, C.POINTER(CgParams), u8p, C.c_uint32, dp, ip, ip, ip]
+    L.vssr_batch_relax_cg_driver.restype = C.c_int
+    L.vssr_batch_relax_cg_driver.argtypes = [vp, C.c_int32, ip]
     L.vssr_eam_create.restype = C.c_int
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_create_alloy.restype = C.c_int
@@ -632,11 +646,26 @@ class _AnalyticEngine(_Handle):
         e, ea, f = self.evaluate_arrays_f64(n_atoms, T, info["positions"], cell, pbc)
         return e, ea, f, info["positions"], info["n_steps"], info["converged"]
 
-    def relax_cg_f64(self, structs, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5, dmax=0.1, rerun=True):
+    last_cg_driver = None         # "lockstep" / "resident": the driver the last relax_cg_f64 / relax_cg_arrays_f64 of this engine ran
+
+    def relax_cg_f64(self, structs, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5, dmax=0.1, rerun=True,
+                     driver="auto"):
         """LAMMPS ``min_style cg`` / ``minimize etol ftol max_iter max_eval`` on the device (vssr_batch_relax_cg).  Returns
-        (energy [B], e_atom [N], forces [N,3], positions [N,3], n_iter [B], n_eval [B], stop_reason [B])."""
+        (energy [B], e_atom [N], forces [N,3], positions [N,3], n_iter [B], n_eval [B], stop_reason [B]).  ``driver``:
+        ``"lockstep"`` (one batch-wide evaluation per step), ``"resident"`` (one workgroup minimises one chain from start to stop:
+        chains of <= 256 atoms, any other batch runs in lock step) or ``"auto"`` (the library's rule: chain-resident for small
+        Tersoff batches); same results bit for bit, ``last_cg_driver`` says which one ran."""
+        cg_driver_code(driver)
         return self.relax_cg_arrays_f64(*pack_batch(structs), fixed=fixed, max_iter=max_iter, max_eval=max_eval, etol=etol, ftol=ftol,
-                                        dmax=dmax, rerun=rerun)
+                                        dmax=dmax, rerun=rerun, driver=driver)
+
+    def cg_driver(self, driver=None):
+        """Set the handle's CG driver (``None``: leave it) and return the name of the one its last CG relaxation ran, ``None`` before
+        the first (vssr_batch_relax_cg_driver)."""
+        code = -1 if driver is None else cg_driver_code(driver)
+        last = C.c_int32(0)
+        self._check(self._lib.vssr_batch_relax_cg_driver(self._h, code, C.byref(last)))
+        return CG_DRIVER_NAMES.get(last.value)
 
     def results_f64(self):
         """fp64 (energy [B], e_atom [N], forces [N,3]) of the resident batch as the last evaluation or relaxation left them on the
@@ -646,11 +675,14 @@ class _AnalyticEngine(_Handle):
         return e, ea, f
 
     def relax_cg_arrays_f64(self, n_atoms, T, pos, cell, pbc, fixed=None, max_iter=100, max_eval=10000, etol=1e-5, ftol=1e-5,
-                            dmax=0.1, rerun=True):
+                            dmax=0.1, rerun=True, driver="auto"):
         """``relax_cg_f64`` on the ABI's packed arrays: the minimisation, then the static evaluation of the minimised geometries
         (the reference's ``run_lammps_opt`` followed by ``run_lammps_energy``).  ``dmax``: LAMMPS ``min_modify dmax``.
-        ``rerun=False`` returns the results the minimiser left on the device instead (no second upload, no second run)."""
+        ``rerun=False`` returns the results the minimiser left on the device instead (no second upload, no second run).
+        ``driver``: see ``relax_cg_f64``."""
+        code = cg_driver_code(driver)
         self.upload_arrays(n_atoms, T, pos, cell, pbc)
+        self._check(self._lib.vssr_batch_relax_cg_driver(self._h, code, None))
         N, B = self._n_atoms, self._n_cfg
         fx = None
         if fixed is not None:
@@ -664,6 +696,7 @@ class _AnalyticEngine(_Handle):
                                                   WANT_ENERGY | WANT_FORCES | WANT_PER_ATOM, _ptr(out, C.c_double),
                                                   _ptr(it, C.c_int32), _ptr(ev, C.c_int32), _ptr(why, C.c_int32)))
         self.last_relax_counts = self.relax_counts()
+        self.last_cg_driver = self.cg_driver()
         e, ea, f = self.evaluate_arrays_f64(n_atoms, T, out, cell, pbc) if rerun else self.results_f64()
         return e, ea, f, out, it, ev, why
 
@@ -721,7 +754,7 @@ class TersoffEngine(_AnalyticEngine):
 
 class SWEngine(_AnalyticEngine):
     """Stillinger-Weber (LAMMPS ``pair_style sw``) evaluator, fp64 on device.  Relaxes with FIRE / BFGS and the lock-step CG driver
-    (the chain-resident minimiser serves Tersoff handles only)."""
+    (the chain-resident minimiser on request: ``relax_cg_f64(..., driver="resident")``)."""
 
     def __init__(self, params, device=0, species=None):
         """``params``: array [nt, nt, nt, 11] (LAMMPS columns eps sig a lambda gamma costheta0 A B p q tol), or the TEXT of a

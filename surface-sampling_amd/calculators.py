@@ -928,7 +928,8 @@ class _AnalyticSurfCalc(_Base):
     (reference ``calculators.py:707-719,766-777``), batched evaluation and lock-step relaxation for ``mc.ChainEnsemble``.
     ``stress`` (Voigt 6-vector, eV / A^3, ASE's sign: what ``ase.Atoms.get_stress`` asks for and the reference's ``lammpsrun``
     fills from ``pxx .. pxy``) is the device virial of the same evaluation (``vssr_batch_stress``), computed only when a call
-    asks for it."""
+    asks for it.  ``cg_driver`` (``set(cg_driver=...)``, or a keyword of ``relax_batch`` / ``run_lammps_opt`` / ``evaluate_packed``):
+    ``"auto"`` (default), ``"lockstep"`` or ``"resident"`` -- the driver of the device CG minimiser (``backend.relax_cg_f64``)."""
 
     # what a calculate() without ``properties`` produces (its default argument); "stress" is served on request only
     _default_properties = ("energy", "relaxed_energy", "forces", "per_atom_energies", "surface_energy")
@@ -940,6 +941,7 @@ class _AnalyticSurfCalc(_Base):
         self.all_periodic = bool(all_periodic)
         self.run_dir = None
         self.relax_steps = 100
+        self.cg_driver = "auto"      # driver of the device CG minimiser: "auto" | "lockstep" | "resident" (backend.relax_cg_f64)
         self.logger = logger or logging.getLogger(__name__)
         self._engine = None
 
@@ -959,12 +961,22 @@ class _AnalyticSurfCalc(_Base):
         return new
 
     def set(self, **kwargs) -> dict:
+        if "cg_driver" in kwargs:
+            backend.cg_driver_code(kwargs["cg_driver"])   # (ValueError before anything is stored)
         changed = _Base.set(self, **kwargs)
         if "run_dir" in self.parameters:
             self.run_dir = self.parameters["run_dir"]
         if "relax_steps" in self.parameters:
             self.relax_steps = self.parameters["relax_steps"]
+        if "cg_driver" in self.parameters:
+            self.cg_driver = self.parameters["cg_driver"]
         return changed
+
+    def _cg_driver_of(self, kwargs) -> str:
+        """The CG driver of one relaxation call: its ``cg_driver`` keyword, else the calculator's setting."""
+        driver = kwargs.get("cg_driver", self.cg_driver)
+        backend.cg_driver_code(driver)
+        return driver
 
     def _pack(self, atoms):
         Z, pos, cell, pbc = structures.as_arrays(atoms)
@@ -1031,7 +1043,7 @@ class _AnalyticSurfCalc(_Base):
         if str(optimizer).upper() in ("CG", "LAMMPS"):
             e, ea, f, new_pos, it, ev, why = eng.relax_cg_f64(
                 [(types, pos, cell, pbc)], fixed=fixed, max_iter=int(self.relax_steps), etol=kwargs.get("etol", 1e-5),
-                ftol=kwargs.get("ftol", 1e-5))
+                ftol=kwargs.get("ftol", 1e-5), driver=self._cg_driver_of(kwargs))
             self.last_opt = {"optimizer": "CG", "iterations": int(it[0]), "evaluations": int(ev[0]),
                              "stop": backend.CG_STOP_REASONS.get(int(why[0]), str(int(why[0])))}
         else:
@@ -1055,10 +1067,12 @@ class _AnalyticSurfCalc(_Base):
         use the ASE-style optimizers with ``fmax``.  ``relax_steps`` defaults to ``self.relax_steps`` (the reference takes it
         from ``calc.relax_steps``).  Returns per slab ``(relaxed, None, energy, energy_oob, results)`` like
         ``EnsembleNFFSurface.relax_batch``; results carry ``per_atom_energies`` of the relaxed slab, with ``want_stress`` also its
-        ``stress``."""
+        ``stress``.  ``cg_driver="auto" | "lockstep" | "resident"`` (default: the calculator's ``cg_driver`` setting) selects the
+        driver of the CG minimiser (``backend.relax_cg_f64``): same results bit for bit."""
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "LAMMPS")
         steps = int(self.relax_steps if relax_steps is None else relax_steps)
+        driver = self._cg_driver_of(kwargs)
         packs = [self._pack(a) for a in atoms_list]
         fixed = None
         if fixed_indices is not None:
@@ -1071,7 +1085,7 @@ class _AnalyticSurfCalc(_Base):
         eng = self._get_engine()
         if str(optimizer).upper() in ("CG", "LAMMPS"):
             e, ea, f, pos, it, ev, why = eng.relax_cg_f64(packs, fixed=fixed, max_iter=steps, etol=kwargs.get("etol", 1e-5),
-                                                          ftol=kwargs.get("ftol", 1e-5))
+                                                          ftol=kwargs.get("ftol", 1e-5), driver=driver)
             extra = [{"iterations": int(it[b]), "evaluations": int(ev[b]),
                       "stop": backend.CG_STOP_REASONS.get(int(why[b]), str(int(why[b])))} for b in range(len(packs))]
         else:
@@ -1136,11 +1150,13 @@ class _AnalyticSurfCalc(_Base):
         bookkeeping was 41 % of an MC step, ``profiles/r04/bench_gan.jsonl``).  Returns fp64 ``energy [B]`` (the static energies of
         the final geometries), ``forces``, ``energy_atoms``, ``positions``, ``cfg_start``, ``oob [B]`` (the +-1000 guard of
         ``mcmc/dynamics.py:159-168``), ``energy_std`` / ``saturated`` (zeros: one deterministic fp64 potential), and for
-        relaxations ``iterations`` / ``evaluations`` / ``stop`` (CG) or ``n_steps`` / ``converged`` (FIRE, BFGS)."""
+        relaxations ``iterations`` / ``evaluations`` / ``stop`` (CG) or ``n_steps`` / ``converged`` (FIRE, BFGS).  CG relaxations
+        take the calculator's ``cg_driver`` setting (or a ``cg_driver`` keyword)."""
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "LAMMPS")
         if relax and not self.packed_supported(True, optimizer):
             raise backend.BackendError(f"evaluate_packed relaxes on the device only (CG / LAMMPS, FIRE, BFGS), not with {optimizer!r}")
+        driver = self._cg_driver_of(kwargs)
         n_atoms = np.ascontiguousarray(n_atoms, dtype=np.int32)
         B = len(n_atoms)
         types = self._types_of(Z)
@@ -1156,7 +1172,8 @@ class _AnalyticSurfCalc(_Base):
         elif str(optimizer).upper() in ("CG", "LAMMPS"):
             steps = int(self.relax_steps if relax_steps is None else relax_steps)
             e, ea, f, new_pos, it, ev, why = eng.relax_cg_arrays_f64(n_atoms, types, pos, cell, pbc, fixed=fixed_mask, max_iter=steps,
-                                                                     etol=kwargs.get("etol", 1e-5), ftol=kwargs.get("ftol", 1e-5))
+                                                                     etol=kwargs.get("etol", 1e-5), ftol=kwargs.get("ftol", 1e-5),
+                                                                     driver=driver)
             ls, ce = getattr(eng, "last_relax_counts", (0, 0))
             extra = {"iterations": it, "evaluations": ev, "stop": why, "lockstep_evaluations": ls, "dispatched_chain_evaluations": ce}
         else:
@@ -1208,7 +1225,8 @@ class SWSurfCalc(_AnalyticSurfCalc):
     """Stillinger-Weber energy / per-atom energies / forces on MI355X (LAMMPS ``pair_style sw``, or ``pair_style kim`` with a
     built-in SW model such as ``SW_StillingerWeber_1985_Si__MO_405512056662_005`` of the reference's Si(111) 5x5 run directory).
     ``per_atom_energies`` follow LAMMPS ``pe/atom`` for ``pair_style sw`` (pair terms half / half, three-body terms in thirds).
-    Relaxations (``run_lammps_opt``, ``relax_batch``, ``evaluate_packed(relax=True)``) use the lock-step CG / FIRE / BFGS drivers.
+    Relaxations (``run_lammps_opt``, ``relax_batch``, ``evaluate_packed(relax=True)``) use the lock-step CG / FIRE / BFGS drivers;
+    ``set(cg_driver="resident")`` selects the chain-resident CG minimiser instead (same results bit for bit).
     ``all_periodic=False`` keeps the atoms' own ``pbc`` (the Si templates say ``boundary p p f``)."""
 
     name = "sw_mi355x"
@@ -1245,7 +1263,8 @@ class PairSurfCalc(_AnalyticSurfCalc):
     ``coul/dsf`` and ``hybrid`` / ``hybrid/overlay`` of them, given as the LAMMPS commands a template would carry (``pair_style``,
     ``pair_coeff``, ``pair_modify shift | mix``, ``set type N charge q``; ``pair.parse``).  ``per_atom_energies`` follow LAMMPS
     ``pe/atom`` (pair energies half / half, the coul/dsf self term on its atom).  Relaxations use the lock-step CG / FIRE / BFGS
-    drivers.  ``all_periodic=False`` keeps the atoms' own ``pbc``."""
+    drivers; ``set(cg_driver="resident")`` selects the chain-resident CG minimiser instead (same results bit for bit).
+    ``all_periodic=False`` keeps the atoms' own ``pbc``."""
 
     name = "pair_mi355x"
 

@@ -244,11 +244,12 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
     VSSR_HIP(h, hipSetDevice(h->device));
     h->relax_regrows = 0;
     h->last_want = want | VSSR_WANT_FORCES;
-    // chains of <= 256 atoms on the Tersoff potential: one workgroup minimises one chain from start to stop (chain_min.hip); else
-    // the lock-step driver (relax_cg.hip).  Same results bit for bit.
+    // one workgroup minimises one chain from start to stop (chain_min.hip: analytic kinds, chains of <= 256 atoms, where the handle's
+    // driver setting / VSSR_CG_FUSED / the automatic rule choose it); else the lock-step driver (relax_cg.hip).  Same results bit for bit.
     const bool resident = chain_min_supported(h);
     int rc = resident ? chain_min_cg(h, params, fixed, want) : relax_cg(h, params, fixed, want);
     if (rc) return rc;
+    h->cg_last_driver = resident ? VSSR_CG_DRIVER_RESIDENT : VSSR_CG_DRIVER_LOCKSTEP;
     h->graph_partial = resident;     // (the lock-step driver ends with a full batch-wide evaluation of the final positions; the
                                      //  chain-resident one numbers its rows per chain: introspection wants one plain run first)
     rc = sync_and_check(h);          // ... which may itself have overflowed the neighbor capacity: grow and repeat it
@@ -261,6 +262,16 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
         if (n_eval) n_eval[b] = rep[3 * b + 1];
         if (stop_reason) stop_reason[b] = rep[3 * b + 2];
     }
+    return VSSR_OK;
+}
+
+int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_used) {
+    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
+    if (!is_analytic(h)) return set_err(h, VSSR_E_BADARG, "vssr_batch_relax_cg_driver: a PaiNN handle has no conjugate-gradient minimiser");
+    if (driver > VSSR_CG_DRIVER_RESIDENT)
+        return set_err(h, VSSR_E_BADARG, "vssr_batch_relax_cg_driver: driver %d is none of 0 (automatic), 1 (lock-step), 2 (chain-resident)", (int)driver);
+    if (driver >= 0) h->cg_driver = driver;
+    if (last_used) *last_used = h->cg_last_driver;
     return VSSR_OK;
 }
 

@@ -64,29 +64,11 @@ void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1
     }
 }
 
-// the tables of a handle (layout: see EamTyped); a funcfl handle (eam_nel == 0) is one element
-static EamTyped eam_tables(const vssr_handle *h) {
-    const int n = h->eam_nel > 0 ? h->eam_nel : 1;
-    const size_t sF = 7 * (size_t)(h->eam_grid.nrho + 1), sR = 7 * (size_t)(h->eam_grid.nr + 1);
-    const double *frho = h->pot_params.as<double>(), *rhor = frho + sF * n;
-    return EamTyped{frho, rhor, rhor + sR * (h->eam_fs ? n * n : n), n, h->eam_fs, sF, sR};
-}
-
-// d_gbar of an EAM handle between the two passes and the virial kernel: F(rho) [atoms] | F'(rho) [atoms]
-struct EamAtoms {
-    double *e_embed, *fp;
-    static size_t doubles(const vssr_handle *h) { return 2 * (size_t)h->n_atoms; }
-};
-static EamAtoms slots_of(const vssr_handle *h) {
-    double *e_embed = h->d_gbar.as<double>();
-    return {e_embed, e_embed + h->n_atoms};
-}
-
 int eam_stress(vssr_handle *h) {
     if (h->d_stress.ensure(sizeof(double) * 12 * (size_t)h->n_cfg)) return set_err(h, VSSR_E_NOMEM, "out of device memory (stress)");
     double *out = h->d_stress.as<double>();
     hipLaunchKernelGGL(h->eam_nel > 0 ? k_eam_stress<true> : k_eam_stress<false>, dim3(h->n_cfg), dim3(VIR_THREADS), 0, h->stream,
-                       pot_view(h), h->eam_grid, eam_tables(h), slots_of(h).fp, out, out + 6 * (size_t)h->n_cfg);
+                       pot_view(h), h->eam_grid, eam_tables(h), EamAtoms::of(h).fp, out, out + 6 * (size_t)h->n_cfg);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;
 }
@@ -96,7 +78,7 @@ int eam_run(vssr_handle *h, uint32_t want) {
     int rc = analytic_begin(h, h->eam_grid.cutoff, EamAtoms::doubles, "EAM");
     if (rc) return rc;
     const PotView V = pot_view(h);
-    const EamAtoms S = slots_of(h);
+    const EamAtoms S = EamAtoms::of(h);
     const EamTyped T = eam_tables(h);
     const bool typed = h->eam_nel > 0;   // (a funcfl handle never takes the typed kernels: 2.6 .. 3.4 % slower on pure Cu, profiles/r10/NOTES_eam_alloy.md)
     dim3 blk(64), grd((V.n_atoms + 63) / 64);

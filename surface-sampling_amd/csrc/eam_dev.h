@@ -147,5 +147,24 @@ __device__ __forceinline__ void eam_stress_chain(int b, double (*red)[VIR_THREAD
     virial_reduce_store(red, w, 0.5, b, cell, stress, stress_std);
 }
 
+// the tables of a handle (layout: see EamTyped); a funcfl handle (eam_nel == 0) is one element
+inline EamTyped eam_tables(const vssr_handle *h) {
+    const int n = h->eam_nel > 0 ? h->eam_nel : 1;
+    const size_t sF = 7 * (size_t)(h->eam_grid.nrho + 1), sR = 7 * (size_t)(h->eam_grid.nr + 1);
+    const double *frho = h->pot_params.as<double>(), *rhor = frho + sF * n;
+    return EamTyped{frho, rhor, rhor + sR * (h->eam_fs ? n * n : n), n, h->eam_fs, sF, sR};
+}
+
+// d_gbar of an EAM handle between the two passes and the virial kernel: F(rho) [atoms] | F'(rho) [atoms]
+// (eam.hip and the chain-resident minimiser, chain_min.hip)
+struct EamAtoms {
+    double *e_embed, *fp;
+    static size_t doubles(const vssr_handle *h) { return 2 * (size_t)h->n_atoms; }
+    static EamAtoms of(const vssr_handle *h) {
+        double *e_embed = h->d_gbar.as<double>();
+        return {e_embed, e_embed + h->n_atoms};
+    }
+};
+
 }  // namespace vssr
 #endif

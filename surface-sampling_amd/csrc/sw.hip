@@ -36,24 +36,14 @@ __global__ void k_sw_gather(PotView V, const double *__restrict__ eo, const doub
     sw_gather_atom(c, V.row_start, V.rev, eo, ej, gslot, e_atom, forces);
 }
 
-// d_gbar of a Stillinger-Weber handle between the site kernel, the gather and the virial kernel: eo [slots] | ej [slots] | G [slots][3]
-struct SwSlots {
-    double *eo, *ej, *gslot;
-    static size_t doubles(const vssr_handle *h) { return 5 * (size_t)h->slot_cap; }
-};
-static SwSlots slots_of(const vssr_handle *h) {
-    double *eo = h->d_gbar.as<double>();
-    return {eo, eo + h->slot_cap, eo + 2 * h->slot_cap};
-}
-
-int sw_stress(vssr_handle *h) { return slot_stress(h, slots_of(h).gslot); }
+int sw_stress(vssr_handle *h) { return slot_stress(h, SwSlots::of(h).gslot); }
 
 int sw_run(vssr_handle *h, uint32_t want) {
     (void)want;
     int rc = analytic_begin(h, h->pot_cutoff, SwSlots::doubles, "sw");
     if (rc) return rc;
     const PotView V = pot_view(h);
-    const SwSlots S = slots_of(h);
+    const SwSlots S = SwSlots::of(h);
     const int N = V.n_atoms;
     hipLaunchKernelGGL(k_sw_site, dim3((N + SW_CENTRES - 1) / SW_CENTRES), dim3(SW_CENTRES * SW_LANES), 0, h->stream, V,
                        h->pot_params.as<SwP>(), S.eo, S.ej, S.gslot);

@@ -190,5 +190,16 @@ __device__ __forceinline__ void sw_gather_atom(int c, const int *__restrict__ ro
     forces[3 * c] = f0; forces[3 * c + 1] = f1; forces[3 * c + 2] = f2;
 }
 
+// d_gbar of a Stillinger-Weber handle between the site kernel, the gather and the virial kernel: eo [slots] | ej [slots] | G [slots][3]
+// (sw.hip and the chain-resident minimiser, chain_min.hip)
+struct SwSlots {
+    double *eo, *ej, *gslot;
+    static size_t doubles(const vssr_handle *h) { return 5 * (size_t)h->slot_cap; }
+    static SwSlots of(const vssr_handle *h) {
+        double *eo = h->d_gbar.as<double>();
+        return {eo, eo + h->slot_cap, eo + 2 * h->slot_cap};
+    }
+};
+
 }  // namespace vssr
 #endif

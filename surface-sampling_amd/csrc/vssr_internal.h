@@ -395,6 +395,8 @@ struct vssr_handle {
     const void *zero_entry_tab[2] = {nullptr, nullptr};
     int cap_per_atom = 64;        // initial neighbor capacity (slots per atom); vssr_debug_capacity
     int cm_cap_per_atom = 0;      // slots per atom the chain-resident CG minimiser's per-chain pools grew to (chain_min.hip)
+    int cg_driver = 0;            // VSSR_CG_DRIVER_*: the handle's choice of CG driver (vssr_batch_relax_cg_driver; 0 = automatic)
+    int cg_last_driver = 0;       // the driver the last vssr_batch_relax_cg ran: 0 none yet, 1 lock-step, 2 chain-resident
     bool cap_tight = false;       // regrow to the exact need only (tests: forces repeated overflows)
     uint32_t last_want = 0;                       // outputs produced by the last run
     int64_t slot_cap = 0;
@@ -550,7 +552,8 @@ int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_ch
 int relax_regrow(vssr_handle *h, int cap, long long &it, int window);   // after an overflow seen at a poll: grow, give the poll window back
 // lock-step LAMMPS-style CG for the fp64 potentials (relax_cg.hip); results in d_relax_steps [B][3] = {iterations, evaluations, stop reason}
 int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want);
-// chain_min.hip: the same minimisation with one workgroup per chain (Tersoff handles, chains of <= 256 atoms; VSSR_CG_FUSED=0 disables)
+// chain_min.hip: the same minimisation with one workgroup per chain (Tersoff / SW / EAM / pair handles, chains of <= 256 atoms).
+// chain_min_supported: this relaxation takes it (the kernel applies AND VSSR_CG_FUSED / the handle's cg_driver / the automatic rule say so)
 bool chain_min_supported(const vssr_handle *h);
 int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want);
 // MFMA node stages (painn_node_mfma.hip)

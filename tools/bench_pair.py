@@ -6,7 +6,11 @@ resident chains of two workloads, each chain rattled by its own seed:
   * sw      tools/bench_si.py's Stillinger-Weber single point on the Si(111) 5x5 slab at the same chain counts, for scale.
 For each: the resident batch re-evaluated (neighbor list + site + energy kernels; vssr_batch_run + synchronize) and the whole call
 with upload and fp64 download (evaluate_arrays_f64); mean slots per atom from vssr_batch_stats.  One JSON line per measurement.
-Usage: python tools/bench_pair.py [--chains 1024,4096] [--reps 10] [--no-sw]"""
+--cg-driver lockstep | resident | both adds CG relaxations/s of the rocksalt slab (the device part of an MC proposal that relaxes:
+B chains rattled by their own seeds, the lower half held, vssr_batch_relax_cg with that driver) with the chain-evaluations dispatched
+and needed; both: the two drivers one after the other in this process.
+Usage: python tools/bench_pair.py [--chains 1024,4096] [--reps 10] [--no-sw] [--cg-driver lockstep|resident|both] [--cg-only]
+       [--relax-steps 20]"""
 import argparse, json, os, sys, time
 
 import numpy as np
@@ -73,18 +77,60 @@ def single_point(name, lines, n_types, struct, B, reps):
                       "mean_slots_per_atom": round(st["edges"] / st["atoms"], 1), "reps": reps}), flush=True)
 
 
+def relax_cg(name, eng, struct, B, max_iter, driver, sigma=0.05, reps=2):
+    """CG relaxations/s of B rattled copies of ``struct`` (atoms below the middle height held) with one driver: the best of ``reps``
+    timed calls behind a warm-up call (the chain-resident pools and the lock-step buffers have grown by then)."""
+    import bench_si
+
+    T1, X, Cl, pbc = struct
+    n = len(T1)
+    rng = np.random.default_rng(0)
+    held = X[:, 2] < 0.5 * (X[:, 2].min() + X[:, 2].max())
+    pos = np.concatenate([X + np.where(held[:, None], 0.0, rng.normal(0, sigma, X.shape)) for _ in range(B)])
+    arrays = (np.full(B, n, np.int32), np.tile(T1, B), pos, np.tile(Cl.reshape(1, 9), (B, 1)), np.tile(np.asarray(pbc, np.uint8).reshape(1, 3), (B, 1)))
+    mask = np.tile(held.astype(np.uint8), B)
+    count = bench_si.RelaxCounter(eng)
+    try:
+        eng.relax_cg_arrays_f64(*arrays, fixed=mask, max_iter=max_iter, rerun=False, driver=driver)
+        best = None
+        for _ in range(reps):
+            count.reset()
+            t0 = time.perf_counter()
+            out = eng.relax_cg_arrays_f64(*arrays, fixed=mask, max_iter=max_iter, rerun=False, driver=driver)
+            dt = time.perf_counter() - t0
+            if best is None or dt < best[0]:
+                best = (dt, count.report())
+    finally:
+        del eng.relax_cg_arrays_f64          # (the counter's wrapper)
+    print(json.dumps({"metric": f"CG relaxations/s, {name} ({n} atoms, {int(held.sum())} held, <= {max_iter} iterations)", "chains": B,
+                      "cg_driver": driver, "relaxations_per_s": round(B / best[0], 1), "s_per_batch": round(best[0], 4),
+                      "mean_n_eval": round(float(out[5].mean()), 2), "min_n_eval": int(out[5].min()), "max_n_eval": int(out[5].max()),
+                      "regrows_last_call": eng.debug_capacity(), **best[1]}), flush=True)
+
+
 def main():
+    import bench_si
+
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cg-driver", choices=("none",) + bench_si.CG_DRIVERS, default="none", help="also measure CG relaxations of the rocksalt slab")
+    ap.add_argument("--cg-only", action="store_true", help="skip the single-point figures")
+    ap.add_argument("--relax-steps", type=int, default=20)
     ap.add_argument("--chains", default="1024,4096")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-sw", action="store_true", help="skip the Stillinger-Weber figure of tools/bench_si.py")
     args = ap.parse_args()
-    for B in [int(x) for x in args.chains.split(",") if x]:
+    if args.cg_driver != "none":
+        from surface_sampling_amd import backend, pair
+
+        eng = backend.PairEngine(pair.parse(BORN_DSF, 2), device=0)
+        for B in [int(x) for x in args.chains.split(",") if x]:
+            for driver in bench_si.drivers_of(args.cg_driver):
+                relax_cg("rocksalt slab, Born + damped-shifted Coulomb", eng, rocksalt_slab(), B, args.relax_steps, driver)
+        eng.close()
+    for B in [] if args.cg_only else [int(x) for x in args.chains.split(",") if x]:
         single_point("Lennard-Jones fcc(100) slab", LJ, 1, lj_slab(), B, args.reps)
         single_point("rocksalt slab, Born + damped-shifted Coulomb", BORN_DSF, 2, rocksalt_slab(), B, args.reps)
         if not args.no_sw:
-            import bench_si
-
             bench_si.single_point(B, args.reps)
 
 

@@ -2,7 +2,9 @@
 256 bench chains (BASELINE configs[3] workload), lower slab layers held fixed; for several convergence thresholds:
 wall time of vssr_batch_relax_{bfgs,fire}, sum over chains of (steps + 1) = evaluations an ideal driver performs, and the
 time per chain-evaluation -- constant if converged chains cost nothing.  Prints one JSON line per run.
-Usage: python tools/bench_relax.py [--chains 256] [--relax-steps 20]"""
+--cg-driver lockstep | resident | both measures the CG minimiser of the fp64 potentials instead (vssr_batch_relax_cg with that driver):
+--chains rattled Si(111) 5x5 slabs on Stillinger-Weber, wall time and dispatched / needed chain-evaluations per driver.
+Usage: python tools/bench_relax.py [--chains 256] [--relax-steps 20] [--cg-driver lockstep|resident|both]"""
 import argparse, json, os, sys, time
 
 import numpy as np
@@ -12,11 +14,29 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (golden loaders)
 
 
+def cg_main(args):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import bench_pair
+    import bench_si
+    from surface_sampling_amd import backend, sw as sw_io
+
+    Z, X, Cl, pbc, fixed = bench_si.slab()
+    # (bench_pair.relax_cg holds the atoms below the middle height: the lower layers of the slab)
+    eng = backend.SWEngine(sw_io.parse_sw(sw_io.builtin_text(bench_si.MODEL), ["Si"]), device=0)
+    for driver in bench_si.drivers_of(args.cg_driver):
+        bench_pair.relax_cg("Si(111) 5x5 slab, Stillinger-Weber", eng, (np.zeros(len(Z), np.int32), X, Cl, pbc), args.chains,
+                            args.relax_steps, driver, sigma=0.1)
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", type=int, default=256)
     ap.add_argument("--relax-steps", type=int, default=20)
+    ap.add_argument("--cg-driver", choices=("none", "auto", "lockstep", "resident", "both"), default="none")
     args = ap.parse_args()
+    if args.cg_driver != "none":
+        return cg_main(args)
     from surface_sampling_amd import backend
     from surface_sampling_amd.calculators import stoich_offset_table
 
