@@ -238,6 +238,25 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
 enum { VSSR_CG_DRIVER_AUTO = 0, VSSR_CG_DRIVER_LOCKSTEP = 1, VSSR_CG_DRIVER_RESIDENT = 2 };
 int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_used);
 
+/* ASE BFGSLineSearch (ase/optimize/bfgslinesearch.py + ase/utils/linesearch.py: alpha = 10, maxstep = 0.2, c1 = 0.23, c2 = 0.46,
+ * stpmax = 50; fixed inside: stpmin 1e-8, xtol 1e-14, xtrapl 1.1, xtrapu 4.0) in lock step on every handle kind that relaxes: PaiNN
+ * (fp64 ensemble-mean energy, fp32 forces widened), Tersoff, SW, EAM and pair (fp64 throughout).  A trial of a line search costs one
+ * batch-wide evaluation; the evaluation that ends a line search opens the next step (csrc/bfgsls_dev.h, csrc/relax_bfgsls.hip).
+ * PROVENANCE: restated from the two ASE files as remembered and NOT pinned by an executed ASE (it cannot be installed next to this
+ * project); the contract is the numpy restatement tests/bfgsls_oracle.py, whose interpolation is scipy's MINPACK-2 dcstep.
+ * Parameters are doubles so that the restatement sees the same values.  max_eval: evaluations a chain may spend (>= 1; the Python
+ * default is 20 max_steps + 20).  n_steps / n_eval / stop_reason [B], pos_out [sum N][3] may each be NULL.  stop_reason: 1 converged
+ * (max_i |F_i| < fmax, tested when a step opens), 2 max_steps, 3 the line search failed (where ASE raises "LineSearch failed!";
+ * positions back at the point the step opened at), 4 max_eval spent (positions at the best point of the interrupted search),
+ * 5 non-finite energy or force (positions back at the point the step opened at).  One chain's failure is never an error of the call.
+ * Afterwards the batch holds the final positions and a complete evaluation of them over all chains (download, vssr_batch_stress,
+ * vssr_batch_results_f64, vssr_batch_stats work at once).  With vssr_batch_traj_configure armed a chain records at the evaluations that
+ * open a step (steps % interval == 0), never at a line-search trial.  No live-chain compaction, no chain-resident form.
+ * VSSR_E_BADARG (with a message): max_steps < 0, max_eval < 1, fmax / alpha / maxstep <= 0, c1 or c2 outside (0, 1), stpmax < 1. */
+typedef struct { int32_t max_steps, max_eval; double fmax, alpha, maxstep, c1, c2, stpmax; } vssr_bfgsls_params;
+int vssr_batch_relax_bfgs_linesearch(vssr_handle *h, const vssr_bfgsls_params *p, const uint8_t *fixed, uint32_t want,
+                                     double *pos_out, int32_t *n_steps, int32_t *n_eval, int32_t *stop_reason);
+
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
  * vssr_profile_read synchronises and returns, for each kernel class, the number of launches and

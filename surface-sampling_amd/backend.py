@@ -37,6 +37,7 @@ EXPORTS = (
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
     "vssr_pair_create", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
+    "vssr_batch_relax_bfgs_linesearch",
 )
 
 
@@ -109,6 +110,36 @@ class BfgsParams(C.Structure):
     @classmethod
     def default(cls, max_steps=20, fmax=0.01):
         return cls(int(max_steps), float(fmax), 70.0, 0.2)
+
+
+class BfgsLsParams(C.Structure):
+    """vssr_bfgsls_params; defaults = ASE BFGSLineSearch defaults (alpha 10, maxstep 0.2, c1 0.23, c2 0.46, stpmax 50), the reference's
+    relax_steps / fmax, and an evaluation budget of ``20 * max_steps + 20`` per chain.  Doubles: the numpy restatement
+    (tests/bfgsls_oracle.py) sees the same values."""
+    _fields_ = [("max_steps", C.c_int32), ("max_eval", C.c_int32), ("fmax", C.c_double), ("alpha", C.c_double), ("maxstep", C.c_double),
+                ("c1", C.c_double), ("c2", C.c_double), ("stpmax", C.c_double)]
+
+    @classmethod
+    def default(cls, max_steps=20, fmax=0.01, max_eval=None, alpha=10.0, maxstep=0.2, c1=0.23, c2=0.46, stpmax=50.0):
+        if max_eval is None:
+            max_eval = 20 * int(max_steps) + 20
+        return cls(int(max_steps), int(max_eval), float(fmax), float(alpha), float(maxstep), float(c1), float(c2), float(stpmax))
+
+
+BFGSLS_STOP_REASONS = {1: "converged", 2: "max steps", 3: "line search failed", 4: "max force evaluations",
+                       5: "non-finite energy or force"}
+
+
+# who runs optimizer="BFGSLineSearch" for a calculator: ASE's class on the host, one optimizer per chain ("ase", the default), or the
+# lock-step device optimizer (vssr_batch_relax_bfgs_linesearch)
+LINESEARCH_DRIVERS = ("ase", "device")
+
+
+def linesearch_driver_check(driver) -> str:
+    """``driver`` if it is ``"ase"`` or ``"device"``; ``ValueError`` for anything else."""
+    if not isinstance(driver, str) or driver not in LINESEARCH_DRIVERS:
+        raise ValueError(f"linesearch driver {driver!r}: one of {', '.join(repr(k) for k in LINESEARCH_DRIVERS)}")
+    return driver
 
 
 class GmmConfig(C.Structure):
@@ -235,6 +266,8 @@ def load_library():
     L.vssr_batch_relax_cg.argtypes = [vp, C.POINTER(CgParams), u8p, C.c_uint32, dp, ip, ip, ip]
     L.vssr_batch_relax_cg_driver.restype = C.c_int
     L.vssr_batch_relax_cg_driver.argtypes = [vp, C.c_int32, ip]
+    L.vssr_batch_relax_bfgs_linesearch.restype = C.c_int
+    L.vssr_batch_relax_bfgs_linesearch.argtypes = [vp, C.POINTER(BfgsLsParams), u8p, C.c_uint32, dp, ip, ip, ip]
     L.vssr_eam_create.restype = C.c_int
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_create_alloy.restype = C.c_int
@@ -490,7 +523,8 @@ class _Handle:
     # -- lock-step relaxation ------------------------------------------------------------------------
     def relax(self, optimizer="FIRE", **kw):
         """Dispatch on the reference's optimizer names (``mcmc/dynamics.py:119-127``: a name containing "BFGS" selects
-        BFGS, everything else FIRE; BFGSLineSearch / CG / LAMMPS are not provided by this backend)."""
+        BFGS, everything else FIRE; BFGSLineSearch / CG / LAMMPS are not dispatched here: ``relax_bfgs_linesearch`` and ``relax_cg_f64``
+        are called by name, the calculators' ``linesearch_driver`` / ``relax_batch`` choose them)."""
         name = str(optimizer)
         if "BFGSLineSearch" in name or "CG" in name or "LAMMPS" in name:
             raise BackendError(f"optimizer {optimizer!r} is not available on the device (FIRE and BFGS are)")
@@ -511,6 +545,23 @@ class _Handle:
         forces [R, sum N, 3] with FixAtoms applied, energies [R, B]); entries of chain b beyond n_records[b] are unused."""
         p = params or FireParams.default(max_steps, fmax)
         return self._relax_call(self._lib.vssr_batch_relax_fire, p, fixed, want, record_interval)
+
+    def relax_bfgs_linesearch(self, fixed=None, max_steps=20, fmax=0.01, max_eval=None, want=WANT_ALL, params=None, record_interval=0):
+        """BFGSLineSearch-relax every chain of the resident batch on the device (vssr_batch_relax_bfgs_linesearch: ASE's
+        BFGSLineSearch restated, one lock-step evaluation per line-search trial).  Arguments as :meth:`relax_fire`, plus ``max_eval``,
+        the evaluations a chain may spend (default ``20 * max_steps + 20``).  Returns the dict of :meth:`relax_fire` plus
+        ``n_eval`` [B] and ``stop_reason`` [B] (``BFGSLS_STOP_REASONS``); ``converged`` is ``stop_reason == 1``.  The batch is left
+        with a complete evaluation of the final positions: ``download()`` / ``results_f64()`` / ``stress()`` need no run.
+        ``record_interval`` k records the points at which steps 0, k, 2k, ... open, never a line-search trial."""
+        p = params or BfgsLsParams.default(max_steps, fmax, max_eval)
+        ev, why = np.zeros(self._n_cfg, np.int32), np.zeros(self._n_cfg, np.int32)
+
+        def call(h, pp, fx, want_, pos, steps, conv):
+            return self._lib.vssr_batch_relax_bfgs_linesearch(h, pp, fx, want_, pos, steps, _ptr(ev, C.c_int32), _ptr(why, C.c_int32))
+
+        out = self._relax_call(call, p, fixed, want, record_interval)
+        out["n_eval"], out["stop_reason"], out["converged"] = ev, why, why == 1
+        return out
 
     def relax_counts(self):
         """``(lock-step evaluations, dispatched chain-evaluations)`` of the last relaxation (vssr_batch_relax_counts)."""

@@ -381,6 +381,8 @@ class EnsembleNFFSurface(_Base):
     def set(self, **kwargs) -> dict:
         """Set parameters; ``chem_pots`` / ``offset_data`` are mirrored onto attributes
         (reference ``calculators.py:448-466``)."""
+        if "linesearch_driver" in kwargs:
+            backend.linesearch_driver_check(kwargs["linesearch_driver"])   # (ValueError before anything is stored)
         changed = _Base.set(self, **kwargs)
         if "chem_pots" in self.parameters:
             self.chem_pots = self.parameters["chem_pots"]
@@ -614,7 +616,7 @@ class EnsembleNFFSurface(_Base):
         return out
 
     def relax_batch(self, atoms_list, fixed_indices=None, relax_steps: int = 20, fmax: float = 0.01, optimizer=None,
-                    save_traj: bool = False, record_interval: int = 5):
+                    save_traj: bool = False, record_interval: int = 5, linesearch_driver=None):
         """Relax B independent slabs at once on the device — the batched counterpart of
         ``optimize_slab(slab, optimizer=..., relax_steps=..., save_traj=..., record_interval=...)`` (reference
         ``mcmc/dynamics.py:83-170``).  ``optimizer``: "BFGS" (ASE BFGS, the reference's SrTiO3 setting,
@@ -626,7 +628,12 @@ class EnsembleNFFSurface(_Base):
         the same +-1000 guard (a saturated evaluation counts as out of bounds), plus the results dict of the final
         evaluation.  ``save_traj=True``: ``traj`` is the reference's dict ``{"atoms", "energies", "forces"}`` recorded like
         its TrajectoryObserver attached with ``interval=record_interval`` (after 0, k, 2k, ... optimizer steps; forces with
-        FixAtoms applied); otherwise None."""
+        FixAtoms applied); otherwise None.
+        ``linesearch_driver`` (default: ``set(linesearch_driver=...)``, else "ase"): who runs ``optimizer="BFGSLineSearch"`` --
+        "ase": ASE's class, one host optimizer per chain (an error where ASE is not importable); "device": the lock-step device
+        optimizer (``backend.relax_bfgs_linesearch``), whose results dicts also carry ``n_eval`` and ``stop_reason``."""
+        ls_driver = backend.linesearch_driver_check(self.parameters.get("linesearch_driver", "ase") if linesearch_driver is None
+                                                    else linesearch_driver)
         eng = self._get_engine()
         packs = [structures.as_arrays(a) for a in atoms_list]
         eng.upload(packs)
@@ -642,7 +649,8 @@ class EnsembleNFFSurface(_Base):
             optimizer = self.parameters.get("optimizer", "FIRE")
         host_traj = None
         opt_cls = optimizer if callable(optimizer) else None
-        if opt_cls is None and "BFGSLineSearch" in str(optimizer):
+        device_ls = opt_cls is None and "BFGSLineSearch" in str(optimizer) and ls_driver == "device"
+        if opt_cls is None and "BFGSLineSearch" in str(optimizer) and not device_ls:
             try:   # the reference's import (mcmc/dynamics.py:7): only where ASE is installed
                 from ase.optimize import BFGSLineSearch as opt_cls
             except Exception as exc:
@@ -687,6 +695,9 @@ class EnsembleNFFSurface(_Base):
             host_traj = info["traj"]
             eng.set_positions(info["positions"])
             eng.run()
+        elif device_ls:
+            info = eng.relax_bfgs_linesearch(fixed=fixed, max_steps=relax_steps, fmax=fmax,
+                                             record_interval=int(record_interval) if save_traj else 0)
         else:
             info = eng.relax(optimizer, fixed=fixed, max_steps=relax_steps, fmax=fmax,
                              record_interval=int(record_interval) if save_traj else 0)
@@ -719,6 +730,8 @@ class EnsembleNFFSurface(_Base):
                 energy = self.ENERGY_THRESHOLD
             r["n_steps"] = int(info["n_steps"][b])
             r["converged"] = bool(info["converged"][b])
+            if device_ls:
+                r["n_eval"], r["stop_reason"] = int(info["n_eval"][b]), int(info["stop_reason"][b])
             if opt_cls is not None:   # ASE's criterion on the final forces (constraints applied)
                 ff = np.array(r["forces"], dtype=np.float64, copy=True)
                 if fixed_indices is not None and fixed_indices[b] is not None and len(fixed_indices[b]):
@@ -942,6 +955,7 @@ class _AnalyticSurfCalc(_Base):
         self.run_dir = None
         self.relax_steps = 100
         self.cg_driver = "auto"      # driver of the device CG minimiser: "auto" | "lockstep" | "resident" (backend.relax_cg_f64)
+        self.linesearch_driver = "ase"   # who runs optimizer="BFGSLineSearch": "ase" | "device" (backend.relax_bfgs_linesearch)
         self.logger = logger or logging.getLogger(__name__)
         self._engine = None
 
@@ -963,6 +977,8 @@ class _AnalyticSurfCalc(_Base):
     def set(self, **kwargs) -> dict:
         if "cg_driver" in kwargs:
             backend.cg_driver_code(kwargs["cg_driver"])   # (ValueError before anything is stored)
+        if "linesearch_driver" in kwargs:
+            backend.linesearch_driver_check(kwargs["linesearch_driver"])
         changed = _Base.set(self, **kwargs)
         if "run_dir" in self.parameters:
             self.run_dir = self.parameters["run_dir"]
@@ -970,6 +986,8 @@ class _AnalyticSurfCalc(_Base):
             self.relax_steps = self.parameters["relax_steps"]
         if "cg_driver" in self.parameters:
             self.cg_driver = self.parameters["cg_driver"]
+        if "linesearch_driver" in self.parameters:
+            self.linesearch_driver = self.parameters["linesearch_driver"]
         return changed
 
     def _cg_driver_of(self, kwargs) -> str:
@@ -1068,11 +1086,17 @@ class _AnalyticSurfCalc(_Base):
         from ``calc.relax_steps``).  Returns per slab ``(relaxed, None, energy, energy_oob, results)`` like
         ``EnsembleNFFSurface.relax_batch``; results carry ``per_atom_energies`` of the relaxed slab, with ``want_stress`` also its
         ``stress``.  ``cg_driver="auto" | "lockstep" | "resident"`` (default: the calculator's ``cg_driver`` setting) selects the
-        driver of the CG minimiser (``backend.relax_cg_f64``): same results bit for bit."""
+        driver of the CG minimiser (``backend.relax_cg_f64``): same results bit for bit.  ``optimizer="BFGSLineSearch"`` runs on the
+        device (``backend.relax_bfgs_linesearch``; results carry ``n_steps`` / ``n_eval`` / ``stop_reason``, and with ``save_traj`` /
+        ``record_interval`` the tuple's trajectory) where ``linesearch_driver="device"`` says so -- a keyword here, else the
+        calculator's ``set(linesearch_driver=...)``; with the default "ase" the name is refused as before."""
+        ls_driver = kwargs.get("linesearch_driver")
+        ls_driver = backend.linesearch_driver_check(getattr(self, "linesearch_driver", "ase") if ls_driver is None else ls_driver)
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "LAMMPS")
         steps = int(self.relax_steps if relax_steps is None else relax_steps)
         driver = self._cg_driver_of(kwargs)
+        trajs = None
         packs = [self._pack(a) for a in atoms_list]
         fixed = None
         if fixed_indices is not None:
@@ -1088,6 +1112,17 @@ class _AnalyticSurfCalc(_Base):
                                                           ftol=kwargs.get("ftol", 1e-5), driver=driver)
             extra = [{"iterations": int(it[b]), "evaluations": int(ev[b]),
                       "stop": backend.CG_STOP_REASONS.get(int(why[b]), str(int(why[b])))} for b in range(len(packs))]
+        elif "BFGSLineSearch" in str(optimizer) and ls_driver == "device":
+            eng.upload(packs)
+            rec = int(kwargs.get("record_interval", 5)) if kwargs.get("save_traj") else 0
+            info = eng.relax_bfgs_linesearch(fixed=fixed, max_steps=steps, fmax=fmax, max_eval=kwargs.get("max_eval"),
+                                             want=backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM, record_interval=rec)
+            (e, ea, f), pos = eng.results_f64(), info["positions"]   # (the driver ends with a complete evaluation of the final positions)
+            extra = [{"n_steps": int(info["n_steps"][b]), "n_eval": int(info["n_eval"][b]), "stop_reason": int(info["stop_reason"][b]),
+                      "converged": bool(info["converged"][b])} for b in range(len(packs))]
+            if rec:
+                cs = np.concatenate([[0], np.cumsum([len(p[0]) for p in packs])])
+                trajs = [_traj_of_chain(info["traj"], b, int(cs[b]), int(cs[b + 1]), a) for b, a in enumerate(atoms_list)]
         else:
             e, ea, f, pos, nst, conv = eng.relax_f64(packs, fixed=fixed, max_steps=steps, fmax=fmax, optimizer=optimizer)
             extra = [{"n_steps": int(nst[b]), "converged": bool(conv[b])} for b in range(len(packs))]
@@ -1106,7 +1141,7 @@ class _AnalyticSurfCalc(_Base):
             r = {"energy": energy, "per_atom_energies": ea[o:o + n].copy(), "forces": f[o:o + n].copy(), **extra[b]}
             if stress is not None:
                 r["stress"] = stress[b].copy()
-            out.append((relaxed, None, self.ENERGY_THRESHOLD if oob else energy, oob, r))
+            out.append((relaxed, None if trajs is None else trajs[b], self.ENERGY_THRESHOLD if oob else energy, oob, r))
             o += n
         return out
 

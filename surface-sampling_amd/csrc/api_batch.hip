@@ -275,6 +275,35 @@ int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_use
     return VSSR_OK;
 }
 
+int vssr_batch_relax_bfgs_linesearch(vssr_handle *h, const vssr_bfgsls_params *p, const uint8_t *fixed, uint32_t want, double *pos_out,
+                                     int32_t *n_steps, int32_t *n_eval, int32_t *stop_reason) {
+    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
+    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_bfgs_linesearch before vssr_batch_upload");
+    if (!p) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: null");
+    if (p->max_steps < 0) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: max_steps %d < 0", (int)p->max_steps);
+    if (p->max_eval < 1) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: max_eval %d < 1", (int)p->max_eval);
+    if (!(p->fmax > 0) || !(p->alpha > 0) || !(p->maxstep > 0))
+        return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: fmax %g, alpha %g and maxstep %g must be positive", p->fmax, p->alpha, p->maxstep);
+    if (!(p->c1 > 0 && p->c1 < 1)) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: c1 %g outside (0, 1)", p->c1);
+    if (!(p->c2 > 0 && p->c2 < 1)) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: c2 %g outside (0, 1)", p->c2);
+    if (!(p->stpmax >= 1)) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: stpmax %g < 1", p->stpmax);
+    VSSR_HIP(h, hipSetDevice(h->device));
+    h->relax_regrows = 0;
+    h->last_want = want | VSSR_WANT_FORCES;
+    if (int rc = relax_bfgsls(h, p, fixed, want)) return rc;
+    h->graph_partial = false;        // (the driver ends with a batch-wide evaluation of the final positions)
+    if (int rc = sync_and_check(h)) return rc;   // ... which may itself have overflowed the neighbor capacity: grow and repeat it
+    if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
+    std::vector<int> rep((size_t)3 * h->n_cfg);
+    VSSR_HIP(h, hipMemcpy(rep.data(), h->d_relax_steps.p, sizeof(int) * rep.size(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < h->n_cfg; ++b) {
+        if (n_steps) n_steps[b] = rep[3 * b];
+        if (n_eval) n_eval[b] = rep[3 * b + 1];
+        if (stop_reason) stop_reason[b] = rep[3 * b + 2];
+    }
+    return VSSR_OK;
+}
+
 int vssr_batch_relax_bfgs(vssr_handle *h, const vssr_bfgs_params *params, const uint8_t *fixed, uint32_t want,
                           double *pos_out, int32_t *n_steps, uint8_t *converged) {
     if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;

@@ -552,6 +552,8 @@ int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_ch
 int relax_regrow(vssr_handle *h, int cap, long long &it, int window);   // after an overflow seen at a poll: grow, give the poll window back
 // lock-step LAMMPS-style CG for the fp64 potentials (relax_cg.hip); results in d_relax_steps [B][3] = {iterations, evaluations, stop reason}
 int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want);
+// lock-step BFGSLineSearch on every kind that relaxes (relax_bfgsls.hip, bfgsls_dev.h); results in d_relax_steps [B][3] = {steps, evaluations, stop reason}
+int relax_bfgsls(vssr_handle *h, const vssr_bfgsls_params *bp, const uint8_t *fixed_host, uint32_t want);
 // chain_min.hip: the same minimisation with one workgroup per chain (Tersoff / SW / EAM / pair handles, chains of <= 256 atoms).
 // chain_min_supported: this relaxation takes it (the kernel applies AND VSSR_CG_FUSED / the handle's cg_driver / the automatic rule say so)
 bool chain_min_supported(const vssr_handle *h);
