@@ -417,7 +417,8 @@ int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, co
  * shift != 0 (pair_modify shift yes) subtracts E(rc) from the four non-Coulomb styles; coul/dsf ignores it.  Every atom whose type
  * has a coul/dsf term gets the self energy -(erfc(alpha rc)/(2 rc) + alpha/sqrt(pi)) qqrd2e q_i^2 in its pe/atom; pair energies
  * are split half / half. */
-enum { VSSR_PAIR_NONE = 0, VSSR_PAIR_LJ_CUT = 1, VSSR_PAIR_MORSE = 2, VSSR_PAIR_BUCK = 3, VSSR_PAIR_BORN = 4, VSSR_PAIR_COUL_DSF = 5 };
+enum { VSSR_PAIR_NONE = 0, VSSR_PAIR_LJ_CUT = 1, VSSR_PAIR_MORSE = 2, VSSR_PAIR_BUCK = 3, VSSR_PAIR_BORN = 4, VSSR_PAIR_COUL_DSF = 5,
+       VSSR_PAIR_COUL_LONG = 6 /* qqrd2e q_a q_b erfc(g r)/r, the real-space part of an Ewald sum: vssr_pair_create_kspace only */ };
 typedef struct vssr_pair_term {
     int32_t type_a, type_b, style;
     double c[5], rc;
@@ -432,6 +433,32 @@ typedef struct vssr_pair_term {
  * than 100 images on either side (the neighbor search's limit); nothing is truncated. */
 int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
                      vssr_handle **out);
+/* A pair handle whose Coulomb term is an Ewald sum (LAMMPS pair_style coul/long, buck/coul/long, born/coul/long, lj/cut/coul/long
+ * with kspace_style ewald): the terms of vssr_pair_create plus VSSR_PAIR_COUL_LONG terms (c is ignored: the damping is ks->g_ewald;
+ * rc is the real-space cutoff) and the k-space parameters.  For a chain with cell volume V, charges q_i and total charge Q:
+ *   E = E_real + E_k + E_self + E_bg
+ *   E_real = sum over pairs with r < rc of qqrd2e q_a q_b erfc(g r) / r                        (no shift, as LAMMPS coul/long)
+ *   E_k    = sum over k != 0, |k| <= k_cut of u(k) |S(k)|^2,  u(k) = qqrd2e (2 pi / V) exp(-k^2 / 4 g^2) / k^2,
+ *            S(k) = sum_j q_j exp(i k.r_j),  k = h b1 + k b2 + l b3 over the reciprocal vectors of the chain's own cell
+ *   E_self = -qqrd2e g / sqrt(pi) sum q_i^2,   E_bg = -qqrd2e pi Q^2 / (2 g^2 V)  (neutralising background: charged cells are served)
+ * pe/atom as LAMMPS ewald: q_i sum_k u(k) Re(exp(-i k.r_i) S(k)) - qqrd2e g q_i^2 / sqrt(pi) - qqrd2e pi q_i Q / (2 g^2 V) on top of
+ * the half / half pair split.  The k set is a function of (g_ewald, k_cut) and the chain's cell only (a sphere in reciprocal space,
+ * any cell shape) -- not LAMMPS' accuracy estimator, which depends on the atom count and the charges; energies agree with LAMMPS to
+ * the accuracy asked for, not digit for digit.  vssr_batch_stress adds the reciprocal and background virials.
+ * Refused with VSSR_E_BADARG before any device is touched, besides what vssr_pair_create refuses: ks NULL, charge NULL, g_ewald or
+ * k_cut not finite and positive, VSSR_PAIR_COUL_LONG terms that do not cover every type pair or that differ in rc, and a
+ * VSSR_PAIR_COUL_LONG term next to a VSSR_PAIR_COUL_DSF term.  vssr_pair_create itself refuses a VSSR_PAIR_COUL_LONG term.
+ * vssr_batch_upload refuses a chain with a non-periodic axis (VSSR_E_BADARG: a 3-D Ewald sum needs three periodic axes; no slab
+ * correction) and, with VSSR_E_CAPACITY, a chain whose k sphere needs a per-axis index floor(k_cut |a_i| / 2 pi) above 63 or a half
+ * box (m1 + 1)(2 m2 + 1)(2 m3 + 1) of more than 65 536 cells; nothing is ever truncated.
+ * Relaxations: FIRE, BFGS, BFGSLineSearch and the lock-step CG serve these handles; the chain-resident CG minimiser does not
+ * (VSSR_CG_DRIVER_RESIDENT runs in lock step, same results, as for chains of more than 256 atoms).  Entry points that hand out
+ * per-slot gradients (the gradient buffers of vssr_debug_read) carry the real-space part only. */
+typedef struct vssr_kspace {
+    double g_ewald, k_cut;   /* 1 / A */
+} vssr_kspace;
+int vssr_pair_create_kspace(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                            const vssr_kspace *ks, vssr_handle **out);
 /* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
 int vssr_pair_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                          const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,

@@ -36,7 +36,7 @@ EXPORTS = (
     "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
-    "vssr_pair_create", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
+    "vssr_pair_create", "vssr_pair_create_kspace", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
     "vssr_batch_relax_bfgs_linesearch",
 )
 
@@ -69,6 +69,11 @@ class FireParams(C.Structure):
 
 class EamGrid(C.Structure):
     _fields_ = [("nrho", C.c_int32), ("nr", C.c_int32), ("drho", C.c_double), ("dr", C.c_double), ("cutoff", C.c_double)]
+
+
+class KSpace(C.Structure):
+    """vssr_kspace: Ewald damping and reciprocal cutoff (1 / A)."""
+    _fields_ = [("g_ewald", C.c_double), ("k_cut", C.c_double)]
 
 
 class PairTerm(C.Structure):
@@ -282,6 +287,8 @@ def load_library():
     L.vssr_sw_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_pair_create.restype = C.c_int
     L.vssr_pair_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(vp)]
+    L.vssr_pair_create_kspace.restype = C.c_int
+    L.vssr_pair_create_kspace.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(KSpace), C.POINTER(vp)]
     L.vssr_pair_eval_batch.restype = C.c_int
     L.vssr_pair_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_batch_relax_fire.restype = C.c_int
@@ -834,18 +841,20 @@ class SWEngine(_AnalyticEngine):
 
 
 class PairEngine(_AnalyticEngine):
-    """Pair potentials with damped-shifted-force Coulomb (LAMMPS ``pair_style lj/cut``, ``morse``, ``buck``, ``born``, ``coul/dsf``
-    and ``hybrid`` / ``hybrid/overlay`` of them) evaluator, fp64 on device.  Relaxes with FIRE / BFGS and the lock-step CG driver."""
+    """Pair potentials with damped-shifted-force or Ewald Coulomb (LAMMPS ``pair_style lj/cut``, ``morse``, ``buck``, ``born``,
+    ``coul/dsf``, ``coul/long`` + ``kspace_style ewald``, and ``hybrid`` / ``hybrid/overlay`` of them) evaluator, fp64 on device.
+    Relaxes with FIRE / BFGS and the lock-step CG driver (a handle with k-space: always lock step)."""
 
-    def __init__(self, terms, charges=None, n_types=None, device=0):
-        """``terms``: a ``pair.PairModel`` (then ``charges`` / ``n_types`` come from it), or a list of ``(type_a, type_b, style, c,
-        rc, shift)`` with 0-based types, a style code or name of ``pair.STYLES`` and up to five coefficients in LAMMPS order;
-        ``charges``: per-type charges [n_types] (needed by coul/dsf)."""
+    def __init__(self, terms, charges=None, n_types=None, device=0, kspace=None):
+        """``terms``: a ``pair.PairModel`` (then ``charges`` / ``n_types`` / ``kspace`` come from it), or a list of ``(type_a, type_b,
+        style, c, rc, shift)`` with 0-based types, a style code or name of ``pair.STYLES`` and up to five coefficients in LAMMPS
+        order; ``charges``: per-type charges [n_types] (needed by coul/dsf and coul/long); ``kspace``: ``(g_ewald, k_cut)`` or a
+        ``pair.KSpace`` -- the Ewald sum behind the coul/long terms (vssr_pair_create_kspace)."""
         super().__init__()
         from . import pair as pair_io
 
         if isinstance(terms, pair_io.PairModel):
-            terms, charges, n_types = terms.terms, terms.charges, terms.n_types
+            terms, charges, n_types, kspace = terms.terms, terms.charges, terms.n_types, terms.kspace
         terms = list(terms)
         if n_types is None:
             raise ValueError("n_types is required with a plain term list")
@@ -862,10 +871,18 @@ class PairEngine(_AnalyticEngine):
             if q.size != int(n_types):
                 raise ValueError("charges must hold one value per type")
         self.n_types = int(n_types)
-        rc = self._lib.vssr_pair_create(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double), C.byref(self._h))
+        self.kspace = kspace
+        if kspace is None:
+            name = "vssr_pair_create"
+            rc = self._lib.vssr_pair_create(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double), C.byref(self._h))
+        else:
+            name = "vssr_pair_create_kspace"
+            g, kc = (kspace.g_ewald, kspace.k_cut) if hasattr(kspace, "g_ewald") else kspace
+            rc = self._lib.vssr_pair_create_kspace(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double),
+                                                   C.byref(KSpace(float(g), float(kc))), C.byref(self._h))
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
-            raise BackendError(f"vssr_pair_create failed ({rc}): {msg.decode() if msg else '?'}")
+            raise BackendError(f"{name} failed ({rc}): {msg.decode() if msg else '?'}")
 
 
 class EAMEngine(_AnalyticEngine):

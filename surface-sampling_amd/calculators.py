@@ -1299,18 +1299,33 @@ class PairSurfCalc(_AnalyticSurfCalc):
     ``pair_coeff``, ``pair_modify shift | mix``, ``set type N charge q``; ``pair.parse``).  ``per_atom_energies`` follow LAMMPS
     ``pe/atom`` (pair energies half / half, the coul/dsf self term on its atom).  Relaxations use the lock-step CG / FIRE / BFGS
     drivers; ``set(cg_driver="resident")`` selects the chain-resident CG minimiser instead (same results bit for bit).
-    ``all_periodic=False`` keeps the atoms' own ``pbc``."""
+    ``all_periodic=False`` keeps the atoms' own ``pbc``.
+
+    ``coul/long``, ``buck/coul/long``, ``born/coul/long`` and ``lj/cut/coul/long`` with ``kspace_style ewald A`` run an Ewald sum on
+    the device (periodic in three directions, charged cells with the neutralising background): g = sqrt(-ln A) / rc and
+    k_cut = 2 g sqrt(-ln A) unless ``kspace_modify gewald`` / the ``g_ewald=`` and ``k_cut=`` keywords say otherwise.  Energies agree
+    with LAMMPS to the accuracy asked for, not digit for digit (LAMMPS picks its k vectors from the atom count and the charges);
+    ``cg_driver="resident"`` runs in lock step for such a model."""
 
     name = "pair_mi355x"
 
-    def __init__(self, commands=None, text=None, species=None, device="cuda", all_periodic=False, logger=None, **kwargs):
-        """commands: list of LAMMPS command lines, or ``text``: the same as one string; species: symbols in LAMMPS type order."""
+    def __init__(self, commands=None, text=None, species=None, device="cuda", all_periodic=False, logger=None, g_ewald=None, k_cut=None,
+                 **kwargs):
+        """commands: list of LAMMPS command lines, or ``text``: the same as one string; species: symbols in LAMMPS type order;
+        g_ewald / k_cut (1 / A): override what ``kspace_style ewald`` / ``kspace_modify gewald`` give."""
         if (commands is None) == (text is None):
             raise ValueError("give the pair commands either as commands=[...] or as text=...")
         if not species:
             raise ValueError("species (LAMMPS type order) are required")
         self.species = list(species)
         self.pair_model = pair_io.parse(text if commands is None else list(commands), len(self.species))
+        if g_ewald is not None or k_cut is not None:
+            ks = self.pair_model.kspace
+            if ks is None:
+                raise ValueError("g_ewald / k_cut need a */coul/long pair_style with kspace_style ewald")
+            rc = next(t.rc for t in self.pair_model.terms if t.style == pair_io.STYLES["coul/long"])
+            self.pair_model = self.pair_model._replace(kspace=pair_io.ewald_defaults(
+                ks.accuracy, rc, g_ewald=ks.g_ewald if g_ewald is None else g_ewald, k_cut=k_cut))
         self._init_common(device, all_periodic, logger)
         super().__init__(**kwargs)
 
@@ -1675,6 +1690,9 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             model = pair_io.parse(text, len(species))
             b = re.search(r"^\s*boundary\s+([^#\n]+)", text, re.M)
             boundary = self._boundary_pbc(b.group(1).split() if b else None)
+            if model.kspace is not None and boundary is not None and not all(boundary):
+                raise ValueError(f"boundary {b.group(1).strip()!r}: kspace_style ewald needs 'boundary p p p' (the Ewald sum is periodic in "
+                                 "three directions; the slab correction is not provided)")
         except ValueError as e:
             raise backend.BackendError(f"{path}: the pair commands cannot be read: {e}") from None
         self.pair_model = model

@@ -1,7 +1,7 @@
 // api_batch.hip — the resident batch: upload, run, download, the relaxation entry points and introspection.
 #include <cmath>
 
-#include "vssr_internal.h"
+#include "ewald_dev.h"
 
 namespace vssr {
 
@@ -72,6 +72,29 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
             }
         const long long imgs = (2LL * nimg[3 * b] + 1) * (2 * nimg[3 * b + 1] + 1) * (2 * nimg[3 * b + 2] + 1);
         if (b == 0 || imgs > h->max_images) h->max_images = (int)(imgs > 1000000 ? 1000000 : imgs);
+    }
+    if (h->ew_on) {   // the k sphere of every chain from its own cell (ewald_dev.h): capacity, and the stride of the S(k) array
+        long long stride = 0;
+        for (int b = 0; b < n_cfg; ++b) {
+            if (!(pbc[3 * b] && pbc[3 * b + 1] && pbc[3 * b + 2]))
+                return set_err(h, VSSR_E_BADARG, "configuration %d: an Ewald sum needs three periodic axes (pbc %d %d %d; no slab correction)", b,
+                               (int)pbc[3 * b], (int)pbc[3 * b + 1], (int)pbc[3 * b + 2]);
+            EwaldGeom G;
+            ewald_geom(cell + 9 * b, h->ew_kcut, 1e-9, G);
+            for (int k = 0; k < 3; ++k)
+                if (G.m[k] > EW_MAX_INDEX)
+                    return set_err(h, VSSR_E_CAPACITY, "configuration %d: k_cut %g 1/A needs the reciprocal index %d along axis %d, the k-space "
+                                   "kernels hold %d at the most (nothing is truncated: lower k_cut with a larger real-space cutoff)",
+                                   b, h->ew_kcut, G.m[k], k, EW_MAX_INDEX);
+            if (G.cells > EW_MAX_CELLS)
+                return set_err(h, VSSR_E_CAPACITY, "configuration %d: k_cut %g 1/A needs a box of %lld reciprocal vectors, the k-space kernels hold "
+                               "%d at the most (nothing is truncated: lower k_cut with a larger real-space cutoff)", b, h->ew_kcut, G.cells,
+                               EW_MAX_CELLS);
+            stride = std::max(stride, G.cells);
+        }
+        h->ew_stride = (int)stride;
+        if (h->d_ew_S.ensure(sizeof(double) * 2 * (size_t)n_cfg * (size_t)(stride + 1)))
+            return set_err(h, VSSR_E_NOMEM, "k-space structure factors: out of device memory");
     }
     if (h->d_pos.ensure(sizeof(double) * 3 * N) || h->d_Z.ensure(sizeof(int) * N) ||
         h->d_atom_cfg.ensure(sizeof(int) * N) || h->d_cfg_start.ensure(sizeof(int) * (n_cfg + 1)) ||

@@ -261,11 +261,11 @@ int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_s
 }
 
 // ---- pair potentials --------------------------------------------------------------------------------------------------------
-static const char *const kPairStyle[6] = {"none", "lj/cut", "morse", "buck", "born", "coul/dsf"};
+static const char *const kPairStyle[7] = {"none", "lj/cut", "morse", "buck", "born", "coul/dsf", "coul/long"};
 
-// Checks one caller term and derives the kernel's entry (pair_dev.h PairTerm); qq = q_a q_b.
-static int pair_derive(const vssr_pair_term &t, int idx, double qq, PairTerm &d) {
-    static const int n_coef[6] = {0, 2, 3, 3, 5, 1};
+// Checks one caller term and derives the kernel's entry (pair_dev.h PairTerm); qq = q_a q_b, g: the Ewald damping of a coul/long term.
+static int pair_derive(const vssr_pair_term &t, int idx, double qq, double g, PairTerm &d) {
+    static const int n_coef[7] = {0, 2, 3, 3, 5, 1, 0};
     const char *nm = kPairStyle[t.style];
     for (int k = 0; k < n_coef[t.style]; ++k)
         if (!std::isfinite(t.c[k])) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (%s %d %d): coefficient %d is not finite", idx, nm, t.type_a, t.type_b, k);
@@ -302,6 +302,10 @@ static int pair_derive(const vssr_pair_term &t, int idx, double qq, PairTerm &d)
         }
         break;
     }
+    case VSSR_PAIR_COUL_LONG:
+        d.c[0] = g;
+        d.c[3] = PAIR_QQRD2E * qq;
+        break;
     default: {   // coul/dsf
         const double a = t.c[0];
         if (!(a >= 0)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (coul/dsf %d %d): bad alpha %g (must be >= 0)", idx, t.type_a, t.type_b, a);
@@ -313,17 +317,23 @@ static int pair_derive(const vssr_pair_term &t, int idx, double qq, PairTerm &d)
         break;
     }
     }
-    if (t.style != VSSR_PAIR_COUL_DSF && t.shift) {
+    if (t.style != VSSR_PAIR_COUL_DSF && t.style != VSSR_PAIR_COUL_LONG && t.shift) {
         if (!std::isfinite(e_rc)) return set_err(nullptr, VSSR_E_BADARG, "pair term %d (%s %d %d): E(rc) is not finite", idx, nm, t.type_a, t.type_b);
         d.eshift = e_rc;
     }
     return VSSR_OK;
 }
 
-int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
-                     vssr_handle **out) {
+// vssr_pair_create (ks == nullptr) and vssr_pair_create_kspace
+static int pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                       const vssr_kspace *ks, vssr_handle **out) {
     if (!terms || !out || n_terms < 1) return set_err(nullptr, VSSR_E_BADARG, "bad pair arguments");
     *out = nullptr;
+    if (ks) {
+        if (!charge) return set_err(nullptr, VSSR_E_BADARG, "pair: an Ewald sum needs per-type charges (charge is NULL)");
+        if (!std::isfinite(ks->g_ewald) || !(ks->g_ewald > 0) || !std::isfinite(ks->k_cut) || !(ks->k_cut > 0))
+            return set_err(nullptr, VSSR_E_BADARG, "pair: bad k-space parameters g_ewald %g, k_cut %g (both must be finite and > 0)", ks->g_ewald, ks->k_cut);
+    }
     if (n_types < 1 || n_types > PAIR_MAX_TYPES) return set_err(nullptr, VSSR_E_BADARG, "pair: %d types (1 .. 8 are supported)", n_types);
     if (charge)
         for (int t = 0; t < n_types; ++t)
@@ -334,15 +344,30 @@ int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vss
     int count[PAIR_MAX_TYPES][PAIR_MAX_TYPES] = {};
     double cutmax = 0.0, dsf_alpha = 0.0, dsf_rc = 0.0;
     bool dsf = false, dsf_type[PAIR_MAX_TYPES] = {};
+    bool long_pair[PAIR_MAX_TYPES][PAIR_MAX_TYPES] = {};
+    int n_long = 0;
+    double long_rc = 0.0;
     for (int n = 0; n < n_terms; ++n) {
         const vssr_pair_term &t = terms[n];
         if (t.type_a < 0 || t.type_a >= n_types || t.type_b < 0 || t.type_b >= n_types)
             return set_err(nullptr, VSSR_E_BADARG, "pair term %d: types %d %d outside [0,%d)", n, t.type_a, t.type_b, n_types);
-        if (t.style < VSSR_PAIR_LJ_CUT || t.style > VSSR_PAIR_COUL_DSF) return set_err(nullptr, VSSR_E_BADARG, "pair term %d: unknown style %d", n, t.style);
+        if (t.style < VSSR_PAIR_LJ_CUT || t.style > VSSR_PAIR_COUL_LONG) return set_err(nullptr, VSSR_E_BADARG, "pair term %d: unknown style %d", n, t.style);
+        if (t.style == VSSR_PAIR_COUL_LONG && !ks)
+            return set_err(nullptr, VSSR_E_BADARG, "pair term %d: coul/long is the real-space part of an Ewald sum: create the handle with "
+                           "vssr_pair_create_kspace", n);
         if (t.style == VSSR_PAIR_COUL_DSF && !charge)
             return set_err(nullptr, VSSR_E_BADARG, "pair term %d: coul/dsf needs per-type charges (charge is NULL)", n);
         PairTerm d;
-        if (int rc = pair_derive(t, n, charge ? charge[t.type_a] * charge[t.type_b] : 0.0, d)) return rc;
+        if (int rc = pair_derive(t, n, charge ? charge[t.type_a] * charge[t.type_b] : 0.0, ks ? ks->g_ewald : 0.0, d)) return rc;
+        if (t.style == VSSR_PAIR_COUL_LONG) {
+            if (n_long && t.rc != long_rc)
+                return set_err(nullptr, VSSR_E_BADARG, "pair term %d: coul/long terms differ in rc (%g vs %g)", n, t.rc, long_rc);
+            if (long_pair[t.type_a][t.type_b])
+                return set_err(nullptr, VSSR_E_BADARG, "pair term %d: a second coul/long term on the type pair %d %d", n, t.type_a, t.type_b);
+            long_pair[t.type_a][t.type_b] = long_pair[t.type_b][t.type_a] = true;
+            long_rc = t.rc;
+            ++n_long;
+        }
         if (t.style == VSSR_PAIR_COUL_DSF) {
             if (dsf && (t.c[0] != dsf_alpha || t.rc != dsf_rc))
                 return set_err(nullptr, VSSR_E_BADARG, "pair term %d: coul/dsf terms differ in alpha or rc (%g %g vs %g %g)", n, t.c[0], t.rc, dsf_alpha, dsf_rc);
@@ -362,12 +387,37 @@ int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vss
         for (int t = 0; t < n_types; ++t)
             if (dsf_type[t])
                 T.self_e[t] = -(erfc(dsf_alpha * dsf_rc) / (2.0 * dsf_rc) + 0.5 * PAIR_2_SQRTPI * dsf_alpha) * PAIR_QQRD2E * charge[t] * charge[t];
+    if (ks) {
+        if (dsf) return set_err(nullptr, VSSR_E_BADARG, "pair: coul/long and coul/dsf terms in one handle (one Coulomb sum at a time)");
+        for (int a = 0; a < n_types; ++a)
+            for (int b = a; b < n_types; ++b)
+                if (!long_pair[a][b])
+                    return set_err(nullptr, VSSR_E_BADARG, "pair: the coul/long terms do not cover the type pair %d %d (the reciprocal sum runs over every "
+                                   "pair of charges, so must the real-space part)", a, b);
+    }
     return create_handle(Kind::PAIR, device, out, [&](vssr_handle *h) {
         h->n_types = n_types;
         h->n_embed = n_types;
         h->pot_cutoff = cutmax;
+        if (ks) {
+            h->ew_on = true;
+            h->ew_g = ks->g_ewald;
+            h->ew_kcut = ks->k_cut;
+            for (int t = 0; t < n_types; ++t) h->ew_q[t] = charge[t];
+        }
         return upload_params(h, tab.data(), sizeof(PairTable), "pair table", "pair table upload failed");
     });
+}
+
+int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                     vssr_handle **out) {
+    return pair_create(device, n_types, n_terms, terms, charge, nullptr, out);
+}
+
+int vssr_pair_create_kspace(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                            const vssr_kspace *ks, vssr_handle **out) {
+    if (!ks) return set_err(nullptr, VSSR_E_BADARG, "vssr_pair_create_kspace: null k-space parameters");
+    return pair_create(device, n_types, n_terms, terms, charge, ks, out);
 }
 
 }  // extern "C"

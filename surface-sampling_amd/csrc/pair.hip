@@ -5,6 +5,8 @@
 //   lj/cut    4 eps [(sig/r)^12 - (sig/r)^6]                      morse  D0 [exp(-2 alpha (r - r0)) - 2 exp(-alpha (r - r0))]
 //   buck      A exp(-r/rho) - C/r^6                                born   A exp((sig - r)/rho) - C/r^6 + D/r^8
 //   coul/dsf  qqrd2e q_a q_b [erfc(alpha r)/r - erfc(alpha rc)/rc + B (r - rc)],  B = erfc(alpha rc)/rc^2 + 2 alpha/sqrt(pi) exp(-alpha^2 rc^2)/rc
+//   coul/long qqrd2e q_a q_b erfc(g r)/r, no shift: the real-space part of the Ewald sum of a handle with k-space (ewald.hip runs
+//             behind the site kernel and adds the reciprocal, self and background terms to the same per-atom results)
 // (Fennell & Gezelter 2006: energy and force both vanish at rc), minus E(rc) for the first four under pair_modify shift yes.  pe/atom
 // splits every pair half / half; the coul/dsf self term -(erfc(alpha rc)/(2 rc) + alpha/sqrt(pi)) qqrd2e q_i^2 goes to atom i.
 //
@@ -44,7 +46,8 @@ int pair_stress(vssr_handle *h) {
     if (h->d_gbar.ensure(sizeof(double) * 3 * (size_t)h->slot_cap)) return set_err(h, VSSR_E_NOMEM, "pair gradients: out of device memory");
     launch_site<true>(h, pot_view(h), h->d_gbar.as<double>());
     VSSR_HIP(h, hipGetLastError());
-    return slot_stress(h, h->d_gbar.as<double>());
+    if (int rc = slot_stress(h, h->d_gbar.as<double>())) return rc;
+    return h->ew_on ? ewald_stress(h) : VSSR_OK;
 }
 
 int pair_run(vssr_handle *h, uint32_t want) {
@@ -53,6 +56,7 @@ int pair_run(vssr_handle *h, uint32_t want) {
     if (rc) return rc;
     const PotView V = pot_view(h);
     launch_site<false>(h, V, nullptr);
+    if (h->ew_on) ewald_run(h, V);
     return analytic_end(h, V);
 }
 

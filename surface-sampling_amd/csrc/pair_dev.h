@@ -18,6 +18,7 @@ constexpr double PAIR_2_SQRTPI = 1.12837916709551257390;   // 2 / sqrt(pi)
 //   buck      A, 1 / rho, C
 //   born      A, 1 / rho, sig, C, D
 //   coul/dsf  alpha, erfc(alpha rc) / rc, B = erfc(alpha rc) / rc^2 + 2 alpha / sqrt(pi) exp(-alpha^2 rc^2) / rc, qqrd2e q_a q_b
+//   coul/long g, -, -, qqrd2e q_a q_b   (qqrd2e q_a q_b erfc(g r) / r: the real-space part of the Ewald sum of ewald.hip)
 // eshift: E(rc) of the four non-Coulomb styles under pair_modify shift yes, else 0.
 struct PairTerm {
     double c[5], rc, eshift;
@@ -57,6 +58,12 @@ __device__ __forceinline__ void pair_term(const PairTerm &t, double r, double &e
         const double x = t.c[0] * exp((t.c[2] - r) * t.c[1]), i2 = ir * ir, i6 = i2 * i2 * i2, i8 = i6 * i2;
         e = x - t.c[3] * i6 + t.c[4] * i8;
         de = -x * t.c[1] + 6.0 * t.c[3] * i6 * ir - 8.0 * t.c[4] * i8 * ir;
+        break;
+    }
+    case VSSR_PAIR_COUL_LONG: {   // the real-space part of an Ewald sum: no shift (c: g, -, -, qqrd2e q_a q_b)
+        const double a = t.c[0], ec = erfc(a * r) * ir;
+        e = t.c[3] * ec;
+        de = t.c[3] * (-ec * ir - PAIR_2_SQRTPI * a * exp(-a * a * r * r) * ir);
         break;
     }
     default: {   // VSSR_PAIR_COUL_DSF

@@ -352,6 +352,14 @@ struct vssr_handle {
     // the fp64 analytic potentials (Tersoff, EAM, Stillinger-Weber, pair)
     int n_types = 0;
     double pot_cutoff = 0;       // Tersoff, SW, pair: largest cutoff of the table (EAM: eam_grid.cutoff)
+    // pair handles with k-space (vssr_pair_create_kspace, ewald.hip): Ewald damping g, reciprocal cutoff, per-type charges; ew_stride:
+    // k cells per chain in d_ew_S = the largest half box of the uploaded batch (ewald_dev.h), [n_cfg][ew_stride + 1] double2
+    // (vssr_batch_upload is the only writer of d_cell: any new entry point that changes a cell must recompute ew_stride and re-size
+    // d_ew_S as it does; a chain whose half box exceeds the stride gets NaN results from the kernels, never a partial sum)
+    bool ew_on = false;
+    double ew_g = 0, ew_kcut = 0, ew_q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int ew_stride = 0;
+    vssr::DevBuf d_ew_S;
     vssr::DevBuf pot_params;     // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h); EAM: spline tables (eam.hip); pair: PairTable (pair_dev.h)
 
     // resident batch
@@ -533,6 +541,9 @@ int cluster_pad_dims(int d);   // stored width of a point: 1, 2, 3, 4, 8, 16 or 
 int tersoff_stress(vssr_handle *h);
 int eam_stress(vssr_handle *h);
 int sw_stress(vssr_handle *h);
+struct PotView;
+void ewald_run(vssr_handle *h, const PotView &V);   // ewald.hip: reciprocal, self and background terms added to d_pot_ea / d_pot_f
+int ewald_stress(vssr_handle *h);                   // their virial added to d_stress
 int pair_stress(vssr_handle *h);   // runs the site kernel's gradient form first: a plain evaluation keeps no per-slot gradients
 // What differs between the kinds that evaluate a batch, one row per Kind (api_handle.hip); run == nullptr: the kind evaluates nothing.
 // f64: an analytic potential -- results in d_pot_e / _ea / _f (fp64, one "model"), driven by relax_cg / chain_min as well.

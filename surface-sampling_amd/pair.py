@@ -1,8 +1,16 @@
 """The LAMMPS pair commands of a template -> the term list and charges of a device pair potential (``vssr_pair_create``).
 
-Read: ``pair_style`` (``lj/cut``, ``morse``, ``buck``, ``born``, ``coul/dsf``, and ``hybrid`` / ``hybrid/overlay`` of these),
-``pair_coeff`` with LAMMPS' type wildcards, ``pair_modify shift`` / ``mix`` and ``set type N charge q``; every other command of the
-template is skipped.  Units are LAMMPS ``metal``.  Whatever cannot be read raises ``ValueError`` with the offending line.
+Read: ``pair_style`` (``lj/cut``, ``morse``, ``buck``, ``born``, ``coul/dsf``, ``coul/long``, ``buck/coul/long``,
+``born/coul/long``, ``lj/cut/coul/long``, and ``hybrid`` / ``hybrid/overlay`` of these), ``pair_coeff`` with LAMMPS' type wildcards,
+``pair_modify shift`` / ``mix``, ``set type N charge q``, ``kspace_style ewald A`` and ``kspace_modify gewald G``; every other
+command of the template is skipped.  Units are LAMMPS ``metal``.  Whatever cannot be read raises ``ValueError`` with the offending
+line.
+
+The ``*/coul/long`` styles become their short-range term plus a ``coul/long`` term (the real-space part of the Ewald sum, cutoff
+``RC_COUL``) on EVERY type pair: the reciprocal sum runs over all charges.  ``kspace_style ewald A`` sets the model's ``kspace``:
+L = sqrt(-ln A), g = L / rc, k_cut = 2 g L (``kspace_modify gewald G``: g = G).  This rule depends on (A, rc) only -- LAMMPS' own
+estimator also looks at the atom count and the charges, which would change g between the proposals of a semigrand MC run -- so
+energies agree with LAMMPS to the accuracy asked for, not digit for digit.
 """
 
 from __future__ import annotations
@@ -13,15 +21,31 @@ from collections import namedtuple
 import numpy as np
 
 # style codes of include/vssr_eval.h (VSSR_PAIR_*), numbers after the type pair in a pair_coeff line, arguments in pair_style
-STYLES = {"lj/cut": 1, "morse": 2, "buck": 3, "born": 4, "coul/dsf": 5}
-N_COEF = {"lj/cut": 2, "morse": 3, "buck": 3, "born": 5, "coul/dsf": 0}
-N_ARGS = {"lj/cut": 1, "morse": 1, "buck": 1, "born": 1, "coul/dsf": 2}
-PAIR_STYLES = (*STYLES, "hybrid", "hybrid/overlay")
+STYLES = {"lj/cut": 1, "morse": 2, "buck": 3, "born": 4, "coul/dsf": 5, "coul/long": 6}
+N_COEF = {"lj/cut": 2, "morse": 3, "buck": 3, "born": 5, "coul/dsf": 0, "coul/long": 0}
+N_ARGS = {"lj/cut": 1, "morse": 1, "buck": 1, "born": 1, "coul/dsf": 2, "coul/long": 1}
+# pair_style X/coul/long RC [RC_COUL]: the short-range style X with cutoff RC plus coul/long with cutoff RC_COUL (default RC)
+COMPOSITE = {"buck/coul/long": "buck", "born/coul/long": "born", "lj/cut/coul/long": "lj/cut"}
+PAIR_STYLES = (*STYLES, *COMPOSITE, "hybrid", "hybrid/overlay")
 MAX_TYPES, MAX_TERMS = 8, 3
 QQRD2E = 14.399645
 
 Term = namedtuple("Term", "type_a type_b style c rc shift")      # 0-based types with a <= b, style code, c [5], cutoff, 0 / 1
-PairModel = namedtuple("PairModel", "n_types terms charges cutoff")   # charges: [n_types] or None (no ``set type ... charge``)
+# charges: [n_types] or None (no ``set type ... charge``); kspace: None, or the Ewald sum behind the coul/long terms
+PairModel = namedtuple("PairModel", "n_types terms charges cutoff kspace", defaults=(None,))
+KSpace = namedtuple("KSpace", "accuracy g_ewald k_cut")   # relative accuracy A asked for, damping g and reciprocal cutoff (1 / A)
+
+
+def ewald_defaults(accuracy, rc, g_ewald=None, k_cut=None) -> KSpace:
+    """``kspace_style ewald A`` with the real-space cutoff ``rc``: L = sqrt(-ln A), g = L / rc, k_cut = 2 g L unless given."""
+    if not (0.0 < accuracy < 1.0):
+        raise ValueError(f"kspace accuracy {accuracy} must lie in (0, 1)")
+    L = math.sqrt(-math.log(accuracy))
+    g = L / rc if g_ewald is None else float(g_ewald)
+    kc = 2.0 * g * L if k_cut is None else float(k_cut)
+    if not (math.isfinite(g) and g > 0 and math.isfinite(kc) and kc > 0):
+        raise ValueError(f"k-space parameters g_ewald {g}, k_cut {kc} must be finite and > 0")
+    return KSpace(float(accuracy), g, kc)
 
 
 def _number(tok, line, what):
@@ -71,6 +95,10 @@ def _parse_style(tok, line):
     """``pair_style`` arguments -> (mode, {sub-style: its arguments}) with mode "single", "hybrid" or "overlay"."""
     if not tok:
         raise ValueError(f"{line!r}: pair_style without a style")
+    if tok[0] in COMPOSITE:
+        if len(tok) - 1 not in (1, 2):
+            raise ValueError(f"{line!r}: pair_style {tok[0]} takes the cutoff and an optional Coulomb cutoff")
+        return "single", {tok[0]: [_number(t, line, "argument") for t in tok[1:]]}
     if tok[0] not in ("hybrid", "hybrid/overlay"):
         if tok[0] not in STYLES:
             raise ValueError(f"{line!r}: pair_style {tok[0]!r} is not a pair style of this kind ({', '.join(STYLES)})")
@@ -81,16 +109,20 @@ def _parse_style(tok, line):
     subs, k = {}, 1
     while k < len(tok):
         name = tok[k]
-        if name not in STYLES:
+        if name not in STYLES and name not in COMPOSITE:
             raise ValueError(f"{line!r}: sub-style {name!r} is not a pair style of this kind ({', '.join(STYLES)}); "
                              "mixing with the many-body potentials is not provided")
         if name in subs:
             raise ValueError(f"{line!r}: sub-style {name} appears twice (numbered sub-styles are not provided)")
-        args = tok[k + 1:k + 1 + N_ARGS[name]]
-        if len(args) != N_ARGS[name]:
-            raise ValueError(f"{line!r}: sub-style {name} takes {N_ARGS[name]} argument(s)")
+        if name in COMPOSITE:   # one or two numbers: whatever follows up to the next sub-style
+            n_args = 1 + (k + 2 < len(tok) and tok[k + 2] not in STYLES and tok[k + 2] not in COMPOSITE)
+        else:
+            n_args = N_ARGS[name]
+        args = tok[k + 1:k + 1 + n_args]
+        if len(args) != n_args:
+            raise ValueError(f"{line!r}: sub-style {name} takes {n_args} argument(s)")
         subs[name] = [_number(t, line, "argument") for t in args]
-        k += 1 + N_ARGS[name]
+        k += 1 + n_args
     if not subs:
         raise ValueError(f"{line!r}: {tok[0]} without sub-styles")
     return ("hybrid" if tok[0] == "hybrid" else "overlay"), subs
@@ -109,16 +141,17 @@ def parse(lines, n_types) -> PairModel:
     n_types = int(n_types)
     if not 1 <= n_types <= MAX_TYPES:
         raise ValueError(f"{n_types} atom types (1 .. {MAX_TYPES} are supported)")
-    mode, subs = None, None
+    mode, subs, style_line = None, None, None
     coeff = {}            # (i, j) 1-based, i <= j -> {sub-style: (coefficients, cutoff)} in assignment order
     none = set()          # pairs a hybrid line switched off (pair_coeff i j none)
     shift, mix = 0, "geometric"
     charges, has_charge = np.zeros(n_types), False
+    accuracy, gewald = None, None
     for line in _commands(lines):
         tok = line.split()
         cmd = tok[0]
         if cmd == "pair_style":
-            mode, subs = _parse_style(tok[1:], line)
+            mode, subs, style_line = *_parse_style(tok[1:], line), line
             coeff.clear(); none.clear()
         elif cmd == "pair_coeff":
             if mode is None:
@@ -145,11 +178,13 @@ def parse(lines, n_types) -> PairModel:
                     coeff.pop(p, None)
                     none.add(p)
                 continue
-            nc = N_COEF[name]
-            if len(rest) not in ((nc,) if name == "coul/dsf" else (nc, nc + 1)):
-                raise ValueError(f"{line!r}: {name} takes {nc} coefficient(s)" + ("" if name == "coul/dsf" else " and an optional cutoff"))
+            nc = N_COEF[COMPOSITE.get(name, name)]
+            coul = name in ("coul/dsf", "coul/long")
+            if len(rest) not in ((nc,) if coul else (nc, nc + 1)):
+                raise ValueError(f"{line!r}: {name} takes {nc} coefficient(s)" + ("" if coul else " and an optional cutoff"))
             c = tuple(_number(t, line, "coefficient") for t in rest[:nc])
-            rc = _number(rest[nc], line, "cutoff") if len(rest) > nc else subs[name][-1]
+            # (the optional cutoff of a */coul/long line is that of the short-range part, as in LAMMPS)
+            rc = _number(rest[nc], line, "cutoff") if len(rest) > nc else subs[name][0 if name in COMPOSITE else -1]
             for p in pairs:
                 none.discard(p)
                 if mode == "hybrid":
@@ -166,6 +201,21 @@ def parse(lines, n_types) -> PairModel:
                 else:
                     raise ValueError(f"{line!r}: pair_modify {' '.join(tok[k:k + 2])!r} is not provided (shift yes|no, mix geometric|arithmetic)")
                 k += 2
+        elif cmd == "kspace_style":
+            if len(tok) != 3 or tok[1] != "ewald":
+                raise ValueError(f"{line!r}: only 'kspace_style ewald ACCURACY' is provided (no pppm, msm, ewald/disp, ...)")
+            accuracy = _number(tok[2], line, "accuracy")
+            if not 0.0 < accuracy < 1.0:
+                raise ValueError(f"{line!r}: the accuracy must lie in (0, 1)")
+        elif cmd == "kspace_modify":
+            if len(tok) == 3 and tok[1] == "gewald":
+                gewald = _number(tok[2], line, "gewald")
+                if not gewald > 0:
+                    raise ValueError(f"{line!r}: gewald must be > 0")
+            elif len(tok) > 1 and tok[1] == "slab":
+                raise ValueError(f"{line!r}: the slab correction is not provided (the Ewald sum is periodic in three directions)")
+            else:
+                raise ValueError(f"{line!r}: kspace_modify {' '.join(tok[1:])!r} is not provided (gewald G)")
         elif cmd == "set" and "charge" in tok:
             if len(tok) != 5 or tok[1] != "type" or tok[3] != "charge":
                 raise ValueError(f"{line!r}: charges are per type ('set type N charge q')")
@@ -180,26 +230,50 @@ def parse(lines, n_types) -> PairModel:
             if (i, j) in coeff or (i, j) in none:
                 continue
             di, dj = coeff.get((i, i)), coeff.get((j, j))
-            if di is not None and dj is not None and list(di) == ["lj/cut"] and list(dj) == ["lj/cut"]:
-                coeff[(i, j)] = {"lj/cut": _mix_lj(di["lj/cut"], dj["lj/cut"], mix)}
+            for lj in ("lj/cut", "lj/cut/coul/long"):
+                if di is not None and dj is not None and list(di) == [lj] and list(dj) == [lj]:
+                    coeff[(i, j)] = {lj: _mix_lj(di[lj], dj[lj], mix)}
     unset = [(i, j) for i in range(1, n_types + 1) for j in range(i, n_types + 1) if (i, j) not in coeff and (i, j) not in none]
     if unset:
         raise ValueError("All pair coeffs are not set: " + ", ".join(f"{i} {j}" for i, j in unset)
                          + " (only lj/cut mixes; morse, buck and born need explicit i j lines)")
+    # the Ewald sum: one real-space cutoff, coul/long on every type pair, kspace_style given
+    long_rc = sorted({subs[n][-1] for n in subs if n in COMPOSITE or n == "coul/long"})
+    if len(long_rc) > 1:
+        raise ValueError(f"the coul/long sub-styles differ in their Coulomb cutoff ({', '.join(map(str, long_rc))}): one Ewald sum has one")
+    if long_rc and accuracy is None:
+        raise ValueError(f"{style_line!r}: pair style requires a KSpace style: a */coul/long pair_style needs 'kspace_style ewald ACCURACY'")
+    if accuracy is not None and not long_rc:
+        raise ValueError("kspace_style ewald without a */coul/long pair_style (KSpace style is incompatible with Pair style)")
+    if long_rc and "coul/dsf" in subs:
+        raise ValueError("coul/dsf next to a */coul/long style: one Coulomb sum at a time")
+    if long_rc and not has_charge:
+        raise ValueError("a */coul/long pair_style needs charges ('set type N charge q')")
+    if "coul/long" in subs:
+        bare = [(i, j) for i in range(1, n_types + 1) for j in range(i, n_types + 1) if "coul/long" not in coeff.get((i, j), {})]
+        if bare and not any(n in COMPOSITE for n in subs):
+            raise ValueError("coul/long must cover every type pair (pair_coeff * * coul/long): the reciprocal sum runs over all charges; "
+                             "missing " + ", ".join(f"{i} {j}" for i, j in bare))
     terms = []
-    for (i, j) in sorted(coeff):
-        entry = coeff[(i, j)]
-        if len(entry) > MAX_TERMS:
+    for (i, j) in sorted(set(coeff) | ({(i, j) for i in range(1, n_types + 1) for j in range(i, n_types + 1)} if long_rc else set())):
+        entry = coeff.get((i, j), {})
+        if len(entry) - ("coul/long" in entry) + bool(long_rc) > MAX_TERMS:
             raise ValueError(f"type pair {i} {j} carries {len(entry)} sub-styles ({MAX_TERMS} at the most)")
         for name in subs:                      # the order of the pair_style line
-            if name not in entry:
+            if name not in entry or name == "coul/long":
                 continue
             c, rc = entry[name]
             if name == "coul/dsf":
                 c = (subs[name][0],)           # alpha
             if not rc > 0:
                 raise ValueError(f"type pair {i} {j}, {name}: cutoff {rc} must be > 0")
-            terms.append(Term(i - 1, j - 1, STYLES[name], tuple(c) + (0.0,) * (5 - len(c)), float(rc), 0 if name == "coul/dsf" else shift))
+            terms.append(Term(i - 1, j - 1, STYLES[COMPOSITE.get(name, name)], tuple(c) + (0.0,) * (5 - len(c)), float(rc),
+                              0 if name == "coul/dsf" else shift))
+        if long_rc:                            # last on every pair, 'none' pairs included
+            if not long_rc[0] > 0:
+                raise ValueError(f"coul/long: cutoff {long_rc[0]} must be > 0")
+            terms.append(Term(i - 1, j - 1, STYLES["coul/long"], (0.0,) * 5, float(long_rc[0]), 0))
     if not terms:
         raise ValueError("every type pair is 'none': nothing to evaluate")
-    return PairModel(n_types, terms, charges if has_charge else None, max(t.rc for t in terms))
+    kspace = ewald_defaults(accuracy, long_rc[0], g_ewald=gewald) if long_rc else None
+    return PairModel(n_types, terms, charges if has_charge else None, max(t.rc for t in terms), kspace)
