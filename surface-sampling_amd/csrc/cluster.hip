@@ -6,7 +6,8 @@
 //       v_mfma_f64_16x16x4_f64 with unit responsibilities, k_fit_cov_finish with the divisor N - 1) -> C;  k_clu_eigh: cyclic Jacobi with
 //       the round-robin parallel ordering in ONE workgroup (D / 2 disjoint rotations per step, D - 1 steps per sweep; the matrix and
 //       the eigenvectors stay in a global workspace that L2 holds: 2 x 256 x 256 doubles do not fit LDS), a rotation is skipped once
-//       |a_pq| <= eps |C|_F / D, the solve ends with the first sweep that rotates nothing;  k_clu_components: order by decreasing
+//       |a_pq| <= eps |C|_F / D, every sweep ends by mirroring the upper triangle into the lower, the solve ends with the first sweep
+//       that rotates nothing;  k_clu_components: order by decreasing
 //       eigenvalue, sign (largest-magnitude loading positive), explained variance and ratio;  k_clu_project: X_r and the points.
 // Ward linkage without a distance matrix (the hot path).  Live clusters are (centroid [d_pad], size, id) in list order.  Per round:
 //   k_ward_nn      one thread per query cluster; the candidates stream through LDS in tiles of 256 (every lane reads the same LDS
@@ -132,6 +133,13 @@ k_clu_eigh(const double *__restrict__ cov, double *A, double *Vt, int m, int ld,
                 Vt[(size_t)q * ld + k] = s * vp + c * vq;
             }
             __syncthreads();
+        }
+        // The column and the row pass round a_pq and a_qp differently, and a rotation (an orthogonal similarity) keeps the norm of
+        // an antisymmetric part: what the first sweeps round into it (eps times the entries of then, about tol) would stay above
+        // tol in a_pq for good, and a covariance of low rank (N << D) never ended.  The upper triangle is the matrix: mirror it.
+        for (int t = tid; t < m * m; t += nt) {
+            const int i = t / m, j = t - i * m;
+            if (j < i) A[(size_t)i * ld + j] = A[(size_t)j * ld + i];
         }
         conv = rotated ? 0 : 1;
         __syncthreads();

@@ -30,18 +30,45 @@ def pca_svd(X, n_components=32, whiten=True):
                  "explained_variance_ratio_": ev[:n_components] / ev.sum()}
 
 
-def ward_rnn(points):
-    """(Z, rounds): Ward linkage by rounds of reciprocal nearest neighbours, lowest position wins a tie."""
+def pca_longdouble(X, n_components=32, whiten=True):
+    """The PCA with the mean and the centred covariance accumulated in np.longdouble, the covariance then rounded to fp64 and solved
+    by numpy.linalg.eigh; components by decreasing eigenvalue (clamped at 0), the largest-magnitude loading positive, whitening by
+    max(sqrt(l), eps).  A second, equally valid solver: its distance from pca_svd says how far two correct answers lie apart."""
+    Xl = np.asarray(X, dtype=np.float64).astype(np.longdouble)
+    n, D = Xl.shape
+    mean = Xl.sum(axis=0) / np.longdouble(n)
+    Xc = Xl - mean
+    cov = (Xc.T @ Xc) / np.longdouble(n - 1)
+    lam, V = np.linalg.eigh(cov.astype(np.float64))
+    order = np.argsort(-lam, kind="stable")
+    lam, Vt = np.maximum(lam[order], 0.0), V[:, order].T
+    sign = np.sign(Vt[np.arange(D), np.argmax(np.abs(Vt), axis=1)])
+    sign[sign == 0] = 1.0
+    comp, ev = (Vt * sign[:, None])[:n_components], lam[:n_components]
+    X_r = (Xc @ comp.T.astype(np.longdouble)).astype(np.float64)
+    if whiten:
+        X_r = X_r / np.maximum(np.sqrt(ev), np.finfo(np.float64).eps)
+    return X_r, {"mean_": mean.astype(np.float64), "components_": comp, "explained_variance_": ev,
+                 "explained_variance_ratio_": ev / lam.sum()}
+
+
+def ward_rnn(points, margin=False):
+    """(Z, rounds): Ward linkage by rounds of reciprocal nearest neighbours, lowest position wins a tie.  With ``margin`` also the
+    smallest relative gap (second - best) / second between the best and the second-best key of any cluster in any round (rounds with
+    two live clusters have no second key and are skipped): how far the tree is from a decision that rounding could turn."""
     P = np.asarray(points, dtype=np.float64)
     n = len(P)
     cen, siz, cid = [p for p in P], [1.0] * n, list(range(n))
-    rec, rounds = [], 0
+    rec, rounds, gap = [], 0, np.inf
     while len(cid) > 1:
         C, s = np.array(cen), np.array(siz)
         d2 = sum((C[:, None, e] - C[None, :, e]) ** 2 for e in range(C.shape[1]))
         key = d2 * (s[:, None] * s[None, :] / (s[:, None] + s[None, :]))
         np.fill_diagonal(key, np.inf)
         nn = key.argmin(axis=1)
+        if margin and len(cid) > 2:
+            two = np.partition(key, 1, axis=1)[:, :2]
+            gap = min(gap, float(np.min(np.where(two[:, 1] > 0, (two[:, 1] - two[:, 0]) / np.where(two[:, 1] > 0, two[:, 1], 1.0), 0.0))))
         dead = set()
         for i in range(len(cid)):
             j = int(nn[i])
@@ -63,7 +90,7 @@ def ward_rnn(points):
     for r, o in enumerate(order):
         a, b = (int(v) if v < n else n + int(rank[int(v) - n]) for v in rec[o, :2])
         Z[r] = (min(a, b), max(a, b), rec[o, 2], rec[o, 3])
-    return Z, rounds
+    return (Z, rounds, gap) if margin else (Z, rounds)
 
 
 def partition(Z, t, criterion):

@@ -1,6 +1,7 @@
 """Latent-space clustering without a GPU: the numpy restatements (tests/cluster_oracle.py and the package's host path) against the
 scikit-learn / SciPy fixtures of tools/make_cluster_golden.py, fcluster's numbering, select_data_and_save's rule, the ABI refusals
-that need no device, and the launcher's rebinding of mcmc.utils.clustering."""
+that need no device, and the launcher's rebinding of mcmc.utils.clustering; and the rehearsal of tests/cluster_cases.py: every case of the
+device shape sweep is what it is listed as (spectral gaps, linkage margins, the closed-form tree) and the host path passes it."""
 import ctypes as C
 import os
 import pickle
@@ -11,6 +12,7 @@ import textwrap
 import numpy as np
 import pytest
 
+import cluster_cases as cs
 import cluster_oracle as co
 from conftest import ROOT
 from surface_sampling_amd import backend, clustering as cl
@@ -100,6 +102,115 @@ def test_get_cluster_centers_and_closest_points_on_the_host():
     assert centers.shape == (12, 3) and np.array_equal(labels, co.load("ward_n1000_d3")["labels_maxclust_12"])
     idx = cl.find_closest_points_indices(P, centers, labels)
     assert np.array_equal(labels[idx], np.arange(1, 13))
+
+
+# ---- the rehearsal of tests/cluster_cases.py -----------------------------------------------------------------------------------------
+def test_pca_case_names_are_the_cases():
+    assert tuple(c.name for c in cs.pca_cases()) == cs.PCA_NAMES
+    for c in cs.pca_cases():
+        N, D = c.X.shape
+        assert 1 <= c.n_components <= min(N, D) and c.whiten in (0, 1) and np.all(np.isfinite(c.X)), c.name
+    shapes = {c.X.shape[1]: c.X.shape[0] for c in cs.pca_cases() if c.name.startswith("shapes")}
+    assert shapes == {1: 257, 2: 257, 3: 257, 15: 257, 16: 257, 17: 257, 100: 257, 255: 600, 256: 600}
+
+
+@pytest.mark.parametrize("name", cs.PCA_NAMES)
+def test_pca_cases_are_what_they_claim_and_the_host_path_passes_them(name):
+    c = cs.pca_case(name)
+    N, D = c.X.shape
+    with np.errstate(all="ignore"):
+        lam = co.pca_svd(c.X, min(N, D), False)[1]["explained_variance_"]      # the oracle's whole spectrum
+    compared = [k for g in c.groups for k in g]
+    assert compared == sorted(set(compared)) and all(list(g) == list(range(g[0], g[-1] + 1)) for g in c.groups)
+    assert compared == [k for k in range(c.n_components) if lam[k] > cs.NULL_EV * lam[0]]     # exactly the non-zero components
+    gaps = []
+    for g in c.groups:
+        lo, hi = g[0], g[-1]
+        assert lam[lo] - lam[hi] <= cs.GROUP_EQ * lam[lo], (name, g)
+        gaps += [(lam[lo - 1] - lam[lo]) / lam[lo - 1]] if lo > 0 else []
+        gaps += [(lam[hi] - lam[hi + 1]) / lam[hi]] if hi + 1 < len(lam) else []
+    print(f"{name}: {len(c.groups)} groups over {len(compared)} of {c.n_components} components, smallest relative gap "
+          f"{min(gaps, default=np.inf):.2e}, l_min / l_0 {lam[compared[-1]] / lam[0]:.2e}")
+    assert min(gaps, default=np.inf) >= cs.SINGLE_GAP
+    if name.startswith("rank_deficient"):
+        assert len(compared) == N - 1 < c.n_components
+    if name == "constant_column":
+        assert len(compared) == D - 2 and np.all(c.X[:, [4, 11]] == c.X[0, [4, 11]])
+    if name == "degenerate":
+        assert np.max(np.abs(lam - [4, 4, 4, 2, 1, 1, 0.5, 0.4, 0.3, 0.25, 0.2, 0.15, 0.1, 0.08, 0.06, 0.05])) <= 1e-13
+        assert [len(g) for g in c.groups[:3]] == [3, 1, 2]
+    if name == "diagonal":
+        cov = np.cov(c.X.T)
+        assert np.max(np.abs(cov - np.diag(np.diag(cov)))) <= 1e-14
+    with np.errstate(all="ignore"):
+        Xr, p = cl.pca_host(c.X, c.n_components, bool(c.whiten))
+    cs.pca_check(c, cs.pca_figures(c, Xr, p), "host path, ")
+    if name == "offset" or name in cs.SPREAD_XR:
+        sp = cs.pca_spread(name)
+        print(f"{name}: |pca_svd - pca_longdouble| " + ", ".join(f"{k} {sp[k]:.2e}" for k in ("mean", "ev", "ratio", "vec", "sub", "xr")))
+        assert sp["sign_ok"] and sp["finite"]
+        assert all(sp[k] <= 1e3 * b for k, b in cs.pca_bounds(c).items())      # the two oracles describe the same PCA
+
+
+@pytest.mark.parametrize("name", cs.GENERAL_NAMES)
+def test_general_linkage_cases_keep_their_margin_and_the_host_path_gives_the_oracles_tree(name):
+    P = cs.general(name).points
+    Zo, rounds_o, gap = cs.tree(name)
+    Z, rounds = cl.ward_linkage_host(P)
+    same, err, same_rounds = cs.tree_figures(Z, rounds, Zo, rounds_o)
+    print(f"{name}: {rounds_o} rounds, margin {gap:.2e} (at least {cs.MARGIN:.0e}), host path height error {err:.2e}")
+    assert gap >= cs.MARGIN
+    assert same and same_rounds and err <= 1e-10
+    assert co.ward_rnn(P)[1] == rounds_o                     # the default return is (Z, rounds)
+    if P.shape[0] in (257, 513):
+        assert 15 <= rounds_o <= 27
+
+
+def test_pca_to_linkage_inputs_keep_their_margin():
+    Xr0, _ = cs.pca_reference("shapes_d17_w1")
+    for cd in (5, 9):
+        Z, rounds, gap = co.ward_rnn(Xr0[:, :cd], margin=True)
+        print(f"whitened coordinates of shapes_d17, {cd} columns: {rounds} rounds, margin {gap:.2e}")
+        assert gap >= cs.MARGIN
+
+
+@pytest.mark.parametrize("permuted", [False, True])
+def test_hierarchy_gives_the_closed_form_tree_through_the_oracle(permuted):
+    k = 8
+    perm = np.random.default_rng(5).permutation(1 << k) if permuted else None
+    P = cs.hierarchy(k, perm=perm)
+    h, s = cs.hierarchy_heights(k)
+    for what, (Z, rounds) in (("oracle", co.ward_rnn(P)), ("host path", cl.ward_linkage_host(P))):
+        assert rounds == k, what
+        cs.check_hierarchy_tree(Z, k, perm)
+        assert np.array_equal(Z[:, 2], h) and np.array_equal(Z[:, 3], s), what       # exact heights and sizes
+    _, _, gap = co.ward_rnn(P, margin=True)
+    print(f"hierarchy({k}): margin {gap:.3f}")
+    assert gap >= 0.75                                        # the sibling key is at most a quarter of any other key (x = 1 and 3)
+    x = cs.hierarchy(17)[:, 0]                                # the size of the device test: exact integers, all distinct
+    assert x[-1] == (3.0 ** 17 - 1) / 2 and len(np.unique(x)) == 1 << 17 and 9.0 ** 16 < 2.0 ** 53
+
+
+def test_the_tree_checker_rejects_wrong_trees():
+    k = 8
+    Z, _ = co.ward_rnn(cs.hierarchy(k))
+    cs.check_hierarchy_tree(Z, k)
+    bad = Z.copy()                                            # one swapped pair: leaves 1 and 2 change partners
+    r1, r2 = (int(np.flatnonzero((Z[:, 0] == a) & (Z[:, 1] == a + 1))[0]) for a in (0, 2))
+    bad[r1, 1], bad[r2, 0] = 2, 1
+    with pytest.raises(AssertionError, match="sibling"):
+        cs.check_hierarchy_tree(bad, k)
+    bad = Z.copy()                                            # a pair of the next level merged one level early
+    top = int(np.flatnonzero(Z[:, 3] == 4)[0])
+    bad[[0, top]] = bad[[top, 0]]
+    with pytest.raises(AssertionError):
+        cs.check_hierarchy_tree(bad, k)
+    bad = Z.copy()                                            # a node used twice
+    bad[-1, 0] = bad[-2, 0]
+    with pytest.raises(AssertionError):
+        cs.check_hierarchy_tree(bad, k)
+    with pytest.raises(AssertionError):                       # the right tree of other points
+        cs.check_hierarchy_tree(Z, k, np.random.default_rng(5).permutation(1 << k))
 
 
 def _create(dim, n_components, cluster_dims, whiten=1, device=0):

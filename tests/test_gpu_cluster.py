@@ -3,12 +3,18 @@ scikit-learn / SciPy fixtures of tools/make_cluster_golden.py.  Bounds: explaine
 100 x D x 2^-53, the backward error of a symmetric eigen-solver with two orders of margin); the first three whitened coordinates
 within the fixture's own ref_spread (how far sklearn's default randomized solver lies from its full solver on these rows);
 trailing components as a subspace (singular values of V_dev^T V_ref within 1e-9 of 1); tree pairs and sizes identical, heights
-within 1e-10 x the largest (N - 1 weighted-mean updates of 2^-53 each, one order of margin at 1e5 rows); labels identical."""
+within 1e-10 x the largest (N - 1 weighted-mean updates of 2^-53 each, one order of margin at 1e5 rows); labels identical.
+The shape sweep (tests/cluster_cases.py, rehearsed in tests/test_cluster_cpu.py) holds the same bounds against co.pca_svd and
+co.ward_rnn: single components 1 - |<v_dev, v_ref>| <= 1e-9, unwhitened coordinates 1e-9 sqrt(l_0), whitened coordinates 1e-6 for
+l_c >= 1e-6 l_0 (a perturbation eps l_0 of the covariance turns such a vector by eps l_0 / gap, scaled up by 1 / sqrt(l_c)); the
+offset case max(bound, 10 x |pca_svd - pca_longdouble|).  Above 65 536 points the reference is the closed-form tree of
+cluster_cases.hierarchy.  Measured figures: profiles/r21/NOTES_cluster_shapes.md."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import cluster_cases as cs
 import cluster_oracle as co
 from surface_sampling_amd import backend, clustering as cl
 from test_gpu_uncertainty import _engine, _structs
@@ -41,6 +47,80 @@ def test_pca_against_sklearn_fixture():
         assert p["components_"][c, np.argmax(np.abs(p["components_"][c]))] > 0
     assert np.array_equal(eng.projected(10, 5), Xr[10:15])
     eng.close()
+
+
+@pytest.mark.parametrize("name", cs.PCA_NAMES)
+def test_pca_shapes_against_the_svd(name):
+    c = cs.pca_case(name)
+    N, D = c.X.shape
+    eng = backend.ClusterEngine(D, n_components=c.n_components, whiten=bool(c.whiten), cluster_dims=1)
+    cut = max(1, N // 3)                                   # two unequal parts (equal only where N = 2)
+    eng.append_rows(c.X[:cut])
+    eng.append_rows(c.X[cut:])
+    info = eng.pca()
+    p, Xr = eng.pca_params(), eng.projected()
+    first, n = N // 3, min(5, N - N // 3)
+    window, rows = eng.projected(first, n), np.stack([eng.projected(r, 1)[0] for r in (0, N - 1)])
+    eng.close()
+    print(f"{name}: D = {D}, N = {N}, n_components = {c.n_components}, whiten = {c.whiten}, {info}")
+    f = cs.pca_figures(c, Xr, p)
+    cs.pca_check(c, f, "device, ")
+    assert info["converged"] and info["n_rows"] == N and info["n_sweeps"] < 60
+    assert Xr.shape == (N, c.n_components) and p["components_"].shape == (c.n_components, D)
+    assert np.array_equal(window, Xr[first:first + n]) and np.array_equal(rows, Xr[[0, N - 1]])
+
+
+def _linkage(P):
+    eng = backend.ClusterEngine(P.shape[1], n_components=1, cluster_dims=P.shape[1])
+    eng.set_points(P)
+    Z, rounds = eng.linkage()
+    eng.close()
+    return Z, rounds
+
+
+@pytest.mark.parametrize("name", cs.GENERAL_NAMES)
+def test_linkage_trees_at_every_width_and_edge(name):
+    P = cs.general(name).points
+    Zo, rounds_o, gap = cs.tree(name)
+    Z, rounds = _linkage(P)
+    Z2, rounds2 = _linkage(P)
+    same, err, same_rounds = cs.tree_figures(Z, rounds, Zo, rounds_o)
+    print(f"{name}: {rounds} rounds (oracle {rounds_o}, margin {gap:.2e}), pairs and sizes identical {same}, "
+          f"height error {err:.2e} (bound 1e-10)")
+    assert Z.shape == (len(P) - 1, 4)
+    assert same and same_rounds and err <= 1e-10
+    assert Z.tobytes() == Z2.tobytes() and rounds == rounds2
+
+
+@pytest.mark.parametrize("permuted", [False, True])
+def test_linkage_above_65536_points_follows_the_closed_form(permuted):
+    k = 17                                                 # 131 072 points: 512 workgroups, two entries per thread of k_ward_scan
+    perm = np.random.default_rng(5).permutation(1 << k) if permuted else None
+    Z, rounds = _linkage(cs.hierarchy(k, perm=perm))
+    h, s = cs.hierarchy_heights(k)
+    print(f"hierarchy({k}), permuted {permuted}: {rounds} rounds, heights exact {np.array_equal(Z[:, 2], h)}, "
+          f"sizes exact {np.array_equal(Z[:, 3], s)}")
+    assert rounds == k
+    assert np.array_equal(Z[:, 2], h) and np.array_equal(Z[:, 3], s)
+    cs.check_hierarchy_tree(Z, k, perm)
+
+
+@pytest.mark.parametrize("cluster_dims", [5, 9])
+def test_pca_feeds_the_linkage_at_padded_widths(cluster_dims):
+    c = cs.pca_case("shapes_d17_w1")
+    eng = backend.ClusterEngine(17, n_components=9, cluster_dims=cluster_dims)
+    eng.append_rows(c.X)
+    eng.pca()
+    Xr = eng.projected()
+    Z, rounds = eng.linkage()
+    eng.close()
+    Z2, rounds2 = _linkage(Xr[:, :cluster_dims])           # the same coordinates through set_points: the pad columns are zero
+    Zo, rounds_o = co.ward_rnn(cs.pca_reference(c.name)[0][:, :cluster_dims])
+    same, err, same_rounds = cs.tree_figures(Z, rounds, Zo, rounds_o)
+    print(f"cluster_dims = {cluster_dims}: {rounds} rounds (oracle {rounds_o}), bit-identical to set_points "
+          f"{Z.tobytes() == Z2.tobytes()}, pairs and sizes identical to the oracle {same}, height error {err:.2e}")
+    assert Z.tobytes() == Z2.tobytes() and rounds == rounds2
+    assert same and same_rounds and err <= 1e-10
 
 
 @pytest.mark.parametrize("name", ["ward_n1000_d3", "ward_n3000_d3"])
@@ -79,9 +159,13 @@ def test_other_point_widths_against_the_restatement(d):
     rng = np.random.default_rng(d)
     P = rng.normal(size=(700, d)) + 3.0 * rng.integers(0, 4, size=(700, 1))
     centers, labels = cl.get_cluster_centers(P, 9)
-    Zo, _ = co.ward_rnn(P)
+    Zo, rounds_o = co.ward_rnn(P)
     assert np.array_equal(labels, cl.fcluster(Zo, 9, "maxclust"))
     assert centers.shape == (9, d)
+    Z, rounds = _linkage(P)
+    same, err, same_rounds = cs.tree_figures(Z, rounds, Zo, rounds_o)
+    print(f"d = {d}: {rounds} rounds (oracle {rounds_o}), pairs and sizes identical {same}, height error {err:.2e} (bound 1e-10)")
+    assert same and same_rounds and err <= 1e-10
 
 
 def test_whole_pipeline_equals_the_fixture(tmp_path):
