@@ -140,9 +140,9 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
             if (c <= EDGE_CLASS_FS16M && h->fs16_max_atoms >= 0 && n_atoms[b] > h->fs16_max_atoms) c = EDGE_CLASS_FS8;
             if (bc == EDGE_BCLASS_FS16 && h->fs16_max_atoms >= 0 && n_atoms[b] > h->fs16_max_atoms) bc = EDGE_BCLASS_FS8;
             if (c == EDGE_CLASS_FS8 && h->fs8_max_atoms >= 0 && n_atoms[b] > h->fs8_max_atoms) { c = EDGE_CLASS_FS4; bc = EDGE_BCLASS_FS4; }
-            if (c == EDGE_CLASS_FS4 && h->fs4_max_atoms >= 0 && n_atoms[b] > h->fs4_max_atoms) { c = EDGE_CLASS_GATHER; bc = EDGE_BCLASS_GATHER; }
-            // the 8-feature forward class (406 .. 787 atoms by the chain's own size) also takes the 16-feature multi-pass form
-            if (h->fwd_mpass_fs8 && h->fwd_two_pass == 16 && c == EDGE_CLASS_FS8 && edge_class_of(n_atoms[b]) == EDGE_CLASS_FS8) c = EDGE_CLASS_FS4;
+            // the 8-feature forward class (406 .. 787 atoms by the chain's own size) also takes the 16-feature multi-pass form (-9 % against
+            // the single-pass 8-feature kernel, profiles/r05/NOTES_large_chains.md); VSSR_EDGE_FWD_2PASS=0 | 8 keeps the 8-feature kernel
+            if (h->fwd_two_pass == 16 && c == EDGE_CLASS_FS8 && edge_class_of(n_atoms[b]) == EDGE_CLASS_FS8) c = EDGE_CLASS_FS4;
             // reverse pass of chains beyond the single-pass 16-feature form (by the chain's OWN size, not by a test knob that moved it):
             // the same kernel in several passes over neighbor sub-ranges
             if (bc != EDGE_BCLASS_GATHER && ((h->bwd_multi_pass == 1 && edge_bclass_of(n_atoms[b]) != EDGE_BCLASS_FS16) || h->bwd_multi_pass == 2))

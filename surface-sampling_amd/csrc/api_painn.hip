@@ -155,6 +155,31 @@ static int upload_weights(vssr_handle *h, const vssr_painn_config *cfg) {
     return VSSR_OK;
 }
 
+// The environment knobs of a PaiNN handle, read once at create (debugging and tests; DESIGN.md lists them).
+static void read_env_knobs(vssr_handle *h) {
+    // general: the general-width fp32 path although the shape is 128 / 20 (tests: A/B of the two paths)
+    if (const char *e = getenv("VSSR_PAINN_PATH")) h->painn_general = h->painn_general || strcmp(e, "general") == 0;
+    // gather: every chain takes the scalar gather kernels
+    if (const char *e = getenv("VSSR_EDGE_IMPL")) h->edge_impl = (strcmp(e, "gather") == 0) ? 0 : 1;
+    // 0: layer 0 on the gather kernels instead of the species factorisation (the general path never factorises)
+    if (const char *e = getenv("VSSR_L0_FACTORISE")) h->l0_enabled = atoi(e);
+    if (h->painn_general) h->l0_enabled = 0;
+    // 1: update_fwd stores its intermediates, the reverse kernel loads them instead of recomputing
+    if (const char *e = getenv("VSSR_UPD_SAVE")) h->upd_save = atoi(e);
+    // 1: also materialise what only vssr_debug_read looks at
+    if (const char *e = getenv("VSSR_DEBUG_KEEP")) h->debug_keep = atoi(e);
+    // chains above this atom count leave the 16-feature classes although they fit (tests)
+    if (const char *e = getenv("VSSR_EDGE_FS16_MAX")) h->fs16_max_atoms = atoi(e);
+    // chains above this atom count leave the 8-feature class for the 4-feature one although they fit (tests)
+    if (const char *e = getenv("VSSR_EDGE_FS8_MAX")) h->fs8_max_atoms = atoi(e);
+    // 0: large chains take the 8- / 4-feature reverse kernels; 1: the 16-feature kernel in several passes; 2: every chain multi-pass
+    if (const char *e = getenv("VSSR_EDGE_BWD_MPASS")) h->bwd_multi_pass = atoi(e);
+    // atoms per neighbor sub-range of the multi-pass forms instead of what LDS holds (>= 8; tests)
+    if (const char *e = getenv("VSSR_EDGE_SUB_CHUNK")) { const int c = atoi(e); if (c >= 8) { h->sub_chunk_fwd = c; h->sub_chunk_bwd = c; } }
+    // 0 | 8 | 16: the 4-feature forward class runs the 4-feature kernel, or the 8- / 16-feature kernel in several passes
+    if (const char *e = getenv("VSSR_EDGE_FWD_2PASS")) { const int w = atoi(e); h->fwd_two_pass = (w == 8 || w == 16) ? w : w ? 16 : 0; }
+}
+
 }  // namespace vssr
 
 using namespace vssr;
@@ -184,27 +209,16 @@ int vssr_create(const vssr_painn_config *cfg, vssr_handle **out) {
         h->excl_power = cfg->excl_power; h->excl_sigma = cfg->excl_sigma; h->units_per_ev = cfg->model_units_per_ev;
         h->feat_dim = cfg->feat_dim;
         h->painn_general = !(cfg->feat_dim == F && cfg->n_rbf == 20);
-        if (const char *e = getenv("VSSR_PAINN_PATH")) h->painn_general = h->painn_general || strcmp(e, "general") == 0;   // (tests: A/B at 128 / 20)
+        read_env_knobs(h);
         int rc = VSSR_OK;
-        if (h->painn_general) {   // none of the fp16-split / sliced / species-factorised machinery of the 128 / 20 path
-            h->l0_enabled = 0;
+        if (h->painn_general)   // none of the fp16-split / sliced / species-factorised machinery of the 128 / 20 path
             rc = painn_gen_upload(h, cfg);
-        } else {
+        else {
             rc = upload_weights(h, cfg);
             if (!rc) rc = node_mfma_init(h);
             if (!rc) rc = edge_mfma_init(h);
             if (!rc) rc = l0_mfma_init(h);
         }
-        if (const char *e = getenv("VSSR_EDGE_IMPL")) h->edge_impl = (strcmp(e, "gather") == 0) ? 0 : 1;
-        if (const char *e = getenv("VSSR_L0_FACTORISE")) h->l0_enabled = h->painn_general ? 0 : atoi(e);
-        if (const char *e = getenv("VSSR_UPD_SAVE")) h->upd_save = atoi(e);
-        if (const char *e = getenv("VSSR_DEBUG_KEEP")) h->debug_keep = atoi(e);
-        // test knobs: send chains above these atom counts to the next class (8-feature slices / gather kernels) although they fit
-        if (const char *e = getenv("VSSR_EDGE_FS16_MAX")) h->fs16_max_atoms = atoi(e);
-        if (const char *e = getenv("VSSR_EDGE_FS8_MAX")) h->fs8_max_atoms = atoi(e);
-        if (const char *e = getenv("VSSR_EDGE_BWD_MPASS")) h->bwd_multi_pass = atoi(e);
-        if (const char *e = getenv("VSSR_EDGE_SUB_CHUNK")) { const int c = atoi(e); if (c >= 8) { h->sub_chunk_fwd = c; h->sub_chunk_bwd = c; } }
-        if (const char *e = getenv("VSSR_EDGE_FWD_2PASS")) { const int w = atoi(e); h->fwd_two_pass = (w == 8 || w == 16) ? w : w ? 16 : 0; }
         if (!rc && cfg->offset_per_z) {
             h->has_offset = true;
             h->offset_const = cfg->offset_const;

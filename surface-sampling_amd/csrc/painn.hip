@@ -229,7 +229,7 @@ k_edge_bwd(int N, int l, int accumulate, const ModelW *__restrict__ MW, GraphVie
     __shared__ float tots[ECHUNK][4];
     if (counters[2] || !G.act.atom(blockIdx.x)) return;
     if (only_class >= 0 && G.chain_class[G.atom_cfg[blockIdx.x]] != only_class) return;
-    // (compact partial buffers: the final buffer of a matrix-pipe chain holds nothing yet when layer 0 arrives)
+    // (the final buffer of a matrix-pipe chain holds nothing yet when layer 0 arrives: its layers >= 1 wrote partial records)
     if (fresh_mfma && G.chain_class[G.atom_cfg[blockIdx.x]] != EDGE_BCLASS_GATHER) accumulate = 0;
     const int c = blockIdx.x, m = blockIdx.y, f = threadIdx.x;
     const LayerW &W = MW[m].layer[l];
@@ -336,11 +336,10 @@ k_edge_bwd(int N, int l, int accumulate, const ModelW *__restrict__ MW, GraphVie
 
 // ---- ensemble reduction -----------------------------------------------------------------------------------------
 // forces: dE/dx_c = sum_{slots (c,n)} ( G[(n->c)] - G[(c->n)] ), G[(c->n)] lives at rev[slot].
-// Partial edge gradients of the feature slices (one buffer per workgroup group) -> one buffer per model (group 0, in place): a streaming,
-// coalesced pass in fixed group order, so that the gather through `rev` below touches one buffer per model only.  A chain's
-// slots carry as many partial buffers as its class has slices (grid.x = chain).
-// Compact partial buffers (gbar_mode 2): P [M][n_groups][slot_cap][3] floats, one set of `per_set` groups per reverse layer;
-// a chain's slots carry `slices` groups per set.  final G [M][slot_cap] float4 already holds the layer-0 part.
+// Partial edge gradients of the feature slices -> the final buffer of every model: a streaming, coalesced pass in fixed group order,
+// so that the gather through `rev` below touches one buffer per model only.  P [M][n_groups][slot_cap][3] floats, one set of
+// `per_set` groups per reverse layer; a chain's slots carry `slices` groups per set (as many as its class has slices).
+// final G [M][slot_cap] float4 already holds the layer-0 part.
 __global__ void __launch_bounds__(256)
 k_reduce_gpart(int M, int n_groups, int layer_sets, GraphView G, const int *__restrict__ counters, const float *__restrict__ P,
                float4 *__restrict__ gbar, long long slot_cap, int uniform_slices) {
@@ -371,52 +370,13 @@ k_reduce_gpart(int M, int n_groups, int layer_sets, GraphView G, const int *__re
         }
 }
 
-// (every chain of the batch in one class -- the usual case: one thread per slot of the whole batch)
-__global__ void k_reduce_gbar_groups_uniform(int M, int n_groups, const int *__restrict__ counters, float4 *__restrict__ gbar,
-                                             long long gbar_stride) {
-    const long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (counters[2] || slot >= counters[0]) return;
-    for (int m = 0; m < M; ++m) {
-        float4 *g0 = gbar + (size_t)(m * n_groups) * gbar_stride + slot;
-        float4 acc = *g0;
-        for (int grp = 1; grp < n_groups; ++grp) {
-            const float4 v = g0[(size_t)grp * gbar_stride];
-            acc.x += v.x; acc.y += v.y; acc.z += v.z;
-        }
-        *g0 = acc;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_reduce_gbar_groups(int M, int n_groups, int layer_sets, GraphView G, const int *__restrict__ counters, float4 *__restrict__ gbar,
-                     long long gbar_stride) {
-    if (counters[2]) return;
-    const int b = blockIdx.x;   // (x: no 65 535 limit on the chain count)
-    if (!G.act.chain(b)) return;
-    const int slices = edge_bclass_slices(G.chain_class[b]);   // buffers the chain's reverse kernels wrote per layer set
-    if (slices == 1) return;
-    const int per_set = n_groups / layer_sets;   // group index of layer set k, slice f: k * per_set + f
-    const int s0 = G.row_start[G.cfg_start[b]], s1 = G.row_start[G.cfg_start[b + 1]];
-    for (int slot = s0 + blockIdx.y * blockDim.x + threadIdx.x; slot < s1; slot += gridDim.y * blockDim.x)
-        for (int m = 0; m < M; ++m) {
-            float4 *g0 = gbar + (size_t)(m * n_groups) * gbar_stride + slot;
-            float4 acc = *g0;
-            for (int k = 0; k < layer_sets; ++k)
-                for (int grp = k ? 0 : 1; grp < slices; ++grp) {
-                    const float4 v = g0[(size_t)(k * per_set + grp) * gbar_stride];
-                    acc.x += v.x; acc.y += v.y; acc.z += v.z;
-                }
-            *g0 = acc;
-        }
-}
-
-// forces = - sum_slots (G[slot] - G[rev[slot]]) per model, then ensemble mean / std.  gbar_model_stride: distance between
-// the (group-reduced) buffers of consecutive models.
+// forces = - sum_slots (G[slot] - G[rev[slot]]) per model, then ensemble mean / std.  model_stride: distance between
+// the final buffers of consecutive models.
 // One wave per centre, lanes over its slots: the row's gradients are read as contiguous float4 (thread-per-atom reads were
 // one L1 access per lane), the reverse slots are gathered, and the 3 x M partial sums are combined by a fixed shuffle tree.
 __global__ void __launch_bounds__(256)
 k_finalize_forces(int N, int M, GraphView G, const int *__restrict__ counters,
-                  const float4 *__restrict__ gbar, long long gbar_model_stride, double units_per_ev,
+                  const float4 *__restrict__ gbar, long long model_stride, double units_per_ev,
                   float *__restrict__ forces, float *__restrict__ forces_std) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -425,7 +385,7 @@ k_finalize_forces(int N, int M, GraphView G, const int *__restrict__ counters,
     double fm[3] = {0, 0, 0}, f2[3] = {0, 0, 0};
     for (int m = 0; m < M; ++m) {
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
-        const float4 *gb = gbar + (size_t)m * gbar_model_stride;
+        const float4 *gb = gbar + (size_t)m * model_stride;
         for (int e = e0 + lane; e < e1; e += 64) {
             const int r = G.rev[e];
             if (r < 0) continue;
@@ -453,7 +413,7 @@ k_finalize_forces(int N, int M, GraphView G, const int *__restrict__ counters,
 // symmetrised, Voigt order xx yy zz yz xz xy, eV / A^3; ensemble mean and population std over the models (like the forces).
 // The stoichiometric offset does not depend on the strain.  One workgroup per chain, fp64 accumulation, fixed order.
 __global__ void __launch_bounds__(256)
-k_stress(int M, GraphView G, const int *__restrict__ counters, const float4 *__restrict__ gbar, long long gbar_model_stride,
+k_stress(int M, GraphView G, const int *__restrict__ counters, const float4 *__restrict__ gbar, long long model_stride,
          const double *__restrict__ cell, double units_per_ev, double *__restrict__ stress, double *__restrict__ stress_std) {
     __shared__ double red[9][256];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -463,7 +423,7 @@ k_stress(int M, GraphView G, const int *__restrict__ counters, const float4 *__r
     const double vol = fabs(c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]));
     double mean[6] = {0, 0, 0, 0, 0, 0}, sq[6] = {0, 0, 0, 0, 0, 0};
     for (int m = 0; m < M; ++m) {
-        const float4 *gb = gbar + (size_t)m * gbar_model_stride;
+        const float4 *gb = gbar + (size_t)m * model_stride;
         double w[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int e = s0 + tid; e < s1; e += 256) {
             const float4 r = G.edge[e];
@@ -558,14 +518,36 @@ k_finalize_energy(int N, int M, const unsigned char *__restrict__ active, const 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// partial edge-gradient buffers per model: as many as the widest class present writes (one without the reverse edge kernels)
-static int gbar_layer_sets(const vssr_handle *h) { return h->gbar_mode == 2 ? h->num_conv - 1 : h->gbar_mode == 1 && h->num_conv > 2 ? h->num_conv - 1 : 1; }
+// partial edge-gradient buffers per model (d_gpart): one set per matrix-pipe layer, each as many groups as the narrowest slice class
+// present writes; 1 = no partial buffers (one layer, or every chain gathers)
 int painn_gbar_groups(const vssr_handle *h) {
     if (h->num_conv < 2) return 1;
     const int per_set = h->n_bclass[EDGE_BCLASS_FS4] ? edge_class_groups(EDGE_BCLASS_FS4)
                         : h->n_bclass[EDGE_BCLASS_FS8] ? edge_class_groups(EDGE_BCLASS_FS8)
                         : (h->n_bclass[EDGE_BCLASS_FS16] || h->n_bclass[EDGE_BCLASS_FS16P]) ? edge_class_groups(EDGE_BCLASS_FS16) : 1;
-    return per_set > 1 ? per_set * gbar_layer_sets(h) : 1;
+    return per_set > 1 ? per_set * (h->num_conv - 1) : 1;
+}
+
+GraphView graph_view(const vssr_handle *h) {
+    GraphView G;
+    G.n_atoms = h->n_atoms;
+    G.n_cfg = h->n_cfg;
+    G.atom_cfg = h->d_atom_cfg.as<int>();
+    G.cfg_start = h->d_cfg_start.as<int>();
+    G.row_start = h->d_row_start.as<int>();
+    G.deg = h->d_deg.as<int>();
+    G.edge = h->d_edge.as<float4>();
+    G.rev = h->d_rev.as<int>();
+    G.erec = h->d_erec.as<float4>();
+    G.rho = h->d_rho.as<float>();
+    G.rho16 = h->d_rho16.as<uint4>();
+    G.drho16 = h->d_drho16.as<uint4>();
+    G.zslot = h->d_zslot.as<unsigned char>();
+    G.dist2 = h->d_dist.as<float2>();
+    G.bundle = h->d_bundle.as<int4>();
+    G.chain_class = h->d_chain_class.as<unsigned char>();
+    G.act = ActiveView{h->active_mask, h->d_atom_cfg.as<int>(), h->d_sat.as<unsigned>()};
+    return G;
 }
 
 int painn_alloc_state(vssr_handle *h) {
@@ -595,9 +577,8 @@ int painn_alloc_state(vssr_handle *h) {
         h->d_upd_save.ensure(update_save_bytes((int)N, (int)M) * L))
         return set_err(h, VSSR_E_NOMEM, "forward intermediates of the update blocks: out of device memory");
     const size_t groups = (size_t)painn_gbar_groups(h);
-    const bool compact = h->gbar_mode == 2 && groups > 1;
-    if (h->d_gbar.ensure(sizeof(float4) * M * (compact ? 1 : groups) * (size_t)h->slot_cap) ||
-        (compact && h->d_gpart.ensure(sizeof(float) * 3 * M * groups * (size_t)h->slot_cap + 256)))
+    if (h->d_gbar.ensure(sizeof(float4) * M * (size_t)h->slot_cap) ||
+        (groups > 1 && h->d_gpart.ensure(sizeof(float) * 3 * M * groups * (size_t)h->slot_cap + 256)))
         return set_err(h, VSSR_E_NOMEM, "edge-gradient buffer: out of device memory");
     sv.gbar = h->d_gbar.as<float4>();
     return painn_alloc_results(h);
@@ -631,24 +612,7 @@ int painn_run(vssr_handle *h, uint32_t want) {
     if (rc) return rc;
     StateView &sv = h->sv;
     sv.e_excl = h->d_excl.as<float>();
-    GraphView G;
-    G.n_atoms = N;
-    G.n_cfg = h->n_cfg;
-    G.atom_cfg = h->d_atom_cfg.as<int>();
-    G.cfg_start = h->d_cfg_start.as<int>();
-    G.row_start = h->d_row_start.as<int>();
-    G.deg = h->d_deg.as<int>();
-    G.edge = h->d_edge.as<float4>();
-    G.rev = h->d_rev.as<int>();
-    G.erec = h->d_erec.as<float4>();
-    G.rho = h->d_rho.as<float>();
-    G.dist2 = h->d_dist.as<float2>();
-    G.rho16 = h->d_rho16.as<uint4>();
-    G.drho16 = h->d_drho16.as<uint4>();
-    G.zslot = h->d_zslot.as<unsigned char>();
-    G.bundle = h->d_bundle.as<int4>();
-    G.chain_class = h->d_chain_class.as<unsigned char>();
-    G.act = ActiveView{h->active_mask, h->d_atom_cfg.as<int>(), h->d_sat.as<unsigned>()};
+    const GraphView G = graph_view(h);
     const ActiveView &av = G.act;
     const ModelW *MW = h->model_table.as<ModelW>();
     const int *counters = h->d_counters.as<int>();
@@ -661,10 +625,9 @@ int painn_run(vssr_handle *h, uint32_t want) {
     // slices; larger chains: the gather kernels) -- up to three launches per layer and direction, each over the chains of one
     // class.  Layer 0 is factorised by species (painn_l0.hip) or, with more than 8 species / VSSR_L0_FACTORISE=0, runs the
     // gather kernels for every chain (its v input is zero and only two filter sections matter).
-    const int n_groups = painn_gbar_groups(h);   // partial gbar buffers per model
-    const int layer_sets = n_groups > 1 ? gbar_layer_sets(h) : 1;
-    const bool compact = h->gbar_mode == 2 && n_groups > 1;   // 12-byte partial records in d_gpart, final float4 buffer per model
-    const int fin_groups = compact ? 1 : n_groups;             // buffers between two models in the final float4 array
+    const int n_groups = painn_gbar_groups(h);   // partial edge-gradient buffers per model: L - 1 layer sets of per_set groups
+    const bool partial = n_groups > 1;           // some chain takes the matrix-pipe reverse kernels: 12-byte records in d_gpart
+    const int layer_sets = partial ? L - 1 : 1, per_set = n_groups / layer_sets;
     const int *cls_list[EDGE_MFMA_CLASSES];
     const int *bcls_list[EDGE_MFMA_BCLASSES];
     {
@@ -760,32 +723,26 @@ int painn_run(vssr_handle *h, uint32_t want) {
             P.begin((l == 0 && l0_fact) ? KC_L0_BWD : KC_EDGE_BWD, st);
             int accumulate = (l != L - 1);
             if (l == 0 && l0_fact) {
-                rc = l0_run_reverse(h, G, (int)(L == 1), (int)compact, sbar_msg_l, sv.vbar_msg, sv.gbar, (long long)h->slot_cap,
-                                    fin_groups);
+                rc = l0_run_reverse(h, G, (int)(L == 1), (int)partial, sbar_msg_l, sv.vbar_msg, sv.gbar);
                 if (rc) return rc;
-            } else if (l == 0)   // adds into partial buffer 0 of every model (model stride = n_groups buffers)
+            } else if (l == 0)   // adds into the final buffer of every model
                 hipLaunchKernelGGL(k_edge_bwd<true>, g_atom, blk, 0, st, N, l, accumulate, MW, G, counters,
                                    h->cutoff, h->excl_vol, h->excl_sigma, h->excl_power, sv.v_in[l], sv.phi[l],
                                    sbar_msg_l, sv.vbar_msg, sv.phibar, sv.vbar, sv.gbar,
-                                   (long long)h->slot_cap * fin_groups, -1, (int)compact);
+                                   (long long)h->slot_cap, -1, (int)partial);
             else {
-                // (a launch that writes a partial-gradient set for the first time writes compact records: k_edge_bwd_mfma<.., FIRST = true>
-                //  has their stride compiled in)
-                if ((l == L - 1 || layer_sets > 1) && !compact && h->n_cfg > n_gather)
-                    return set_err(h, VSSR_E_STATE, "matrix-pipe reverse kernels need the compact partial-gradient records");
+                // (every layer has its own set of partial records, so no launch adds to what another wrote)
                 for (int cls = 0; cls < EDGE_MFMA_BCLASSES; ++cls)
-                    launch_edge_bwd_mfma(st, cls, N, bcls_list[cls], h->n_bclass[cls], M, l, (int)(l == L - 1 || layer_sets > 1),
-                                         h->max_bclass_atoms[cls], MW, G, counters, (int)(h->slot_cap - 1), sv.v_in[l], sv.phi[l],
-                                         sbar_msg_l, sv.vbar_msg, sv.phibar, sv.vbar,
-                                         compact ? h->d_gpart.as<float>() : reinterpret_cast<float *>(sv.gbar), (long long)h->slot_cap,
-                                         n_groups, layer_sets > 1 ? (L - 1 - l) * (n_groups / layer_sets) : 0, compact ? 3 : 4,
+                    launch_edge_bwd_mfma(st, cls, N, bcls_list[cls], h->n_bclass[cls], M, l, h->max_bclass_atoms[cls], MW, G, counters,
+                                         (int)(h->slot_cap - 1), sv.v_in[l], sv.phi[l], sbar_msg_l, sv.vbar_msg, sv.phibar, sv.vbar,
+                                         h->d_gpart.as<float>(), (long long)h->slot_cap, n_groups, (L - 1 - l) * per_set,
                                          cls == EDGE_BCLASS_FS16P ? h->d_bundle_subb.as<int4>() : (const int4 *)nullptr,
                                          h->sub_chunk_bwd ? h->sub_chunk_bwd : sub_chunk_max_bwd());
-                if (n_gather)   // partial buffer 0 of every model
+                if (n_gather)   // the final buffer of every model
                     hipLaunchKernelGGL(k_edge_bwd<false>, g_atom, blk, 0, st, N, l, accumulate, MW, G, counters,
                                        h->cutoff, h->excl_vol, h->excl_sigma, h->excl_power, sv.v_in[l], sv.phi[l],
                                        sbar_msg_l, sv.vbar_msg, sv.phibar, sv.vbar, sv.gbar,
-                                       (long long)h->slot_cap * fin_groups, (int)EDGE_BCLASS_GATHER, 0);
+                                       (long long)h->slot_cap, (int)EDGE_BCLASS_GATHER, 0);
             }
             P.end(st);
             if (l > 0 && !fused) {
@@ -796,51 +753,27 @@ int painn_run(vssr_handle *h, uint32_t want) {
         }
     }
     P.begin(KC_FINALIZE, st);
-    if (want & VSSR_WANT_FORCES) {
-#ifdef ABL_LDS_FORCE   // ablation build (profiles/r04/NOTES_force_accum.md): no per-slot partial records, nothing to reduce (results incomplete)
-        if (compact) {   // (skipped)
-        } else if (false) {
-#else
-        if (compact) {
-#endif
-            const int uni = h->active_mask ? 0 : h->n_bclass[EDGE_BCLASS_FS16] + h->n_bclass[EDGE_BCLASS_FS16P] == h->n_cfg ? 8 : h->n_bclass[EDGE_BCLASS_FS8] == h->n_cfg ? 16
-                            : h->n_bclass[EDGE_BCLASS_FS4] == h->n_cfg ? 32 : 0;
-            const dim3 grid = uni ? dim3((unsigned)((h->slot_cap + 255) / 256), 1) : dim3(h->n_cfg, 12);
-            hipLaunchKernelGGL(k_reduce_gpart, grid, dim3(256), 0, st, M, n_groups, layer_sets, G, counters, h->d_gpart.as<float>(),
-                               sv.gbar, (long long)h->slot_cap, uni);
-        } else if (n_groups > 1) {
-            const int cls_only = h->n_bclass[EDGE_BCLASS_FS16] + h->n_bclass[EDGE_BCLASS_FS16P] == h->n_cfg ? EDGE_BCLASS_FS16
-                                 : h->n_bclass[EDGE_BCLASS_FS8] == h->n_cfg ? EDGE_BCLASS_FS8
-                                 : h->n_bclass[EDGE_BCLASS_FS4] == h->n_cfg ? EDGE_BCLASS_FS4 : -1;
-            if (cls_only >= 0 && !h->active_mask && (layer_sets == 1 || n_gather == 0))   // (switched-off chains keep their reduced gradients: the per-chain form skips them)
-                hipLaunchKernelGGL(k_reduce_gbar_groups_uniform, dim3((unsigned)((h->slot_cap + 255) / 256)), dim3(256), 0, st, M,
-                                   n_groups, counters, sv.gbar, (long long)h->slot_cap);
-            else
-                hipLaunchKernelGGL(k_reduce_gbar_groups, dim3(h->n_cfg, 12), dim3(256), 0, st, M, n_groups, layer_sets, G, counters, sv.gbar,
-                                   (long long)h->slot_cap);
-        }
-        hipLaunchKernelGGL(k_finalize_forces, dim3((N + 3) / 4), dim3(256), 0, st, N, M, G, counters, sv.gbar,
-                           (long long)h->slot_cap * fin_groups, h->units_per_ev, h->d_forces.as<float>(),
-                           h->d_forces_std.as<float>());
+    if (want_forces && partial) {
+        const int uni = h->active_mask ? 0 : h->n_bclass[EDGE_BCLASS_FS16] + h->n_bclass[EDGE_BCLASS_FS16P] == h->n_cfg ? 8 : h->n_bclass[EDGE_BCLASS_FS8] == h->n_cfg ? 16
+                        : h->n_bclass[EDGE_BCLASS_FS4] == h->n_cfg ? 32 : 0;
+        const dim3 grid = uni ? dim3((unsigned)((h->slot_cap + 255) / 256), 1) : dim3(h->n_cfg, 12);
+        hipLaunchKernelGGL(k_reduce_gpart, grid, dim3(256), 0, st, M, n_groups, layer_sets, G, counters, h->d_gpart.as<float>(),
+                           sv.gbar, (long long)h->slot_cap, uni);
     }
-    hipLaunchKernelGGL(k_finalize_energy, dim3(h->n_cfg), dim3(256), 0, st, N, M, h->active_mask, G.cfg_start, Z, sv.e_atom,
-                       h->units_per_ev, h->has_offset ? h->offset_per_z.as<double>() : (const double *)nullptr,
-                       h->offset_const, h->d_energy.as<float>(), h->d_energy_std.as<float>(),
-                       h->d_energy_models.as<float>(), h->d_energy64.as<double>(), h->d_e_atoms.as<float>(),
-                       h->d_sat.as<unsigned>(), h->d_sat_out.as<unsigned>());
+    painn_finalize(h, G, want);
     P.end(st);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;
 }
 
-// force assembly and energy reduction of the general path (painn_gen.hip): its reverse pass leaves one reduced edge-gradient
-// buffer per model (model stride gbar_model_stride), as the compact records of this path do after k_reduce_gpart
-void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want, long long gbar_model_stride) {
+// force assembly and energy reduction of both paths: the reverse pass leaves one final edge-gradient buffer per model (model stride
+// slot_cap) -- the general path (painn_gen.hip) directly, this path after k_reduce_gpart
+void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want) {
     const int N = h->n_atoms, M = h->n_models;
     hipStream_t st = h->stream;
     if (want & VSSR_WANT_FORCES)
         hipLaunchKernelGGL(k_finalize_forces, dim3((N + 3) / 4), dim3(256), 0, st, N, M, G, h->d_counters.as<int>(), h->sv.gbar,
-                           gbar_model_stride, h->units_per_ev, h->d_forces.as<float>(), h->d_forces_std.as<float>());
+                           (long long)h->slot_cap, h->units_per_ev, h->d_forces.as<float>(), h->d_forces_std.as<float>());
     hipLaunchKernelGGL(k_finalize_energy, dim3(h->n_cfg), dim3(256), 0, st, N, M, h->active_mask, G.cfg_start, h->d_Z.as<int>(),
                        h->sv.e_atom, h->units_per_ev, h->has_offset ? h->offset_per_z.as<double>() : (const double *)nullptr,
                        h->offset_const, h->d_energy.as<float>(), h->d_energy_std.as<float>(), h->d_energy_models.as<float>(),
@@ -850,16 +783,9 @@ void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want, long long
 // vssr_batch_stress: the virial of the last evaluation (forces must have been computed: gbar holds the reduced edge gradients)
 int painn_stress(vssr_handle *h) {
     if (h->d_stress.ensure(sizeof(double) * 12 * (size_t)h->n_cfg)) return set_err(h, VSSR_E_DEVICE, "out of device memory (stress)");
-    GraphView G{};
-    G.n_atoms = h->n_atoms;
-    G.n_cfg = h->n_cfg;
-    G.cfg_start = h->d_cfg_start.as<int>();
-    G.row_start = h->d_row_start.as<int>();
-    G.edge = h->d_edge.as<float4>();
-    const int fin_groups = h->gbar_mode == 2 ? 1 : painn_gbar_groups(h);
     double *out = h->d_stress.as<double>();
-    hipLaunchKernelGGL(k_stress, dim3(h->n_cfg), dim3(256), 0, h->stream, h->n_models, G, h->d_counters.as<int>(), h->sv.gbar,
-                       (long long)h->slot_cap * fin_groups, h->d_cell.as<double>(), h->units_per_ev, out, out + 6 * (size_t)h->n_cfg);
+    hipLaunchKernelGGL(k_stress, dim3(h->n_cfg), dim3(256), 0, h->stream, h->n_models, graph_view(h), h->d_counters.as<int>(), h->sv.gbar,
+                       (long long)h->slot_cap, h->d_cell.as<double>(), h->units_per_ev, out, out + 6 * (size_t)h->n_cfg);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;
 }

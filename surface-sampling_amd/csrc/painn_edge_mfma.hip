@@ -86,8 +86,8 @@ __device__ __forceinline__ void mfma_pre_fence(u32x4 &a, u32x4 &b) {
 __device__ __forceinline__ void arrival_fence(u32x4 &a, u32x4 &b) {
     asm volatile("; arrival_fence" : "+v"(a), "+v"(b) : : "memory");
 }
-__device__ __forceinline__ void arrival_fence(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d, float &g) {
-    asm volatile("; arrival_fence" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(g) : : "memory");
+__device__ __forceinline__ void arrival_fence(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d) {
+    asm volatile("; arrival_fence" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : : "memory");
 }
 // Explicit register copy.  The table buffers are refilled (for the step after next) in the middle of the step that consumes
 // them; small values that stay live to the end of the step are first moved out with a real v_mov, so that the buffer is
@@ -366,11 +366,7 @@ struct BundleWalk {
     __device__ __forceinline__ static int steps(const int4 &q) { return max(__builtin_amdgcn_readfirstlane(q.z) >> 2, 2); }
     __device__ __forceinline__ void init(const int4 *table, int n, int w, int stream) {
         tab = table; Nc = n; wave = w; st = stream;
-#ifdef ABL_NO_TAIL   // ablation: the bundles beyond the last full round of the workgroup's waves are dropped (results wrong)
-        const int NB0 = (n + 3) >> 2, NB = NB0 >= NW ? NB0 - NB0 % NW : NB0, full = NB / NW, rem = NB - full * NW;
-#else
         const int NB = (n + 3) >> 2, full = NB / NW, rem = NB - full * NW;
-#endif
         nj = full + ((((full & 1) ? NW - 1 - w : w) < rem) ? 1 : 0);
         j = 0; t = 0;
         bool ok0, ok1;
@@ -531,9 +527,6 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
     }
     bw.init((SUB ? bundle_tab : G.bundle) + a0, n_entries, __builtin_amdgcn_readfirstlane(wave), p >> 2);
     if (bw.nj == 0) return;   // (no barrier below)
-#ifdef ABL_STAGE_ONLY   // ablation: staging + prologue only (results wrong)
-    if (bw.nj > 0) return;
-#endif
     float ds[NF], dvx[NF], dvy[NF], dvz[NF];
 #pragma unroll
     for (int r = 0; r < NF; ++r) { ds[r] = 0.f; dvx[r] = 0.f; dvy[r] = 0.f; dvz[r] = 0.f; }
@@ -565,11 +558,7 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
     // so a table load has ~1.6 steps to arrive (L2 / HBM latency is of the order of one step).
     u32x4 rq[2][2];
     auto fetch = [&](int buf, int quad_first_slot, bool valid) {   // quad_first_slot: first slot of the stream's quad
-#ifdef ABL_TABLE_L2   // ablation: every table read hits a 256 KB window (results wrong)
-        const u32x4 *rp = rho_lane + (size_t)(valid ? ((quad_first_slot >> 2) & 511) : zero_quad) * 32;
-#else
         const u32x4 *rp = rho_lane + (size_t)(unsigned)(valid ? (quad_first_slot >> 2) : zero_quad) * 32;   // (unsigned: no sign extension, one shift-add)
-#endif
         rq[buf][0] = rp[0]; rq[buf][1] = rp[16];
     };
     {
@@ -617,15 +606,11 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
         for (int ph = 0; ph < 2; ++ph) {   // two steps per iteration: one table buffer per step parity
             arrival_fence(rq[ph][0], rq[ph][1]);
             EPH(1)   // wait for this step's table entries
-#ifdef ABL_LDS_BCAST   // ablation: every gather reads row 0 or 1 (no LDS bank conflicts; results wrong)
-            const int jn = (int)(rq[ph][0][3] >> 16) & 1;
-#else
             int jn = (int)rq[ph][1][3];           // chain-local neighbor of this lane's slot (last word of the record's unit 1)
             if constexpr (SUB) {   // staged row of the neighbor, or the zero row for a neighbor of the other half
                 const unsigned jl = (unsigned)(jn - lo);
                 jn = jl < (unsigned)ns ? (int)jl : ns;
             }
-#endif
             if (bw.t == bw.Lc) {   // wave-uniform: the bundle is complete
                 flush_bundle();
                 bw.advance();
@@ -695,13 +680,8 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
             EPH(5)   // matrix results arrive + first feature
             fetch(ph, nq, nv);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef ABL_HALF_VALU
-#pragma unroll
-            for (int r = 1; r < NF / 2; ++r) message(r);
-#else
 #pragma unroll
             for (int r = 1; r < NF; ++r) message(r);
-#endif
             ++bw.t;
             EPH(6)   // prefetch issue + remaining features
         }
@@ -718,10 +698,9 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
 //   dE/du(n->c) = sum_f  phi_c[c] w[c] vbar_n            (dw = Wd_ext . d rho/dd)
 // Same slot-major lane layout as the forward kernel: lane (p, fq) owns slot p and features 4fq..4fq+3, so
 // the sums over features are 4 in-lane terms + a reduction over the 4 feature quarters (lanes p, p+16,
-// p+32, p+48).  One workgroup = (chain, model, group of SLICES_PER_WG feature slices) with its own partial edge-gradient
-// buffer G[m][group][slot]: within a layer every slot is written once per group, across layers the SAME lane adds to
-// it in a fixed order (deterministic read-modify-write, old value prefetched one step ahead); finalize reduces the
-// groups in a streaming pass.
+// p+32, p+48).  One workgroup = (chain, model, feature slice) with its own partial edge-gradient buffer
+// P[m][layer set][slice][slot] of 12-byte records: every slot is written exactly once per launch sequence of a layer and nothing is
+// read back; k_reduce_gpart (painn.hip) sums the sets and slices into the final float4 buffer in a streaming pass.
 // Workgroup width WAVES.  4 waves: two workgroups share a CU (81 KB of LDS each at 272 atoms, 16-feature slices), one stages its
 // slice while the other computes (6.4 -> 6.0 ms / step), 2 waves per SIMD with the 256-register budget.  When the slice of the
 // launch's largest chain is too big for two workgroups per CU (> 301 atoms with 16-feature slices, > 573 with 8-feature
@@ -731,13 +710,8 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
 template <int NF, int WAVES>
 constexpr int cen_floats() { return WAVES * 4 * 4 * 6 * NF; }   // current-centre store: [stream][feature quarter][phi a, b, c, v x, y, z][NF]
 template <int NF, int WAVES>
-#ifdef ABL_LDS_FORCE   // ablation (profiles/r04/NOTES_force_accum.md): per-atom fixed-point force accumulators in LDS instead of per-slot records
-size_t edge_bwd_lds_bytes_t(int max_atoms) { return sizeof(float) * ((size_t)max_atoms * EdgeGeo<NF>::ROWB + cen_floats<NF, WAVES>()) + 24 * (size_t)max_atoms + 32; }
-#else
 size_t edge_bwd_lds_bytes_t(int max_atoms) { return sizeof(float) * ((size_t)max_atoms * EdgeGeo<NF>::ROWB + cen_floats<NF, WAVES>()); }
-#endif
 
-// FIRST: the launch writes the partial edge-gradient buffers for the first time (last layer): nothing to add to.
 // (The narrow slices need fewer registers -- 145 / 110 with 8- / 4-feature slices -- but wider workgroups, 12 resp. 16 waves when one
 // workgroup owns the CU, changed nothing: 9.08 vs 9.01 .. 9.22 ms at 700 atoms, 37.1 vs 36.9 at 1 400, profiles/r04/ab_bwd_wide.txt;
 // these launches are bound by the L2 -> L1 stream of the per-slot tables, which every slice re-reads, not by latency.)
@@ -746,14 +720,14 @@ size_t edge_bwd_lds_bytes_t(int max_atoms) { return sizeof(float) * ((size_t)max
 // zeros (every term of its contribution carries sbar_n / vbar_n) and sends its gradient record to the spare entry, so the record of
 // a slot is written by exactly one pass.  Pass 0 writes phibar_c / vbar_c (+ the residual vbar_msg_c, from memory); a later pass
 // adds to what is there.
-template <int NF, bool FIRST, int WAVES, bool SUB = false>
+template <int NF, int WAVES, bool SUB = false>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))   // 2 waves per SIMD either way: use the 256 VGPRs
 k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
                 const int *__restrict__ counters, int zero_slot, int n_models, int max_atoms,
                 const int *__restrict__ list, int n_list,
                 const float *__restrict__ v_in, const float *__restrict__ phi, const float *__restrict__ sbar_msg,
                 const float *__restrict__ vbar_msg, typename EdgeOut<SUB>::ptr phibar, typename EdgeOut<SUB>::ptr vbar_in,
-                float *__restrict__ gbar, long long gbar_stride, int n_groups, int group_off, int rec,
+                float *__restrict__ gpart, long long slot_cap, int n_groups, int group_off,
                 const int4 *__restrict__ bundle_tab, const int *__restrict__ n_entries_tab, int pass, int chunk_max) {
     using LY = EdgeGeo<NF>;
     constexpr int FS = LY::FS, NSG = LY::NSLICE, NT = LY::NT, ROWB = LY::ROWB, BWD_THREADS = 64 * WAVES;
@@ -775,14 +749,11 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
         ns = min(chunk, Nc - lo);
     }
     const int lane = tid & 63, wave = tid >> 6, p = lane & 15, fq = lane >> 4, e = p & 3;
-    const int last_slot = max(G.row_start[a0 + Nc] - 1, 0);
     const LayerW &W = MW[m].layer[l];
-    // partial edge-gradient buffer of this (model, layer set, slice): rec floats per slot -- 4 (float4 records, group 0 doubles
-    // as the final buffer) or 3 (compact per-layer buffers, reduced into the separate final buffer by k_reduce_gpart)
-    // records of a FIRST launch are the compact 12-byte ones (painn.hip launches FIRST only onto them): a constant stride lets the
-    // per-step store address be a shift-add instead of a quarter-rate 64-bit multiply-add
-    const int rec_c = FIRST ? 3 : rec;
-    float *gb = gbar + (size_t)(m * n_groups + group_off + fs) * gbar_stride * rec_c;
+    // partial edge-gradient buffer of this (model, layer set, slice): 12-byte records, written once per slot and summed into the
+    // final float4 buffer by k_reduce_gpart (painn.hip); the constant stride makes the per-step store address a shift-add
+    constexpr int REC = 3;
+    float *gb = gpart + (size_t)(m * n_groups + group_off + fs) * slot_cap * REC;
     const u32x4 *rho_lane = reinterpret_cast<const u32x4 *>(G.rho16) + fq * 4 + e;   // quad-interleaved tables, see forward
     const u32x4 *drho_lane = reinterpret_cast<const u32x4 *>(G.drho16) + fq * 4 + e;
     const int zero_quad = (zero_slot + 1) / 4 - 1;
@@ -840,11 +811,6 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
 #pragma unroll
         for (int i3 = 0; i3 < 2; ++i3) wA[T][i3] = sec < 0 ? (u32x4){0u, 0u, 0u, 0u} : gload_u32x4(wsrc + i3);
     }
-#ifdef ABL_LDS_FORCE
-    unsigned long long *facc = reinterpret_cast<unsigned long long *>(tile + (((size_t)max_atoms * ROWB + cen_floats<NF, WAVES>() + 1) & ~(size_t)1));
-    for (int i = tid; i < 3 * Nc + 3; i += BWD_THREADS) facc[i] = 0ull;
-    float gown = 0.f;
-#endif
     __syncthreads();
 
     BundleWalk<BWD_THREADS / 64> bw;   // work list: bundles of 4 centres, see the forward kernel
@@ -855,9 +821,6 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
     }
     bw.init((SUB ? bundle_tab : G.bundle) + a0, n_entries, __builtin_amdgcn_readfirstlane(wave), p >> 2);
     if (bw.nj == 0) return;   // (no barrier below)
-#ifdef ABL_STAGE_ONLY   // ablation: staging + prologue only (results wrong)
-    if (bw.nj > 0) return;
-#endif
 
     // ---- per-centre data of this lane's NF features: phi_c (a, b, c) and v_c -------------------------------------------
     // The CURRENT centre's values live in a small LDS record per (stream, feature quarter) and are re-read every step
@@ -907,14 +870,6 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
         quad_sum_n<NF>(accb); quad_sum_n<NF>(accc); quad_sum_n<NF>(accx); quad_sum_n<NF>(accy); quad_sum_n<NF>(accz);
         const float (&tb)[NF] = accb, (&tc)[NF] = accc, (&tx)[NF] = accx, (&ty)[NF] = accy, (&tz)[NF] = accz;
         const int c = bw.cur.x;
-#ifdef ABL_LDS_FORCE
-        {
-            const float go = quad_sum(gown);
-            gown = 0.f;
-            if (e == 0 && c >= 0 && gcomp_id < 3)
-                atomicAdd(&facc[3 * c + gcomp_id], (unsigned long long)__float2ll_rn(go * 4294967296.f));
-        }
-#endif
         if (e == 0 && c >= 0) {
             const size_t ga = mN + a0 + c;
             const fvx cv[6] = {cen[0], cen[1], cen[2], cen[3], cen[4], cen[5]};   // record of the completed centre
@@ -950,29 +905,18 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
 
     // Table entries of this lane's slot; exhausted streams read the all-zero quad.  Two buffers, one per step parity:
     // buffer ph is consumed by the step of parity ph and refilled right after that step's MFMAs for the step after next
-    // (~1.6 steps for a load to arrive).  The old partial edge gradient of the slot (written by the previous layer for
-    // this lane's slot; a slot is visited once per launch, so the early read is safe) travels with the tables.
-    float *gcomp = gb + min(gcomp_id, rec_c - 1);   // component this row ends up with (id 3: none -- that row only ever writes the spare entry)
+    // (~1.6 steps for a load to arrive).
+    float *gcomp = gb + min(gcomp_id, REC - 1);   // component this row ends up with (id 3: none -- that row only ever writes the spare entry)
     u32x4 rq[2][2], dq[2][2];
-    float gold[2] = {0.f, 0.f};
     auto fetch = [&](int buf, int quad_first_slot, bool valid) {
-#ifdef ABL_TABLE_L2
-        const size_t off = (size_t)(valid ? ((quad_first_slot >> 2) & 511) : zero_quad) * 32;
-#else
         const size_t off = (size_t)(unsigned)(valid ? (quad_first_slot >> 2) : zero_quad) * 32;   // (unsigned: no sign extension, one shift-add)
-#endif
         const u32x4 *rp = rho_lane + off, *dp = drho_lane + off;
         rq[buf][0] = rp[0]; rq[buf][1] = rp[16];
-#ifdef ABL_3LOADS   // ablation: three table loads per step instead of four (results wrong)
-        dq[buf][0] = dp[0]; dq[buf][1] = dq[buf][0];
-#else
         dq[buf][0] = dp[0]; dq[buf][1] = dp[16];
-#endif
-#ifdef ABL_NO_GBAR   // ablation build (tools/build_variant.sh): same instruction stream, the partial edge-gradient buffers stay in L2
-        if (!FIRST) gold[buf] = gcomp[(size_t)min((quad_first_slot + e) & 1023, last_slot) * rec_c];
-#else
-        if (!FIRST) gold[buf] = gcomp[(size_t)min(quad_first_slot + e, last_slot) * rec_c];
-#endif
+        // (layout pin: with `e` among this lambda's captures the hot loop has its compact block layout; without it the compiler splits
+        //  two loop edges and the common path takes two more branches per iteration -- otherwise the same instruction stream; measured
+        //  3.625 -> 3.646 ms per step on the 260-atom workload with AMD clang 22.0.0git / roc-7.2.0, profiles/r22/NOTES_painn_one_layout.md)
+        (void)e;
     };
     {
         bool v0, v1;
@@ -990,20 +934,15 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
     while (bw.j < bw.nj) {
 #pragma unroll
         for (int ph = 0; ph < 2; ++ph) {
-            arrival_fence(rq[ph][0], rq[ph][1], dq[ph][0], dq[ph][1], gold[ph]);
+            arrival_fence(rq[ph][0], rq[ph][1], dq[ph][0], dq[ph][1]);
             EPH(1)
             bool in_range = true;
-#ifdef ABL_LDS_BCAST   // ablation: every gather reads row 0 or 1 (no LDS bank conflicts; results wrong)
-            const int jn = (int)(rq[ph][0][3] >> 16) & 1;
-#else
             int jn = (int)rq[ph][1][3];           // chain-local neighbor of this lane's slot (last word of the record's unit 1)
             if constexpr (SUB) {   // staged row of the neighbor, or the zero row for a neighbor of another range
                 const unsigned jl = (unsigned)(jn - lo);
                 in_range = jl < (unsigned)ns;
                 jn = in_range ? (int)jl : ns;
             }
-#endif
-            const float gold_cur = FIRST ? 0.f : take(gold[ph]);
             if (bw.t == bw.Lc) {   // wave-uniform: the bundle is complete
                 flush_bundle();
                 bw.advance();
@@ -1082,13 +1021,8 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
             EPH(5)
             fetch(ph, nq, nv);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef ABL_HALF_VALU   // ablation: half of the per-feature arithmetic (results wrong; profiles/r03/NOTES_packed_fp32.md)
-#pragma unroll
-            for (int r = 1; r < NF / 2; ++r) feature(r);
-#else
 #pragma unroll
             for (int r = 1; r < NF; ++r) feature(r);
-#endif
             EPH(6)   // prefetch issue + remaining features
             // Gradient of edge (n -> c), unit vector -u:  g = -(dE/dd) u + (ub - (ub.u) u) / d, linear in (dpart, ub).
             // The map is applied to the lane's partial sums BEFORE the reduction over the 4 feature quarters (lanes
@@ -1110,51 +1044,21 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
                 // three rows of a real slot write one component each; every other lane writes the spare entry, so the
                 // store is unconditional and the memory-operation count of a step does not depend on the path
                 const bool real = gcomp_id < 3 && real_slot && invd > 0.f && (!SUB || in_range);
-#if defined(ABL_LDS_FORCE)
-                gown += real ? gsum : 0.f;
-                atomicAdd(&facc[real ? 3 * jn + gcomp_id : 3 * Nc], (unsigned long long)__float2ll_rn(-gsum * 4294967296.f));
-#elif defined(ABL_NO_GSTORE)   // ablation: the store only happens for a value the arithmetic never produces
-                if (gsum == 1.2345e33f) gcomp[(size_t)(real ? my_slot : zero_slot) * rec_c] = gsum + gold_cur;
-#elif defined(ABL_STORE4)   // ablation: one 16-byte store every fourth step instead of a dword store per step (same bytes, results wrong)
-                if ((bw.t & 3) == 3) {
-                    float *dst = gcomp + (size_t)(real ? my_slot : zero_slot) * rec_c;
-                    asm volatile("global_store_dwordx4 %0, %1, off" : : "v"(dst), "v"((f32x4){gsum, gsum, gsum, gsum}) : "memory");
-                }
-#elif defined(ABL_ROW3_NO_GSTORE)   // ablation: the row without a component does not store
-                if (gcomp_id < 3) gcomp[(size_t)(real ? my_slot : zero_slot) * rec_c] = gsum + gold_cur;
-#elif defined(ABL_NO_GBAR)
-                gcomp[(size_t)(real ? (my_slot & 1023) : zero_slot) * rec_c] = gsum + gold_cur;
-#else
-                gcomp[(unsigned)(real ? my_slot : zero_slot) * (unsigned)rec_c] = gsum + gold_cur;   // (32-bit index: shift-add for the constant stride)
-#endif
+                gcomp[(unsigned)(real ? my_slot : zero_slot) * (unsigned)REC] = gsum;   // (32-bit index: shift-add for the constant stride)
             }
             ++bw.t;
             EPH(7)   // reduce-scatter + store
         }
     }
     EPH_FLUSH(8)
-#ifdef ABL_LDS_FORCE   // partial forces of this (chain, slice, model, layer) leave as Nc x 3 fixed-point values (here: into the head of its gradient buffer)
-    __syncthreads();
-    {
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(gb) + (size_t)3 * a0;
-        for (int i = tid; i < 3 * Nc; i += BWD_THREADS) dst[i] = facc[i];
-    }
-#endif
 }
-
-
 
 int edge_mfma_init(vssr_handle *h) {
 #define SET_LDS(K) VSSR_HIP(h, hipFuncSetAttribute((const void *)(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
     SET_LDS((k_edge_fwd_mfma<4, true, 16>)); SET_LDS((k_edge_fwd_mfma<4, false, 16>)); SET_LDS((k_edge_fwd_mfma<2, false, 16>)); SET_LDS((k_edge_fwd_mfma<2, false, 16, true>)); SET_LDS((k_edge_fwd_mfma<4, false, SUB16_WAVES, true>));
     SET_LDS((k_edge_fwd_mfma<4, true, 8>)); SET_LDS((k_edge_fwd_mfma<4, true, 4>)); SET_LDS((k_edge_fwd_mfma<1, false, 16>));
-    SET_LDS((k_edge_bwd_mfma<1, true, 4>)); SET_LDS((k_edge_bwd_mfma<1, false, 4>));
-    SET_LDS((k_edge_bwd_mfma<1, true, 8>)); SET_LDS((k_edge_bwd_mfma<1, false, 8>));
-    SET_LDS((k_edge_bwd_mfma<4, true, 4>)); SET_LDS((k_edge_bwd_mfma<4, false, 4>));
-    SET_LDS((k_edge_bwd_mfma<2, true, 4>)); SET_LDS((k_edge_bwd_mfma<2, false, 4>));
-    SET_LDS((k_edge_bwd_mfma<4, true, 8>)); SET_LDS((k_edge_bwd_mfma<4, false, 8>));
-    SET_LDS((k_edge_bwd_mfma<4, true, 8, true>)); SET_LDS((k_edge_bwd_mfma<4, false, 8, true>));
-    SET_LDS((k_edge_bwd_mfma<2, true, 8>)); SET_LDS((k_edge_bwd_mfma<2, false, 8>));
+    SET_LDS((k_edge_bwd_mfma<1, 4>)); SET_LDS((k_edge_bwd_mfma<1, 8>)); SET_LDS((k_edge_bwd_mfma<2, 4>)); SET_LDS((k_edge_bwd_mfma<2, 8>));
+    SET_LDS((k_edge_bwd_mfma<4, 4>)); SET_LDS((k_edge_bwd_mfma<4, 8>)); SET_LDS((k_edge_bwd_mfma<4, 8, true>));
 #undef SET_LDS
     return VSSR_OK;
 }
@@ -1185,44 +1089,40 @@ static_assert(edge_bclass_slices(EDGE_BCLASS_FS16) == EdgeGeo<4>::NSLICE && edge
 // EDGE_CLASS_FS16 / _FS16M / _FS8 (forward); list / n_list: the chains of that class; max_atoms: the largest of them.
 // bundle_sub != nullptr: the multi-pass 16-feature form (per-pass bundle tables of these chains, cut for the reverse chunk size; the
 // partial edge-gradient buffers are then those of the 16-feature class: 8 slices)
-void launch_edge_bwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int layer_first, int max_atoms,
+void launch_edge_bwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int max_atoms,
                           const ModelW *MW, const GraphView &G, const int *counters, int zero_slot,
                           const float *v_in, const float *phi, const float *sbar_msg, const float *vbar_msg,
-                          float *phibar, float *vbar_in, float *gbar, long long gbar_stride, int n_groups, int group_off, int rec,
+                          float *phibar, float *vbar_in, float *gpart, long long slot_cap, int n_groups, int group_off,
                           const int4 *bundle_sub, int sub_chunk) {
     if (n_list <= 0) return;
     if (cls == EDGE_BCLASS_FS16P) {
         const int chunk_max = sub_chunk, passes = sub_passes(max_atoms, chunk_max), staged = min(chunk_max, max_atoms) + 1;
         const int *n_entries = reinterpret_cast<const int *>(bundle_sub + (size_t)SUB_MAX_PASSES * N);
-        for (int pass = 0; pass < passes; ++pass) {
-#define LAUNCH_BWD_SUB(FIRST)                                                                                                    \
-    hipLaunchKernelGGL((k_edge_bwd_mfma<4, FIRST, 8, true>), dim3(((n_list + 7) / 8) * 8 * EdgeGeo<4>::NSLICE * M), dim3(64 * 8),   \
-                       (edge_bwd_lds_bytes_t<4, 8>(staged)), st, N, l, MW, G, counters, zero_slot, M, staged, list, n_list, v_in, phi, \
-                       sbar_msg, vbar_msg, phibar, vbar_in, gbar, gbar_stride, n_groups, group_off, rec, bundle_sub + (size_t)pass * N, \
-                       n_entries, pass, chunk_max)
-            if (layer_first) LAUNCH_BWD_SUB(true); else LAUNCH_BWD_SUB(false);
-#undef LAUNCH_BWD_SUB
-        }
+        for (int pass = 0; pass < passes; ++pass)
+            hipLaunchKernelGGL((k_edge_bwd_mfma<4, 8, true>), dim3(((n_list + 7) / 8) * 8 * EdgeGeo<4>::NSLICE * M), dim3(64 * 8),
+                               (edge_bwd_lds_bytes_t<4, 8>(staged)), st, N, l, MW, G, counters, zero_slot, M, staged, list, n_list, v_in, phi,
+                               sbar_msg, vbar_msg, phibar, vbar_in, gpart, slot_cap, n_groups, group_off, bundle_sub + (size_t)pass * N,
+                               n_entries, pass, chunk_max);
         return;
     }
-#define LAUNCH_BWD(NF, FIRST, WAVES)                                                                                             \
-    hipLaunchKernelGGL((k_edge_bwd_mfma<NF, FIRST, WAVES>), dim3(((n_list + 7) / 8) * 8 * EdgeGeo<NF>::NSLICE * M), dim3(64 * WAVES), \
+#define LAUNCH_BWD(NF, WAVES)                                                                                                    \
+    hipLaunchKernelGGL((k_edge_bwd_mfma<NF, WAVES>), dim3(((n_list + 7) / 8) * 8 * EdgeGeo<NF>::NSLICE * M), dim3(64 * WAVES),   \
                        (edge_bwd_lds_bytes_t<NF, WAVES>(max_atoms)), st, N, l, MW, G, counters, zero_slot, M, max_atoms, list, n_list, \
-                       v_in, phi, sbar_msg, vbar_msg, phibar, vbar_in, gbar, gbar_stride, n_groups, group_off, rec,                \
+                       v_in, phi, sbar_msg, vbar_msg, phibar, vbar_in, gpart, slot_cap, n_groups, group_off,                     \
                        (const int4 *)nullptr, (const int *)nullptr, 0, 0)
     // 4-wave workgroups when two of them can share a CU (LDS) AND there are enough workgroups to give every CU two; a small batch (a
     // single chain = 24 workgroups) takes 8 waves so that a lone workgroup still fills its CU's SIMDs: the per-workgroup walk is the
     // latency of the launch (1 chain of 260 atoms: 103 -> 55 us).  The width never changes a result (a centre's sums run in slot order
     // inside one wave whichever wave that is).
-#define LAUNCH_BWD_W(NF, FIRST)                                                                                                  \
+#define LAUNCH_BWD_W(NF)                                                                                                         \
     do {                                                                                                                         \
         const bool two_fit = 2 * edge_bwd_lds_bytes_t<NF, 4>(max_atoms) <= 160 * 1024;                                           \
         const bool many = (long long)n_list * EdgeGeo<NF>::NSLICE * M > 256;                                                     \
-        if (two_fit && many) LAUNCH_BWD(NF, FIRST, 4); else LAUNCH_BWD(NF, FIRST, 8);                                            \
+        if (two_fit && many) LAUNCH_BWD(NF, 4); else LAUNCH_BWD(NF, 8);                                                          \
     } while (0)
-    if (cls == EDGE_BCLASS_FS4) { if (layer_first) LAUNCH_BWD_W(1, true); else LAUNCH_BWD_W(1, false); }
-    else if (cls == EDGE_BCLASS_FS8) { if (layer_first) LAUNCH_BWD_W(2, true); else LAUNCH_BWD_W(2, false); }
-    else { if (layer_first) LAUNCH_BWD_W(4, true); else LAUNCH_BWD_W(4, false); }
+    if (cls == EDGE_BCLASS_FS4) LAUNCH_BWD_W(1);
+    else if (cls == EDGE_BCLASS_FS8) LAUNCH_BWD_W(2);
+    else LAUNCH_BWD_W(4);
 #undef LAUNCH_BWD_W
 #undef LAUNCH_BWD
 }

@@ -602,16 +602,7 @@ int painn_gen_run(vssr_handle *h, uint32_t want) {
     sv.e_excl = h->d_excl.as<float>();
     sv.gbar = h->d_gbar.as<float4>();
 
-    GraphView G{};
-    G.n_atoms = N;
-    G.n_cfg = h->n_cfg;
-    G.atom_cfg = h->d_atom_cfg.as<int>();
-    G.cfg_start = h->d_cfg_start.as<int>();
-    G.row_start = h->d_row_start.as<int>();
-    G.deg = h->d_deg.as<int>();
-    G.edge = h->d_edge.as<float4>();
-    G.rev = h->d_rev.as<int>();
-    G.act = ActiveView{h->active_mask, h->d_atom_cfg.as<int>(), h->d_sat.as<unsigned>()};
+    const GraphView G = graph_view(h);
     const ActiveView &av = G.act;
     const int *counters = h->d_counters.as<int>();
     const GenLayout gl = gen_layout(F, R, H, NE, L);
@@ -704,7 +695,7 @@ int painn_gen_run(vssr_handle *h, uint32_t want) {
     }
 #undef GEN_EDGE
     P.begin(KC_FINALIZE, st);
-    painn_finalize(h, G, want, (long long)h->slot_cap);
+    painn_finalize(h, G, want);
     P.end(st);
     VSSR_HIP(h, hipGetLastError());
     return VSSR_OK;

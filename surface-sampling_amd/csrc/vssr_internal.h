@@ -327,7 +327,7 @@ struct vssr_handle {
     vssr::DevBuf d_chain_class, d_class_list;
     int n_class[5] = {0, 0, 0, 0, 0}, max_class_atoms[5] = {0, 0, 0, 0, 0};   // forward classes (EDGE_CLASS_*)
     int n_bclass[5] = {0, 0, 0, 0, 0}, max_bclass_atoms[5] = {0, 0, 0, 0, 0};   // reverse classes (EDGE_BCLASS_*); lists follow the forward lists
-    int fs16_max_atoms = -1, fs8_max_atoms = -1, fs4_max_atoms = -1;   // test knobs (VSSR_EDGE_FS16_MAX / _FS8_MAX): lower the class limits (fs4: no knob, always the LDS limit)
+    int fs16_max_atoms = -1, fs8_max_atoms = -1;   // test knobs (VSSR_EDGE_FS16_MAX / _FS8_MAX): lower the class limits
     int max_images = 0;          // largest number of periodic images any configuration of the batch scans per pair
 
     // configuration
@@ -372,8 +372,6 @@ struct vssr_handle {
     vssr::DevBuf d_bundle_sub;   // [2][n_atoms] per-pass bundle tables of the two-pass forward neighbor sum (chains of the 4-feature class)
     int bwd_multi_pass = 1;      // VSSR_EDGE_BWD_MPASS=0: chains of > 557 atoms take the 8- / 4-feature reverse kernels (round 4) instead of the
                                  // 16-feature kernel in several passes; 2: every chain of the matrix-pipe classes takes the multi-pass form (tests)
-    int fwd_mpass_fs8 = 1;       // chains of 406 .. 787 atoms take the 16-feature multi-pass forward form (-9 % against the single-pass
-                                 // 8-feature kernel of round 4, profiles/r05/NOTES_large_chains.md; 0 = that kernel, no knob any more)
     int sub_chunk_fwd = 0, sub_chunk_bwd = 0;   // VSSR_EDGE_SUB_CHUNK=n (tests): atoms per neighbor sub-range instead of what LDS holds
     vssr::DevBuf d_bundle_subb;  // per-pass bundle tables of the reverse multi-pass form (its ranges are larger than the forward's)
     int fwd_two_pass = 16;       // VSSR_EDGE_FWD_2PASS = 0 | 8 | 16: chains of 788 .. 1 462 atoms take the 4-feature forward kernel, or the 8- / 16-feature
@@ -415,13 +413,11 @@ struct vssr_handle {
     vssr::StateView sv;
     vssr::DevBuf d_gbar;
     vssr::DevBuf d_upd_save;     // forward intermediates of every update block for the reverse pass (update_save_bytes per layer)
-    // Partial edge gradients of the reverse neighbor pass (fixed to mode 2 since round 6; modes 0 / 1 are what rounds 2 / 3 measured,
-    // profiles/r03/NOTES_edge_traffic.md, and still serve the gather kernels' float4 records):
-    //   0  one set of float4 buffers per model, the second reverse layer adds to it (read-modify-write), group 0 is reduced in place
-    //   1  one set per reverse layer (no read-modify-write: TA relief in the second launch), float4 records
-    //   2  one set per reverse layer, 12-byte records in a separate buffer, reduced into the final float4 buffer  (default)
-    int gbar_mode = 2;
-    vssr::DevBuf d_gpart;        // mode 2: [M][groups][slot_cap][3] floats
+    // Edge gradients: d_gbar is the final buffer, [M][slot_cap] float4.  Layer 0 and the gather kernels write it directly.  The matrix-pipe
+    // reverse kernels (layers >= 1) write 12-byte partial records into d_gpart, [M][groups][slot_cap][3] floats with groups = (num_conv - 1)
+    // layer sets x the slices of the narrowest class present; k_reduce_gpart adds them to the final buffer.  d_gpart exists exactly
+    // when painn_gbar_groups(h) > 1.
+    vssr::DevBuf d_gpart;
     int debug_keep = 0;          // VSSR_DEBUG_KEEP=1: also materialise what only vssr_debug_read looks at (the last block's vector output)
     int upd_save = 0;            // VSSR_UPD_SAVE=1: update_fwd stores its intermediates and the reverse kernel loads them instead of
                                  // recomputing (measured: update_bwd 2.45 -> 2.21, update_fwd 1.30 -> 1.57..1.60 ms / step: no gain;
@@ -495,8 +491,9 @@ int painn_alloc_state(vssr_handle *h);
 int painn_run(vssr_handle *h, uint32_t want);
 int painn_stress(vssr_handle *h);   // enqueues k_stress: d_stress from the edge gradients of the last run (forces wanted)
 int painn_alloc_results(vssr_handle *h);   // result buffers and saturation flags (both PaiNN paths)
-// energy reduction and force assembly from sv.e_atom / sv.gbar (one reduced edge-gradient buffer per model)
-void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want, long long gbar_model_stride);
+// energy reduction and force assembly from sv.e_atom / sv.gbar (one reduced edge-gradient buffer per model, stride slot_cap): both paths
+void painn_finalize(vssr_handle *h, const GraphView &G, uint32_t want);
+GraphView graph_view(const vssr_handle *h);   // every table of the resident neighbor graph (null where the path built none) + the active mask
 // general-width PaiNN path (painn_gen.hip): weights of any accepted (feat_dim, n_rbf), and the run
 int painn_gen_upload(vssr_handle *h, const vssr_painn_config *cfg);
 int painn_gen_run(vssr_handle *h, uint32_t want);
@@ -596,7 +593,7 @@ int l0_mfma_init(vssr_handle *h);
 int l0_run_forward(vssr_handle *h, const GraphView &G, float *s_msg, float *v_msg);
 // fresh_mfma: chains of the matrix-pipe classes have nothing in the final buffer yet (overwrite), gather-class chains accumulate
 int l0_run_reverse(vssr_handle *h, const GraphView &G, int first_write, int fresh_mfma, const float *sbar_msg, const float *vbar_msg,
-                   float4 *gbar, long long gbar_stride, int n_groups);
+                   float4 *gbar);
 // LDS-slice + MFMA edge stages (painn_edge_mfma.hip)
 int edge_mfma_init(vssr_handle *h);
 // forward neighbor-sum paths: 16-feature slices with / without the scalar residual in LDS, 8- and 4-feature slices, gather kernels
@@ -617,10 +614,11 @@ __host__ __device__ constexpr int sub_chunk_max_bwd() { return 550; }   // rever
 __host__ __device__ constexpr int sub_passes(int n_atoms, int chunk_max) { return (n_atoms + chunk_max - 1) / chunk_max; }
 __host__ __device__ constexpr int sub_chunk(int n_atoms, int chunk_max) { return (n_atoms + sub_passes(n_atoms, chunk_max) - 1) / sub_passes(n_atoms, chunk_max); }
 int edge_class_groups(int cls);       // partial edge-gradient buffers a chain of that class writes per model
-void launch_edge_bwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int layer_first, int max_atoms,
+// gpart: the partial 12-byte records [M][n_groups][slot_cap][3]; this launch writes groups group_off .. group_off + slices - 1
+void launch_edge_bwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int max_atoms,
                           const ModelW *MW, const GraphView &G, const int *counters, int zero_slot,
                           const float *v_in, const float *phi, const float *sbar_msg, const float *vbar_msg,
-                          float *phibar, float *vbar_in, float *gbar, long long gbar_stride, int n_groups, int group_off, int rec,
+                          float *phibar, float *vbar_in, float *gpart, long long slot_cap, int n_groups, int group_off,
                           const int4 *bundle_sub, int sub_chunk);
 void launch_edge_fwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int max_atoms, const ModelW *MW,
                           const GraphView &G, const int *counters, int zero_slot, const float *s_in, const float *v_in,

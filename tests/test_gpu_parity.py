@@ -458,8 +458,9 @@ def test_other_readout_width_runs_the_unfused_reverse_path(golden, oracle_mod):
 
 @pytest.mark.gpu
 def test_fallback_paths_large_chain_many_species_and_forced_gather(golden, oracle_mod):
-    """Paths that the BASELINE workload does not touch: (1) a chain too large for the LDS slices (960 atoms) runs
-    the gather kernels, (2) more than 8 species disables the layer-0 factorisation, (3) forcing the gather kernels
+    """Paths that the BASELINE workload does not touch: (1) a 960-atom chain, beyond the single-pass slice kernels (the
+    4-feature forward class in several passes of the 16-feature kernel, the multi-pass reverse form; the matrix-pipe classes
+    reach 1 462 atoms, only larger chains run the gather kernels), (2) more than 8 species disables the layer-0 factorisation, (3) forcing the gather kernels
     (VSSR_EDGE_IMPL=gather) or the per-edge layer 0 (VSSR_L0_FACTORISE=0) gives the same physics."""
     import os
 
@@ -467,7 +468,7 @@ def test_fallback_paths_large_chain_many_species_and_forced_gather(golden, oracl
 
     table, const = golden.offset_table()
     base = golden.structure("SrTiO3_2x2_pristine")
-    big = base.repeat((4, 4, 1))                       # 960 atoms > LDS-slice capacity
+    big = base.repeat((4, 4, 1))                       # 960 atoms: multi-pass forms
     rng = np.random.default_rng(3)
     big.positions += rng.normal(0, 0.03, big.positions.shape)
     small = structures.synth_chain(base, 5, grid=(4, 4))
