@@ -640,6 +640,18 @@ int painn_run(vssr_handle *h, uint32_t want) {
     const bool keep = h->upd_save && (want & VSSR_WANT_FORCES) && readout_mfma_supported(H);
     auto save_of = [&](int l) -> void * { return keep ? (char *)h->d_upd_save.p + update_save_bytes(N, M) * (size_t)l : nullptr; };
     h->l0_used = l0_fact;
+    // With forces wanted the last block's forward pass runs inside its reverse kernel (mode 3, painn_node_mfma.hip): no
+    // update_fwd launch for layer L - 1.  On request (VSSR_DEBUG_KEEP) update_fwd still runs, only to materialise v_in[L].
+    const bool fuse_last = readout_mfma_supported(H) && (want & VSSR_WANT_FORCES) && !keep;
+    auto update_fwd = [&](int l) {
+        const bool last = l + 1 == L;
+        if (last && fuse_last && !h->debug_keep) return;
+        P.begin(KC_UPDATE_FWD, st);
+        // (nothing reads the vector output of the LAST block -- the readout takes s only: it is written for vssr_debug_read only)
+        launch_update_fwd_mfma(st, N, M, l, av, MW, sv.s_msg[l], sv.v_msg[l], sv.s_in[l + 1],
+                               (!last || h->debug_keep) ? sv.v_in[l + 1] : nullptr, !last ? sv.phi[l + 1] : nullptr, save_of(l));
+        P.end(st);
+    };
 
     if (!l0_fact) {   // s0 = Emb[Z], v0 = 0 (the factorised layer 0 reads the embedding directly)
         P.begin(KC_EMBED, st);
@@ -652,10 +664,7 @@ int painn_run(vssr_handle *h, uint32_t want) {
             rc = l0_run_forward(h, G, sv.s_msg[0], sv.v_msg[0]);
             if (rc) return rc;
             P.end(st);
-            P.begin(KC_UPDATE_FWD, st);
-            launch_update_fwd_mfma(st, N, M, l, av, MW, sv.s_msg[l], sv.v_msg[l], sv.s_in[l + 1],
-                                   (l + 1 < L || h->debug_keep) ? sv.v_in[l + 1] : nullptr, l + 1 < L ? sv.phi[l + 1] : nullptr, save_of(l));
-            P.end(st);
+            update_fwd(l);
             continue;
         }
         if (l == 0) {   // (phi of layers >= 1 is the tail of the previous layer's update kernel)
@@ -680,13 +689,9 @@ int painn_run(vssr_handle *h, uint32_t want) {
                                    sv.v_msg[l], (int)EDGE_BCLASS_GATHER);
         }
         P.end(st);
-        P.begin(KC_UPDATE_FWD, st);
-        // (nothing reads the vector output of the LAST block -- the readout takes s only: it is written for vssr_debug_read only)
-        launch_update_fwd_mfma(st, N, M, l, av, MW, sv.s_msg[l], sv.v_msg[l], sv.s_in[l + 1],
-                               (l + 1 < L || h->debug_keep) ? sv.v_in[l + 1] : nullptr, l + 1 < L ? sv.phi[l + 1] : nullptr, save_of(l));
-        P.end(st);
+        update_fwd(l);
     }
-    // Readout.  With forces wanted (and the compiled readout width) it runs as the head of the last layer's reverse kernel;
+    // Readout.  With forces wanted (and the compiled readout width) it runs inside the last layer's reverse kernel;
     // energy-only evaluations use the stand-alone kernel built from the same code (identical per-atom energies).
     const bool fused = readout_mfma_supported(H);
     const bool want_forces = (want & VSSR_WANT_FORCES) != 0;
@@ -711,13 +716,16 @@ int painn_run(vssr_handle *h, uint32_t want) {
             P.begin(KC_UPDATE_BWD, st);
             if (!fused)
                 launch_update_bwd_mfma(st, N, M, l, 0, (int)(l == L - 1), av, MW, sv.s_msg[l], sv.v_msg[l], sv.sbar, sv.vbar,
-                                       nullptr, nullptr, nullptr, nullptr, sbar_msg_l, sv.vbar_msg, nullptr);
+                                       nullptr, nullptr, nullptr, nullptr, sbar_msg_l, sv.vbar_msg, nullptr, nullptr);
+            else if (l == L - 1 && fuse_last)   // forward pass of the block, readout and reverse in one kernel: writes s_in[L]
+                launch_update_bwd_mfma(st, N, M, l, 3, 1, av, MW, sv.s_msg[l], sv.v_msg[l], nullptr, sv.vbar, nullptr, nullptr,
+                                       e_excl, sv.e_atom, sbar_msg_l, sv.vbar_msg, sv.s_in[L], nullptr);
             else if (l == L - 1)
                 launch_update_bwd_mfma(st, N, M, l, 1, 1, av, MW, sv.s_msg[l], sv.v_msg[l], nullptr, sv.vbar, sv.s_in[L], nullptr,
-                                       e_excl, sv.e_atom, sbar_msg_l, sv.vbar_msg, save_of(l));
+                                       e_excl, sv.e_atom, sbar_msg_l, sv.vbar_msg, nullptr, save_of(l));
             else
                 launch_update_bwd_mfma(st, N, M, l, 2, 0, av, MW, sv.s_msg[l], sv.v_msg[l], sbar_msg_up, sv.vbar, sv.s_in[l + 1],
-                                       sv.phibar, nullptr, nullptr, sbar_msg_l, sv.vbar_msg, save_of(l));
+                                       sv.phibar, nullptr, nullptr, sbar_msg_l, sv.vbar_msg, nullptr, save_of(l));
             P.end(st);
             sv.sbar_msg_l0 = sbar_msg_l;
             P.begin((l == 0 && l0_fact) ? KC_L0_BWD : KC_EDGE_BWD, st);

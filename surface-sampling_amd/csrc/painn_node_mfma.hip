@@ -365,9 +365,28 @@ struct UpdRegs {
     f32x4 nrm[RT], inner[RT];
 };
 
+// Saturation watch of update_forward's two plane-storing epilogues: each takes a tracker of its own from the scope and hands it
+// back right behind the pass (no tracker register lives across a GEMM).  SatUnwatched: values another kernel of the evaluation
+// has watched; SatWatched: the fused last block, where this IS the forward pass.
+struct SatUnwatched {
+    __device__ __forceinline__ SatNone begin() const { return SatNone(); }
+    __device__ __forceinline__ void end(const SatNone &) const {}
+};
+struct SatWatched {
+    const ActiveView &av;
+    int a0, N;
+    __device__ __forceinline__ SatTrack begin() const { return SatTrack(); }
+    __device__ __forceinline__ void end(const SatTrack &t) const { t.commit(av, a0, N); }
+};
+
 // Shared forward part: needs vt (v_msg tile, rows x*TA+atom) and hs[:, :F] (s_msg tile) loaded + synced.
-template <int RT, int PHB, int PF, class Sat>   // PHB: first phase-timing slot (debug builds); PF: pipelined GEMMs
-__device__ __forceinline__ void update_forward(const LayerW &W, _Float16 *ldsh, const LaneGeo &L, UpdRegs<RT> &R, Sat &sat) {
+// FULL: the forward pass of record (fused last block) -- the values must be those of k_update_fwd_mfma bit for bit: the gate
+// MLP's first layer is summed as there (two K = F halves into one accumulator, the s half first: with fewer than three tiles
+// gemm16 interleaves two partial accumulators per call, so one K = 2F call rounds differently), and the a_ss column of the
+// gates is produced as well (ass).  The per-tile order of the U / V and W4 GEMMs (>= 3 tiles) does not depend on the column count.
+template <int RT, int PHB, int PF, bool FULL, class Scope>   // PHB: first phase-timing slot (debug builds); PF: pipelined GEMMs
+__device__ __forceinline__ void update_forward(const LayerW &W, _Float16 *ldsh, const LaneGeo &L, UpdRegs<RT> &R, f32x4 (&ass)[RT],
+                                               const Scope &scope) {
     constexpr int TA = 16 * RT, OFF_VT = UpdLds<RT>::OFF_VT, OFF_HS = UpdLds<RT>::OFF_HS, OFF_AS = UpdLds<RT>::OFF_AS;
     const Planes vt = make_planes(ldsh + OFF_VT, 3 * TA, F), hs = make_planes(ldsh + OFF_HS, TA, 2 * F),
                  as_ = make_planes(ldsh + OFF_AS, TA, F);
@@ -378,21 +397,25 @@ __device__ __forceinline__ void update_forward(const LayerW &W, _Float16 *ldsh, 
         gemm16<F, 3 * RT, 2, PF>(vt, wp, R.uv);
     }
     PH(PHB + 1)
+    {
+        auto sat = scope.begin();
 #pragma unroll
-    for (int t = 0; t < RT; ++t) {
+        for (int t = 0; t < RT; ++t) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float n2 = 0.f, in = 0.f;
+            for (int i = 0; i < 4; ++i) {
+                float n2 = 0.f, in = 0.f;
 #pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                const float vv = R.uv[RT * x + t][1][i];
-                n2 += fmaf(vv, vv, 1e-15f);
-                in = fmaf(R.uv[RT * x + t][0][i], vv, in);
+                for (int x = 0; x < 3; ++x) {
+                    const float vv = R.uv[RT * x + t][1][i];
+                    n2 += fmaf(vv, vv, 1e-15f);
+                    in = fmaf(R.uv[RT * x + t][0][i], vv, in);
+                }
+                R.nrm[t][i] = sqrtf(n2);
+                R.inner[t][i] = in;
             }
-            R.nrm[t][i] = sqrtf(n2);
-            R.inner[t][i] = in;
+            store_split4(hs, L.row(t), F + L.col0, R.nrm[t], sat);
         }
-        store_split4(hs, L.row(t), F + L.col0, R.nrm[t], sat);
+        scope.end(sat);
     }
     PH(PHB + 2)
     __syncthreads();
@@ -403,7 +426,15 @@ __device__ __forceinline__ void update_forward(const LayerW &W, _Float16 *ldsh, 
         const uint4 *wp[1] = {WTILE(W3, L.w, 2 * F)};
         const f32x4 b = gload4f(W.b3 + L.col0);
         __builtin_amdgcn_sched_barrier(0);   // the bias is requested in front of the GEMM whose epilogue adds it
-        gemm16<2 * F, RT, 1, PF>(hs, wp, acc);
+        if constexpr (FULL) {
+            const Planes hn = Planes{hs.h + F, hs.l + F, hs.ld};                // the |Vv| half of [s ; |Vv|]
+            const uint4 *wn[1] = {WTILE(W3, L.w, 2 * F) + (F / 32) * 2 * 64};   // chunks F/32 .. 2F/32 - 1 of the same column tile
+            gemm16<F, RT, 1, PF>(hs, wp, acc);
+            gemm16<F, RT, 1, PF>(hn, wn, acc);
+        } else {
+            gemm16<2 * F, RT, 1, PF>(hs, wp, acc);
+        }
+        auto sat = scope.begin();
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
             R.h3[t] = acc[t][0] + b;
@@ -412,11 +443,27 @@ __device__ __forceinline__ void update_forward(const LayerW &W, _Float16 *ldsh, 
             for (int i = 0; i < 4; ++i) sw[i] = swish(R.h3[t][i]);
             store_split4(as_, L.row(t), L.col0, sw, sat);
         }
+        scope.end(sat);
     }
     PH(PHB + 4)
     __syncthreads();
     PH(PHB + 5)
-    {   // only the gates the reverse pass reads: a_vv and a_sv (a_ss enters the forward output alone)
+    if constexpr (FULL) {   // a_vv, a_sv for the reverse part, a_ss for the scalar output
+        f32x4 g3[RT][3];
+        zero_acc(g3);
+        const uint4 *wp[3] = {WTILE(W4, L.w, F), WTILE(W4, NW + L.w, F), WTILE(W4, 2 * NW + L.w, F)};
+        f32x4 b4[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b4[c] = gload4f(W.b4 + c * F + L.col0);
+        __builtin_amdgcn_sched_barrier(0);
+        gemm16<F, RT, 3, PF>(as_, wp, g3);
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            R.gate[t][0] = g3[t][0] + b4[0];
+            R.gate[t][1] = g3[t][1] + b4[1];
+            ass[t] = g3[t][2] + b4[2];
+        }
+    } else {   // only the gates the reverse pass reads: a_vv and a_sv (a_ss enters the forward output alone)
         zero_acc(R.gate);
         const uint4 *wp[2] = {WTILE(W4, L.w, F), WTILE(W4, NW + L.w, F)};
         f32x4 b4[2];
@@ -788,9 +835,16 @@ k_readout_mfma(int N, ActiveView av, const ModelW *__restrict__ MW, const float 
 // The producer of sbar is fused in as the kernel's HEAD (the result is born in the accumulator layout the body wants, so it
 // never travels through HBM and the scalar, uncoalesced sbar reads / writes of separate kernels disappear):
 //   MODE 0: sbar is read from memory (readout widths other than RH);
-//   MODE 1: last layer -- the readout and its reverse (e_atom is written here; vbar is zero by construction);
+//   MODE 1: last layer -- the readout and its reverse (e_atom is written here; vbar is zero by construction).  Launched with
+//           SAVED only (VSSR_UPD_SAVE=1); without stored intermediates the last layer takes MODE 3;
 //   MODE 2: layer l < L - 1 -- the reverse of the message MLP of layer l + 1:
 //           sbar = sbar_msg(l+1) + W1^T[(W2^T phibar) * swish'(W1 s_in(l+1) + b1)]   (weights of layer l + 1)
+//   MODE 3: last layer, forward pass included (the default with forces wanted): nothing runs between update_fwd(L - 1) and
+//           this kernel, so the block's forward pass is done HERE, once -- update_forward<FULL> on the watched tile, the scalar
+//           output s_in(L) = s_msg + a_sv <Uv, Vv> + a_ss (the operations of k_update_fwd_mfma<2>: same bits) written to
+//           s_last and split into the readout's tile, the readout head of MODE 1, then the body on the values in registers.
+//           No update_fwd launch for this layer, no second tile load, no second set of U / V / W3 / W4 GEMMs, no read-back
+//           of s_in(L).
 // s_next: MODE 1: final scalar features, MODE 2: s_in(l+1); sbar_src: MODE 0: sbar, MODE 2: sbar_msg(l+1) (a different
 // buffer than the sbar_msg this launch writes).
 // SAVED: the forward intermediates come from the buffer update_fwd wrote (save_slot) instead of being recomputed from
@@ -801,8 +855,11 @@ k_update_bwd_mfma(int N, int l, int vbar_is_zero, ActiveView av, const ModelW *_
                   const float *__restrict__ v_msg, const float *__restrict__ sbar_src, const float *__restrict__ vbar,
                   const float *__restrict__ s_next, const float *__restrict__ phibar, const float *__restrict__ e_excl,
                   float *__restrict__ e_atom, float *__restrict__ sbar_msg, float *__restrict__ vbar_msg,
-                  const f32x4 *__restrict__ save) {
+                  float *__restrict__ s_last, const f32x4 *__restrict__ save) {
     static_assert(!SAVED || RT == 2, "the saved layout is that of the 32-atom forward kernel");
+    constexpr bool FUSED = MODE == 3;
+    static_assert(!FUSED || (!SAVED && RT == 2), "the fused last block runs its own forward pass on 32-atom tiles");
+    static_assert(MODE != 1 || SAVED, "without stored intermediates the last layer is MODE 3");
     extern __shared__ __attribute__((aligned(16))) _Float16 ldsh[];
     constexpr int TA = 16 * RT, OFF_VT = UpdLds<RT>::OFF_VT, OFF_AS = UpdLds<RT>::OFF_AS, UPD_LDS_HALVES = UpdLds<RT>::HALVES;
     const int m = blockIdx.y, a0 = blockIdx.x * TA;
@@ -815,19 +872,25 @@ k_update_bwd_mfma(int N, int l, int vbar_is_zero, ActiveView av, const ModelW *_
     // evaluation, s_in(l + 1) by its tail: SatNone.  What is new here are the adjoints: the cooperative loads (phibar; final s for
     // the readout) and every epilogue that stores adjoints use an instance of their own, committed right behind the pass: no
     // tracker register lives across a GEMM (the kernel runs at the 256-register limit: two registers across it cost 0.13 ms / step).
+    // MODE 3 is the forward pass of its layer: it watches the tile splits and the forward intermediates itself, the same way.
     SatNone unwatched;
     const LayerW &W = MW[m].layer[l];
     const size_t mN = (size_t)m * N;
     PH_INIT
     f32x4 sb[RT];   // sbar in the accumulator layout
-    if (MODE != 1) {   // requested first, needed after the head / the forward recomputation
+    if (MODE != 1 && !FUSED) {   // requested first, needed after the head / the forward recomputation
 #pragma unroll
         for (int t = 0; t < RT; ++t) sb[t] = gload4f(sbar_src + (mN + min(a0 + L.row(t), N - 1)) * F + L.col0);
     }
     // vbar of the tile (96 rows, fp32) stays in LDS behind the planes for the whole kernel: it is needed three times in the
     // accumulator layout (an atom row and four columns per lane): one ds_read_b128 each instead of global round trips
     float *VB = reinterpret_cast<float *>(ldsh + UPD_LDS_HALVES);   // [x * TA + atom][FT]
-    if (MODE == 1) vbar_is_zero = 1;   // (the region hosts the readout scratch)
+    if (MODE == 1 || FUSED) vbar_is_zero = 1;   // (the region hosts the readout scratch)
+    // MODE 3: the fp32 s_msg tile (residual of the scalar output) behind the readout scratch, staging-tile layout
+    float *SR = VB + (plane_halves(TA, RH) / 2 + (RH / 16) * TA);
+    static_assert(!FUSED || ((plane_halves(TA, RH) / 2 + (RH / 16) * TA) % 4 == 0 &&
+                             plane_halves(TA, RH) / 2 + (RH / 16) * TA + TA * FT <= 3 * TA * FT),
+                  "readout scratch + fp32 residual tile fit the vbar region");
     if (!vbar_is_zero) {
         constexpr int NIT = 3 * TA * (F / 4) / NTHREADS;
         float4 vv[NIT];
@@ -856,32 +919,47 @@ k_update_bwd_mfma(int N, int l, int vbar_is_zero, ActiveView av, const ModelW *_
             for (int c = 0; c < 2; ++c) R.gate[t][c] = gload4f(reinterpret_cast<const float *>(sv + (size_t)(UPD_SAVE_GATE + 2 * t + c) * NTHREADS));
         }
     };
-    if (!SAVED) load_update_s<RT>(ldsh, s_msg, mN, a0, N, unwatched);
+    // readout head of the last layer (MODE 1, 3): s tile in `xs` (planes, synced); hidden adjoint + reduction scratch in the
+    // unused vbar region
+    auto readout = [&](const Planes &xs) {
+        const Planes hp = make_planes(ldsh + UPD_LDS_HALVES, TA, RH);
+        float *red = reinterpret_cast<float *>(ldsh + UPD_LDS_HALVES + plane_halves(TA, RH));
+        PH(40)
+        SatTrack sate;
+        readout_head<RT, true>(MW[m], xs, hp, red, L, a0, N, mN, e_excl, e_atom, sb, sate);
+        sate.commit(av, a0, N);
+        PH(41)
+    };
+    if (FUSED) {
+        float4 keep_s[TA * (F / 4) / NTHREADS];
+        SatTrack satc;
+        rows_request<TA>([&](int row) { return s_msg + (mN + min(a0 + row, N - 1)) * F; }, keep_s);
+        load_update_v<RT>(ldsh, v_msg, mN, a0, N, satc);
+        rows_store_split<TA>(make_planes(ldsh + UpdLds<RT>::OFF_HS, TA, 2 * F), 0, keep_s, satc);
+        satc.commit(av, a0, N);
+#pragma unroll
+        for (int it = 0; it < TA * (F / 4) / NTHREADS; ++it) {
+            const int idx = threadIdx.x + it * NTHREADS;
+            *reinterpret_cast<float4 *>(SR + (idx >> 5) * FT + 4 * (idx & 31)) = keep_s[it];
+        }
+        __syncthreads();
+    } else if (!SAVED) load_update_s<RT>(ldsh, s_msg, mN, a0, N, unwatched);
     else load_saved();
     if (MODE == 0) {
         load_update_v<RT>(ldsh, v_msg, mN, a0, N, unwatched);
         __syncthreads();
     } else if (MODE == 1) {
-        // head: readout of s_next (tile in the `as` region; hidden adjoint + reduction scratch in the unused vbar region)
-        if (!SAVED) load_update_v<RT>(ldsh, v_msg, mN, a0, N, unwatched);
+        // head: readout of s_next (tile in the `as` region)
         const Planes xs = make_planes(ldsh + OFF_AS, TA, F);
-        const Planes hp = make_planes(ldsh + UPD_LDS_HALVES, TA, RH);
-        float *red = reinterpret_cast<float *>(ldsh + UPD_LDS_HALVES + plane_halves(TA, RH));
         {
             SatTrack satc;   // (the last layer's output is not split by update_fwd<0>)
             load_rows_split<TA>(xs, 0, [&](int row) { return s_next + (mN + min(a0 + row, N - 1)) * F; }, satc);
             satc.commit(av, a0, N);
         }
         __syncthreads();
-        PH(40)
-        {
-            SatTrack sate;
-            readout_head<RT, true>(MW[m], xs, hp, red, L, a0, N, mN, e_excl, e_atom, sb, sate);
-            sate.commit(av, a0, N);
-        }
-        PH(41)
+        readout(xs);
         // (the body's first barrier orders the last reads of xs before anything overwrites the `as` region)
-    } else {
+    } else if (MODE == 2) {
         // head: reverse of the message MLP of layer l + 1.  phibar tile over the (not yet loaded) v tile, s_next / h1bar in
         // the `as` region; the v tile follows once the head is done with the region.
         const LayerW &Wn = MW[m].layer[l + 1];
@@ -934,8 +1012,31 @@ k_update_bwd_mfma(int N, int l, int vbar_is_zero, ActiveView av, const ModelW *_
         // (the body's first barrier orders the last reads of xs before anything overwrites the `as` region)
     }
     PH(16)
-    if constexpr (!SAVED) {
-        update_forward<RT, 16, BPF>(W, ldsh, L, R, unwatched);
+    f32x4 ass[RT];   // a_ss (MODE 3 only)
+    if constexpr (FUSED) {
+        update_forward<RT, 16, BPF, true>(W, ldsh, L, R, ass, SatWatched{av, a0, N});
+        // scalar output in the accumulator layout (residual + increment: the sum k_update_fwd_mfma's output pass forms), to
+        // memory and, split, into the readout's tile.  The tile takes the place of the v tile (dead since GEMM3's barrier);
+        // the `as` region is still being read by slower waves' gate GEMM.
+        const Planes xs = make_planes(ldsh + OFF_VT, TA, F);
+        {
+            SatTrack sato;
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+                const int row = L.row(t), a = a0 + row;
+                f32x4 o = *reinterpret_cast<const f32x4 *>(SR + row * FT + L.col0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] += fmaf(R.gate[t][1][i], R.inner[t][i], ass[t][i]);
+                store_split4(xs, row, L.col0, o, sato);
+                if (a < N) *reinterpret_cast<f32x4 *>(s_last + (mN + a) * F + L.col0) = o;
+            }
+            sato.commit(av, a0, N);
+        }
+        __syncthreads();
+        readout(xs);
+        // (the head's barrier lies behind the last reads of xs and of the `as` region: the body may overlay both)
+    } else if constexpr (!SAVED) {
+        update_forward<RT, 16, BPF, false>(W, ldsh, L, R, ass, SatUnwatched{});
     } else {
         // <U v, V v> of the saved products (same operations, same order as update_forward: bit-identical)
 #pragma unroll
@@ -1130,7 +1231,7 @@ int node_mfma_init(vssr_handle *h) {
 #define SET_UPD(MODE)                                                                                                     \
     VSSR_HIP(h, hipFuncSetAttribute((const void *)k_update_bwd_mfma<MODE, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                     (int)node_mfma_lds_bytes(3)));
-    SET_UPD(0) SET_UPD(1) SET_UPD(2)
+    SET_UPD(0) SET_UPD(2) SET_UPD(3)   // (mode 1 exists with stored intermediates only, below)
 #undef SET_UPD
     VSSR_HIP(h, hipFuncSetAttribute((const void *)k_update_bwd_mfma<1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)node_mfma_lds_bytes(3)));
@@ -1173,32 +1274,27 @@ void launch_readout_mfma(hipStream_t st, int N, int M, const ActiveView &av, con
     hipLaunchKernelGGL(k_readout_mfma, dim3((N + TA - 1) / TA, M), dim3(NTHREADS), node_mfma_lds_bytes(4), st, N, av, MW, s,
                        e_excl, e_atom);
 }
-// mode 0: sbar_src = sbar ; mode 1: s_next = final s, e_excl (or null), e_atom ; mode 2: s_next = s_in(l+1), phibar,
-// sbar_src = sbar_msg(l+1)
+// mode 0: sbar_src = sbar ; mode 1 (save != nullptr): s_next = final s, e_excl (or null), e_atom ; mode 2: s_next = s_in(l+1), phibar,
+// sbar_src = sbar_msg(l+1) ; mode 3: mode 1 with the block's forward pass included: s_last = final s (WRITTEN here)
 void launch_update_bwd_mfma(hipStream_t st, int N, int M, int l, int mode, int vbar_is_zero, const ActiveView &av, const ModelW *MW,
                             const float *s_msg, const float *v_msg, const float *sbar_src, const float *vbar,
                             const float *s_next, const float *phibar, const float *e_excl, float *e_atom,
-                            float *sbar_msg, float *vbar_msg, const void *save) {
+                            float *sbar_msg, float *vbar_msg, float *s_last, const void *save) {
     const f32x4 *sv = reinterpret_cast<const f32x4 *>(save);
-    if (mode == 1) vbar_is_zero = 1;
+    if (mode == 1 || mode == 3) vbar_is_zero = 1;
 #if defined(UPD_BWD_RT) && UPD_BWD_RT == 1
     // A/B build only (tools/build_variant.sh rt1 -DUPD_BWD_RT=1 [-DUPD_PF=0], profiles/r05/NOTES_node_occupancy.md): 16-atom tiles,
     // 8 waves at 128 registers, two workgroups per CU.  Never shipped: it spills, and the saturation watch attributes rows modulo 32.
-    if (!sv && mode != 0) {
+    if (!sv && mode == 2) {
         const dim3 grid1((N + 15) / 16, M), blk1(NTHREADS);
         const size_t lds1 = sizeof(_Float16) * UpdLds<1>::HALVES + sizeof(float) * 3 * 16 * FT;
         static bool once = [] {
-            (void)hipFuncSetAttribute((const void *)k_update_bwd_mfma<1, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
             (void)hipFuncSetAttribute((const void *)k_update_bwd_mfma<2, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
             return true;
         }();
         (void)once;
-        if (mode == 1)
-            hipLaunchKernelGGL((k_update_bwd_mfma<1, 1, false>), grid1, blk1, lds1, st, N, l, vbar_is_zero, av, MW, s_msg, v_msg, sbar_src,
-                               vbar, s_next, phibar, e_excl, e_atom, sbar_msg, vbar_msg, sv);
-        else
-            hipLaunchKernelGGL((k_update_bwd_mfma<2, 1, false>), grid1, blk1, lds1, st, N, l, vbar_is_zero, av, MW, s_msg, v_msg, sbar_src,
-                               vbar, s_next, phibar, e_excl, e_atom, sbar_msg, vbar_msg, sv);
+        hipLaunchKernelGGL((k_update_bwd_mfma<2, 1, false>), grid1, blk1, lds1, st, N, l, vbar_is_zero, av, MW, s_msg, v_msg, sbar_src,
+                           vbar, s_next, phibar, e_excl, e_atom, sbar_msg, vbar_msg, s_last, sv);
         return;
     }
 #endif
@@ -1206,9 +1302,10 @@ void launch_update_bwd_mfma(hipStream_t st, int N, int M, int l, int mode, int v
     const size_t lds = node_mfma_lds_bytes(3);
 #define LAUNCH_UPD(MODE, SAVED)                                                                                             \
     hipLaunchKernelGGL((k_update_bwd_mfma<MODE, 2, SAVED>), grid, blk, lds, st, N, l, vbar_is_zero, av, MW, s_msg, v_msg, sbar_src, \
-                       vbar, s_next, phibar, e_excl, e_atom, sbar_msg, vbar_msg, sv)
-    if (mode == 1) { if (sv) LAUNCH_UPD(1, true); else LAUNCH_UPD(1, false); }
+                       vbar, s_next, phibar, e_excl, e_atom, sbar_msg, vbar_msg, s_last, sv)
+    if (mode == 1) LAUNCH_UPD(1, true);   // (painn_run: the last layer with stored intermediates; otherwise mode 3)
     else if (mode == 2) { if (sv) LAUNCH_UPD(2, true); else LAUNCH_UPD(2, false); }
+    else if (mode == 3) LAUNCH_UPD(3, false);
     else LAUNCH_UPD(0, false);
 #undef LAUNCH_UPD
 }

@@ -581,7 +581,7 @@ void launch_readout_mfma(hipStream_t st, int N, int M, const ActiveView &av, con
 void launch_update_bwd_mfma(hipStream_t st, int N, int M, int l, int mode, int vbar_is_zero, const ActiveView &av, const ModelW *MW,
                             const float *s_msg, const float *v_msg, const float *sbar_src, const float *vbar,
                             const float *s_next, const float *phibar, const float *e_excl, float *e_atom,
-                            float *sbar_msg, float *vbar_msg, const void *save);
+                            float *sbar_msg, float *vbar_msg, float *s_last, const void *save);
 // layer-0 species factorisation (painn_l0.hip)
 void pack_mfma_tiles16(const float *Wsrc, int rows, int K, unsigned *dst /*[rows/32][K/16][2][64][4]*/);
 void build_wd16(const float *Wd, const float *bd, unsigned *dst /*[3F][4][2][4]*/);
