@@ -263,10 +263,23 @@ k_bfgs_step(const int *__restrict__ cfg_start, const int *__restrict__ counters,
         for (int k = tid; k < n; k += nt) mx = fmax(mx, fabs(x[k] - xr0[k]));
         mx = block_max(mx, red);
         if (mx >= 1e-7 && m + 2 <= mmax) {
-            // a = dr.df ; c1 = Q^T dr
-            double a = 0.0;
-            for (int k = tid; k < n; k += nt) a += (x[k] - xr0[k]) * (F(k) - xf0[k]);
+            // a = dr.df ; c1 = Q^T dr ; xx = |x|^2 over the free coordinates
+            double a = 0.0, xx = 0.0;
+            for (int k = tid; k < n; k += nt) {
+                a += (x[k] - xr0[k]) * (F(k) - xf0[k]);
+                if (!(fx && fx[k / 3])) xx += x[k] * x[k];
+            }
             a = block_sum(a, red);
+            xx = block_sum(xx, red);
+            // From the second update on H dr lies in span(Q) in exact arithmetic: dr is |H|^-1 f up to a factor and the span holds
+            // every earlier force.  What the candidate keeps outside it is the rounding of x = xr0 + step, at most half an ulp per
+            // coordinate and alpha times that in H dr: 1e-13 of |H dr| while the steps are long, 1e-10 once a run has contracted to
+            // steps of 1e-4 A -- far above the relative threshold below.  Such a remainder is no column (it was taken for one: a
+            // contracting chain filled its basis after 51 updates instead of 96; tests/test_relax_gpu_branches.py).  A direction
+            // that H dr really adds measures 1e11 times the rounding (tests/bfgs_oracle.py, dg_noise_ratio); the floor sits 64 x
+            // above it.
+            const double ROUND = 64.0 * alpha * 1.1102230246251565e-16;   // 64 alpha 2^-53
+            const double dg_floor = ROUND * ROUND * xx;
             for (int j = wave; j < m; j += nwaves) {   // one wave per basis vector: no block barrier per dot product
                 double d = 0.0;
                 for (int k = lane; k < n; k += 64) d += Q[(size_t)j * n + k] * (x[k] - xr0[k]);
@@ -326,7 +339,7 @@ k_bfgs_step(const int *__restrict__ cfg_start, const int *__restrict__ counters,
                 double nrm = 0.0;
                 for (int k = tid; k < n; k += nt) nrm += qn[k] * qn[k];
                 nrm = block_sum(nrm, red);
-                if (nrm > 1e-24 * nrm0 && nrm > 0.0) {
+                if (nrm > 1e-24 * nrm0 && nrm > 0.0 && (which == 0 || nrm > dg_floor)) {
                     const double inv = 1.0 / sqrt(nrm);
                     for (int k = tid; k < n; k += nt) qn[k] *= inv;
                     if (tid == 0) cc[m] = sqrt(nrm);
@@ -493,10 +506,12 @@ struct BfgsWork {
     int mmax;
     size_t lds_bytes() const { return sizeof(double) * ((size_t)2 * mmax * (mmax | 1) + 5 * (size_t)mmax + 8); }
     int init(vssr_handle *h, const Params &p) {
-        // Two basis vectors per Hessian update; the rotated matrices of the eigen-decomposition (2 x mmax^2 doubles) live in
-        // LDS, which holds 46 updates.  A longer relaxation keeps stepping with the Hessian of its first 46 updates (the
-        // step kernel skips the update when the basis is full): identical to ASE up to step 46, a frozen quasi-Newton
-        // method beyond (the reference's configurations use 20 steps).
+        // At most two basis vectors per Hessian update; the rotated matrices of the eigen-decomposition (2 x mmax^2 doubles) live
+        // in LDS, which holds mmax = 98 of them.  The first update takes two columns, every later one one (H dr lies in the span
+        // already, see k_bfgs_step): 96 updates.  A longer relaxation keeps stepping with the Hessian of its first 96 updates (the
+        // step kernel skips an update that finds fewer than two columns free): identical to ASE for 97 steps, a frozen
+        // quasi-Newton method beyond (the reference's configurations use 20 steps; a chain with fewer than 33 free atoms never
+        // fills the basis, m <= 3 N).  Pinned step for step by tests/test_relax_gpu_branches.py.
         const size_t nB = h->n_cfg, N = h->n_atoms;
         mmax = 2 * p.max_steps + 2;
         while (lds_bytes() > 160 * 1024 - 4096) mmax -= 2;   // (the kernel also holds 2 KB of static reduction scratch)

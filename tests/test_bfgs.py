@@ -172,9 +172,14 @@ def test_bfgs_gpu_matches_dense_restatement_without_fixatoms(golden, oracle_mod)
 
 @pytest.mark.gpu
 def test_bfgs_gpu_runs_past_the_on_chip_hessian_limit(golden):
-    """The eigen-decomposition workspace in LDS holds 46 Hessian updates.  A longer relaxation is identical up to step 46
-    (same basis capacity) and keeps stepping with that Hessian afterwards instead of being refused: no-FixAtoms chain with
-    a tolerance it cannot reach, 46 vs 70 steps."""
+    """The eigen-decomposition workspace in LDS holds 98 basis vectors: two for the first Hessian update, one for every later one, 96
+    updates -- not 46, as was stated here and in the header when a contracting chain still filled its basis with rounding residue
+    (csrc/relax.hip::k_bfgs_step, dg_floor).  A relaxation is identical to ASE for its first 97 steps and keeps stepping with that
+    Hessian afterwards instead of being refused; tests/test_relax_gpu_branches.py follows a chain step for step through the point
+    where the basis fills and 11 steps beyond.  This test keeps its runs on either side of the old number, 46 vs 47 vs 70 steps of
+    a no-FixAtoms chain with a tolerance it cannot reach: they stay consistent with each other.  (The runs cannot move to 97 / 98 /
+    110 steps: from about step 90 PaiNN's fp32 forces hold this chain at max|F| = 0.0529 eV/A, and the last assertion compares two
+    values of that plateau that differ in their fifth digit.)"""
     from surface_sampling_amd import backend, structures
 
     table, const = golden.offset_table()
