@@ -365,6 +365,17 @@ int vssr_eam_create(int32_t device, const vssr_eam_grid *grid, const double *frh
  * any device is touched: VSSR_E_BADARG for a bad grid, n_elem outside 1 .. 8 or a non-finite table entry. */
 int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
                           const double *rhor, const double *z2r, vssr_handle **out);
+/* Angular-dependent potential (LAMMPS pair_style adp; Mishin, Mehl, Papaconstantopoulos 2005): the eam/alloy tables of
+ * vssr_eam_create_alloy (fs = 0) plus a dipole function u and a quadrupole function w per element pair, [n_elem (n_elem + 1) / 2][nr]
+ * each in the pair order of z2r, on the r grid, NOT scaled by r:
+ *   E = sum_i [F(rho_i) + 1/2 mu_i.mu_i + 1/2 lambda_i:lambda_i - (tr lambda_i)^2 / 6] + 1/2 sum_{i != j} phi(r_ij),
+ *   mu_i = sum_j u(r_ij) r_ij,  lambda_i = sum_j w(r_ij) r_ij (x) r_ij;  pe/atom of i = the bracket + half of its pair energies.
+ * Same splines for u and w as for the other tables.  VSSR_E_BADARG, before any device is touched: null u or w, a non-finite
+ * entry, and everything vssr_eam_create_alloy refuses.  Evaluate with vssr_eam_eval_batch; every vssr_batch_* entry point serves
+ * the handle as it serves an eam/alloy one (stress, FIRE, BFGS, BFGSLineSearch, CG), except that a CG relaxation always runs in
+ * lock step (VSSR_CG_DRIVER_RESIDENT is accepted, last_used reports VSSR_CG_DRIVER_LOCKSTEP). */
+int vssr_eam_create_adp(int32_t device, int32_t n_elem, const vssr_eam_grid *grid, const double *frho, const double *rhor,
+                        const double *z2r, const double *u, const double *w, vssr_handle **out);
 /* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
 int vssr_eam_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                         const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,

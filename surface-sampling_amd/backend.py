@@ -37,7 +37,7 @@ EXPORTS = (
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
     "vssr_pair_create", "vssr_pair_create_kspace", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
-    "vssr_batch_relax_bfgs_linesearch",
+    "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
 )
 
 
@@ -277,6 +277,8 @@ def load_library():
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_create_alloy.restype = C.c_int
     L.vssr_eam_create_alloy.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
+    L.vssr_eam_create_adp.restype = C.c_int
+    L.vssr_eam_create_adp.argtypes = [C.c_int32, C.c_int32, C.POINTER(EamGrid), dp, dp, dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_eval_batch.restype = C.c_int
     L.vssr_eam_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_sw_create.restype = C.c_int
@@ -887,7 +889,9 @@ class PairEngine(_AnalyticEngine):
 
 class EAMEngine(_AnalyticEngine):
     """EAM evaluator, fp64 on device.  ``funcfl``: one funcfl element (every atom has type 0, vssr_eam_create), or an
-    ``eam.EamTables`` of up to 8 types -- eam/alloy, eam/fs or mixed funcfl files (type = table index, vssr_eam_create_alloy)."""
+    ``eam.EamTables`` of up to 8 types -- eam/alloy, eam/fs or mixed funcfl files (type = table index, vssr_eam_create_alloy);
+    tables that carry ``u`` / ``w`` make an angular-dependent potential (pair_style adp, vssr_eam_create_adp: CG relaxations of
+    such an engine always run in lock step)."""
 
     def __init__(self, funcfl, device=0):
         super().__init__()
@@ -912,11 +916,26 @@ class EAMEngine(_AnalyticEngine):
         if frho.size != n * t.nrho or rhor.size != (n * n if t.fs else n) * t.nr or z2r.size != n * (n + 1) // 2 * t.nr:
             raise ValueError("EAM tables do not match their grid / element count")
         self.n_types = n
+        if getattr(t, "u", None) is not None or getattr(t, "w", None) is not None:
+            return self._create_adp(t, device, n, grid, frho, rhor, z2r)
         rc = self._lib.vssr_eam_create_alloy(int(device), n, 1 if t.fs else 0, C.byref(grid), _ptr(frho, C.c_double),
                                              _ptr(rhor, C.c_double), _ptr(z2r, C.c_double), C.byref(self._h))
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"vssr_eam_create_alloy failed ({rc}): {msg.decode() if msg else '?'}")
+
+    def _create_adp(self, t, device, n, grid, frho, rhor, z2r):
+        if t.fs:
+            raise ValueError("ADP tables take alloy densities (fs=False)")
+        # (a missing table goes to the library as a null pointer: it refuses)
+        u, w = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (t.u, t.w))
+        if any(a is not None and a.size != z2r.size for a in (u, w)):
+            raise ValueError("ADP tables u / w do not match their grid / element count")
+        rc = self._lib.vssr_eam_create_adp(int(device), n, C.byref(grid), _ptr(frho, C.c_double), _ptr(rhor, C.c_double),
+                                           _ptr(z2r, C.c_double), _ptr(u, C.c_double), _ptr(w, C.c_double), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_eam_create_adp failed ({rc}): {msg.decode() if msg else '?'}")
 
 
 class GMMEngine(_Handle):

@@ -1333,7 +1333,7 @@ class PairSurfCalc(_AnalyticSurfCalc):
         return backend.PairEngine(self.pair_model, device=_device_index(self.device))
 
 
-EAM_STYLES = ("eam", "eam/alloy", "eam/fs")
+EAM_STYLES = ("eam", "eam/alloy", "eam/fs", "adp")
 
 
 def _parse_pair_coeff(lines):
@@ -1348,7 +1348,7 @@ def _parse_pair_coeff(lines):
 
 
 def eam_tables(style, pair_coeff, resolve, specorder=None):
-    """The potential of ``pair_style eam | eam/alloy | eam/fs`` with LAMMPS ``pair_coeff`` lines: ``(species, source)`` where
+    """The potential of ``pair_style eam | eam/alloy | eam/fs | adp`` with LAMMPS ``pair_coeff`` lines: ``(species, source)`` where
     ``species`` are the symbols of the types (``specorder`` when given, else the elements the lines name) and ``source`` is a
     ``eam.Funcfl`` (pair_style eam with one funcfl element: the one-element path) or ``eam.EamTables``.  ``resolve(name)``
     returns a file's text.  Refused with ValueError: other styles, NULL types, unknown elements, malformed files, a type without a
@@ -1361,11 +1361,15 @@ def eam_tables(style, pair_coeff, resolve, specorder=None):
     coeffs = _parse_pair_coeff(pair_coeff)
     if not coeffs:
         raise ValueError(f"pair_style {style}: pair_coeff is required")
-    if style in ("eam/alloy", "eam/fs"):
+    if style in ("eam/alloy", "eam/fs", "adp"):
         if len(coeffs) != 1 or coeffs[0][:2] != ("*", "*"):
             raise ValueError(f"pair_style {style}: expected one 'pair_coeff * * file el_1 ... el_n'")
-        setfl = eam_io.parse_setfl(resolve(coeffs[0][2]), fs=style == "eam/fs")
-        tables = eam_io.tables_from_setfl(setfl, coeffs[0][3] or setfl.elements)
+        if style == "adp":
+            setfl = eam_io.parse_adp(resolve(coeffs[0][2]))
+            tables = eam_io.tables_from_adp(setfl, coeffs[0][3] or setfl.elements)
+        else:
+            setfl = eam_io.parse_setfl(resolve(coeffs[0][2]), fs=style == "eam/fs")
+            tables = eam_io.tables_from_setfl(setfl, coeffs[0][3] or setfl.elements)
         source, names = tables, list(tables.elements)
     else:
         per_type = {}
@@ -1418,7 +1422,8 @@ class EAMSurfCalc(_AnalyticSurfCalc):
     one funcfl element.  ``set(pair_style=..., pair_coeff=[...], specorder=[...])`` selects the potential as LAMMPS would:
 
     * ``eam`` with ``* * file`` (one funcfl element) or ``i i file_i`` per type (funcfl files mixed on one grid);
-    * ``eam/alloy`` / ``eam/fs`` with ``* * file el_1 ... el_n`` (setfl / Finnis-Sinclair file, up to 8 types).
+    * ``eam/alloy`` / ``eam/fs`` with ``* * file el_1 ... el_n`` (setfl / Finnis-Sinclair file, up to 8 types);
+    * ``adp`` with ``* * file el_1 ... el_n`` (angular-dependent potential: a setfl file with u(r) and w(r) blocks).
 
     Atoms map to types by symbol: ``specorder`` (ASE's keyword) when given, else the elements ``pair_coeff`` names; an atom of
     another element is refused.  ``pair_coeff`` file names are matched against ``files`` (path or base name), else opened as
@@ -1665,9 +1670,14 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
 
             self.tables = eam_io.tables_from_setfl(eam_io.parse_setfl(text, fs=style == "eam/fs"), self.species)
             self.funcfl = self.params = None
+        elif style == "adp":
+            from . import eam as eam_io
+
+            self.tables = eam_io.tables_from_adp(eam_io.parse_adp(text), self.species)
+            self.funcfl = self.params = None
         else:
             raise backend.BackendError(f"pair_style {style!r} is not provided by this backend "
-                                       "(tersoff, eam, eam/alloy, eam/fs, sw, lj/cut, morse, buck, born, coul/dsf and "
+                                       "(tersoff, eam, eam/alloy, eam/fs, adp, sw, lj/cut, morse, buck, born, coul/dsf and "
                                        "hybrid / hybrid/overlay of the last five are)")
         if self._engine is not None:
             self._engine.close()

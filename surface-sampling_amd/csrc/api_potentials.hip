@@ -115,8 +115,11 @@ int vssr_eam_create(int32_t device, const vssr_eam_grid *grid, const double *frh
     });
 }
 
-int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
-                          const double *rhor, const double *z2r, vssr_handle **out) {
+}  // extern "C"
+
+// eam/alloy, eam/fs (u = w = nullptr) and adp (fs = 0; u, w [n_elem (n_elem + 1) / 2][nr]) behind their two exported names
+static int eam_create_typed(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
+                            const double *rhor, const double *z2r, const double *u, const double *w, vssr_handle **out) {
     if (!grid || !frho || !rhor || !z2r || !out) return set_err(nullptr, VSSR_E_BADARG, "null EAM argument");
     *out = nullptr;
     if (n_elem < 1 || n_elem > 8) return set_err(nullptr, VSSR_E_BADARG, "EAM: %d elements (1 .. 8 are supported)", n_elem);
@@ -131,21 +134,43 @@ int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr
         if (!std::isfinite(rhor[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (rho)");
     for (size_t k = 0; k < cP; ++k)
         if (!std::isfinite(z2r[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite EAM table entry (r phi)");
+    for (size_t k = 0; u && k < cP; ++k)
+        if (!std::isfinite(u[k]) || !std::isfinite(w[k])) return set_err(nullptr, VSSR_E_BADARG, "non-finite ADP table entry (u, w)");
     return create_handle(Kind::EAM, device, out, [=](vssr_handle *h) {
         h->n_types = n_elem;
         h->n_embed = n_elem;   // vssr_batch_upload refuses types outside [0, n_elem)
         h->eam_nel = n_elem;
         h->eam_fs = fs ? 1 : 0;
+        h->eam_adp = u != nullptr;
         h->eam_grid = *grid;
-        // spline tables (eam_dev.h EamTyped): F [n][nrho + 1][7] | rho [nR][nr + 1][7] | r phi [nP][nr + 1][7]
+        // spline tables (eam_dev.h EamTyped): F [n][nrho + 1][7] | rho [nR][nr + 1][7] | r phi [nP][nr + 1][7]; an ADP handle
+        // (adp_dev.h AdpTyped) appends u [nP][nr + 1][7] | w [nP][nr + 1][7]
         const size_t sF = 7 * (size_t)(grid->nrho + 1), sR = 7 * (size_t)(grid->nr + 1);
-        std::vector<double> tab(sF * n_elem + sR * (nR + nP));
+        std::vector<double> tab(sF * n_elem + sR * (nR + nP + (u ? 2 * nP : 0)));
         for (int t = 0; t < n_elem; ++t) eam_build_spline(frho + (size_t)t * grid->nrho, grid->nrho, grid->drho, tab.data() + sF * t);
         double *R = tab.data() + sF * n_elem;
         for (int t = 0; t < nR; ++t) eam_build_spline(rhor + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * t);
         for (int t = 0; t < nP; ++t) eam_build_spline(z2r + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * (nR + t));
+        for (int t = 0; u && t < nP; ++t) {
+            eam_build_spline(u + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * (nR + nP + t));
+            eam_build_spline(w + (size_t)t * grid->nr, grid->nr, grid->dr, R + sR * (nR + 2 * nP + t));
+        }
         return upload_params(h, tab.data(), sizeof(double) * tab.size(), "EAM tables", "EAM table upload failed");
     });
+}
+
+extern "C" {
+
+int vssr_eam_create_alloy(int32_t device, int32_t n_elem, int32_t fs, const vssr_eam_grid *grid, const double *frho,
+                          const double *rhor, const double *z2r, vssr_handle **out) {
+    return eam_create_typed(device, n_elem, fs, grid, frho, rhor, z2r, nullptr, nullptr, out);
+}
+
+int vssr_eam_create_adp(int32_t device, int32_t n_elem, const vssr_eam_grid *grid, const double *frho, const double *rhor,
+                        const double *z2r, const double *u, const double *w, vssr_handle **out) {
+    if (out) *out = nullptr;
+    if (!u || !w) return set_err(nullptr, VSSR_E_BADARG, "null ADP argument (u, w)");
+    return eam_create_typed(device, n_elem, 0, grid, frho, rhor, z2r, u, w, out);
 }
 
 // ---- Stillinger-Weber ------------------------------------------------------------------------------------------------------

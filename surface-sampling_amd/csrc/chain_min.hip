@@ -368,8 +368,9 @@ static int cm_launch_kind(vssr_handle *h, void *d_args, const CmCommon &c) {
 // Can the chain-resident kernel serve this handle's resident batch at all?
 static bool cm_capable(const vssr_handle *h) {
     const bool kind = h->kind == Kind::TERSOFF || h->kind == Kind::SW || h->kind == Kind::EAM || h->kind == Kind::PAIR;
-    // (a pair handle with k-space: the reciprocal sum is not part of the chain-resident kernel, those relaxations run in lock step)
-    return kind && !h->ew_on && h->max_cfg_atoms <= CM_MAX_ATOMS;
+    // (a pair handle with k-space: the reciprocal sum is not part of the chain-resident kernel, those relaxations run in lock step;
+    // likewise an ADP handle: the kernel has no site tile for the dipole / quadrupole rows)
+    return kind && !h->ew_on && !h->eam_adp && h->max_cfg_atoms <= CM_MAX_ATOMS;
 }
 
 // Which driver.  The handle's choice (vssr_batch_relax_cg_driver) forces one of them, the chain-resident one only where the kernel

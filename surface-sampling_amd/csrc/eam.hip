@@ -65,6 +65,7 @@ void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1
 }
 
 int eam_stress(vssr_handle *h) {
+    if (h->eam_adp) return adp_stress(h);
     if (h->d_stress.ensure(sizeof(double) * 12 * (size_t)h->n_cfg)) return set_err(h, VSSR_E_NOMEM, "out of device memory (stress)");
     double *out = h->d_stress.as<double>();
     hipLaunchKernelGGL(h->eam_nel > 0 ? k_eam_stress<true> : k_eam_stress<false>, dim3(h->n_cfg), dim3(VIR_THREADS), 0, h->stream,
@@ -74,7 +75,7 @@ int eam_stress(vssr_handle *h) {
 }
 
 int eam_run(vssr_handle *h, uint32_t want) {
-    (void)want;
+    if (h->eam_adp) return adp_run(h, want);
     int rc = analytic_begin(h, h->eam_grid.cutoff, EamAtoms::doubles, "EAM");
     if (rc) return rc;
     const PotView V = pot_view(h);

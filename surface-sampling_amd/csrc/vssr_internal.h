@@ -294,7 +294,7 @@ enum class Kind : int {
     NONE = 0,
     PAINN = 1,     // PaiNN ensemble (painn.hip, painn_gen.hip)
     TERSOFF = 2,   // tersoff.hip
-    EAM = 3,       // funcfl, eam/alloy and eam/fs tables (eam.hip)
+    EAM = 3,       // funcfl, eam/alloy and eam/fs tables (eam.hip); with eam_adp the angular-dependent potential (adp.hip)
     SW = 4,        // Stillinger-Weber (sw.hip)
     GMM = 5,       // Gaussian-mixture scoring (gmm.hip)
     GMM_FIT = 6,   // Gaussian-mixture fit (gmm_fit.hip)
@@ -314,6 +314,7 @@ struct vssr_handle {
     vssr::Kind kind = vssr::Kind::NONE;
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in pot_params
     int eam_nel = 0, eam_fs = 0;   // EAM with typed tables (vssr_eam_create_alloy): elements, 1 = eam/fs densities; 0 = one funcfl
+    bool eam_adp = false;          // EAM with dipole / quadrupole tables (vssr_eam_create_adp): eam_run / eam_stress hand over to adp.hip
     int device = 0;
     vssr::OwnedStream stream;    // null until the handle reaches a device (open_device)
     std::string err;
@@ -501,6 +502,9 @@ int painn_gen_run(vssr_handle *h, uint32_t want);
 int tersoff_run(vssr_handle *h, uint32_t want);
 // EAM (eam.hip)
 int eam_run(vssr_handle *h, uint32_t want);
+// ADP (adp.hip): what eam_run / eam_stress do for a handle with eam_adp
+int adp_run(vssr_handle *h, uint32_t want);
+int adp_stress(vssr_handle *h);
 // Stillinger-Weber (sw.hip)
 int sw_run(vssr_handle *h, uint32_t want);
 // pair potentials (pair.hip)

@@ -1,4 +1,4 @@
-"""LAMMPS ``pair_style eam`` / ``eam/alloy`` / ``eam/fs`` potential files (host side, data formats only).
+"""LAMMPS ``pair_style eam`` / ``eam/alloy`` / ``eam/fs`` / ``adp`` potential files (host side, data formats only).
 
 The reference hands ``mcmc/potentials/Cu_u3.eam`` to LAMMPS through ``LAMMPSRunSurfCalc.set(pair_style="eam",
 pair_coeff=["* * Cu_u3.eam"])`` (``tests/test_Cu.py:41,65-70``, ``tutorials/example.ipynb`` cell 3).  Layout of a funcfl
@@ -9,6 +9,10 @@ values of the electron density rho(r), free format.
 Several elements (``setfl``, ``eam/alloy``; ``eam/fs``; funcfl files mixed per type as LAMMPS ``pair_coeff i i file``) end in one
 :class:`EamTables`: the typed arrays of ``vssr_eam_create_alloy`` on one common grid (restated from LAMMPS ``pair_eam.cpp``,
 ``pair_eam_alloy.cpp``, ``pair_eam_fs.cpp`` ``read_file`` / ``file2array``).
+
+An ``adp`` file (restated from the LAMMPS documentation of ``pair_style adp``) is a setfl file followed, after the r * phi blocks,
+by one u(r) block per element pair and then one w(r) block per element pair, in the same lower-triangle order, ``Nr`` values
+each and NOT scaled by r: the ``u`` / ``w`` fields of :class:`Setfl` and :class:`EamTables`, ``None`` for the other styles.
 """
 
 from __future__ import annotations
@@ -83,6 +87,8 @@ class Setfl:
     z2r: np.ndarray
     fs: bool = False
     comments: tuple = ("", "", "")
+    u: np.ndarray | None = None   # adp: [N (N + 1) / 2][Nr] dipole function u(r) of the pairs, in the order of z2r
+    w: np.ndarray | None = None   # adp: likewise the quadrupole function w(r)
 
 
 @dataclasses.dataclass
@@ -100,6 +106,8 @@ class EamTables:
     frho: np.ndarray
     rhor: np.ndarray
     z2r: np.ndarray
+    u: np.ndarray | None = None   # adp: [n (n + 1) / 2][nr] in the pair order of z2r (vssr_eam_create_adp), else None
+    w: np.ndarray | None = None
 
 
 def pair_index(a: int, b: int) -> int:
@@ -138,7 +146,15 @@ class _Lines:
 
 
 def parse_setfl(text: str, fs: bool = False) -> Setfl:
-    what = "eam/fs file" if fs else "setfl file"
+    return _parse_setfl(text, "eam/fs file" if fs else "setfl file", fs=fs)
+
+
+def parse_adp(text: str) -> Setfl:
+    """An ``adp`` file: the setfl blocks, then u(r) and w(r) of every element pair (``Setfl.u`` / ``Setfl.w``)."""
+    return _parse_setfl(text, "adp file", adp=True)
+
+
+def _parse_setfl(text, what, fs=False, adp=False):
     rd = _Lines(text, what)
     lines = text.splitlines()
     if len(lines) < 5:
@@ -185,7 +201,13 @@ def parse_setfl(text: str, fs: bool = False) -> Setfl:
     z2r = np.zeros((n * (n + 1) // 2, nr))
     for p in range(len(z2r)):
         z2r[p] = rd.values(nr)
-    return Setfl(list(elements), zs, masses, lats, ltypes, nrho, drho, nr, dr, cutoff, frho, rhor, z2r, bool(fs), comments)
+    u = w = None
+    if adp:
+        u, w = np.zeros_like(z2r), np.zeros_like(z2r)
+        for tab in (u, w):
+            for p in range(len(tab)):
+                tab[p] = rd.values(nr)
+    return Setfl(list(elements), zs, masses, lats, ltypes, nrho, drho, nr, dr, cutoff, frho, rhor, z2r, bool(fs), comments, u, w)
 
 
 def read_setfl(path, fs: bool = False) -> Setfl:
@@ -193,12 +215,47 @@ def read_setfl(path, fs: bool = False) -> Setfl:
         return parse_setfl(fh.read(), fs=fs)
 
 
+def read_adp(path) -> Setfl:
+    with open(path) as fh:
+        return parse_adp(fh.read())
+
+
+def write_adp(setfl: Setfl, path=None) -> str:
+    """The text of an ``adp`` file: ``write_setfl`` followed by the u and the w blocks (``setfl.u`` / ``setfl.w`` are required)."""
+    n = len(setfl.elements)
+    if setfl.fs or setfl.u is None or setfl.w is None:
+        raise ValueError("adp file: needs alloy densities and the u and w tables")
+    if np.shape(setfl.u) != (n * (n + 1) // 2, setfl.nr) or np.shape(setfl.w) != (n * (n + 1) // 2, setfl.nr):
+        raise ValueError("adp file: u and w must be [N (N + 1) / 2][Nr]")
+    return _write(_setfl_lines(setfl) + _table_lines(setfl.u) + _table_lines(setfl.w), path)
+
+
 def write_setfl(setfl: Setfl, path=None) -> str:
     """The text of ``setfl`` (values as ``%.16e``, five per line, so that parse_setfl gives back the same doubles); also
     written to ``path`` when given."""
-    def table(v):
+    return _write(_setfl_lines(setfl), path)
+
+
+def _write(lines, path):
+    text = "\n".join(lines) + "\n"
+    if path is not None:
+        with open(path, "w") as fh:
+            fh.write(text)
+    return text
+
+
+def _table_lines(tables):
+    """One block per row of ``tables``, five values per line."""
+    out = []
+    for v in tables:
         v = np.asarray(v, np.float64).reshape(-1)
-        return ["".join(f" {x:.16e}" for x in v[k:k + 5]).strip() for k in range(0, len(v), 5)]
+        out += ["".join(f" {x:.16e}" for x in v[k:k + 5]).strip() for k in range(0, len(v), 5)]
+    return out
+
+
+def _setfl_lines(setfl):
+    def table(v):
+        return _table_lines([v])
 
     n = len(setfl.elements)
     out = [str(c) for c in (list(setfl.comments) + ["", "", ""])[:3]]
@@ -213,13 +270,7 @@ def write_setfl(setfl: Setfl, path=None) -> str:
                 out += table(setfl.rhor[i][j])
         else:
             out += table(setfl.rhor[i])
-    for p in range(len(setfl.z2r)):
-        out += table(setfl.z2r[p])
-    text = "\n".join(out) + "\n"
-    if path is not None:
-        with open(path, "w") as fh:
-            fh.write(text)
-    return text
+    return out + _table_lines(setfl.z2r)
 
 
 def funcfl_to_setfl(f: Funcfl, element: str | None = None) -> Setfl:
@@ -241,10 +292,20 @@ def _check_names(names, what):
         raise ValueError(f"{what}: NULL types (pair_style hybrid) are not supported")
 
 
+def tables_from_adp(setfl: Setfl, elements) -> EamTables:
+    """``tables_from_setfl`` for a parsed ``adp`` file: the tables carry ``u`` / ``w`` of the chosen types."""
+    if setfl.fs or setfl.u is None or setfl.w is None:
+        raise ValueError("adp: the file holds no u and w tables (parse it with parse_adp)")
+    return _tables(setfl, elements, "adp", True)
+
+
 def tables_from_setfl(setfl: Setfl, elements) -> EamTables:
     """LAMMPS ``pair_coeff * * file el_1 ... el_n``: type t is element ``elements[t]`` of the file."""
+    return _tables(setfl, elements, "eam/fs" if setfl.fs else "eam/alloy", False)
+
+
+def _tables(setfl, elements, what, adp):
     names = [str(x) for x in elements]
-    what = "eam/fs" if setfl.fs else "eam/alloy"
     _check_names(names, what)
     idx = []
     for x in names:
@@ -257,8 +318,10 @@ def tables_from_setfl(setfl: Setfl, elements) -> EamTables:
         rhor = np.stack([setfl.rhor[a][b] for a in idx for b in idx])
     else:
         rhor = np.stack([setfl.rhor[a] for a in idx])
-    z2r = np.stack([setfl.z2r[pair_index(idx[a], idx[b])] for a in range(n) for b in range(a + 1)])
-    return EamTables(names, setfl.fs, setfl.nrho, setfl.drho, setfl.nr, setfl.dr, setfl.cutoff, frho, rhor, z2r)
+    pairs = [pair_index(idx[a], idx[b]) for a in range(n) for b in range(a + 1)]
+    z2r = np.stack([setfl.z2r[k] for k in pairs])
+    u, w = (np.stack([t[k] for k in pairs]) for t in (setfl.u, setfl.w)) if adp else (None, None)
+    return EamTables(names, setfl.fs, setfl.nrho, setfl.drho, setfl.nr, setfl.dr, setfl.cutoff, frho, rhor, z2r, u, w)
 
 
 def _lagrange(f, delta_file, n_file, x):
