@@ -381,6 +381,30 @@ def pack_batch(structs):
     return n_atoms, Z, pos, cell, pbc
 
 
+def _batch_arrays(n_atoms, Z, pos, cell, pbc):
+    """The five batch arrays in the ABI's dtypes, C-contiguous (``n_atoms`` int32 [B], ``Z`` -- atomic numbers or types -- int32 [N],
+    ``pos`` float64 [N, 3], ``cell`` float64 [B, 9], ``pbc`` uint8 [B, 3]); ``ValueError`` when their sizes disagree."""
+    n_atoms = np.ascontiguousarray(n_atoms, dtype=np.int32)
+    Z = np.ascontiguousarray(Z, dtype=np.int32)
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    cell = np.ascontiguousarray(cell, dtype=np.float64)
+    pbc = np.ascontiguousarray(pbc, dtype=np.uint8)
+    B, N = len(n_atoms), Z.shape[0]
+    if N != int(n_atoms.sum()) or pos.size != 3 * N or cell.size != 9 * B or pbc.size != 3 * B:
+        raise ValueError("inconsistent batch arrays")
+    return n_atoms, Z, pos, cell, pbc
+
+
+def _fixed_arg(fixed, N):
+    """A FixAtoms mask as the ABI takes it: uint8 [N], C-contiguous, or None."""
+    if fixed is None:
+        return None
+    fx = np.ascontiguousarray(fixed, dtype=np.uint8)
+    if fx.size != N:
+        raise ValueError("fixed mask does not match the resident batch")
+    return fx
+
+
 class _DeviceArray:
     """A float32 (or int32) vector in device memory owned by an engine (``__cuda_array_interface__`` v2)."""
 
@@ -397,8 +421,7 @@ class _Handle:
         self._lib = load_library()
         self._h = C.c_void_p(None)
         self.n_models = 1
-        self._n_cfg = 0
-        self._n_atoms = 0
+        self._set_resident(np.zeros(0, np.int32))   # (no batch yet)
 
     def _check(self, rc):
         if rc != 0:
@@ -421,20 +444,17 @@ class _Handle:
         n_atoms, Z, pos, cell, pbc = pack_batch(structs)
         self.upload_arrays(n_atoms, Z, pos, cell, pbc)
 
+    def _set_resident(self, n_atoms):
+        """The shape of the batch the handle now holds: what ``download``, ``set_positions`` and the relaxations size arrays by."""
+        self._n_cfg, self._n_atoms = len(n_atoms), int(n_atoms.sum())
+        self._cfg_start = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+
     def upload_arrays(self, n_atoms, Z, pos, cell, pbc):
-        n_atoms = np.ascontiguousarray(n_atoms, dtype=np.int32)
-        Z = np.ascontiguousarray(Z, dtype=np.int32)
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        cell = np.ascontiguousarray(cell, dtype=np.float64)
-        pbc = np.ascontiguousarray(pbc, dtype=np.uint8)
-        if Z.shape[0] != int(n_atoms.sum()) or pos.size != 3 * Z.shape[0] or cell.size != 9 * len(n_atoms) \
-                or pbc.size != 3 * len(n_atoms):
-            raise ValueError("inconsistent batch arrays")
+        n_atoms, Z, pos, cell, pbc = _batch_arrays(n_atoms, Z, pos, cell, pbc)
         self._check(self._lib.vssr_batch_upload(self._h, len(n_atoms), _ptr(n_atoms, C.c_int32),
                                                 _ptr(Z, C.c_int32), _ptr(pos, C.c_double),
                                                 _ptr(cell, C.c_double), _ptr(pbc, C.c_uint8)))
-        self._n_cfg, self._n_atoms = len(n_atoms), int(Z.shape[0])
-        self._cfg_start = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+        self._set_resident(n_atoms)
 
     def set_positions(self, pos):
         pos = np.ascontiguousarray(pos, dtype=np.float64)
@@ -587,11 +607,7 @@ class _Handle:
     def _relax_call(self, fn, p, fixed, want, record_interval=0):
         N, B = self._n_atoms, self._n_cfg
         self._check(self._lib.vssr_batch_traj_configure(self._h, int(record_interval or 0)))
-        fx = None
-        if fixed is not None:
-            fx = np.ascontiguousarray(fixed, dtype=np.uint8)
-            if fx.size != N:
-                raise ValueError("fixed mask does not match the resident batch")
+        fx = _fixed_arg(fixed, N)
         pos = np.zeros((N, 3), np.float64)
         steps = np.zeros(B, np.int32)
         conv = np.zeros(B, np.uint8)
@@ -744,11 +760,7 @@ class _AnalyticEngine(_Handle):
         self.upload_arrays(n_atoms, T, pos, cell, pbc)
         self._check(self._lib.vssr_batch_relax_cg_driver(self._h, code, None))
         N, B = self._n_atoms, self._n_cfg
-        fx = None
-        if fixed is not None:
-            fx = np.ascontiguousarray(fixed, dtype=np.uint8)
-            if fx.size != N:
-                raise ValueError("fixed mask does not match the resident batch")
+        fx = _fixed_arg(fixed, N)
         p = CgParams.default(max_iter, max_eval, etol, ftol, dmax)
         out = np.zeros((N, 3), np.float64)
         it, ev, why = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
@@ -766,21 +778,14 @@ class _AnalyticEngine(_Handle):
 
     def evaluate_arrays_f64(self, n_atoms, T, pos, cell, pbc, want=WANT_ENERGY | WANT_FORCES | WANT_PER_ATOM):
         """``evaluate_f64`` on the ABI's packed arrays."""
-        n_atoms = np.ascontiguousarray(n_atoms, dtype=np.int32)
-        T = np.ascontiguousarray(T, dtype=np.int32)
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        cell = np.ascontiguousarray(cell, dtype=np.float64)
-        pbc = np.ascontiguousarray(pbc, dtype=np.uint8)
+        n_atoms, T, pos, cell, pbc = _batch_arrays(n_atoms, T, pos, cell, pbc)
         B, N = len(n_atoms), len(T)
-        if N != int(n_atoms.sum()) or pos.size != 3 * N or cell.size != 9 * B or pbc.size != 3 * B:
-            raise ValueError("inconsistent batch arrays")
         e = np.zeros(B); ea = np.zeros(N); f = np.zeros((N, 3))
         self._check(self._lib.vssr_tersoff_eval_batch(
             self._h, B, _ptr(n_atoms, C.c_int32), _ptr(T, C.c_int32), _ptr(pos, C.c_double),
             _ptr(cell, C.c_double), _ptr(pbc, C.c_uint8), int(want), None, _ptr(e, C.c_double),
             _ptr(ea, C.c_double), _ptr(f, C.c_double)))
-        self._n_cfg, self._n_atoms = B, N
-        self._cfg_start = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+        self._set_resident(n_atoms)
         return e, ea, f
 
 

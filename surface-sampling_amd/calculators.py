@@ -29,7 +29,7 @@ from collections import Counter
 
 import numpy as np
 
-from . import backend, checkpoint, pair as pair_io, structures, sw as sw_io, tersoff as tersoff_io
+from . import backend, checkpoint, host_opt, pair as pair_io, structures, sw as sw_io, tersoff as tersoff_io
 
 EV_TO_KCAL_MOL = 23.0605   # nff/utils/constants.py
 HARTREE_TO_EV = 27.2114    # nff/utils/constants.py (reference import: calculators.py:21)
@@ -193,6 +193,64 @@ def surface_energy_from_energy(energy: float, symbols, chem_pots: dict, offset_d
         if ele != ref_element:
             pot += (ads_count[ele] - stoics[ele] / stoics[ref_element] * ads_count[ref_element]) * chem_pots[ele]
     return surface_energy - pot
+
+
+# thresholds of the reference's out-of-bounds guard (mcmc/dynamics.py:17-18,159-168): class attributes of both calculator families
+ENERGY_THRESHOLD = 1000.0
+MAX_FORCE_THRESHOLD = 1000.0
+
+
+def _cfg_start(n_atoms) -> np.ndarray:
+    """int64 prefix sum ``[B + 1]`` of the chains' atom counts: chain b holds the atoms ``start[b]:start[b + 1]``."""
+    return np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+
+
+def _fixed_mask(sizes, fixed_indices):
+    """uint8 mask ``[sum N]`` (1 = held, FixAtoms) of per-slab index lists, ``fixed_indices[b]`` counting inside slab b; a slab whose
+    entry is None or empty holds nothing.  ``fixed_indices=None``: no mask at all (None)."""
+    if fixed_indices is None:
+        return None
+    start = _cfg_start(sizes)
+    mask = np.zeros(int(start[-1]), np.uint8)
+    held = [o + np.asarray(idx, dtype=np.int64) for o, idx in zip(start, fixed_indices) if idx is not None and len(idx)]
+    if held:
+        mask[np.concatenate(held)] = 1
+    return mask
+
+
+def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:
+    """bool ``[B]``: the reference's out-of-bounds guard (``mcmc/dynamics.py:159-168``) for every chain of a batch -- a non-finite energy
+    or force, ``|E| > e_max``, a force component beyond ``f_max``, or a ``saturated`` evaluation."""
+    fabs = np.abs(forces).max(axis=1) if len(forces) else np.zeros(0, forces.dtype)
+    nonempty = cfg_start[1:] > cfg_start[:-1]
+    max_force = np.zeros(len(cfg_start) - 1, fabs.dtype)
+    if nonempty.any():
+        max_force[nonempty] = np.maximum.reduceat(fabs, cfg_start[:-1][nonempty])
+    with np.errstate(invalid="ignore"):
+        oob = (~np.isfinite(energy)) | (~np.isfinite(max_force)) | (np.abs(energy) > e_max) | (max_force > f_max)
+    return oob if saturated is None else oob | np.asarray(saturated, dtype=bool)
+
+
+def _chain_counts(counts, b) -> dict:
+    """Chain b's entries of a relaxation's per-chain count arrays as Python values, a CG ``stop`` code as its text."""
+    out = {}
+    for key, values in counts.items():
+        if key == "stop":
+            out[key] = backend.CG_STOP_REASONS.get(int(values[b]), str(int(values[b])))
+        else:
+            out[key] = bool(values[b]) if key == "converged" else int(values[b])
+    return out
+
+
+def _lockstep_evaluate(eng):
+    """``evaluate(pos_all) -> (fp64 energies [B], fp64 forces [N, 3])`` of the engine's resident batch, for host_opt.py's drivers."""
+    def evaluate(pos_all):
+        eng.set_positions(pos_all)
+        eng.run()
+        r = eng.download()
+        return np.asarray(r.get("energy_f64", r["energy"]), dtype=np.float64), np.asarray(r["forces"], dtype=np.float64)
+
+    return evaluate
 
 
 class _LockstepProxy(_Base):
@@ -424,8 +482,8 @@ class EnsembleNFFSurface(_Base):
             pos = np.asarray(pos, dtype=np.float64).astype(np.float32).astype(np.float64)
         return Z, pos, cell, pbc
 
-    def _fill_results(self, res, b=0):
-        a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
+    def _fill_results(self, res, b, a0, a1):
+        """The results dict of configuration ``b`` (atoms ``a0:a1``) of a downloaded batch."""
         return {
             "energy": res["energy"][b:b + 1].copy(),            # shape (1,), like the reference
             "energy_std": res["energy_std"][b:b + 1].copy(),
@@ -453,7 +511,7 @@ class EnsembleNFFSurface(_Base):
         res = eng.evaluate([self._arrays(atoms)])
         # a fresh dict per calculation, like nff's NeuralFF / EnsembleNFF.calculate: entries of an earlier structure that this
         # call does not produce (surface_energy, stress, embedding) must not survive a direct calculate() on another one
-        self.results = dict(self._fill_results(res, 0))
+        self.results = self._fill_results(res, 0, 0, int(res["cfg_start"][1]))
         if "stress" in properties or "stress_std" in properties:
             st, sd = eng.stress()
             self.results["stress"], self.results["stress_std"] = st[0], sd[0]
@@ -498,25 +556,22 @@ class EnsembleNFFSurface(_Base):
         per_atom_unc = unc is not None and uncertainty_rows == "atoms" and "system" not in uncertainty.order
         out = []
         for b, atoms in enumerate(atoms_list):
-            r = self._fill_results(res, b)
+            a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
+            r = self._fill_results(res, b, a0, a1)
             if want_surface_energy:
                 r["surface_energy"] = self.surface_energy_of(r["energy"], atoms)
             if stress is not None:
                 r["stress"], r["stress_std"] = stress[0][b].copy(), stress[1][b].copy()
             if emb is not None:
-                a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
                 r["embedding"] = emb[0, a0:a1].copy()
                 r["embedding_models"] = emb[:, a0:a1].copy()
             if unc is not None:
-                a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
                 r["uncertainty"] = unc[a0:a1].copy() if per_atom_unc else np.float64(unc.reshape(-1)[b])
             out.append(r)
         return out
 
 
-    # thresholds of the reference's out-of-bounds guard (mcmc/dynamics.py:17-18,159-168)
-    ENERGY_THRESHOLD = 1000.0
-    MAX_FORCE_THRESHOLD = 1000.0
+    ENERGY_THRESHOLD, MAX_FORCE_THRESHOLD = ENERGY_THRESHOLD, MAX_FORCE_THRESHOLD   # (the module's; an instance may override them)
     # evaluate_packed: engines (HIP streams) the chains of a batch are split over, and the smallest part worth a stream
     streams = 2
     MIN_CHAINS_PER_STREAM = 32
@@ -587,7 +642,7 @@ class EnsembleNFFSurface(_Base):
             from concurrent.futures import ThreadPoolExecutor
 
             cb = [(k * B) // n_str for k in range(n_str + 1)]
-            ab = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+            ab = _cfg_start(n_atoms)
             engines = self._get_engines(n_str)
             with ThreadPoolExecutor(max_workers=n_str) as pool:
                 parts = list(pool.map(lambda k: one(engines[k], cb[k], cb[k + 1], int(ab[cb[k]]), int(ab[cb[k + 1]])), range(n_str)))
@@ -597,23 +652,59 @@ class EnsembleNFFSurface(_Base):
             if relax:
                 info = {k: np.concatenate([p[1][k] for p in parts]) for k in ("positions", "n_steps", "converged")}
         start = np.asarray(res["cfg_start"], dtype=np.int64)
-        fabs = np.abs(res["forces"]).max(axis=1) if len(res["forces"]) else np.zeros(0, np.float32)
-        nonempty = start[1:] > start[:-1]
-        max_force = np.zeros(len(start) - 1, np.float32)
-        if nonempty.any():
-            max_force[nonempty] = np.maximum.reduceat(fabs, start[:-1][nonempty])
         energy = res["energy"]
         e64 = np.asarray(res["energy_f64"] if "energy_f64" in res else energy, dtype=np.float64)
-        with np.errstate(invalid="ignore"):
-            oob = (~np.isfinite(energy)) | (~np.isfinite(max_force)) | (np.abs(energy) > self.ENERGY_THRESHOLD) \
-                | (max_force > self.MAX_FORCE_THRESHOLD) | np.asarray(res["saturated"], dtype=bool)
+        saturated = np.asarray(res["saturated"], dtype=bool)
         out = {"energy": energy, "energy_std": res["energy_std"], "forces": res["forces"], "energy_atoms": res["energy_atoms"],
                "positions": info["positions"] if info is not None else np.asarray(pos, dtype=np.float64).reshape(-1, 3),
-               "cfg_start": start, "saturated": np.asarray(res["saturated"], dtype=bool), "oob": oob, "energy_f64": e64,
+               "cfg_start": start, "saturated": saturated, "energy_f64": e64,
+               "oob": _oob_flags(energy, res["forces"], start, saturated, e_max=self.ENERGY_THRESHOLD, f_max=self.MAX_FORCE_THRESHOLD),
                "energy_std_f64": np.asarray(res["energy_std_f64"] if "energy_std_f64" in res else res["energy_std"], dtype=np.float64)}
         if info is not None:
             out["n_steps"], out["converged"] = info["n_steps"], info["converged"]
         return out
+
+    # -- who drives relax_batch's resident batch.  Each returns ``(info, trajs)``: ``info`` = ``positions``, the count arrays ``n_steps`` /
+    # ``converged`` (line search: also ``n_eval`` / ``stop_reason``), ``results`` (the final download); ``trajs`` per chain, or None ----
+    def _relax_by_class(self, eng, opt_cls, atoms_list, start, fixed_indices, fixed, steps, fmax, record_interval, quiet):
+        """Any optimizer of the ASE protocol, one per chain on the host, served by lock-step evaluations (host_opt.py)."""
+        info = host_opt.optimizer_class_batch(opt_cls, atoms_list, _LockstepProxy, _lockstep_evaluate(eng), start, fixed_indices=fixed_indices,
+                                              steps=steps, fmax=fmax, record_interval=record_interval,
+                                              optimizer_kwargs={"logfile": None} if quiet else {})
+        eng.set_positions(info["positions"])
+        eng.run()
+        res = eng.download()
+        # ASE optimizers count their steps; converged: ASE's criterion on the final forces (constraints applied)
+        ff = np.array(res["forces"], dtype=np.float64, copy=True)
+        if fixed is not None:
+            ff[fixed.astype(bool)] = 0.0
+        f2 = (ff ** 2).sum(axis=1)
+        return {"positions": info["positions"], "n_steps": np.array([int(getattr(d, "nsteps", -1)) for d in info["optimizers"]], np.int32),
+                "converged": np.array([a1 == a0 or bool(f2[a0:a1].max() < fmax ** 2) for a0, a1 in zip(start[:-1], start[1:])], bool),
+                "results": res}, info["traj"]
+
+    def _relax_by_host_cg(self, eng, atoms_list, start, fixed, steps, fmax, record_interval):
+        """The reference maps "CG" to ASE's SciPyFminCG (mcmc/dynamics.py:123-124): scipy owns the control flow, so every chain's
+        optimizer runs on the host and their energy / force requests are served by lock-step evaluations (host_opt.py)."""
+        pos0 = np.concatenate([np.asarray(a.get_positions(), dtype=np.float64).reshape(-1, 3) for a in atoms_list])
+        info = host_opt.scipy_cg_batch(_lockstep_evaluate(eng), start, pos0, fixed=fixed, steps=steps, fmax=fmax, record_interval=record_interval)
+        eng.set_positions(info["positions"])
+        eng.run()
+        info["results"] = eng.download()
+        return info, [{"atoms": _traj_frames(atoms, [p for p, _, _ in recs]), "energies": [float(e) for _, e, _ in recs],
+                       "forces": [np.asarray(f, dtype=np.float32) for _, _, f in recs]} for atoms, recs in zip(atoms_list, info["traj"] or [])]
+
+    def _relax_by_linesearch(self, eng, atoms_list, start, fixed, steps, fmax, record_interval):
+        """The device's lock-step BFGSLineSearch (``backend.relax_bfgs_linesearch``)."""
+        info = eng.relax_bfgs_linesearch(fixed=fixed, max_steps=steps, fmax=fmax, record_interval=record_interval)
+        info["results"] = eng.download()
+        return info, [_traj_of_chain(info.get("traj"), b, int(start[b]), int(start[b + 1]), a) for b, a in enumerate(atoms_list)]
+
+    def _relax_by_device(self, eng, optimizer, atoms_list, start, fixed, steps, fmax, record_interval):
+        """The device's lock-step FIRE / BFGS, chosen by the optimizer's name (``backend.relax``)."""
+        info = eng.relax(optimizer, fixed=fixed, max_steps=steps, fmax=fmax, record_interval=record_interval)
+        info["results"] = eng.download()
+        return info, [_traj_of_chain(info.get("traj"), b, int(start[b]), int(start[b + 1]), a) for b, a in enumerate(atoms_list)]
 
     def relax_batch(self, atoms_list, fixed_indices=None, relax_steps: int = 20, fmax: float = 0.01, optimizer=None,
                     save_traj: bool = False, record_interval: int = 5, linesearch_driver=None):
@@ -637,107 +728,41 @@ class EnsembleNFFSurface(_Base):
         eng = self._get_engine()
         packs = [structures.as_arrays(a) for a in atoms_list]
         eng.upload(packs)
-        fixed = None
-        if fixed_indices is not None:
-            fixed = np.zeros(sum(len(p[0]) for p in packs), np.uint8)
-            o = 0
-            for p, idx in zip(packs, fixed_indices):
-                if idx is not None and len(idx):
-                    fixed[o + np.asarray(idx, dtype=np.int64)] = 1
-                o += len(p[0])
+        start = _cfg_start([len(p[0]) for p in packs])
+        fixed = _fixed_mask(np.diff(start), fixed_indices)
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "FIRE")
-        host_traj = None
+        record = int(record_interval) if save_traj else 0
         opt_cls = optimizer if callable(optimizer) else None
-        device_ls = opt_cls is None and "BFGSLineSearch" in str(optimizer) and ls_driver == "device"
-        if opt_cls is None and "BFGSLineSearch" in str(optimizer) and not device_ls:
+        line_search = opt_cls is None and "BFGSLineSearch" in str(optimizer)
+        if line_search and ls_driver != "device":
             try:   # the reference's import (mcmc/dynamics.py:7): only where ASE is installed
                 from ase.optimize import BFGSLineSearch as opt_cls
             except Exception as exc:
                 raise backend.BackendError('optimizer "BFGSLineSearch" is ASE\'s class and ASE is not importable here; pass an '
                                            "optimizer class, or use BFGS / FIRE / CG") from exc
         if opt_cls is not None:
-            # any optimizer of the ASE protocol, one per chain on the host, served by lock-step evaluations (host_opt.py)
-            from . import host_opt
-
-            def evaluate(pos_all):
-                eng.set_positions(pos_all)
-                eng.run()
-                r = eng.download()
-                return np.asarray(r.get("energy_f64", r["energy"]), dtype=np.float64), np.asarray(r["forces"], dtype=np.float64)
-
-            cfg = np.concatenate([[0], np.cumsum([len(p[0]) for p in packs])])
-            kw = {"logfile": None} if HAVE_ASE and not callable(optimizer) else {}
-            info = host_opt.optimizer_class_batch(opt_cls, atoms_list, _LockstepProxy, evaluate, cfg, fixed_indices=fixed_indices,
-                                                  steps=relax_steps, fmax=fmax, record_interval=int(record_interval) if save_traj else 0,
-                                                  optimizer_kwargs=kw)
-            info["n_steps"] = np.array([int(getattr(d, "nsteps", -1)) for d in info["optimizers"]], np.int32)   # ASE optimizers count
-            info["converged"] = np.zeros(len(packs), bool)   # judged below from the final forces
-            class_traj = info["traj"]
-            info["traj"] = None
-            eng.set_positions(info["positions"])
-            eng.run()
+            info, trajs = self._relax_by_class(eng, opt_cls, atoms_list, start, fixed_indices, fixed, relax_steps, fmax, record,
+                                               quiet=HAVE_ASE and not callable(optimizer))
         elif "CG" in str(optimizer) and "LAMMPS" not in str(optimizer):
-            # the reference maps "CG" to ASE's SciPyFminCG (mcmc/dynamics.py:123-124): scipy owns the control flow, so every chain's
-            # optimizer runs on the host and their energy / force requests are served by lock-step evaluations (host_opt.py)
-            from . import host_opt
-
-            def evaluate(pos_all):
-                eng.set_positions(pos_all)
-                eng.run()
-                r = eng.download()
-                return np.asarray(r.get("energy_f64", r["energy"]), dtype=np.float64), np.asarray(r["forces"], dtype=np.float64)
-
-            cfg = np.concatenate([[0], np.cumsum([len(p[0]) for p in packs])])
-            pos0 = np.concatenate([np.asarray(p[1], dtype=np.float64).reshape(-1, 3) for p in packs])
-            info = host_opt.scipy_cg_batch(evaluate, cfg, pos0, fixed=fixed, steps=relax_steps, fmax=fmax,
-                                           record_interval=int(record_interval) if save_traj else 0)
-            host_traj = info["traj"]
-            eng.set_positions(info["positions"])
-            eng.run()
-        elif device_ls:
-            info = eng.relax_bfgs_linesearch(fixed=fixed, max_steps=relax_steps, fmax=fmax,
-                                             record_interval=int(record_interval) if save_traj else 0)
+            info, trajs = self._relax_by_host_cg(eng, atoms_list, start, fixed, relax_steps, fmax, record)
+        elif line_search:
+            info, trajs = self._relax_by_linesearch(eng, atoms_list, start, fixed, relax_steps, fmax, record)
         else:
-            info = eng.relax(optimizer, fixed=fixed, max_steps=relax_steps, fmax=fmax,
-                             record_interval=int(record_interval) if save_traj else 0)
-        res = eng.download()
+            info, trajs = self._relax_by_device(eng, optimizer, atoms_list, start, fixed, relax_steps, fmax, record)
+        res = info["results"]
+        e64 = np.asarray(res["energy_f64"] if "energy_f64" in res else res["energy"], dtype=np.float64)
+        oob = _oob_flags(e64, res["forces"], start, res.get("saturated"), e_max=self.ENERGY_THRESHOLD, f_max=self.MAX_FORCE_THRESHOLD)
         out = []
         for b, atoms in enumerate(atoms_list):
-            a0, a1 = int(res["cfg_start"][b]), int(res["cfg_start"][b + 1])
+            a0, a1 = int(start[b]), int(start[b + 1])
             relaxed = atoms.copy()
             relaxed.set_positions(info["positions"][a0:a1])
-            if opt_cls is not None:
-                traj = class_traj[b] if (save_traj and class_traj is not None) else None
-            elif host_traj is not None:
-                frames = []
-                for fpos, _, _ in host_traj[b]:
-                    frame = atoms.copy()
-                    frame.set_positions(fpos)
-                    if hasattr(frame, "calc"):
-                        frame.calc = None
-                    frames.append(frame)
-                traj = {"atoms": frames, "energies": [float(e) for _, e, _ in host_traj[b]],
-                        "forces": [np.asarray(f, dtype=np.float32) for _, _, f in host_traj[b]]}
-            else:
-                traj = _traj_of_chain(info.get("traj"), b, a0, a1, atoms) if save_traj else None
-            r = self._fill_results(res, b)
-            energy = float(r["energy_f64"]) if "energy_f64" in r else float(r["energy"][0])
-            max_force = float(np.abs(r["forces"]).max()) if a1 > a0 else 0.0
-            oob = bool(not np.isfinite(energy) or not np.isfinite(max_force) or abs(energy) > self.ENERGY_THRESHOLD
-                       or max_force > self.MAX_FORCE_THRESHOLD or r["saturated"])
-            if oob:
-                energy = self.ENERGY_THRESHOLD
-            r["n_steps"] = int(info["n_steps"][b])
-            r["converged"] = bool(info["converged"][b])
-            if device_ls:
+            r = self._fill_results(res, b, a0, a1)
+            r["n_steps"], r["converged"] = int(info["n_steps"][b]), bool(info["converged"][b])
+            if "n_eval" in info:
                 r["n_eval"], r["stop_reason"] = int(info["n_eval"][b]), int(info["stop_reason"][b])
-            if opt_cls is not None:   # ASE's criterion on the final forces (constraints applied)
-                ff = np.array(r["forces"], dtype=np.float64, copy=True)
-                if fixed_indices is not None and fixed_indices[b] is not None and len(fixed_indices[b]):
-                    ff[np.asarray(fixed_indices[b], dtype=np.int64)] = 0.0
-                r["converged"] = bool((ff ** 2).sum(axis=1).max() < fmax ** 2) if len(ff) else True
-            out.append((relaxed, traj, energy, oob, r))
+            out.append((relaxed, trajs[b] if trajs else None, self.ENERGY_THRESHOLD if oob[b] else float(e64[b]), bool(oob[b]), r))
         return out
 
 
@@ -763,19 +788,24 @@ def surface_energy_from_counts(energy, counts: dict, chem_pots: dict, offset_dat
     return surface_energy - pot
 
 
+def _traj_frames(atoms, positions):
+    """Copies of ``atoms`` at each of ``positions``, without the calculator (the reference's observer stores such copies)."""
+    frames = []
+    for pos in positions:
+        frame = atoms.copy()
+        frame.set_positions(pos)
+        if hasattr(frame, "calc"):
+            frame.calc = None
+        frames.append(frame)
+    return frames
+
+
 def _traj_of_chain(traj, b, a0, a1, atoms):
-    """Records of chain b in the layout of the reference's ``optimize_slab`` (``mcmc/dynamics.py:145-151``)."""
+    """Records of chain b of a device trajectory in the layout of the reference's ``optimize_slab`` (``mcmc/dynamics.py:145-151``)."""
     if traj is None:
         return None
-    frames = []
     n = int(traj["n_records"][b])
-    for r in range(n):
-        frame = atoms.copy()
-        frame.set_positions(traj["positions"][r, a0:a1])
-        if hasattr(frame, "calc"):
-            frame.calc = None   # the observer stores copies without the calculator
-        frames.append(frame)
-    return {"atoms": frames, "energies": [float(traj["energies"][r, b]) for r in range(n)],
+    return {"atoms": _traj_frames(atoms, traj["positions"][:n, a0:a1]), "energies": [float(traj["energies"][r, b]) for r in range(n)],
             "forces": [traj["forces"][r, a0:a1].copy() for r in range(n)]}
 
 
@@ -991,22 +1021,29 @@ class _AnalyticSurfCalc(_Base):
         return changed
 
     def _cg_driver_of(self, kwargs) -> str:
-        """The CG driver of one relaxation call: its ``cg_driver`` keyword, else the calculator's setting."""
-        driver = kwargs.get("cg_driver", self.cg_driver)
+        """The CG driver of one relaxation call, validated: its ``cg_driver`` keyword, else (absent or None) the calculator's setting."""
+        driver = self.cg_driver if kwargs.get("cg_driver") is None else kwargs["cg_driver"]
         backend.cg_driver_code(driver)
         return driver
 
     def _pack(self, atoms):
         Z, pos, cell, pbc = structures.as_arrays(atoms)
-        idx = {structures.ATOMIC_NUMBERS[s]: t for t, s in enumerate(self.species)}
-        try:
-            types = np.array([idx[int(z)] for z in Z], dtype=np.int32)
-        except KeyError as e:
-            raise ValueError(f"element Z={e.args[0]} is not covered by the potential {self.species}") from None
+        types = self._types_of(Z)
         fixed_pbc = self._fixed_pbc()
         if fixed_pbc is not None:
             pbc = fixed_pbc.copy()
         return types, pos, cell, pbc
+
+    def _types_of(self, Z) -> np.ndarray:
+        """LAMMPS types of atomic numbers (the order of ``species``), vectorised; an element outside ``species`` or the symbol table raises."""
+        table = np.full(len(structures.SYMBOLS) + 1, -1, np.int32)   # (the last slot: where atomic numbers beyond the symbols land)
+        for t, sym in enumerate(self.species):
+            table[structures.ATOMIC_NUMBERS[sym]] = t
+        Z = np.asarray(Z, dtype=np.int64)
+        types = table[np.clip(Z, 0, len(table) - 1)]
+        if len(Z) and (types.min() < 0 or Z.min() < 0):   # (a negative Z was clipped onto X, which may be among the species)
+            raise ValueError(f"element Z={int(Z[np.argmax((types < 0) | (Z < 0))])} is not covered by the potential {self.species}")
+        return types
 
     def _fixed_pbc(self):
         """The boundary the run directory's template (or ``all_periodic``) imposes on every slab, None: the atoms' own ``pbc``."""
@@ -1018,19 +1055,28 @@ class _AnalyticSurfCalc(_Base):
             atoms = self.atoms
         return self.get_potential_energy(atoms=atoms)
 
+    def _evaluate_slabs(self, atoms_list, want_stress: bool = False) -> list[dict]:
+        """One device evaluation of the slabs: per slab ``energy`` / ``per_atom_energies`` / ``forces``, with ``want_stress`` also the
+        virial of that evaluation.  ``calculate``, ``run_lammps_energy`` and ``calculate_batch`` return it in their own shapes."""
+        packs = [self._pack(a) for a in atoms_list]
+        eng = self._get_engine()
+        e, ea, f = eng.evaluate_f64(packs)
+        stress = eng.stress()[0] if want_stress else None
+        start = _cfg_start([len(p[0]) for p in packs])
+        out = []
+        for b, (a0, a1) in enumerate(zip(start[:-1], start[1:])):
+            out.append({"energy": float(e[b]), "per_atom_energies": ea[a0:a1].copy(), "forces": f[a0:a1].copy()})
+            if stress is not None:
+                out[-1]["stress"] = stress[b].copy()
+        return out
+
     def calculate(self, atoms=None, properties=_default_properties, system_changes=all_changes):
         if atoms is None:
             atoms = self.atoms
         _Base.calculate(self, atoms, properties, system_changes)
-        eng = self._get_engine()
-        e, ea, f = eng.evaluate_f64([self._pack(atoms)])
-        self.results["energy"] = float(e[0])
-        self.results["per_atom_energies"] = ea
-        self.results["forces"] = f
         # the virial of THIS evaluation, or none: an entry an earlier call left behind must not answer a later get_stress()
         self.results.pop("stress", None)
-        if "stress" in properties:
-            self.results["stress"] = eng.stress()[0][0]
+        self.results.update(self._evaluate_slabs([atoms], want_stress="stress" in properties)[0])
         if "relaxed_energy" in properties:   # reference calculators.py:688-691
             _, e_rel, ea_rel = self.run_lammps_opt(atoms)
             self.results["relaxed_energy"] = e_rel
@@ -1042,123 +1088,95 @@ class _AnalyticSurfCalc(_Base):
         """``LAMMMPSCalc.run_lammps_energy`` (reference ``calculators.py:621-640``: the static energy through the run
         directory's ``lammps_energy_template.txt``): one device evaluation; returns the reference's tuple
         ``(slab, energy, per_atom_energies)``."""
-        e, ea, _ = self._get_engine().evaluate_f64([self._pack(slab)])
-        return slab, float(e[0]), ea
+        r = self._evaluate_slabs([slab])[0]
+        return slab, r["energy"], r["per_atom_energies"]
+
+    def calculate_batch(self, atoms_list, want_stress: bool = False) -> list[dict]:
+        return self._evaluate_slabs(atoms_list, want_stress)
+
+    def _relax_packed(self, n_atoms, types, pos, cell, pbc, fixed, optimizer, steps, fmax, *, etol, ftol, cg_driver, linesearch_driver,
+                      max_eval, record_interval):
+        """THE optimizer table of the analytic calculators, on the ABI's packed arrays: "CG" / "LAMMPS" (any case) -> the device CG
+        minimiser (``etol`` / ``ftol`` / ``cg_driver``); a name with "BFGSLineSearch" where ``linesearch_driver`` is "device" -> the device
+        line search (``fmax`` / ``max_eval`` / ``record_interval``); anything else -> FIRE / BFGS with ``fmax`` (the engine refuses other
+        names).  Every branch ends with a complete evaluation of the relaxed geometries.  Returns fp64 ``(energy [B], e_atom [N], forces,
+        positions, counts, traj)``: ``counts`` the per-chain arrays ``iterations`` / ``evaluations`` / ``stop`` (CG) or ``n_steps`` /
+        ``converged`` (line search: also ``n_eval`` / ``stop_reason``), ``traj`` the device trajectory or None."""
+        eng = self._get_engine()
+        if str(optimizer).upper() in ("CG", "LAMMPS"):
+            e, ea, f, new_pos, it, ev, why = eng.relax_cg_arrays_f64(n_atoms, types, pos, cell, pbc, fixed=fixed, max_iter=steps, etol=etol,
+                                                                     ftol=ftol, driver=cg_driver)
+            return e, ea, f, new_pos, {"iterations": it, "evaluations": ev, "stop": why}, None
+        if "BFGSLineSearch" in str(optimizer) and linesearch_driver == "device":
+            eng.upload_arrays(n_atoms, types, pos, cell, pbc)
+            info = eng.relax_bfgs_linesearch(fixed=fixed, max_steps=steps, fmax=fmax, max_eval=max_eval, record_interval=record_interval,
+                                             want=backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
+            e, ea, f = eng.results_f64()   # (the driver ends with a complete evaluation of the final positions)
+            return e, ea, f, info["positions"], {k: info[k] for k in ("n_steps", "n_eval", "stop_reason", "converged")}, info.get("traj")
+        e, ea, f, new_pos, nst, conv = eng.relax_arrays_f64(n_atoms, types, pos, cell, pbc, fixed=fixed, max_steps=steps, fmax=fmax,
+                                                            optimizer=optimizer)
+        return e, ea, f, new_pos, {"n_steps": nst, "converged": conv}, None
 
     def run_lammps_opt(self, slab, run_dir=None, fixed_indices=None, optimizer="CG", **kwargs):
         """Relaxation counterpart of ``LAMMMPSCalc.run_lammps_opt`` (reference ``calculators.py:600-619``: LAMMPS
         ``min_style cg``, ``minimize 1e-5 1e-5 {relax_steps} 10000``, bulk atoms with ``setforce 0``): the same minimiser on
         the device (``vssr_batch_relax_cg``; ``etol`` / ``ftol`` keywords override 1e-5).  ``optimizer="FIRE"`` / ``"BFGS"``
         select the ASE-style optimizers with ``fmax`` (default 0.01) instead.  Returns the reference's tuple
-        ``(relaxed_slab, energy, per_atom_energies)``; ``self.last_opt`` holds iteration / evaluation counts and the stop
-        reason."""
-        types, pos, cell, pbc = self._pack(slab)
-        fixed = None
-        if fixed_indices is not None and len(fixed_indices):
-            fixed = np.zeros(len(types), np.uint8)
-            fixed[np.asarray(fixed_indices, dtype=np.int64)] = 1
-        eng = self._get_engine()
-        if str(optimizer).upper() in ("CG", "LAMMPS"):
-            e, ea, f, new_pos, it, ev, why = eng.relax_cg_f64(
-                [(types, pos, cell, pbc)], fixed=fixed, max_iter=int(self.relax_steps), etol=kwargs.get("etol", 1e-5),
-                ftol=kwargs.get("ftol", 1e-5), driver=self._cg_driver_of(kwargs))
-            self.last_opt = {"optimizer": "CG", "iterations": int(it[0]), "evaluations": int(ev[0]),
-                             "stop": backend.CG_STOP_REASONS.get(int(why[0]), str(int(why[0])))}
-        else:
-            e, ea, f, new_pos, steps, conv = eng.relax_f64(
-                [(types, pos, cell, pbc)], fixed=fixed, max_steps=int(self.relax_steps), fmax=kwargs.get("fmax", 0.01),
-                optimizer=optimizer)
-            self.last_opt = {"optimizer": str(optimizer), "iterations": int(steps[0]), "converged": bool(conv[0])}
+        ``(relaxed_slab, energy, per_atom_energies)``; ``self.last_opt`` holds iteration / evaluation counts and the stop reason."""
+        n_atoms, types, pos, cell, pbc = backend.pack_batch([self._pack(slab)])
+        fixed = _fixed_mask(n_atoms, [fixed_indices] if fixed_indices is not None and len(fixed_indices) else None)
+        e, ea, _, new_pos, counts, _ = self._relax_packed(
+            n_atoms, types, pos, cell, pbc, fixed, optimizer, int(self.relax_steps),
+            kwargs.get("fmax", 0.01), etol=kwargs.get("etol", 1e-5), ftol=kwargs.get("ftol", 1e-5), cg_driver=self._cg_driver_of(kwargs),
+            linesearch_driver="ase", max_eval=None, record_interval=0)   # (one slab: no device line search, no trajectory)
+        c = _chain_counts(counts, 0)
+        self.last_opt = {"optimizer": "CG", **c} if "stop" in c else \
+            {"optimizer": str(optimizer), "iterations": c["n_steps"], "converged": c["converged"]}
         relaxed = slab.copy()
         relaxed.set_positions(new_pos)
         relaxed.calc = getattr(slab, "calc", None)
         return relaxed, float(e[0]), ea
 
-    ENERGY_THRESHOLD = 1000.0
-    MAX_FORCE_THRESHOLD = 1000.0
+    ENERGY_THRESHOLD, MAX_FORCE_THRESHOLD = ENERGY_THRESHOLD, MAX_FORCE_THRESHOLD   # (the module's; an instance may override them)
 
     def relax_batch(self, atoms_list, fixed_indices=None, relax_steps: int | None = None, fmax: float = 0.01,
-                    optimizer=None, want_stress: bool = False, **kwargs):
+                    optimizer=None, want_stress: bool = False, *, etol: float = 1e-5, ftol: float = 1e-5, cg_driver=None,
+                    linesearch_driver=None, max_eval=None, save_traj: bool = False, record_interval: int = 5, **kwargs):
         """Relax B slabs in ONE lock-step call -- what ``mc.ChainEnsemble(relax=True)`` needs from a calculator.  Default
         ``optimizer`` "LAMMPS" / "CG": the reference's GaN minimiser (``optimize_slab(optimizer="LAMMPS")`` ->
-        ``run_lammps_opt``, ``mcmc/dynamics.py:107-116``) for all slabs at once (``vssr_batch_relax_cg``); "FIRE" / "BFGS"
-        use the ASE-style optimizers with ``fmax``.  ``relax_steps`` defaults to ``self.relax_steps`` (the reference takes it
-        from ``calc.relax_steps``).  Returns per slab ``(relaxed, None, energy, energy_oob, results)`` like
-        ``EnsembleNFFSurface.relax_batch``; results carry ``per_atom_energies`` of the relaxed slab, with ``want_stress`` also its
-        ``stress``.  ``cg_driver="auto" | "lockstep" | "resident"`` (default: the calculator's ``cg_driver`` setting) selects the
-        driver of the CG minimiser (``backend.relax_cg_f64``): same results bit for bit.  ``optimizer="BFGSLineSearch"`` runs on the
-        device (``backend.relax_bfgs_linesearch``; results carry ``n_steps`` / ``n_eval`` / ``stop_reason``, and with ``save_traj`` /
-        ``record_interval`` the tuple's trajectory) where ``linesearch_driver="device"`` says so -- a keyword here, else the
-        calculator's ``set(linesearch_driver=...)``; with the default "ase" the name is refused as before."""
-        ls_driver = kwargs.get("linesearch_driver")
-        ls_driver = backend.linesearch_driver_check(getattr(self, "linesearch_driver", "ase") if ls_driver is None else ls_driver)
+        ``run_lammps_opt``, ``mcmc/dynamics.py:107-116``) for all slabs at once (``vssr_batch_relax_cg``; ``etol`` / ``ftol``); "FIRE" /
+        "BFGS" use the ASE-style optimizers with ``fmax`` (the table: ``_relax_packed``).  ``relax_steps`` defaults to
+        ``self.relax_steps`` (the reference takes it from ``calc.relax_steps``).  Returns per slab ``(relaxed, None, energy,
+        energy_oob, results)`` like ``EnsembleNFFSurface.relax_batch``; results carry ``per_atom_energies`` of the relaxed slab, with
+        ``want_stress`` also its ``stress``.  ``cg_driver="auto" | "lockstep" | "resident"`` (None: the calculator's setting) selects the
+        driver of the CG minimiser (``backend.relax_cg_f64``): same results bit for bit.  ``optimizer="BFGSLineSearch"`` runs on the device
+        (``backend.relax_bfgs_linesearch``, at most ``max_eval`` evaluations per chain; results carry ``n_steps`` / ``n_eval`` /
+        ``stop_reason``, and with ``save_traj`` / ``record_interval`` the tuple's trajectory) where ``linesearch_driver="device"`` says so --
+        the keyword, else ``set(linesearch_driver=...)``; with the default "ase" the name is refused.  Other keywords are ignored."""
+        ls_driver = backend.linesearch_driver_check(getattr(self, "linesearch_driver", "ase") if linesearch_driver is None
+                                                    else linesearch_driver)
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "LAMMPS")
         steps = int(self.relax_steps if relax_steps is None else relax_steps)
-        driver = self._cg_driver_of(kwargs)
-        trajs = None
-        packs = [self._pack(a) for a in atoms_list]
-        fixed = None
-        if fixed_indices is not None:
-            fixed = np.zeros(sum(len(p[0]) for p in packs), np.uint8)
-            o = 0
-            for p, idx in zip(packs, fixed_indices):
-                if idx is not None and len(idx):
-                    fixed[o + np.asarray(idx, dtype=np.int64)] = 1
-                o += len(p[0])
-        eng = self._get_engine()
-        if str(optimizer).upper() in ("CG", "LAMMPS"):
-            e, ea, f, pos, it, ev, why = eng.relax_cg_f64(packs, fixed=fixed, max_iter=steps, etol=kwargs.get("etol", 1e-5),
-                                                          ftol=kwargs.get("ftol", 1e-5), driver=driver)
-            extra = [{"iterations": int(it[b]), "evaluations": int(ev[b]),
-                      "stop": backend.CG_STOP_REASONS.get(int(why[b]), str(int(why[b])))} for b in range(len(packs))]
-        elif "BFGSLineSearch" in str(optimizer) and ls_driver == "device":
-            eng.upload(packs)
-            rec = int(kwargs.get("record_interval", 5)) if kwargs.get("save_traj") else 0
-            info = eng.relax_bfgs_linesearch(fixed=fixed, max_steps=steps, fmax=fmax, max_eval=kwargs.get("max_eval"),
-                                             want=backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM, record_interval=rec)
-            (e, ea, f), pos = eng.results_f64(), info["positions"]   # (the driver ends with a complete evaluation of the final positions)
-            extra = [{"n_steps": int(info["n_steps"][b]), "n_eval": int(info["n_eval"][b]), "stop_reason": int(info["stop_reason"][b]),
-                      "converged": bool(info["converged"][b])} for b in range(len(packs))]
-            if rec:
-                cs = np.concatenate([[0], np.cumsum([len(p[0]) for p in packs])])
-                trajs = [_traj_of_chain(info["traj"], b, int(cs[b]), int(cs[b + 1]), a) for b, a in enumerate(atoms_list)]
-        else:
-            e, ea, f, pos, nst, conv = eng.relax_f64(packs, fixed=fixed, max_steps=steps, fmax=fmax, optimizer=optimizer)
-            extra = [{"n_steps": int(nst[b]), "converged": bool(conv[b])} for b in range(len(packs))]
-        # (both relaxation calls end with one plain evaluation of the relaxed geometries -- also after the chain-resident CG, which
-        # leaves no batch-wide gradients: the virial is that of the relaxed slabs)
-        stress = eng.stress()[0] if want_stress else None
-        out, o = [], 0
-        for b, (atoms, p) in enumerate(zip(atoms_list, packs)):
-            n = len(p[0])
+        driver = self._cg_driver_of({"cg_driver": cg_driver})
+        n_atoms, types, pos, cell, pbc = backend.pack_batch([self._pack(a) for a in atoms_list])
+        e, ea, f, new_pos, counts, traj = self._relax_packed(
+            n_atoms, types, pos, cell, pbc, _fixed_mask(n_atoms, fixed_indices), optimizer, steps, fmax, etol=etol, ftol=ftol,
+            cg_driver=driver, linesearch_driver=ls_driver, max_eval=max_eval, record_interval=int(record_interval) if save_traj else 0)
+        # (every relaxation, the chain-resident CG too, ends with one plain evaluation of the relaxed slabs: the virial is theirs)
+        stress = self._get_engine().stress()[0] if want_stress else None
+        start = _cfg_start(n_atoms)
+        oob = _oob_flags(e, f, start, e_max=self.ENERGY_THRESHOLD, f_max=self.MAX_FORCE_THRESHOLD)
+        out = []
+        for b, atoms in enumerate(atoms_list):
+            a0, a1 = int(start[b]), int(start[b + 1])
             relaxed = atoms.copy()
-            relaxed.set_positions(pos[o:o + n])
-            energy = float(e[b])
-            max_force = float(np.abs(f[o:o + n]).max()) if n else 0.0
-            oob = bool(not np.isfinite(energy) or not np.isfinite(max_force) or abs(energy) > self.ENERGY_THRESHOLD
-                       or max_force > self.MAX_FORCE_THRESHOLD)
-            r = {"energy": energy, "per_atom_energies": ea[o:o + n].copy(), "forces": f[o:o + n].copy(), **extra[b]}
+            relaxed.set_positions(new_pos[a0:a1])
+            r = {"energy": float(e[b]), "per_atom_energies": ea[a0:a1].copy(), "forces": f[a0:a1].copy(), **_chain_counts(counts, b)}
             if stress is not None:
                 r["stress"] = stress[b].copy()
-            out.append((relaxed, None if trajs is None else trajs[b], self.ENERGY_THRESHOLD if oob else energy, oob, r))
-            o += n
+            out.append((relaxed, _traj_of_chain(traj, b, a0, a1, atoms), self.ENERGY_THRESHOLD if oob[b] else r["energy"], bool(oob[b]), r))
         return out
-
-    def calculate_batch(self, atoms_list, want_stress: bool = False) -> list[dict]:
-        packs = [self._pack(a) for a in atoms_list]
-        eng = self._get_engine()
-        e, ea, f = eng.evaluate_f64(packs)
-        stress = eng.stress()[0] if want_stress else None
-        out, o = [], 0
-        for b, p in enumerate(packs):
-            n = len(p[0])
-            out.append({"energy": float(e[b]), "per_atom_energies": ea[o:o + n].copy(), "forces": f[o:o + n].copy()})
-            if stress is not None:
-                out[-1]["stress"] = stress[b].copy()
-            o += n
-        return out
-
 
     @staticmethod
     def packed_supported(relax: bool, optimizer) -> bool:
@@ -1166,32 +1184,23 @@ class _AnalyticSurfCalc(_Base):
         return not relax or optimizer is None or (isinstance(optimizer, str)
                                                   and optimizer.upper() in ("CG", "LAMMPS", "FIRE", "BFGS"))
 
-    def _types_of(self, Z) -> np.ndarray:
-        """LAMMPS types of atomic numbers (the order of ``species``), vectorised."""
-        table = np.full(len(structures.SYMBOLS) + 1, -1, np.int32)
-        for t, sym in enumerate(self.species):
-            table[structures.ATOMIC_NUMBERS[sym]] = t
-        Z = np.asarray(Z, dtype=np.int64)
-        types = table[np.clip(Z, 0, len(table) - 1)]
-        if len(types) and types.min() < 0:
-            raise ValueError(f"element Z={int(Z[np.argmin(types)])} is not covered by the potential {self.species}")
-        return types
-
     def evaluate_packed(self, n_atoms, Z, pos, cell, pbc, relax: bool = False, fixed_mask=None, relax_steps: int | None = None,
-                        fmax: float = 0.01, optimizer=None, **kwargs) -> dict:
+                        fmax: float = 0.01, optimizer=None, *, etol: float = 1e-5, ftol: float = 1e-5, cg_driver=None,
+                        linesearch_driver=None, max_eval=None, save_traj: bool = False, record_interval: int = 5, **kwargs) -> dict:
         """``calculate_batch`` (``relax=False``) / ``relax_batch`` (``relax=True``) with the ABI's packed arrays on both sides
         (``n_atoms [B]``, atomic numbers ``Z [sum N]``, ``pos [sum N, 3]``, ``cell [B, 9]``, ``pbc [B, 3]``, ``fixed_mask
         [sum N]``): what ``mc.ChainEnsemble`` calls every MC step -- no per-slab objects (4 096 GaN chains: the per-slab
         bookkeeping was 41 % of an MC step, ``profiles/r04/bench_gan.jsonl``).  Returns fp64 ``energy [B]`` (the static energies of
         the final geometries), ``forces``, ``energy_atoms``, ``positions``, ``cfg_start``, ``oob [B]`` (the +-1000 guard of
         ``mcmc/dynamics.py:159-168``), ``energy_std`` / ``saturated`` (zeros: one deterministic fp64 potential), and for
-        relaxations ``iterations`` / ``evaluations`` / ``stop`` (CG) or ``n_steps`` / ``converged`` (FIRE, BFGS).  CG relaxations
-        take the calculator's ``cg_driver`` setting (or a ``cg_driver`` keyword)."""
+        relaxations ``iterations`` / ``evaluations`` / ``stop`` (CG, with ``lockstep_evaluations`` / ``dispatched_chain_evaluations``) or
+        ``n_steps`` / ``converged`` (FIRE, BFGS).  ``etol`` / ``ftol`` / ``cg_driver`` as in ``relax_batch``; "BFGSLineSearch" is refused and
+        nothing is recorded: ``linesearch_driver``, ``max_eval``, ``save_traj``, ``record_interval`` and other keywords are ignored."""
         if optimizer is None:
             optimizer = self.parameters.get("optimizer", "LAMMPS")
         if relax and not self.packed_supported(True, optimizer):
             raise backend.BackendError(f"evaluate_packed relaxes on the device only (CG / LAMMPS, FIRE, BFGS), not with {optimizer!r}")
-        driver = self._cg_driver_of(kwargs)
+        driver = self._cg_driver_of({"cg_driver": cg_driver})
         n_atoms = np.ascontiguousarray(n_atoms, dtype=np.int32)
         B = len(n_atoms)
         types = self._types_of(Z)
@@ -1199,32 +1208,18 @@ class _AnalyticSurfCalc(_Base):
         cell = np.asarray(cell, dtype=np.float64).reshape(B, 9)
         fixed_pbc = self._fixed_pbc()
         pbc = np.tile(fixed_pbc, (B, 1)) if fixed_pbc is not None else np.asarray(pbc).astype(np.uint8).reshape(B, 3)
-        eng = self._get_engine()
         extra = {}
         if not relax:
-            e, ea, f = eng.evaluate_arrays_f64(n_atoms, types, pos, cell, pbc)
-            new_pos = pos
-        elif str(optimizer).upper() in ("CG", "LAMMPS"):
-            steps = int(self.relax_steps if relax_steps is None else relax_steps)
-            e, ea, f, new_pos, it, ev, why = eng.relax_cg_arrays_f64(n_atoms, types, pos, cell, pbc, fixed=fixed_mask, max_iter=steps,
-                                                                     etol=kwargs.get("etol", 1e-5), ftol=kwargs.get("ftol", 1e-5),
-                                                                     driver=driver)
-            ls, ce = getattr(eng, "last_relax_counts", (0, 0))
-            extra = {"iterations": it, "evaluations": ev, "stop": why, "lockstep_evaluations": ls, "dispatched_chain_evaluations": ce}
+            (e, ea, f), new_pos = self._get_engine().evaluate_arrays_f64(n_atoms, types, pos, cell, pbc), pos
         else:
-            steps = int(self.relax_steps if relax_steps is None else relax_steps)
-            e, ea, f, new_pos, nst, conv = eng.relax_arrays_f64(n_atoms, types, pos, cell, pbc, fixed=fixed_mask, max_steps=steps,
-                                                                fmax=fmax, optimizer=optimizer)
-            extra = {"n_steps": nst, "converged": conv}
-        start = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
-        fabs = np.abs(f).max(axis=1) if len(f) else np.zeros(0)
-        nonempty = start[1:] > start[:-1]
-        max_force = np.zeros(B)
-        if nonempty.any():
-            max_force[nonempty] = np.maximum.reduceat(fabs, start[:-1][nonempty])
-        with np.errstate(invalid="ignore"):
-            oob = (~np.isfinite(e)) | (~np.isfinite(max_force)) | (np.abs(e) > self.ENERGY_THRESHOLD) \
-                | (max_force > self.MAX_FORCE_THRESHOLD)
+            e, ea, f, new_pos, extra, _ = self._relax_packed(
+                n_atoms, types, pos, cell, pbc, fixed_mask, optimizer, int(self.relax_steps if relax_steps is None else relax_steps), fmax,
+                etol=etol, ftol=ftol, cg_driver=driver, linesearch_driver="ase", max_eval=None, record_interval=0)
+            if "stop" in extra:   # CG: how much of the lock-step work the chains needed (tools/bench_gan.py)
+                ls, ce = getattr(self._get_engine(), "last_relax_counts", (0, 0))
+                extra = {**extra, "lockstep_evaluations": ls, "dispatched_chain_evaluations": ce}
+        start = _cfg_start(n_atoms)
+        oob = _oob_flags(e, f, start, e_max=self.ENERGY_THRESHOLD, f_max=self.MAX_FORCE_THRESHOLD)
         return {"energy": e, "energy_std": np.zeros(B), "forces": f, "energy_atoms": ea, "positions": new_pos, "cfg_start": start,
                 "saturated": np.zeros(B, bool), "oob": oob, **extra}
 
@@ -1811,10 +1806,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         if relax:
             self._check_relax()
         if relax and fixed_mask is None and self.bulk_index > 0:
-            n_atoms = np.asarray(n_atoms, dtype=np.int64)
-            start = np.concatenate([[0], np.cumsum(n_atoms)])
-            local = np.arange(int(start[-1])) - np.repeat(start[:-1], n_atoms)
-            fixed_mask = (local < self.bulk_index).astype(np.uint8)
+            start = _cfg_start(n_atoms)   # (vectorised: every MC step of a run-directory ensemble without fixed_indices comes here)
+            fixed_mask = ((np.arange(int(start[-1])) - np.repeat(start[:-1], n_atoms)) < self.bulk_index).astype(np.uint8)
         return super().evaluate_packed(n_atoms, Z, pos, cell, pbc, relax=relax, fixed_mask=fixed_mask, **kwargs)
 
 
