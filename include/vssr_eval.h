@@ -417,6 +417,34 @@ int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, co
                        const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                        double *energy_atoms_f64, double *forces_f64);
 
+/* ---- Vashishta (pair_style vashishta: SiC, SiO2, InP, GaAs, Al2O3) ------------------------------------------------------------ */
+/* Handle kind 9.  LAMMPS units metal, qqr2e = 14.399645, fp64 throughout.  params: n_types^3 entries ordered [i][j][k] (i = centre),
+ * 14 doubles each, LAMMPS column order (H eta Zi Zj lambda1 D lambda4 W rc B gamma r0 C costheta):
+ *   V(r)    = H / r^eta + qqr2e Zi Zj / r exp(-r / lambda1) - D / r^4 exp(-r / lambda4) - W / r^6
+ *   phi2(r) = V(r) - V(rc) - (r - rc) V'(rc)                        r < rc, entry (i, j, j): energy and force vanish at rc
+ *   phi3    = B f_ij(r_ij) f_ik(r_ik) dc^2 / (1 + C dc^2),  dc = cos theta_jik - costheta        B, C, costheta: entry (i, j, k)
+ *   f_ij(r) = exp(gamma / (r - r0)) for r < r0, else 0              gamma, r0: entry (i, j, j)
+ * E = sum over pairs phi2 + sum over centres i and unordered neighbor pairs {j, k} phi3; every directed slot i -> j carries half of
+ * phi2 with entry (i, j, j).  pe/atom as LAMMPS: pair terms half / half, three-body terms in thirds between the three atoms.
+ * Refused with VSSR_E_BADARG, by entry and field, before any device is touched: non-finite numbers and negative B / gamma / r0 in
+ * any entry; in the entries (i, j, j), whose two-body and radial columns are the ones read: rc <= 0, eta <= 0, lambda1 <= 0 with
+ * Zi Zj != 0, lambda4 <= 0 with D != 0, r0 > rc; entries (i, j, j), (j, i, i) that differ in H, eta, Zi Zj, lambda1, D, lambda4, W or rc
+ * and entries (i, j, k), (i, k, j) that differ in B, C or costheta (LAMMPS' energy would then depend on the order of its neighbor
+ * list); n_types outside 1 .. 8.  gamma and r0 of (i, j, j) and (j, i, i) may differ.  The two-body columns of an entry with j != k are
+ * read by nobody and only have to be finite (published files write zeros there).  Cutoff of the neighbor list: the largest rc.
+ * Relaxations: FIRE, BFGS, BFGSLineSearch and the lock-step CG serve these handles; the chain-resident CG minimiser does not
+ * (VSSR_CG_DRIVER_RESIDENT runs in lock step, same results, as for ADP and k-space handles). */
+int vssr_vashishta_create(int32_t device, int32_t n_types, const double *params, vssr_handle **out);
+/* The same from the text of a LAMMPS .vashishta file and the species in LAMMPS type order: entries
+ * `e1 e2 e3 H eta Zi Zj lambda1 D lambda4 W rc B gamma r0 C costheta` may span lines, `#` starts a comment; every triplet of the
+ * given species must be present, entries of other elements are skipped.  The input is checked before any device is touched. */
+int vssr_vashishta_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
+                                    vssr_handle **out);
+/* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
+int vssr_vashishta_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                              const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                              double *energy_atoms_f64, double *forces_f64);
+
 /* ---- Pair potentials with damped-shifted-force Coulomb (pair_style lj/cut, morse, buck, born, coul/dsf; hybrid and
  * hybrid/overlay of these) ------------------------------------------------------------------------------------------------------- */
 /* LAMMPS units metal: eV, A, charges in e, qqrd2e = 14.399645.  E(r) for r < rc, coefficients in LAMMPS order:

@@ -38,6 +38,7 @@ EXPORTS = (
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
     "vssr_pair_create", "vssr_pair_create_kspace", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
     "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
+    "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
 )
 
 
@@ -287,6 +288,12 @@ def load_library():
     L.vssr_sw_create_from_text.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.vssr_sw_eval_batch.restype = C.c_int
     L.vssr_sw_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
+    L.vssr_vashishta_create.restype = C.c_int
+    L.vssr_vashishta_create.argtypes = [C.c_int32, C.c_int32, dp, C.POINTER(vp)]
+    L.vssr_vashishta_create_from_text.restype = C.c_int
+    L.vssr_vashishta_create_from_text.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.vssr_vashishta_eval_batch.restype = C.c_int
+    L.vssr_vashishta_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_pair_create.restype = C.c_int
     L.vssr_pair_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(vp)]
     L.vssr_pair_create_kspace.restype = C.c_int
@@ -845,6 +852,37 @@ class SWEngine(_AnalyticEngine):
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"vssr_sw_create failed ({rc}): {msg.decode() if msg else '?'}")
+
+
+class VashishtaEngine(_AnalyticEngine):
+    """Vashishta (LAMMPS ``pair_style vashishta``) evaluator, fp64 on device.  Relaxes with FIRE / BFGS / BFGSLineSearch and the
+    lock-step CG driver; the chain-resident minimiser does not serve this kind (``relax_cg_f64(..., driver="resident")`` runs in lock
+    step, same results)."""
+
+    def __init__(self, params, device=0, species=None):
+        """``params``: array [nt, nt, nt, 14] (LAMMPS columns H eta Zi Zj lambda1 D lambda4 W rc B gamma r0 C costheta), or the TEXT
+        of a ``.vashishta`` file together with ``species`` (LAMMPS type order) -- then the file is parsed by the library
+        (vssr_vashishta_create_from_text)."""
+        super().__init__()
+        if isinstance(params, (str, bytes)):
+            if not species:
+                raise ValueError("species (LAMMPS type order) are required with a potential text")
+            text = params if isinstance(params, bytes) else params.encode()
+            arr = (C.c_char_p * len(species))(*[s.encode() for s in species])
+            self.n_types = len(species)
+            rc = self._lib.vssr_vashishta_create_from_text(int(device), text, len(species), arr, C.byref(self._h))
+            if rc != 0:
+                msg = self._lib.vssr_last_error(None)
+                raise BackendError(f"vssr_vashishta_create_from_text failed ({rc}): {msg.decode() if msg else '?'}")
+            return
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.ndim != 4 or params.shape[3] != 14 or not (params.shape[0] == params.shape[1] == params.shape[2]):
+            raise ValueError("params must be [nt, nt, nt, 14]")
+        self.n_types = params.shape[0]
+        rc = self._lib.vssr_vashishta_create(int(device), self.n_types, _ptr(params, C.c_double), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.vssr_last_error(None)
+            raise BackendError(f"vssr_vashishta_create failed ({rc}): {msg.decode() if msg else '?'}")
 
 
 class PairEngine(_AnalyticEngine):

@@ -29,7 +29,7 @@ from collections import Counter
 
 import numpy as np
 
-from . import backend, checkpoint, host_opt, pair as pair_io, structures, sw as sw_io, tersoff as tersoff_io
+from . import backend, checkpoint, host_opt, pair as pair_io, structures, sw as sw_io, tersoff as tersoff_io, vashishta as vashishta_io
 
 EV_TO_KCAL_MOL = 23.0605   # nff/utils/constants.py
 HARTREE_TO_EV = 27.2114    # nff/utils/constants.py (reference import: calculators.py:21)
@@ -1288,6 +1288,43 @@ class SWSurfCalc(_AnalyticSurfCalc):
         return backend.SWEngine(self.params, device=_device_index(self.device))
 
 
+class VashishtaSurfCalc(_AnalyticSurfCalc):
+    """Vashishta energy / per-atom energies / forces on MI355X (LAMMPS ``pair_style vashishta``: SiC, SiO2, InP, GaAs, Al2O3).
+    ``per_atom_energies`` follow LAMMPS ``pe/atom`` (pair terms half / half, three-body terms in thirds).  Relaxations
+    (``run_lammps_opt``, ``relax_batch``, ``evaluate_packed(relax=True)``) use the lock-step CG / FIRE / BFGS drivers; the
+    chain-resident CG minimiser does not serve this potential: ``set(cg_driver="resident")`` runs in lock step (same results).
+    ``all_periodic=False`` keeps the atoms' own ``pbc``."""
+
+    name = "vashishta_mi355x"
+
+    def __init__(self, potential, species=None, device="cuda", all_periodic=False, logger=None, **kwargs):
+        """potential: path or text of a ``.vashishta`` file, a params array [nt,nt,nt,14], or a built-in model name
+        (``vashishta.MODELS``, e.g. ``SiC_Vashishta_2007``); species: symbols in LAMMPS type order (a built-in model's own species
+        when omitted)."""
+        if isinstance(potential, np.ndarray):
+            if species is None:
+                raise ValueError("species (LAMMPS type order) are required with a params array")
+            self.params = np.ascontiguousarray(potential, dtype=np.float64)
+            vashishta_io.check_params(self.params, list(species))
+        elif vashishta_io.is_builtin(potential):
+            species = vashishta_io.builtin_species(potential) if species is None else species
+            self.params = vashishta_io.parse_vashishta(vashishta_io.builtin_text(potential), list(species))
+        else:
+            if species is None:
+                raise ValueError("species (LAMMPS type order) are required with a .vashishta file")
+            text = potential
+            if "\n" not in str(potential):
+                with open(potential) as fh:
+                    text = fh.read()
+            self.params = vashishta_io.parse_vashishta(text, list(species))
+        self.species = list(species)
+        self._init_common(device, all_periodic, logger)
+        super().__init__(**kwargs)
+
+    def _make_engine(self):
+        return backend.VashishtaEngine(self.params, device=_device_index(self.device))
+
+
 class PairSurfCalc(_AnalyticSurfCalc):
     """Pair potentials with damped-shifted-force Coulomb on MI355X: LAMMPS ``pair_style lj/cut``, ``morse``, ``buck``, ``born``,
     ``coul/dsf`` and ``hybrid`` / ``hybrid/overlay`` of them, given as the LAMMPS commands a template would carry (``pair_style``,
@@ -1511,7 +1548,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
       bulk_index form the group the relaxation template holds with ``fix ... setforce 0``);
     * ``lammps_energy_template.txt`` / ``lammps_opt_template.txt``: the ``pair_style`` line selects the potential -- ``tersoff``
       (multi-element file), ``eam`` (one funcfl element, or a list ``potential_file`` of one funcfl file per species),
-      ``eam/alloy`` / ``eam/fs`` (setfl / Finnis-Sinclair file, elements = ``atoms``), ``sw`` (Stillinger-Weber file) or ``kim <model>`` with a built-in SW
+      ``eam/alloy`` / ``eam/fs`` (setfl / Finnis-Sinclair file, elements = ``atoms``), ``sw`` (Stillinger-Weber file), ``vashishta`` (Vashishta file; the energy template's ``boundary`` applies as for ``sw``) or ``kim <model>`` with a built-in SW
       model (``sw.MODELS``: the Si(111) 5x5 tutorial's ``SW_StillingerWeber_1985_Si__MO_405512056662_005``; no
       ``potential_file`` needed, the species come from ``atoms``) are evaluated on the device, anything else raises.  For the SW
       styles the energy template's ``boundary`` applies (``p`` periodic; ``f``, ``s``, ``m`` open) and pe/atom follows LAMMPS
@@ -1586,7 +1623,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         return np.array([t == "p" for t in tokens], np.uint8)
 
     def _sw_source(self, args, cfg):
-        """(params source, key) of an SW pair style (``sw`` + potential_file, ``kim <built-in model>``); None for other styles."""
+        """(params source, key) of an SW pair style (``sw`` + potential_file, ``kim <built-in model>``) or of ``vashishta`` +
+        potential_file, which is configured the same way; None for other styles."""
         kp = self.parameters.get("kim_potential")
         if (args and args[0] == "kim") or kp:
             model = args[1] if args and args[0] == "kim" and len(args) > 1 else (kp if isinstance(kp, str) else None)
@@ -1598,6 +1636,10 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             if "potential_file" not in cfg:
                 raise KeyError("lammps_config.json: pair_style sw needs potential_file")
             return ("sw", self._find_potential(cfg["potential_file"], str(self.run_dir)))
+        if args and args[0] == "vashishta":
+            if "potential_file" not in cfg:
+                raise KeyError("lammps_config.json: pair_style vashishta needs potential_file")
+            return ("vashishta", self._find_potential(cfg["potential_file"], str(self.run_dir)))
         return None
 
     def _configure(self):
@@ -1672,7 +1714,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             self.funcfl = self.params = None
         else:
             raise backend.BackendError(f"pair_style {style!r} is not provided by this backend "
-                                       "(tersoff, eam, eam/alloy, eam/fs, adp, sw, lj/cut, morse, buck, born, coul/dsf and "
+                                       "(tersoff, eam, eam/alloy, eam/fs, adp, sw, vashishta, lj/cut, morse, buck, born, coul/dsf and "
                                        "hybrid / hybrid/overlay of the last five are)")
         if self._engine is not None:
             self._engine.close()
@@ -1714,7 +1756,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self._cfg_key = key
 
     def _configure_sw(self, cfg_path, cfg, tmpls, args, src):
-        """``pair_style sw`` (``potential_file`` + ``atoms``) or ``pair_style kim <built-in SW model>`` (species from ``atoms``: the
+        """``pair_style sw`` / ``pair_style vashishta`` (``potential_file`` + ``atoms``) or ``pair_style kim <built-in SW model>`` (species from ``atoms``: the
         reference's KIM templates write ``pair_coeff * * {}`` with the element names).  The energy template's ``boundary`` applies.
         An opt template that names another potential the backend lacks makes relaxations refuse (single points still work)."""
         energy_args, energy_bnd = tmpls.get("lammps_energy_template.txt", (None, None))
@@ -1737,7 +1779,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             name = opt_args[1] if opt_args[0] == "kim" and len(opt_args) > 1 else " ".join(opt_args)
             if not (opt_args[0] == "kim" and len(opt_args) > 1 and sw_io.is_builtin(opt_args[1])):
                 refused = name
-        self.params = sw_io.parse_sw(text, species)
+        self.params = vashishta_io.parse_vashishta(text, species) if src[0] == "vashishta" else sw_io.parse_sw(text, species)
         self.funcfl = self.tables = None
         self.species = species
         self.bulk_index = int(cfg.get("bulk_index", 0))
@@ -1751,7 +1793,7 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
         self._cfg_key = key
 
     def _fixed_pbc(self):
-        if self.pair_style in ("sw", "kim", "pair") and self.boundary is not None:
+        if self.pair_style in ("sw", "kim", "pair", "vashishta") and self.boundary is not None:
             return self.boundary
         return super()._fixed_pbc()
 
@@ -1765,6 +1807,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
     def _make_engine(self):
         if self.pair_style in ("sw", "kim"):
             return backend.SWEngine(self.params, device=_device_index(self.device))
+        if self.pair_style == "vashishta":
+            return backend.VashishtaEngine(self.params, device=_device_index(self.device))
         if self.pair_style == "pair":
             return backend.PairEngine(self.pair_model, device=_device_index(self.device))
         if self.pair_style == "tersoff":

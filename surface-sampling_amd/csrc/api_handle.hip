@@ -79,6 +79,7 @@ const Evaluator &evaluator(const vssr_handle *h) {
         /* GMM_FIT */ {false, nullptr, nullptr, nullptr},
         /* CLUSTER */ {false, nullptr, nullptr, nullptr},
         /* PAIR    */ {true, pair_run, pair_stress, [](const vssr_handle *h) { return h->pot_cutoff; }},
+        /* VASHISHTA */ {true, vashishta_run, vashishta_stress, [](const vssr_handle *h) { return h->pot_cutoff; }},
     };
     return table[(int)h->kind];
 }

@@ -1,10 +1,11 @@
-// api_potentials.hip — the fp64 analytic potentials: Tersoff, EAM, Stillinger-Weber and pair creates, the two LAMMPS text parsers,
+// api_potentials.hip — the fp64 analytic potentials: Tersoff, EAM, Stillinger-Weber, Vashishta and pair creates, the LAMMPS text parsers,
 // and the *_eval_batch entry points.
 #include <cmath>
 
 #include "vssr_internal.h"
 #include "sw_dev.h"
 #include "pair_dev.h"
+#include "vashishta_dev.h"
 
 using namespace vssr;
 
@@ -285,6 +286,141 @@ int vssr_sw_create_from_text(int32_t device, const char *param_text, int32_t n_s
     return sw_create_checked(device, n_species, params.data(), species, out);
 }
 
+// ---- Vashishta -----------------------------------------------------------------------------------------------------------------
+static const char *const kVaField[14] = {"H", "eta", "Zi", "Zj", "lambda1", "D", "lambda4", "W", "rc", "B", "gamma", "r0", "C", "costheta"};
+
+// Checks an [i][j][k] table of 14 LAMMPS columns and derives the kernels' entries (vashishta_dev.h VashP).  Refused: non-finite
+// numbers and negative B / gamma / r0 in any entry; in the entries (i, j, j), whose two-body and radial columns are the ones read:
+// rc <= 0, eta <= 0, lambda1 <= 0 with Zi Zj != 0, lambda4 <= 0 with D != 0, r0 > rc; (i, j, j) / (j, i, i) pairs that differ in
+// H, eta, Zi Zj, lambda1, D, lambda4, W or rc and (i, j, k) / (i, k, j) pairs that differ in B, C or costheta (the LAMMPS energy would
+// depend on the order of its neighbor list).  The two-body columns of an entry with j != k are read by nobody and only have to be finite.
+static int vashishta_derive(int nt, const double *params, const char *const *species, std::vector<VashP> &out, double &cutmax,
+                            double &r0max) {
+    const size_t np = (size_t)nt * nt * nt;
+    auto name = [&](size_t e, char *buf, size_t n) {
+        const int a = (int)(e / ((size_t)nt * nt)), b = (int)(e / nt % nt), c = (int)(e % nt);
+        if (species) snprintf(buf, n, "%s %s %s", species[a], species[b], species[c]);
+        else snprintf(buf, n, "(%d,%d,%d)", a, b, c);
+    };
+    char nm[96], nm2[96];
+    auto bad = [&](size_t e, int k, const char *rule) {
+        name(e, nm, sizeof nm);
+        return set_err(nullptr, VSSR_E_BADARG, "vashishta entry %s: bad %s = %g (%s)", nm, kVaField[k], params[14 * e + k], rule);
+    };
+    out.assign(np, VashP{});
+    cutmax = 0.0;
+    r0max = 0.0;
+    for (size_t e = 0; e < np; ++e) {
+        const double *p = params + 14 * e;
+        for (int k = 0; k < 14; ++k)
+            if (!std::isfinite(p[k])) return bad(e, k, "must be finite");
+        for (int k : {9, 10, 11})
+            if (!(p[k] >= 0)) return bad(e, k, "must be >= 0");
+        VashP &d = out[e];
+        d.tri.B = p[9]; d.tri.C = p[12]; d.tri.c0 = p[13];
+        const int b = (int)(e / nt % nt), c = (int)(e % nt);
+        if (b != c) continue;
+        const double zz = p[2] * p[3];
+        if (!(p[8] > 0)) return bad(e, 8, "must be > 0");
+        if (!(p[1] > 0)) return bad(e, 1, "must be > 0");
+        if (zz != 0.0 && !(p[4] > 0)) return bad(e, 4, "must be > 0 with Zi Zj != 0");
+        if (p[5] != 0.0 && !(p[6] > 0)) return bad(e, 6, "must be > 0 with D != 0");
+        if (p[11] > p[8]) return bad(e, 11, "must be <= rc");
+        VashPairP &t = d.two;
+        t.H = p[0]; t.eta = p[1]; t.zz = PAIR_QQRD2E * zz; t.il1 = zz != 0.0 ? 1.0 / p[4] : 0.0;
+        t.D = p[5]; t.il4 = p[5] != 0.0 ? 1.0 / p[6] : 0.0; t.W = p[7]; t.rc = p[8];
+        t.gamma = p[10]; t.r0 = p[11];
+        vash_v(t, t.rc, t.vrc, t.dvrc);
+        if (!std::isfinite(t.vrc) || !std::isfinite(t.dvrc)) {
+            name(e, nm, sizeof nm);
+            return set_err(nullptr, VSSR_E_BADARG, "vashishta entry %s: V(rc) / V'(rc) overflow", nm);
+        }
+        cutmax = std::max(cutmax, t.rc);
+        r0max = std::max(r0max, t.r0);
+    }
+    auto differ = [&](size_t x, size_t y, const char *field, double a, double b, const char *what) {
+        name(x, nm, sizeof nm);
+        name(y, nm2, sizeof nm2);
+        return set_err(nullptr, VSSR_E_BADARG, "vashishta entries %s and %s differ in %s (%g vs %g): the %s term would depend on neighbor order",
+                       nm, nm2, field, a, b, what);
+    };
+    for (int i = 0; i < nt; ++i)
+        for (int j = i + 1; j < nt; ++j) {
+            const size_t x = ((size_t)i * nt + j) * nt + j, y = ((size_t)j * nt + i) * nt + i;
+            const double *a = params + 14 * x, *b = params + 14 * y;
+            for (int f : {0, 1, 4, 5, 6, 7, 8})
+                if (a[f] != b[f]) return differ(x, y, kVaField[f], a[f], b[f], "two-body");
+            if (a[2] * a[3] != b[2] * b[3]) return differ(x, y, "Zi Zj", a[2] * a[3], b[2] * b[3], "two-body");
+        }
+    for (int i = 0; i < nt; ++i)
+        for (int j = 0; j < nt; ++j)
+            for (int k = j + 1; k < nt; ++k) {
+                const size_t x = ((size_t)i * nt + j) * nt + k, y = ((size_t)i * nt + k) * nt + j;
+                for (int f : {9, 12, 13})
+                    if (params[14 * x + f] != params[14 * y + f])
+                        return differ(x, y, kVaField[f], params[14 * x + f], params[14 * y + f], "three-body");
+            }
+    return VSSR_OK;
+}
+
+static int vashishta_create_checked(int32_t device, int32_t n_types, const double *params, const char *const *species, vssr_handle **out) {
+    if (!params || !out || n_types < 1 || n_types > VA_MAXT) return set_err(nullptr, VSSR_E_BADARG, "bad vashishta arguments (1 .. 8 types)");
+    *out = nullptr;
+    std::vector<VashP> tab;
+    double cutmax = 0.0, r0max = 0.0;
+    int rc = vashishta_derive(n_types, params, species, tab, cutmax, r0max);
+    if (rc) return rc;
+    return create_handle(Kind::VASHISHTA, device, out, [&](vssr_handle *h) {
+        h->n_types = n_types;
+        h->n_embed = n_types;
+        h->pot_cutoff = cutmax;
+        h->vash_r0max = r0max;
+        return upload_params(h, tab.data(), sizeof(VashP) * tab.size(), "vashishta params", "vashishta params upload failed");
+    });
+}
+
+int vssr_vashishta_create(int32_t device, int32_t n_types, const double *params, vssr_handle **out) {
+    return vashishta_create_checked(device, n_types, params, nullptr, out);
+}
+
+int vssr_vashishta_create_from_text(int32_t device, const char *param_text, int32_t n_species, const char *const *species,
+                                    vssr_handle **out) {
+    if (!param_text || !species || !out || n_species < 1 || n_species > VA_MAXT)
+        return set_err(nullptr, VSSR_E_BADARG, "bad vashishta arguments (1 .. 8 species)");
+    *out = nullptr;
+    for (int t = 0; t < n_species; ++t)
+        if (!species[t] || !species[t][0]) return set_err(nullptr, VSSR_E_BADARG, "vashishta: species %d has no name", t);
+    const std::vector<std::string> tok = potential_tokens(param_text);
+    if (tok.empty() || tok.size() % 17)
+        return set_err(nullptr, VSSR_E_BADARG, "vashishta file: %zu tokens, not a multiple of 17 (e1 e2 e3 + 14 numbers)", tok.size());
+    auto index_of = [&](const std::string &s) {
+        for (int t = 0; t < n_species; ++t)
+            if (s == species[t]) return t;
+        return -1;
+    };
+    const size_t np = (size_t)n_species * n_species * n_species;
+    std::vector<double> params(14 * np, 0.0);
+    std::vector<char> seen(np, 0);
+    for (size_t o = 0; o < tok.size(); o += 17) {
+        const int a = index_of(tok[o]), b = index_of(tok[o + 1]), c = index_of(tok[o + 2]);
+        if (a < 0 || b < 0 || c < 0) continue;   // entry of another element
+        const size_t e = ((size_t)a * n_species + b) * n_species + c;
+        for (int k = 0; k < 14; ++k) {
+            char *end = nullptr;
+            params[14 * e + k] = strtod(tok[o + 3 + k].c_str(), &end);
+            if (!end || *end || end == tok[o + 3 + k].c_str())
+                return set_err(nullptr, VSSR_E_BADARG, "vashishta file: entry %s %s %s: bad number '%s' for %s", tok[o].c_str(),
+                               tok[o + 1].c_str(), tok[o + 2].c_str(), tok[o + 3 + k].c_str(), kVaField[k]);
+        }
+        seen[e] = 1;
+    }
+    for (size_t e = 0; e < np; ++e)
+        if (!seen[e])
+            return set_err(nullptr, VSSR_E_BADARG, "vashishta file lacks the entry %s %s %s", species[e / ((size_t)n_species * n_species)],
+                           species[e / n_species % n_species], species[e % n_species]);
+    return vashishta_create_checked(device, n_species, params.data(), species, out);
+}
+
 // ---- pair potentials --------------------------------------------------------------------------------------------------------
 static const char *const kPairStyle[7] = {"none", "lj/cut", "morse", "buck", "born", "coul/dsf", "coul/long"};
 
@@ -447,11 +583,11 @@ int vssr_pair_create_kspace(int32_t device, int32_t n_types, int32_t n_terms, co
 
 }  // extern "C"
 
-// ---- evaluation with fp64 results: one body behind the four exported names ------------------------------------------------------
+// ---- evaluation with fp64 results: one body behind the five exported names ------------------------------------------------------
 static int analytic_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                                const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                                double *energy_atoms_f64, double *forces_f64) {
-    // (a refusal names the Tersoff entry point whichever of the four was called: the message is kept as it always was)
+    // (a refusal names the Tersoff entry point whichever of the five was called: the message is kept as it always was)
     if (int rc = check_kind(h, KINDS_EVAL, "vssr_tersoff_eval_batch")) return rc;
     if (!is_analytic(h)) return set_err(h, VSSR_E_STATE, "not a Tersoff / EAM / SW handle");
     vssr_out dummy;
@@ -483,6 +619,12 @@ int vssr_eam_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, c
 int vssr_sw_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                        const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
                        double *energy_atoms_f64, double *forces_f64) {
+    return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
+}
+
+int vssr_vashishta_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
+                              const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,
+                              double *energy_atoms_f64, double *forces_f64) {
     return analytic_eval_batch(h, n_cfg, n_atoms, type, pos, cell, pbc, want, out, energy_f64, energy_atoms_f64, forces_f64);
 }
 

@@ -300,12 +300,13 @@ enum class Kind : int {
     GMM_FIT = 6,   // Gaussian-mixture fit (gmm_fit.hip)
     CLUSTER = 7,   // latent-space clustering (cluster.hip)
     PAIR = 8,      // pair potentials + damped-shifted-force Coulomb (pair.hip)
+    VASHISHTA = 9, // Vashishta two- plus three-body potential (vashishta.hip)
     COUNT
 };
 constexpr unsigned kind_bit(Kind k) { return 1u << (int)k; }
 // kinds that evaluate a resident batch: the vssr_batch_* / vssr_eval* / relaxation / introspection entry points serve these
 constexpr unsigned KINDS_EVAL = kind_bit(Kind::PAINN) | kind_bit(Kind::TERSOFF) | kind_bit(Kind::EAM) | kind_bit(Kind::SW) |
-                                kind_bit(Kind::PAIR);
+                                kind_bit(Kind::PAIR) | kind_bit(Kind::VASHISHTA);
 
 }  // namespace vssr
 
@@ -315,6 +316,7 @@ struct vssr_handle {
     vssr_eam_grid eam_grid = {0, 0, 0.0, 0.0, 0.0};   // EAM: grids; spline tables live in pot_params
     int eam_nel = 0, eam_fs = 0;   // EAM with typed tables (vssr_eam_create_alloy): elements, 1 = eam/fs densities; 0 = one funcfl
     bool eam_adp = false;          // EAM with dipole / quadrupole tables (vssr_eam_create_adp): eam_run / eam_stress hand over to adp.hip
+    double vash_r0max = 0.0;       // Vashishta: the largest r0 of the table (slots below it form a centre's short three-body row)
     int device = 0;
     vssr::OwnedStream stream;    // null until the handle reaches a device (open_device)
     std::string err;
@@ -509,6 +511,8 @@ int adp_stress(vssr_handle *h);
 int sw_run(vssr_handle *h, uint32_t want);
 // pair potentials (pair.hip)
 int pair_run(vssr_handle *h, uint32_t want);
+// Vashishta (vashishta.hip)
+int vashishta_run(vssr_handle *h, uint32_t want);
 // Gaussian-mixture scoring (gmm.hip).  Rows: caller fp64 rows [n][Dp] (padded), or fp32 rows with leading dimension ldx = Dp;
 // writes g->d_gmm_lp [n][K] (logp_k) and g->d_gmm_nll [n] on stream st
 int gmm_upload(vssr_handle *g, const double *means, const double *prec_chol, const double *weights);
@@ -546,6 +550,7 @@ struct PotView;
 void ewald_run(vssr_handle *h, const PotView &V);   // ewald.hip: reciprocal, self and background terms added to d_pot_ea / d_pot_f
 int ewald_stress(vssr_handle *h);                   // their virial added to d_stress
 int pair_stress(vssr_handle *h);   // runs the site kernel's gradient form first: a plain evaluation keeps no per-slot gradients
+int vashishta_stress(vssr_handle *h);   // likewise: a plain evaluation keeps the three-body gradients of the short slots only
 // What differs between the kinds that evaluate a batch, one row per Kind (api_handle.hip); run == nullptr: the kind evaluates nothing.
 // f64: an analytic potential -- results in d_pot_e / _ea / _f (fp64, one "model"), driven by relax_cg / chain_min as well.
 struct Evaluator {
