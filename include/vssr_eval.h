@@ -258,6 +258,60 @@ typedef struct { int32_t max_steps, max_eval; double fmax, alpha, maxstep, c1, c
 int vssr_batch_relax_bfgs_linesearch(vssr_handle *h, const vssr_bfgsls_params *p, const uint8_t *fixed, uint32_t want,
                                      double *pos_out, int32_t *n_steps, int32_t *n_eval, int32_t *stop_reason);
 
+/* ---- molecular dynamics of the resident batch (csrc/md_dev.h, csrc/md.hip, k_md_chain in csrc/chain_min.hip) ----
+ * Velocity Verlet (VSSR_MD_NVE) and Langevin BAOAB (VSSR_MD_LANGEVIN; Leimkuhler & Matthews 2013) on every handle kind that relaxes:
+ * PaiNN (fp64 ensemble-mean energy, fp32 forces widened), Tersoff, SW, EAM / ADP, Vashishta and pair handles with and without k-space.
+ * All integrator arithmetic is fp64.  Units: A, eV, fs, amu, K; velocities in A / fs, friction in 1 / fs; kB = 8.617333262e-5 eV / K,
+ * 1 eV / amu = (1.602176634e-19 / 1.66053906660e-27) 1e-10 A^2 / fs^2.  The numpy restatement is tests/md_oracle.py.
+ * One step n = step0 + (steps completed in this call), with a = F / m in A / fs^2:
+ *   NVE       v += (dt/2) a;  r += dt v;                                                              [evaluate]  v += (dt/2) a
+ *   Langevin  v += (dt/2) a;  r += (dt/2) v;  v = c1 v + sqrt((1 - c1^2) kB T_n / m) xi;  r += (dt/2) v;  [evaluate]  v += (dt/2) a
+ * c1 = exp(-friction dt); T_n runs linearly from `temperature` at n = 0 to `temperature_end` at n = ramp_steps and stays there
+ * (ramp_steps = 0: temperature_end throughout).  xi: standard normals from Philox4x32-10 keyed by (seed, chain id) and counted by
+ * (n, atom index within the chain, draw tag) -- the bit layout is written out in csrc/md_dev.h -- so a chain's trajectory depends on
+ * neither its place in a batch nor the batch around it, and a repeated evaluation (capacity regrow) draws nothing twice.
+ * Atoms under `fixed` (1 = held, NULL = all free) have v = 0, draw no noise and never move.  No centre-of-mass removal.
+ * Velocities are resident on the handle between calls: vssr_batch_md_set_velocities (NULL = zeros) or _draw_velocities
+ * (Maxwell-Boltzmann, v = sqrt(kB T / m) xi per component under its own draw tag, held atoms 0) put them there, vssr_batch_upload voids
+ * them, _get_velocities reads them.  vssr_batch_md and _get_velocities without velocities: VSSR_E_STATE.
+ * vssr_batch_md: mass [sum N] amu; chain_id [B] global chain ids (NULL = 0 .. B-1); thermo (may be NULL)
+ * [n_steps / thermo_interval + 1][B][2] = (E_pot, E_kin = 1/2 sum m v^2) in eV after 0, k, 2k, ... steps of this call (record 0 is the
+ * state the call found; records a chain did not reach are NaN); n_done [B] steps completed; stop_reason [B]: 1 all n_steps taken,
+ * 2 a non-finite energy or force (positions and velocities are those of the last completed step).  One chain's blow-up is never an
+ * error of the call.  pos_out, thermo, n_done, stop_reason may each be NULL.
+ * RESUMABLE: two calls of n steps, the second with step0 = n, leave what one call of 2 n steps leaves, bit for bit (that is how
+ * callers take frames; there are no trajectory rings for MD).  Afterwards the batch holds the final positions and a complete
+ * evaluation of them over all chains: download and vssr_batch_results_f64 work at once with either driver; vssr_batch_stress,
+ * vssr_batch_stats and vssr_batch_neighbors at once after the lock-step driver, after one vssr_batch_run behind the chain-resident one
+ * (it numbers its rows per chain and leaves no batch-wide graph, as the chain-resident CG).
+ * VSSR_E_BADARG (with a message, before anything moves; the handle stays usable): p or mass NULL, n_steps < 0, thermo_interval < 1,
+ * dt not finite or <= 0, a mass not finite or <= 0, an unknown thermostat; Langevin: friction <= 0, a negative temperature,
+ * ramp_steps < 0.  _draw_velocities: mass NULL or bad, a negative temperature.  _set_velocities: a non-finite velocity.
+ * Two drivers, same results bit for bit (vssr_batch_md_driver, as vssr_batch_relax_cg_driver): LOCKSTEP evaluates the whole batch once
+ * per step (every kind); RESIDENT integrates every chain with ONE workgroup for the whole call (k_md_chain, csrc/chain_min.hip: Tersoff, SW, EAM
+ * funcfl / alloy / fs and pair handles without k-space whose largest chain has <= 256 atoms; any other batch runs in lock step
+ * without an error); AUTO (the default) takes the chain-resident kernel for Tersoff batches of <= 256 chains of <= 64 atoms (the measured
+ * regime, profiles/r29/NOTES_md.md) and the lock-step driver for everything else.  driver >= 0 sets the handle's choice, < 0 leaves it;
+ * last_used (may be NULL): the driver the last vssr_batch_md ran (0 none yet, 1 lock-step, 2 chain-resident).  VSSR_E_BADARG: a value
+ * above 2. */
+enum { VSSR_MD_NVE = 0, VSSR_MD_LANGEVIN = 1 };
+enum { VSSR_MD_DRIVER_AUTO = 0, VSSR_MD_DRIVER_LOCKSTEP = 1, VSSR_MD_DRIVER_RESIDENT = 2 };
+typedef struct {
+    int32_t n_steps, thermostat, thermo_interval;   /* thermo_interval >= 1 */
+    double dt;                                      /* fs */
+    double temperature, temperature_end, friction;  /* K, K, 1/fs (Langevin) */
+    int64_t ramp_steps, step0;
+    uint64_t seed;
+} vssr_md_params;
+int vssr_batch_md_set_velocities(vssr_handle *h, const double *vel /*[sum N][3], NULL = zeros*/);
+int vssr_batch_md_draw_velocities(vssr_handle *h, const double *mass, const uint8_t *fixed, const uint64_t *chain_id,
+                                  double temperature, uint64_t seed);
+int vssr_batch_md_get_velocities(vssr_handle *h, double *vel);
+int vssr_batch_md(vssr_handle *h, const vssr_md_params *p, const double *mass /*[sum N] amu*/, const uint8_t *fixed /*or NULL*/,
+                  const uint64_t *chain_id /*[B], NULL = 0..B-1*/, uint32_t want, double *pos_out,
+                  double *thermo /*[n_steps / thermo_interval + 1][B][2]*/, int32_t *n_done, int32_t *stop_reason);
+int vssr_batch_md_driver(vssr_handle *h, int32_t driver, int32_t *last_used);
+
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
  * vssr_profile_read synchronises and returns, for each kernel class, the number of launches and

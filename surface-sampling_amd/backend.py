@@ -39,6 +39,8 @@ EXPORTS = (
     "vssr_pair_create", "vssr_pair_create_kspace", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
     "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
+    "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
+    "vssr_batch_md_driver",
 )
 
 
@@ -134,6 +136,35 @@ class BfgsLsParams(C.Structure):
 
 BFGSLS_STOP_REASONS = {1: "converged", 2: "max steps", 3: "line search failed", 4: "max force evaluations",
                        5: "non-finite energy or force"}
+
+
+class MdParams(C.Structure):
+    """vssr_md_params: fs, K, 1 / fs; ``thermostat`` one of ``MD_THERMOSTATS``."""
+    _fields_ = [("n_steps", C.c_int32), ("thermostat", C.c_int32), ("thermo_interval", C.c_int32), ("dt", C.c_double),
+                ("temperature", C.c_double), ("temperature_end", C.c_double), ("friction", C.c_double), ("ramp_steps", C.c_int64),
+                ("step0", C.c_int64), ("seed", C.c_uint64)]
+
+
+MD_THERMOSTATS = {"nve": 0, "langevin": 1}
+MD_STOP_REASONS = {1: "all steps taken", 2: "non-finite energy or force"}
+# vssr_batch_md_driver: which driver vssr_batch_md takes ("auto": the library's rule -- chain-resident for small Tersoff batches)
+MD_DRIVERS = {"auto": 0, "lockstep": 1, "resident": 2}
+MD_DRIVER_NAMES = {0: None, 1: "lockstep", 2: "resident"}
+KB_EV = 8.617333262e-5   # eV / K, the constant of csrc/md_dev.h
+
+
+def md_driver_code(driver) -> int:
+    """The VSSR_MD_DRIVER_* value of ``"auto"`` / ``"lockstep"`` / ``"resident"``; ``ValueError`` for anything else."""
+    if not isinstance(driver, str) or driver not in MD_DRIVERS:
+        raise ValueError(f"MD driver {driver!r}: one of {', '.join(repr(k) for k in MD_DRIVERS)}")
+    return MD_DRIVERS[driver]
+
+
+def md_thermostat_code(thermostat) -> int:
+    """The VSSR_MD_* value of ``"nve"`` / ``"langevin"``; ``ValueError`` for anything else."""
+    if not isinstance(thermostat, str) or thermostat not in MD_THERMOSTATS:
+        raise ValueError(f"thermostat {thermostat!r}: one of {', '.join(repr(k) for k in MD_THERMOSTATS)}")
+    return MD_THERMOSTATS[thermostat]
 
 
 # who runs optimizer="BFGSLineSearch" for a calculator: ASE's class on the host, one optimizer per chain ("ase", the default), or the
@@ -274,6 +305,17 @@ def load_library():
     L.vssr_batch_relax_cg_driver.argtypes = [vp, C.c_int32, ip]
     L.vssr_batch_relax_bfgs_linesearch.restype = C.c_int
     L.vssr_batch_relax_bfgs_linesearch.argtypes = [vp, C.POINTER(BfgsLsParams), u8p, C.c_uint32, dp, ip, ip, ip]
+    u64p = C.POINTER(C.c_uint64)
+    L.vssr_batch_md.restype = C.c_int
+    L.vssr_batch_md.argtypes = [vp, C.POINTER(MdParams), dp, u8p, u64p, C.c_uint32, dp, dp, ip, ip]
+    L.vssr_batch_md_set_velocities.restype = C.c_int
+    L.vssr_batch_md_set_velocities.argtypes = [vp, dp]
+    L.vssr_batch_md_draw_velocities.restype = C.c_int
+    L.vssr_batch_md_draw_velocities.argtypes = [vp, dp, u8p, u64p, C.c_double, C.c_uint64]
+    L.vssr_batch_md_get_velocities.restype = C.c_int
+    L.vssr_batch_md_get_velocities.argtypes = [vp, dp]
+    L.vssr_batch_md_driver.restype = C.c_int
+    L.vssr_batch_md_driver.argtypes = [vp, C.c_int32, ip]
     L.vssr_eam_create.restype = C.c_int
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_create_alloy.restype = C.c_int
@@ -423,6 +465,8 @@ class _DeviceArray:
 
 class _Handle:
     """Owns a vssr_handle*; shared plumbing for the PaiNN and Tersoff engines."""
+
+    last_md_driver = None         # "lockstep" / "resident": the driver the last md() of this engine ran
 
     def __init__(self):
         self._lib = load_library()
@@ -598,6 +642,82 @@ class _Handle:
         out = self._relax_call(call, p, fixed, want, record_interval)
         out["n_eval"], out["stop_reason"], out["converged"] = ev, why, why == 1
         return out
+
+    # -- molecular dynamics ---------------------------------------------------------------------------
+    def _chain_ids(self, chain_id):
+        if chain_id is None:
+            return None
+        ids = np.ascontiguousarray(chain_id, dtype=np.uint64)
+        if ids.size != self._n_cfg:
+            raise ValueError("chain ids do not match the resident batch")
+        return ids
+
+    def _masses(self, masses):
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if m.size != self._n_atoms:
+            raise ValueError("masses do not match the resident batch")
+        return m
+
+    def set_velocities(self, velocities=None):
+        """Velocities [sum N, 3] in A / fs of the resident batch (``None``: zeros); they stay on the device until the next upload
+        (vssr_batch_md_set_velocities)."""
+        v = None
+        if velocities is not None:
+            v = np.ascontiguousarray(velocities, dtype=np.float64)
+            if v.size != 3 * self._n_atoms:
+                raise ValueError("velocities do not match the resident batch")
+        self._check(self._lib.vssr_batch_md_set_velocities(self._h, _ptr(v, C.c_double)))
+
+    def draw_velocities(self, masses, temperature, seed=0, fixed=None, chain_id=None):
+        """Maxwell-Boltzmann velocities at ``temperature`` K for the resident batch, drawn on the device from (seed, chain id, atom);
+        held atoms get 0, no centre-of-mass removal (vssr_batch_md_draw_velocities)."""
+        m, fx, ids = self._masses(masses), _fixed_arg(fixed, self._n_atoms), self._chain_ids(chain_id)
+        self._check(self._lib.vssr_batch_md_draw_velocities(self._h, _ptr(m, C.c_double), _ptr(fx, C.c_uint8), _ptr(ids, C.c_uint64),
+                                                            float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def get_velocities(self):
+        """The resident velocities, [sum N, 3] float64 in A / fs (vssr_batch_md_get_velocities)."""
+        v = np.zeros((self._n_atoms, 3), np.float64)
+        self._check(self._lib.vssr_batch_md_get_velocities(self._h, _ptr(v, C.c_double)))
+        return v
+
+    def md_driver(self, driver=None):
+        """Set the handle's MD driver (``None``: leave it) and return the name of the one its last ``md`` ran, ``None`` before the
+        first (vssr_batch_md_driver)."""
+        code = -1 if driver is None else md_driver_code(driver)
+        last = C.c_int32(0)
+        self._check(self._lib.vssr_batch_md_driver(self._h, code, C.byref(last)))
+        return MD_DRIVER_NAMES.get(last.value)
+
+    def md(self, masses, steps, timestep, thermostat="nve", temperature=0.0, temperature_end=None, friction=0.0, ramp_steps=None,
+           step0=0, seed=0, fixed=None, chain_id=None, thermo_interval=1, want=WANT_ALL, driver=None):
+        """Integrate every chain of the resident batch for ``steps`` steps of ``timestep`` fs on the device (vssr_batch_md): velocity
+        Verlet (``"nve"``) or Langevin BAOAB (``"langevin"``: ``temperature`` K running linearly to ``temperature_end`` over
+        ``ramp_steps`` steps -- default: the ``steps`` of this call when an end temperature is given, else none --, ``friction`` in
+        1 / fs).  The batch needs velocities (``set_velocities`` / ``draw_velocities``); ``masses`` [sum N] in amu.  ``step0`` is the
+        absolute index of the first step: two calls of n steps, the second with ``step0=n``, equal one call of 2 n steps bit for bit.
+        ``chain_id`` [B]: global chain ids of the random numbers (default 0 .. B-1).  ``driver``: ``"auto"`` / ``"lockstep"`` /
+        ``"resident"`` (None: the handle's setting).  Returns dict(positions [sum N, 3], velocities [sum N, 3], epot / ekin
+        [steps // thermo_interval + 1, B] in eV, n_done [B], stop_reason [B] (``MD_STOP_REASONS``)); ``download()`` /
+        ``results_f64()`` / ``stress()`` serve the final state at once."""
+        N, B = self._n_atoms, self._n_cfg
+        m, fx, ids = self._masses(masses), _fixed_arg(fixed, N), self._chain_ids(chain_id)
+        t_end = temperature if temperature_end is None else temperature_end
+        if ramp_steps is None:
+            ramp_steps = 0 if temperature_end is None else int(steps)
+        p = MdParams(int(steps), md_thermostat_code(thermostat), int(thermo_interval), float(timestep), float(temperature), float(t_end),
+                     float(friction), int(ramp_steps), int(step0), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if driver is not None:
+            self._check(self._lib.vssr_batch_md_driver(self._h, md_driver_code(driver), None))
+        nrec = max(int(steps), 0) // max(int(thermo_interval), 1) + 1
+        pos, thermo = np.zeros((N, 3), np.float64), np.zeros((nrec, B, 2), np.float64)
+        done, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._check(self._lib.vssr_batch_md(self._h, C.byref(p), _ptr(m, C.c_double), _ptr(fx, C.c_uint8), _ptr(ids, C.c_uint64), int(want),
+                                            _ptr(pos, C.c_double), _ptr(thermo, C.c_double), _ptr(done, C.c_int32), _ptr(why, C.c_int32)))
+        self.last_relax_counts = self.relax_counts()
+        self.last_md_driver = self.md_driver()
+        return {"positions": pos, "velocities": self.get_velocities(), "epot": thermo[:, :, 0].copy(), "ekin": thermo[:, :, 1].copy(),
+                "n_done": done, "stop_reason": why}
 
     def relax_counts(self):
         """``(lock-step evaluations, dispatched chain-evaluations)`` of the last relaxation (vssr_batch_relax_counts)."""

@@ -218,6 +218,61 @@ def _fixed_mask(sizes, fixed_indices):
     return mask
 
 
+def _md_batch(get_engine, packs, atoms_list, fixed_indices, steps, timestep, thermostat, temperature, temperature_end, friction, seed, first_chain,
+              velocities, masses, thermo_interval, md_driver, want):
+    """``md_batch`` of every calculator: the argument checks, then on the calculator's engine (``get_engine()``, not touched before) the
+    packed slabs, velocities (given, else Maxwell-Boltzmann at ``temperature``) and ``backend.md``; the per-slab dicts."""
+    backend.md_thermostat_code(thermostat)   # (ValueError before anything is uploaded)
+    if md_driver is not None:
+        backend.md_driver_code(md_driver)
+    if int(steps) < 0 or not float(timestep) > 0 or int(thermo_interval) < 1:
+        raise ValueError(f"md_batch: steps {steps} >= 0, timestep {timestep} > 0 fs and thermo_interval {thermo_interval} >= 1 wanted")
+    if thermostat == "langevin" and not float(friction) > 0:
+        raise ValueError(f"md_batch: Langevin friction {friction} > 0 (1 / fs) wanted")
+    if float(temperature) < 0 or (temperature_end is not None and float(temperature_end) < 0):
+        raise ValueError("md_batch: a temperature is negative")
+    B = len(atoms_list)
+    if masses is not None and len(masses) != B:
+        raise ValueError(f"md_batch: {len(masses)} mass arrays for {B} slabs")
+    if velocities is not None and len(velocities) != B:
+        raise ValueError(f"md_batch: {len(velocities)} velocity arrays for {B} slabs")
+    start = _cfg_start([len(p[0]) for p in packs])
+    m = np.concatenate([structures.masses_of(a, None if masses is None else masses[b]) for b, a in enumerate(atoms_list)])
+    fixed = _fixed_mask(np.diff(start), fixed_indices)
+    ids = np.arange(B, dtype=np.uint64) + np.uint64(int(first_chain))
+    eng = get_engine()
+    eng.upload(packs)
+    if velocities is not None:
+        eng.set_velocities(np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]))
+    else:
+        eng.draw_velocities(m, temperature, seed=seed, fixed=fixed, chain_id=ids)
+    info = eng.md(m, steps, timestep, thermostat=thermostat, temperature=temperature, temperature_end=temperature_end, friction=friction,
+                  seed=seed, fixed=fixed, chain_id=ids, thermo_interval=thermo_interval, want=want, driver=md_driver)
+    out = []
+    for b, atoms in enumerate(atoms_list):
+        a0, a1 = int(start[b]), int(start[b + 1])
+        final = atoms.copy()
+        final.set_positions(info["positions"][a0:a1])
+        n_free = (a1 - a0) - (int(fixed[a0:a1].sum()) if fixed is not None else 0)
+        ekin = info["ekin"][:, b].copy()
+        out.append({"atoms": final, "velocities": info["velocities"][a0:a1].copy(), "epot": info["epot"][:, b].copy(), "ekin": ekin,
+                    "temperature": 2.0 * ekin / (3.0 * n_free * backend.KB_EV) if n_free else np.zeros_like(ekin),
+                    "n_done": int(info["n_done"][b]), "stop_reason": int(info["stop_reason"][b])})
+    return out
+
+
+_MD_DOC = """Molecular dynamics of B independent slabs at once on the device (``backend.md``): ``steps`` steps of ``timestep`` fs of velocity
+        Verlet (``thermostat="nve"``) or Langevin BAOAB (``"langevin"``: ``temperature`` K, running linearly to ``temperature_end``
+        over the call when that is given; ``friction`` in 1 / fs).  ``fixed_indices``: per slab, the atom indices FixAtoms holds (they
+        never move and carry no velocity).  ``velocities``: per slab [N, 3] in A / fs; None draws Maxwell-Boltzmann velocities at
+        ``temperature`` on the device.  ``masses``: per slab [N] in amu; None takes ``atoms.get_masses()`` where the object has it, else
+        the standard atomic weights (``structures.ATOMIC_MASSES``).  Random numbers are keyed by ``seed`` and the global chain id
+        ``first_chain + b``, so a slab's trajectory does not depend on the batch it runs in.  ``md_driver``: "auto" / "lockstep" /
+        "resident" (None: the engine's setting).  Returns per slab a dict: ``atoms`` (a copy at the final positions), ``velocities``,
+        ``epot`` / ``ekin`` / ``temperature`` (= 2 ekin / (3 n_free kB), 0 when nothing is free) after 0, k, 2k, ... steps with
+        k = ``thermo_interval``, ``n_done``, ``stop_reason`` (``backend.MD_STOP_REASONS``)."""
+
+
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:
     """bool ``[B]``: the reference's out-of-bounds guard (``mcmc/dynamics.py:159-168``) for every chain of a batch -- a non-finite energy
     or force, ``|E| > e_max``, a force component beyond ``f_max``, or a ``saturated`` evaluation."""
@@ -766,6 +821,16 @@ class EnsembleNFFSurface(_Base):
         return out
 
 
+    def md_batch(self, atoms_list, fixed_indices=None, steps: int = 100, timestep: float = 1.0, thermostat: str = "nve",
+                 temperature: float = 300.0, temperature_end=None, friction: float = 0.01, seed: int = 0, first_chain: int = 0,
+                 velocities=None, masses=None, thermo_interval: int = 1, md_driver=None):
+        return _md_batch(self._get_engine, [structures.as_arrays(a) for a in atoms_list], atoms_list, fixed_indices, steps, timestep,
+                         thermostat, temperature, temperature_end, friction, seed, first_chain, velocities, masses, thermo_interval,
+                         md_driver, backend.WANT_ALL)
+
+    md_batch.__doc__ = _MD_DOC
+
+
 def surface_energy_from_counts(energy, counts: dict, chem_pots: dict, offset_data: dict, offset_units: str = "atomic"):
     """:func:`surface_energy_from_energy` for MANY slabs at once: ``energy`` ``[B]`` and ``counts`` = element symbol ->
     ``[B]`` atom counts, the dict's key order being the order in which the elements first appear in the slabs' atom lists
@@ -1177,6 +1242,15 @@ class _AnalyticSurfCalc(_Base):
                 r["stress"] = stress[b].copy()
             out.append((relaxed, _traj_of_chain(traj, b, a0, a1, atoms), self.ENERGY_THRESHOLD if oob[b] else r["energy"], bool(oob[b]), r))
         return out
+
+    def md_batch(self, atoms_list, fixed_indices=None, steps: int = 100, timestep: float = 1.0, thermostat: str = "nve",
+                 temperature: float = 300.0, temperature_end=None, friction: float = 0.01, seed: int = 0, first_chain: int = 0,
+                 velocities=None, masses=None, thermo_interval: int = 1, md_driver=None):
+        return _md_batch(self._get_engine, [self._pack(a) for a in atoms_list], atoms_list, fixed_indices, steps, timestep, thermostat,
+                         temperature, temperature_end, friction, seed, first_chain, velocities, masses, thermo_interval, md_driver,
+                         backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
+
+    md_batch.__doc__ = _MD_DOC
 
     @staticmethod
     def packed_supported(relax: bool, optimizer) -> bool:

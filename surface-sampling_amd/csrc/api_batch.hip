@@ -39,6 +39,7 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
     h->batch_valid = false;
     h->ran = false;
+    h->md_vel_valid = false;   // (velocities belong to the batch they were set for)
     std::vector<int> start(n_cfg + 1, 0);
     for (int b = 0; b < n_cfg; ++b) {
         if (n_atoms[b] < 1) return set_err(h, VSSR_E_BADARG, "configuration %d has %d atoms", b, n_atoms[b]);

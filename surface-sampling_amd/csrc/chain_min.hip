@@ -25,8 +25,12 @@
 // and stop reasons equal the lock-step driver's bit for bit (tests/test_cg.py::test_chain_resident_minimiser_equals_the_lock_step_driver,
 // tests/test_cg_resident_kinds_gpu.py).  Only the slot numbering differs: a chain owns the fixed slot range
 // [cfg_start[b], cfg_start[b + 1]) x cap_per_atom instead of a place in a batch-wide scan.
+//
+// The evaluation phase is the device function template cm_evaluate<Site>; a second kernel template, k_md_chain<Site>, puts the
+// molecular-dynamics integrator of md_dev.h behind it instead of the CG state machine (further down; host side: chain_md).
 #include <algorithm>
 #include "cg_dev.h"
+#include "md_dev.h"
 #include "nbr_dev.h"
 #ifdef CM_PHASE_TIMING   // sub-phases of the site tile: slots 10 .. 12 of g_cm_phase
 #include <hip/hip_runtime.h>
@@ -200,6 +204,70 @@ struct PairSite {   // pair.hip: k_pair_site<false> tiles; the body writes e_ato
     }
 };
 
+// One energy + force evaluation of chain b at its current positions, every thread of the workgroup in uniform control flow; false: the
+// slot capacity of the chain's pool is exceeded (nothing downstream of the row scan ran).  Shared by the minimiser (k_cg_chain) and the
+// integrator (k_md_chain) below.  scan: CM_THREADS ints, red: 256 doubles, s_over: one int of LDS, zero at the first call.
+template <class Site>
+__device__ __forceinline__ bool cm_evaluate(typename Site::Shared &sh, double *red, int *scan, int *s_over, const CmCommon &A,
+                                            const typename Site::Params &SP, int b, int a0, int n, long long slot0, long long slot1, int *rs) {
+    const int tid = threadIdx.x, a1 = a0 + n;
+    CMP_INIT
+    for (int i = a0 + tid; i < a1; i += CM_THREADS) wrap_atom(i, A.pos, A.atom_cfg, A.cell, A.invcell, A.pbc, A.wpos, A.wrap);
+    __syncthreads();
+    CMP(0)
+    for (int base = a0; base < a1; base += CM_THREADS / CM_LPC) {   // 16 lanes per centre, 16 centres per pass
+        const int i = base + tid / CM_LPC;
+        if (i < a1)
+            nbr_row<false, CM_LPC>(i, A.wpos, A.atom_cfg, A.cfg_start, A.cell, A.invcell, A.nimg, A.rc2, A.deg, rs, A.edge, A.edge_S, slot1,
+                                   A.hits, A.hits_stride, nullptr);
+    }
+    __syncthreads();
+    CMP(1)
+    {   // rows of the chain: exclusive scan of the padded degrees (n <= 256: one atom per thread)
+        const int pd = tid < n ? max((A.deg[a0 + tid] + 3) & ~3, 8) : 0;
+        scan[tid] = pd;
+        __syncthreads();
+        for (int d = 1; d < CM_THREADS; d <<= 1) {
+            const int v = tid >= d ? scan[tid - d] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        if (tid < n) rs[a0 + tid] = (int)(slot0 + scan[tid] - pd);
+        if (tid == CM_THREADS - 1) {
+            rs[a1] = (int)(slot0 + scan[tid]);
+            if (slot0 + scan[tid] > slot1) *s_over = 1;
+        }
+        __syncthreads();
+        if (*s_over) return false;
+    }
+    CMP(2)
+    for (int base = a0; base < a1; base += CM_THREADS / CM_LPC) {
+        const int i = base + tid / CM_LPC;
+        if (i < a1)
+            nbr_row<true, CM_LPC>(i, A.wpos, A.atom_cfg, A.cfg_start, A.cell, A.invcell, A.nimg, A.rc2, A.deg, rs, A.edge, A.edge_S, slot1,
+                                  A.hits, A.hits_stride, nullptr);
+    }
+    __syncthreads();
+    CMP(3)
+    if (Site::REV) {
+        for (int base = a0; base < a1; base += CM_THREADS / CM_LPC) {
+            const int i = base + tid / CM_LPC;
+            if (i < a1) rev_row<CM_LPC>(i, rs, A.edge, A.edge_S, A.rev);
+        }
+        __syncthreads();
+    }
+    CMP(4)
+    Site::sites(sh, A, SP, a0, a1, rs);
+    {
+        CMP_INIT
+        chain_energy(b, red, A.cfg_start, A.e_atom, A.energy);
+        __syncthreads();
+        CMP(8)
+    }
+    return true;
+}
+
 template <class Site>
 __global__ void __launch_bounds__(CM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_cg_chain(const CmArgs<Site> *__restrict__ Ap) {
@@ -210,7 +278,7 @@ k_cg_chain(const CmArgs<Site> *__restrict__ Ap) {
     __shared__ int scan[CM_THREADS];
     __shared__ int s_over;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int a0 = A.cfg_start[b], n = A.cfg_start[b + 1] - a0, a1 = a0 + n;
+    const int a0 = A.cfg_start[b], n = A.cfg_start[b + 1] - a0;
     const long long slot0 = (long long)a0 * A.cap_per_atom, slot1 = slot0 + (long long)n * A.cap_per_atom;
     int *rs = A.row_start + b;   // rs[i], rs[i + 1] for the global atom index i of this chain: n + 1 entries of its own
     Site::prepare(sh, A, SP);
@@ -220,60 +288,7 @@ k_cg_chain(const CmArgs<Site> *__restrict__ Ap) {
 
     // one energy + force evaluation of the chain at its current positions; false: slot capacity exceeded (nothing was stepped)
     auto evaluate = [&]() -> bool {
-        CMP_INIT
-        for (int i = a0 + tid; i < a1; i += CM_THREADS) wrap_atom(i, A.pos, A.atom_cfg, A.cell, A.invcell, A.pbc, A.wpos, A.wrap);
-        __syncthreads();
-        CMP(0)
-        for (int base = a0; base < a1; base += CM_THREADS / CM_LPC) {   // 16 lanes per centre, 16 centres per pass
-            const int i = base + tid / CM_LPC;
-            if (i < a1)
-                nbr_row<false, CM_LPC>(i, A.wpos, A.atom_cfg, A.cfg_start, A.cell, A.invcell, A.nimg, A.rc2, A.deg, rs, A.edge, A.edge_S, slot1,
-                                       A.hits, A.hits_stride, nullptr);
-        }
-        __syncthreads();
-        CMP(1)
-        {   // rows of the chain: exclusive scan of the padded degrees (n <= 256: one atom per thread)
-            const int pd = tid < n ? max((A.deg[a0 + tid] + 3) & ~3, 8) : 0;
-            scan[tid] = pd;
-            __syncthreads();
-            for (int d = 1; d < CM_THREADS; d <<= 1) {
-                const int v = tid >= d ? scan[tid - d] : 0;
-                __syncthreads();
-                scan[tid] += v;
-                __syncthreads();
-            }
-            if (tid < n) rs[a0 + tid] = (int)(slot0 + scan[tid] - pd);
-            if (tid == CM_THREADS - 1) {
-                rs[a1] = (int)(slot0 + scan[tid]);
-                if (slot0 + scan[tid] > slot1) s_over = 1;
-            }
-            __syncthreads();
-            if (s_over) return false;
-        }
-        CMP(2)
-        for (int base = a0; base < a1; base += CM_THREADS / CM_LPC) {
-            const int i = base + tid / CM_LPC;
-            if (i < a1)
-                nbr_row<true, CM_LPC>(i, A.wpos, A.atom_cfg, A.cfg_start, A.cell, A.invcell, A.nimg, A.rc2, A.deg, rs, A.edge, A.edge_S, slot1,
-                                      A.hits, A.hits_stride, nullptr);
-        }
-        __syncthreads();
-        CMP(3)
-        if (Site::REV) {
-            for (int base = a0; base < a1; base += CM_THREADS / CM_LPC) {
-                const int i = base + tid / CM_LPC;
-                if (i < a1) rev_row<CM_LPC>(i, rs, A.edge, A.edge_S, A.rev);
-            }
-            __syncthreads();
-        }
-        CMP(4)
-        Site::sites(sh, A, SP, a0, a1, rs);
-        {
-            CMP_INIT
-            chain_energy(b, red, A.cfg_start, A.e_atom, A.energy);
-            __syncthreads();
-            CMP(8)
-        }
+        if (!cm_evaluate<Site>(sh, red, scan, &s_over, A, SP, b, a0, n, slot0, slot1, rs)) return false;
         evals += 1;
         return true;
     };
@@ -299,6 +314,62 @@ k_cg_chain(const CmArgs<Site> *__restrict__ Ap) {
     if (tid == 0) A.n_evals[b] += evals;
 }
 
+// ---- the chain-resident integrator: ONE workgroup runs the whole molecular-dynamics call of ONE chain ------------------------
+// MD is the minimiser's argument with thousands of evaluations per call instead of 55: the evaluation phase above, then the integrator
+// of md_dev.h -- the function the lock-step driver launches as k_md_step (md.hip) -- with a barrier instead of ~12 launches in between.
+// Same bits as that driver: positions, velocities, thermo records, step counts, stop reasons, the final static results
+// (tests/test_md_gpu.py).  CmCommon is taken as it is (its CG fields stay unused) so that k_cg_chain's argument block keeps its layout.
+struct CmMd {
+    MdParams P;
+    MdView V;
+    int *stopped;
+};
+template <class Site>
+struct CmMdArgs {
+    CmCommon c;
+    typename Site::Params p;
+    CmMd m;
+};
+
+template <class Site>
+__global__ void __launch_bounds__(CM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_md_chain(const CmMdArgs<Site> *__restrict__ Ap) {
+    const CmCommon &A = Ap->c;
+    const typename Site::Params &SP = Ap->p;
+    const CmMd &M = Ap->m;
+    __shared__ typename Site::Shared sh;
+    __shared__ double red[256];
+    __shared__ int scan[CM_THREADS];
+    __shared__ int s_over;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    // A launch after a capacity regrow finds the chains where they stopped: reason 1 -- the results of the final positions are in
+    // place; reason 2 -- the chain went back to its last completed step, the static evaluation of that state is (still) due.
+    int done = M.V.st[b].reason;   // (uniform: nothing has written it in this launch)
+    if (done == 1) return;
+    const int a0 = A.cfg_start[b], n = A.cfg_start[b + 1] - a0;
+    const long long slot0 = (long long)a0 * A.cap_per_atom, slot1 = slot0 + (long long)n * A.cap_per_atom;
+    int *rs = A.row_start + b;
+    Site::prepare(sh, A, SP);
+    if (tid == 0) s_over = 0;
+    __syncthreads();
+    int evals = 0;
+    // A step closes right behind the evaluation of the positions it moved to, and the chain stops there (md_dev.h): the results of the
+    // LAST evaluation are the static results of the final state, as in k_cg_chain.
+    for (;;) {
+        if (!cm_evaluate<Site>(sh, red, scan, &s_over, A, SP, b, a0, n, slot0, slot1, rs)) {   // (state untouched: the host enlarges the pools)
+            if (tid == 0) { atomicOr(A.flags, 1); A.n_evals[b] += evals; }
+            return;
+        }
+        evals += 1;
+        if (done) break;
+        md_step_chain<double>(b, red, A.cfg_start, A.energy, A.forces, A.fixed, M.P, A.pos, M.V, A.active, M.stopped);
+        __syncthreads();
+        done = M.V.st[b].reason;   // (uniform: written by thread 0 in front of the barrier)
+        if (done == 1) break;
+    }
+    if (tid == 0) A.n_evals[b] += evals;
+}
+
 __global__ void k_cm_init(int B, CgState *__restrict__ st, unsigned char *__restrict__ active, int *__restrict__ n_evals) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -315,16 +386,23 @@ __global__ void k_cm_report(int B, const CgState *__restrict__ st, int *__restri
 }
 
 template <class Site>
-static hipError_t cm_launch(hipStream_t st, int B, void *d_args, const CmCommon &c, const typename Site::Params &p) {
-    static_assert(sizeof(CmArgs<Site>) <= 1024, "argument block");
+static hipError_t cm_launch(hipStream_t st, int B, void *d_args, const CmCommon &c, const typename Site::Params &p, const CmMd *md) {
+    static_assert(sizeof(CmArgs<Site>) <= 1024 && sizeof(CmMdArgs<Site>) <= 1024, "argument block");
+    if (md) {   // the integrator
+        const CmMdArgs<Site> A{c, p, *md};
+        if (hipError_t e = hipMemcpyAsync(d_args, &A, sizeof(A), hipMemcpyHostToDevice, st)) return e;   // (pageable source: copied before the call returns)
+        hipLaunchKernelGGL(k_md_chain<Site>, dim3(B), dim3(CM_THREADS), 0, st, static_cast<const CmMdArgs<Site> *>(d_args));
+        return hipGetLastError();
+    }
     const CmArgs<Site> A{c, p};
     if (hipError_t e = hipMemcpyAsync(d_args, &A, sizeof(A), hipMemcpyHostToDevice, st)) return e;   // (pageable source: copied before the call returns)
     hipLaunchKernelGGL(k_cg_chain<Site>, dim3(B), dim3(CM_THREADS), 0, st, static_cast<const CmArgs<Site> *>(d_args));
     return hipGetLastError();
 }
 
-// The kind's scratch in d_gbar (sized for the slot_cap / atom count of this attempt), its argument block, its instantiation.
-static int cm_launch_kind(vssr_handle *h, void *d_args, const CmCommon &c) {
+// The kind's scratch in d_gbar (sized for the slot_cap / atom count of this attempt), its argument block, its instantiation of the
+// minimiser (md == nullptr) or of the integrator.
+static int cm_launch_kind(vssr_handle *h, void *d_args, const CmCommon &c, const CmMd *md = nullptr) {
     const int B = h->n_cfg;
     hipStream_t st = h->stream;
     size_t scratch = 0;   // doubles
@@ -341,23 +419,23 @@ static int cm_launch_kind(vssr_handle *h, void *d_args, const CmCommon &c) {
     case Kind::TERSOFF: {
         const TersoffSlots S = slots_of(h);
         const int fast = (h->n_types * h->n_types * h->n_types <= TS_MAXP) ? 1 : 0;
-        e = cm_launch<TersoffSite>(st, B, d_args, c, {fast, h->pot_params.as<TersP>(), S.eps, S.gslot});
+        e = cm_launch<TersoffSite>(st, B, d_args, c, {fast, h->pot_params.as<TersP>(), S.eps, S.gslot}, md);
         break;
     }
     case Kind::SW: {
         const SwSlots S = SwSlots::of(h);
-        e = cm_launch<SwSite>(st, B, d_args, c, {h->pot_params.as<SwP>(), S.eo, S.ej, S.gslot});
+        e = cm_launch<SwSite>(st, B, d_args, c, {h->pot_params.as<SwP>(), S.eo, S.ej, S.gslot}, md);
         break;
     }
     case Kind::EAM: {
         const EamAtoms S = EamAtoms::of(h);
         if (h->eam_nel > 0)   // as eam_run chooses: a funcfl handle keeps the untyped bodies
-            e = cm_launch<EamSite<true>>(st, B, d_args, c, {h->eam_grid, eam_tables(h), S.e_embed, S.fp});
+            e = cm_launch<EamSite<true>>(st, B, d_args, c, {h->eam_grid, eam_tables(h), S.e_embed, S.fp}, md);
         else
-            e = cm_launch<EamSite<false>>(st, B, d_args, c, {h->eam_grid, eam_tables(h), S.e_embed, S.fp});
+            e = cm_launch<EamSite<false>>(st, B, d_args, c, {h->eam_grid, eam_tables(h), S.e_embed, S.fp}, md);
         break;
     }
-    case Kind::PAIR: e = cm_launch<PairSite>(st, B, d_args, c, {h->pot_params.as<PairTable>()}); break;
+    case Kind::PAIR: e = cm_launch<PairSite>(st, B, d_args, c, {h->pot_params.as<PairTable>()}, md); break;
     default: h->prof.end(st); return set_err(h, VSSR_E_STATE, "chain-resident minimiser: no kernel for this kind of handle");
     }
     h->prof.end(st);
@@ -392,6 +470,23 @@ bool chain_min_supported(const vssr_handle *h) {
     // win or lose by batch size and kind (profiles/r15/NOTES_chain_resident_kinds.md): those take the lock-step kernels unless the
     // handle asks for the chain-resident one (advisor r5)
     return h->kind == Kind::TERSOFF && h->n_cfg <= 3072 && h->max_cfg_atoms <= 64;
+}
+
+// The resident batch, the graph scratch and the result arrays of one launch attempt (slot pools of `cap` slots per atom).
+static CmCommon cm_batch_args(const vssr_handle *h, const uint8_t *fixed, unsigned long long *hits_buf, int hits_stride, int cap, double rc,
+                              int *flags, int *n_evals) {
+    CmCommon A{};
+    A.n_types = h->n_types;
+    A.type = h->d_Z.as<int>(); A.atom_cfg = h->d_atom_cfg.as<int>(); A.cfg_start = h->d_cfg_start.as<int>(); A.nimg = h->d_nimg.as<int>();
+    A.cell = h->d_cell.as<double>(); A.invcell = h->d_invcell.as<double>();
+    A.pbc = h->d_pbc.as<uint8_t>(); A.fixed = fixed;
+    A.pos = h->d_pos.as<double>();
+    A.wpos = h->d_wpos.as<double>(); A.wrap = h->d_wrap.as<int>(); A.deg = h->d_deg.as<int>(); A.row_start = h->d_row_start.as<int>();
+    A.edge_S = h->d_edge_S.as<int>(); A.rev = h->d_rev.as<int>(); A.edge = h->d_edge.as<float4>();
+    A.hits = hits_buf; A.hits_stride = hits_stride; A.cap_per_atom = cap; A.rc2 = rc * rc;
+    A.e_atom = h->d_pot_ea.as<double>(); A.forces = h->d_pot_f.as<double>(); A.energy = h->d_pot_e.as<double>();
+    A.active = h->d_active.as<unsigned char>(); A.flags = flags; A.n_evals = n_evals;
+    return A;
 }
 
 // Same contract as relax_cg (relax_cg.hip): afterwards the batch holds the minimised positions, d_pot_e / _ea / _f the static results of
@@ -430,19 +525,10 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
         if (h->max_images <= 64 && (size_t)N * hits_stride * 8 <= ((size_t)1 << 30) && !h->d_hits.ensure((size_t)N * hits_stride * 8))
             hits_buf = h->d_hits.as<unsigned long long>();
         VSSR_HIP(h, hipMemsetAsync(flags, 0, sizeof(int) * 8, st));
-        CmCommon A{};
-        A.n_types = h->n_types;
-        A.type = h->d_Z.as<int>(); A.atom_cfg = h->d_atom_cfg.as<int>(); A.cfg_start = h->d_cfg_start.as<int>(); A.nimg = h->d_nimg.as<int>();
-        A.cell = h->d_cell.as<double>(); A.invcell = h->d_invcell.as<double>();
-        A.pbc = h->d_pbc.as<uint8_t>(); A.fixed = fixed;
-        A.pos = h->d_pos.as<double>();
-        A.wpos = h->d_wpos.as<double>(); A.wrap = h->d_wrap.as<int>(); A.deg = h->d_deg.as<int>(); A.row_start = h->d_row_start.as<int>();
-        A.edge_S = h->d_edge_S.as<int>(); A.rev = h->d_rev.as<int>(); A.edge = h->d_edge.as<float4>();
-        A.hits = hits_buf; A.hits_stride = hits_stride; A.cap_per_atom = cap; A.rc2 = rc * rc;
-        A.e_atom = h->d_pot_ea.as<double>(); A.forces = h->d_pot_f.as<double>(); A.energy = h->d_pot_e.as<double>();
+        CmCommon A = cm_batch_args(h, fixed, hits_buf, hits_stride, cap, rc, flags, n_evals);
         A.max_iter = cp->max_iter; A.max_eval = cp->max_eval; A.etol = cp->etol; A.ftol = cp->ftol; A.dmax = cp->dmax;
         A.x0 = W.x0; A.hh = W.hh; A.gg = W.gg;
-        A.st = W.st; A.active = h->d_active.as<unsigned char>(); A.flags = flags; A.n_evals = n_evals;
+        A.st = W.st;
         A.max_launch = (long long)cp->max_eval + 72;   // the lock-step driver's launch budget (relax_cg.hip), per chain here
         if (int e = cm_launch_kind(h, d_args, A)) return e;
         ++h->relax_lockstep;
@@ -469,6 +555,71 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
     h->h_counters[2] = 0;      // (no batch-wide neighbor build ran: nothing for vssr_synchronize to repair)
     h->ran = true;
     h->graph_partial = true;   // (the rows are numbered per chain: the batch-wide introspection calls want one plain run first)
+    return VSSR_OK;
+}
+
+// ---- the integrator's host side ---------------------------------------------------------------------------------------------------
+// RESIDENT applies where the kernel does.  AUTO covers the regime that was measured (Langevin MD of the relaxed 48-atom GaN Tersoff
+// chains, chain-steps/s, lock-step against chain-resident alternating in one run, profiles/r29/NOTES_md.md: the chain-resident kernel
+// wins at 256 chains and loses from 1 024 chains on, for the reason given at chain_min_supported): Tersoff batches of <= 256 chains of
+// <= 64 atoms take the chain-resident kernel, everything else the lock-step driver.
+bool chain_md_supported(const vssr_handle *h) {
+    if (!cm_capable(h) || h->md_driver == VSSR_MD_DRIVER_LOCKSTEP) return false;
+    if (h->md_driver == VSSR_MD_DRIVER_RESIDENT) return true;
+    return h->kind == Kind::TERSOFF && h->n_cfg <= 256 && h->max_cfg_atoms <= 64;
+}
+
+// Same contract as md_lockstep (md.hip): afterwards the batch holds the final positions, d_md_vel the velocities, d_pot_e / _ea / _f the
+// static results of the final state of every chain, the workspace the step counts, stop reasons and thermo records.
+int chain_md(vssr_handle *h, const MdWork &W, uint32_t want) {
+    (void)want;
+    const int B = h->n_cfg, N = h->n_atoms;
+    hipStream_t st = h->stream;
+    if (h->d_cm.ensure(sizeof(int) * ((size_t)B + 8) + 1024) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
+        h->d_wrap.ensure(sizeof(int) * 3 * (size_t)N) || h->d_deg.ensure(sizeof(int) * (size_t)N) ||
+        h->d_row_start.ensure(sizeof(int) * ((size_t)N + B + 1)) || h->d_pot_e.ensure(sizeof(double) * (size_t)B) ||
+        h->d_pot_ea.ensure(sizeof(double) * (size_t)N) || h->d_pot_f.ensure(sizeof(double) * 3 * (size_t)N))
+        return set_err(h, VSSR_E_NOMEM, "chain-resident integrator: out of device memory");
+    void *d_args = h->d_cm.as<char>();   // [arguments (1 KB) | flags [8] | evaluations [B]], as chain_min_cg
+    int *flags = reinterpret_cast<int *>(h->d_cm.as<char>() + 1024), *n_evals = flags + 8;
+    VSSR_HIP(h, hipMemsetAsync(n_evals, 0, sizeof(int) * (size_t)B, st));
+    const CmMd M{W.P, W.V, W.stopped};
+    const double rc = evaluator(h).cutoff(h);
+    int cap = std::max(h->cap_per_atom, h->cm_cap_per_atom);   // (the pools of this driver family grow on their own: chain_min_cg)
+    for (int attempt = 0;; ++attempt) {
+        const long long slots = (long long)N * cap + 64;
+        if (slots > 2147483000LL) return set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots");
+        if (h->slot_cap < slots) h->slot_cap = slots;
+        if (h->d_edge.ensure(sizeof(float4) * h->slot_cap) || h->d_edge_S.ensure(sizeof(int) * h->slot_cap) ||
+            h->d_rev.ensure(sizeof(int) * h->slot_cap))
+            return set_err(h, VSSR_E_NOMEM, "neighbor buffers: out of device memory");
+        unsigned long long *hits_buf = nullptr;
+        const int hits_stride = (h->max_cfg_atoms + 63) & ~63;
+        if (h->max_images <= 64 && (size_t)N * hits_stride * 8 <= ((size_t)1 << 30) && !h->d_hits.ensure((size_t)N * hits_stride * 8))
+            hits_buf = h->d_hits.as<unsigned long long>();
+        VSSR_HIP(h, hipMemsetAsync(flags, 0, sizeof(int) * 8, st));
+        const CmCommon A = cm_batch_args(h, W.fixed, hits_buf, hits_stride, cap, rc, flags, n_evals);
+        if (int e = cm_launch_kind(h, d_args, A, &M)) return e;
+        ++h->relax_lockstep;
+        int over = 0;
+        VSSR_HIP(h, hipMemcpyAsync(&over, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+        VSSR_HIP(h, hipStreamSynchronize(st));
+        if (!over) break;
+        // a chain needed more slots per atom than its pool holds: it kept its state (nothing is stepped on an overflowed evaluation)
+        // and resumes from its own step counter in the next launch
+        if (attempt >= 10) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
+        cap *= 2;
+        ++h->relax_regrows;
+    }
+    h->cm_cap_per_atom = cap;
+    std::vector<int> ne(B);
+    VSSR_HIP(h, hipMemcpyAsync(ne.data(), n_evals, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+    VSSR_HIP(h, hipStreamSynchronize(st));
+    long long tot = 0;
+    for (int b = 0; b < B; ++b) tot += ne[b];
+    h->relax_chain_evals = tot;
+    h->active_mask = nullptr;
+    h->h_counters[2] = 0;      // (no batch-wide neighbor build ran: nothing for vssr_synchronize to repair)
     return VSSR_OK;
 }
 

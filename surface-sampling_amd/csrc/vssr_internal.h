@@ -407,6 +407,12 @@ struct vssr_handle {
     int cg_driver = 0;            // VSSR_CG_DRIVER_*: the handle's choice of CG driver (vssr_batch_relax_cg_driver; 0 = automatic)
     int cg_last_driver = 0;       // the driver the last vssr_batch_relax_cg ran: 0 none yet, 1 lock-step, 2 chain-resident
     bool cap_tight = false;       // regrow to the exact need only (tests: forces repeated overflows)
+    // molecular dynamics (md.hip): the velocities stay resident between calls and are void after vssr_batch_upload
+    vssr::DevBuf d_md_vel;        // [sum N][3] double, A / fs
+    vssr::DevBuf d_md_aux;        // stop counters | chain ids [B] | thermo records (MdWork, md.hip)
+    bool md_vel_valid = false;
+    int md_driver = 0;            // VSSR_MD_DRIVER_*: the handle's choice of MD driver (vssr_batch_md_driver; 0 = automatic)
+    int md_last_driver = 0;       // the driver the last vssr_batch_md ran: 0 none yet, 1 lock-step, 2 chain-resident
     uint32_t last_want = 0;                       // outputs produced by the last run
     int64_t slot_cap = 0;
     vssr::PinnedInts h_counters; // pinned: [0] total slots, [1] total real edges, [2] overflow flag

@@ -24,6 +24,36 @@ SYMBOLS = (
 ).split()
 ATOMIC_NUMBERS = {s: z for z, s in enumerate(SYMBOLS)}
 
+# Standard atomic weights in amu, indexed by atomic number (IUPAC abridged values; an element without one carries the mass of its
+# longest-lived isotope; index 0, the dummy "X", is 1).  What molecular dynamics takes when neither the caller nor the Atoms object
+# supplies masses (``masses_of``).
+ATOMIC_MASSES = np.array([
+    1.0, 1.008, 4.002602, 6.94, 9.0121831, 10.81, 12.011, 14.007, 15.999, 18.998403163, 20.1797, 22.98976928, 24.305, 26.9815385,
+    28.085, 30.973761998, 32.06, 35.45, 39.948, 39.0983, 40.078, 44.955908, 47.867, 50.9415, 51.9961, 54.938044, 55.845, 58.933194,
+    58.6934, 63.546, 65.38, 69.723, 72.630, 74.921595, 78.971, 79.904, 83.798, 85.4678, 87.62, 88.90584, 91.224, 92.90637, 95.95,
+    97.90721, 101.07, 102.90550, 106.42, 107.8682, 112.414, 114.818, 118.710, 121.760, 127.60, 126.90447, 131.293, 132.90545196,
+    137.327, 138.90547, 140.116, 140.90766, 144.242, 144.91276, 150.36, 151.964, 157.25, 158.92535, 162.500, 164.93033, 167.259,
+    168.93422, 173.054, 174.9668, 178.49, 180.94788, 183.84, 186.207, 190.23, 192.217, 195.084, 196.966569, 200.592, 204.38, 207.2,
+    208.98040, 208.98243, 209.98715, 222.01758, 223.01974, 226.02541, 227.02775, 232.0377, 231.03588, 238.02891, 237.04817,
+    244.06421, 243.06138, 247.07035, 247.07031, 251.07959, 252.0830, 257.09511])
+assert len(ATOMIC_MASSES) == len(SYMBOLS)
+
+
+def masses_of(atoms, masses=None) -> np.ndarray:
+    """Masses [N] in amu of an Atoms-like: ``masses`` where given, else ``atoms.get_masses()`` where the object has it, else the
+    standard atomic weights of its atomic numbers.  ``ValueError`` for a wrong length or a mass that is not finite and positive."""
+    if masses is not None:
+        m = np.asarray(masses, dtype=np.float64).reshape(-1)
+    elif hasattr(atoms, "get_masses"):
+        m = np.asarray(atoms.get_masses(), dtype=np.float64).reshape(-1)
+    else:
+        m = ATOMIC_MASSES[np.asarray(atoms.get_atomic_numbers(), dtype=np.int64)]
+    if len(m) != len(atoms):
+        raise ValueError(f"{len(m)} masses for {len(atoms)} atoms")
+    if not (np.isfinite(m).all() and (m > 0).all()):
+        raise ValueError("masses must be finite and positive")
+    return np.ascontiguousarray(m, dtype=np.float64)
+
 
 @dataclass
 class Structure:
