@@ -312,6 +312,56 @@ int vssr_batch_md(vssr_handle *h, const vssr_md_params *p, const double *mass /*
                   double *thermo /*[n_steps / thermo_interval + 1][B][2]*/, int32_t *n_done, int32_t *stop_reason);
 int vssr_batch_md_driver(vssr_handle *h, int32_t driver, int32_t *last_used);
 
+/* ---- harmonic vibrations of the resident batch (csrc/vib.hip, csrc/jacobi_dev.h) ----
+ * Finite-difference Hessian, modes, zero-point energy and vibrational Helmholtz energy of every structure of the resident batch, on
+ * every handle kind that evaluates (PaiNN: fp32 ensemble-mean forces widened to fp64; Tersoff, SW, EAM / ADP, Vashishta and pair
+ * handles with and without k-space: their fp64 forces).  What ASE's Vibrations (+ HarmonicThermo.get_helmholtz_energy minus the
+ * potential energy) does with 6 n serial evaluations and a host eigh; restated from ASE as remembered, NOT pinned by an executed ASE.
+ * The numpy restatement is tests/vib_oracle.py.
+ * GROUPS AND REPLICAS.  A group is one structure, resident as n_rep[g] >= 1 identical consecutive chains (n_rep NULL: every chain is
+ * its own group, n_groups = B).  Its m = 3 (vib atoms) degrees of freedom are numbered by (vib atom in chain order, x / y / z); the
+ * replica of rank k works through the degrees of freedom r = k (mod n_rep[g]), replicas beyond m stay idle, so one structure's
+ * displacements fill the batch.  Replicas must agree bit for bit in atom count, species, cell, pbc, masses, vib mask and positions.
+ * Every displacement is one lock-step evaluation of the whole batch: nfree (largest share of a replica) + 1 evaluations, the last
+ * at x0 over all chains, so download, vssr_batch_results_f64, vssr_batch_stress and vssr_batch_stats work at once afterwards and the
+ * positions equal the input bit for bit (a displaced coordinate is x0 + k delta, k = -1, +1 or -2, -1, +1, +2, from a saved copy).
+ * ROWS.  With F(s) the forces at displacement s delta of degree of freedom r, restricted to the vib atoms and flattened:
+ *   nfree = 2: row = 0.5 (F(-1) - F(+1));  nfree = 4: row = (-F(-2) + 8 F(-1) - 8 F(+1) + F(+2)) / 12;  row /= 2 delta;
+ * VSSR_VIB_FREDERIKSEN: before use, the force on the displaced atom is replaced by itself minus the sum of the forces over all atoms
+ * of the chain (vib or not, in atom order).  Then H <- H + H^T: `hessian` [G][ld][ld] in eV / A^2.
+ * MODES.  A = D H D, D = diag(mass^-1/2) per component; fp64 cyclic Jacobi, one workgroup per group; eigenvalues w2 ascending;
+ * energies[k] = sign(w2) s sqrt(|w2|) eV with s = hbar 1e10 / sqrt(e amu) = 0.0646541513... (CODATA 2018: hbar = 1.054571817e-34,
+ * e = 1.602176634e-19, amu = 1.66053906660e-27); a negative entry is an imaginary mode.  modes [G][ld][ld]: row k is the unit
+ * eigenvector of A (mass-weighted, ASE's modes[k]), signed so that its largest-magnitude entry (the first on ties) is positive.
+ * Entries beyond a group's m in the padded outputs are left untouched.
+ * THERMO.  thermo[g] = (E_pot(x0), zpe, f_vib); over the modes with energy > e_min (imaginary ones are never in):
+ *   zpe = 1/2 sum e_k;  f_vib = sum [e_k / 2 + kT log1p(-exp(-e_k / kT))], kB = 8.617333262e-5 eV / K;  T = 0: f_vib = zpe.
+ * info[g] = (m, modes with w2 < 0, modes left out of the sums, stop reason): 1 done; 2 a non-finite energy or force was met at some
+ * displacement (the group's energies, hessian, modes, zpe and f_vib are NaN, other groups are unaffected); 3 the Jacobi hit its sweep
+ * limit (outputs are what it had).  One group's failure is never an error of the call.  A group with m = 0 has empty outputs.
+ * There is no FixAtoms mask: forces are the raw forces, and a caller who wants ASE-with-FixAtoms behaviour leaves held atoms out of
+ * `vib`.  The same call twice gives the same bits.  energies, hessian, modes, thermo, info may each be NULL.
+ * VSSR_E_BADARG (with a message, before anything moves; the handle stays usable): p or mass NULL, nfree not 2 or 4, an unknown
+ * method, delta not finite or <= 0, a mass not finite or <= 0, a negative or non-finite temperature or e_min, n_rep not summing to B
+ * or holding a value < 1, n_groups != B with n_rep NULL, replicas that differ, a group with m > 256 (85 vib atoms), ld < max m.
+ * VSSR_E_STATE before vssr_batch_upload.
+ * Out of scope: a chain-resident driver, infrared intensities, more than 256 degrees of freedom per structure, projection of
+ * rotations / translations, live-chain compaction. */
+enum { VSSR_VIB_STANDARD = 0, VSSR_VIB_FREDERIKSEN = 1 };
+typedef struct {
+    int32_t nfree;        /* 2 (central) or 4 (five-point) */
+    int32_t method;       /* VSSR_VIB_* */
+    double delta;         /* A; ASE default 0.01 */
+    double temperature;   /* K, >= 0 */
+    double e_min;         /* eV, >= 0: modes with energy <= e_min (imaginary ones included) stay out of zpe / f_vib */
+} vssr_vib_params;
+int vssr_batch_vibrations(vssr_handle *h, const vssr_vib_params *p, const double *mass /*[sum N] amu*/,
+                          const uint8_t *vib /*[sum N] 1 = atom is displaced and its force rows are read; NULL = all*/,
+                          const int32_t *n_rep /*[G], sum = B: consecutive chains that are replicas of one structure; NULL: G = B*/,
+                          int32_t n_groups, int32_t ld, uint32_t want,
+                          double *energies /*[G][ld]*/, double *hessian /*[G][ld][ld]*/, double *modes /*[G][ld][ld]*/,
+                          double *thermo /*[G][3]*/, int32_t *info /*[G][4]*/);
+
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
  * vssr_profile_read synchronises and returns, for each kernel class, the number of launches and

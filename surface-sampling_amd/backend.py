@@ -40,7 +40,7 @@ EXPORTS = (
     "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
     "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
-    "vssr_batch_md_driver",
+    "vssr_batch_md_driver", "vssr_batch_vibrations",
 )
 
 
@@ -165,6 +165,26 @@ def md_thermostat_code(thermostat) -> int:
     if not isinstance(thermostat, str) or thermostat not in MD_THERMOSTATS:
         raise ValueError(f"thermostat {thermostat!r}: one of {', '.join(repr(k) for k in MD_THERMOSTATS)}")
     return MD_THERMOSTATS[thermostat]
+
+
+class VibParams(C.Structure):
+    """vssr_vib_params: A, K, eV; ``method`` one of ``VIB_METHODS``."""
+    _fields_ = [("nfree", C.c_int32), ("method", C.c_int32), ("delta", C.c_double), ("temperature", C.c_double), ("e_min", C.c_double)]
+
+
+VIB_METHODS = {"standard": 0, "frederiksen": 1}
+VIB_STOP_REASONS = {1: "done", 2: "non-finite energy or force at a displacement", 3: "eigen-solver sweep limit"}
+VIB_MAX_DOF = 256        # degrees of freedom per structure the device eigen-solver takes (85 vib atoms)
+# eV per sqrt(eV / A^2 / amu): hbar 1e10 / sqrt(e amu) from the CODATA 2018 values of csrc/md_dev.h and csrc/vib.hip
+VIB_ENERGY_UNIT = 1.054571817e-34 * 1e10 / (1.602176634e-19 * 1.66053906660e-27) ** 0.5
+EV_PER_INV_CM = 1.239841984e-4
+
+
+def vib_method_code(method) -> int:
+    """The VSSR_VIB_* value of ``"standard"`` / ``"frederiksen"``; ``ValueError`` for anything else."""
+    if not isinstance(method, str) or method not in VIB_METHODS:
+        raise ValueError(f"vibrations method {method!r}: one of {', '.join(repr(k) for k in VIB_METHODS)}")
+    return VIB_METHODS[method]
 
 
 # who runs optimizer="BFGSLineSearch" for a calculator: ASE's class on the host, one optimizer per chain ("ase", the default), or the
@@ -316,6 +336,8 @@ def load_library():
     L.vssr_batch_md_get_velocities.argtypes = [vp, dp]
     L.vssr_batch_md_driver.restype = C.c_int
     L.vssr_batch_md_driver.argtypes = [vp, C.c_int32, ip]
+    L.vssr_batch_vibrations.restype = C.c_int
+    L.vssr_batch_vibrations.argtypes = [vp, C.POINTER(VibParams), dp, u8p, ip, C.c_int32, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_eam_create.restype = C.c_int
     L.vssr_eam_create.argtypes = [C.c_int32, C.POINTER(EamGrid), dp, dp, dp, C.POINTER(vp)]
     L.vssr_eam_create_alloy.restype = C.c_int
@@ -718,6 +740,51 @@ class _Handle:
         self.last_md_driver = self.md_driver()
         return {"positions": pos, "velocities": self.get_velocities(), "epot": thermo[:, :, 0].copy(), "ekin": thermo[:, :, 1].copy(),
                 "n_done": done, "stop_reason": why}
+
+    # -- harmonic vibrations -------------------------------------------------------------------------
+    def vibrations(self, masses, vib=None, n_rep=None, delta=0.01, nfree=2, method="standard", temperature=0.0, e_min=0.0, want=WANT_ALL,
+                   return_hessian=False, return_modes=False):
+        """Finite-difference Hessian, modes and thermochemistry of every structure of the resident batch on the device
+        (vssr_batch_vibrations).  ``masses`` [sum N] amu; ``vib`` [sum N] bool, the atoms that are displaced (None: all); ``n_rep`` [G]:
+        consecutive chains that are bit-identical replicas of one structure and share its displacements (None: every chain is its
+        own structure).  ``delta`` in A, ``nfree`` 2 or 4, ``method`` ``"standard"`` / ``"frederiksen"``, ``temperature`` in K; modes
+        with energy <= ``e_min`` eV stay out of the sums.  Returns a dict of per-group lists / arrays: ``energies`` (list of [m], eV,
+        negative = imaginary), ``energy`` / ``zpe`` / ``f_vib`` [G], ``m`` / ``n_imag`` / ``n_left_out`` / ``stop_reason`` [G]
+        (``VIB_STOP_REASONS``), and with the flags ``hessian`` (list of [m, m], eV / A^2) and ``modes`` (list of [m, m], rows =
+        mass-weighted unit eigenvectors).  The batch is back at its input positions, evaluated, afterwards."""
+        N, B = self._n_atoms, self._n_cfg
+        m = self._masses(masses)
+        mask = None
+        if vib is not None:
+            mask = np.ascontiguousarray(np.asarray(vib).astype(bool), dtype=np.uint8).reshape(-1)
+            if mask.size != N:
+                raise ValueError("vib mask does not match the resident batch")
+        if n_rep is None:
+            reps, G = None, B
+        else:
+            reps = np.ascontiguousarray(n_rep, dtype=np.int32).reshape(-1)
+            G = int(reps.size)
+        # ld: the largest m of any chain (a group's m is that of its first chain; a bad n_rep is the library's to refuse)
+        start = self._cfg_start
+        ld = max([3 * (int(start[b + 1] - start[b]) if mask is None else int(np.count_nonzero(mask[start[b]:start[b + 1]]))) for b in range(B)]
+                 + [1])
+        p = VibParams(int(nfree), vib_method_code(method), float(delta), float(temperature), float(e_min))
+        en = np.full((G, ld), np.nan)
+        H = np.full((G, ld, ld), np.nan) if return_hessian else None
+        V = np.full((G, ld, ld), np.nan) if return_modes else None
+        th, info = np.zeros((G, 3), np.float64), np.zeros((G, 4), np.int32)
+        self._check(self._lib.vssr_batch_vibrations(self._h, C.byref(p), _ptr(m, C.c_double), _ptr(mask, C.c_uint8), _ptr(reps, C.c_int32), G, ld,
+                                                    int(want), _ptr(en, C.c_double), _ptr(H, C.c_double), _ptr(V, C.c_double),
+                                                    _ptr(th, C.c_double), _ptr(info, C.c_int32)))
+        self.last_relax_counts = self.relax_counts()
+        ms = info[:, 0]
+        out = {"energies": [en[g, :ms[g]].copy() for g in range(G)], "energy": th[:, 0].copy(), "zpe": th[:, 1].copy(), "f_vib": th[:, 2].copy(),
+               "m": ms.copy(), "n_imag": info[:, 1].copy(), "n_left_out": info[:, 2].copy(), "stop_reason": info[:, 3].copy()}
+        if return_hessian:
+            out["hessian"] = [H[g, :ms[g], :ms[g]].copy() for g in range(G)]
+        if return_modes:
+            out["modes"] = [V[g, :ms[g], :ms[g]].copy() for g in range(G)]
+        return out
 
     def relax_counts(self):
         """``(lock-step evaluations, dispatched chain-evaluations)`` of the last relaxation (vssr_batch_relax_counts)."""

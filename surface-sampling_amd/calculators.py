@@ -273,6 +273,97 @@ _MD_DOC = """Molecular dynamics of B independent slabs at once on the device (``
         k = ``thermo_interval``, ``n_done``, ``stop_reason`` (``backend.MD_STOP_REASONS``)."""
 
 
+def _vib_indices(sizes, indices):
+    """Per structure, the sorted atom indices that vibrate: ``indices`` None (all atoms), one index list for every structure, or one
+    list per structure.  ``ValueError`` for an index out of range or a wrong count of lists."""
+    B = len(sizes)
+    if indices is None:
+        per = [np.arange(n) for n in sizes]
+    else:
+        idx = list(indices)
+        nested = len(idx) > 0 and all(hasattr(i, "__len__") for i in idx)
+        if nested and len(idx) != B:
+            raise ValueError(f"vibrations_batch: {len(idx)} index lists for {B} structures")
+        per = [np.asarray(idx[b] if nested else idx, dtype=np.int64).reshape(-1) for b in range(B)]
+    out = []
+    for b, (n, ix) in enumerate(zip(sizes, per)):
+        if ix.size and (ix.min() < -n or ix.max() >= n):
+            raise ValueError(f"vibrations_batch: structure {b} has {n} atoms, index out of range in {ix.tolist()}")
+        out.append(np.unique(ix % n if n else ix))
+    return out
+
+
+# chains ``replicas="auto"`` fills the batch to: every structure is repeated until the batch has about this many chains, never more
+# often than it has degrees of freedom
+VIB_AUTO_CHAINS = 256
+
+
+def _vibrations_batch(get_engine, pack, atoms_list, indices, masses, delta, nfree, method, temperature, e_min, replicas, return_hessian,
+                      return_modes, want):
+    """``vibrations_batch`` of every calculator: the argument checks, then on the calculator's engine (``get_engine()``, not touched
+    before) every structure uploaded as its replicas and ``backend.vibrations``; the per-structure dicts."""
+    backend.vib_method_code(method)   # (ValueError before anything is uploaded)
+    if int(nfree) not in (2, 4):
+        raise ValueError(f"vibrations_batch: nfree {nfree} (2 or 4 wanted)")
+    if not (np.isfinite(float(delta)) and float(delta) > 0):
+        raise ValueError(f"vibrations_batch: delta {delta} > 0 (A) wanted")
+    T = 0.0 if temperature is None else float(temperature)
+    if not (np.isfinite(T) and T >= 0) or not (np.isfinite(float(e_min)) and float(e_min) >= 0):
+        raise ValueError(f"vibrations_batch: temperature {temperature} >= 0 (K) and e_min {e_min} >= 0 (eV) wanted")
+    if replicas != "auto" and (isinstance(replicas, (str, bool)) or int(replicas) != replicas or int(replicas) < 1):
+        raise ValueError(f"vibrations_batch: replicas {replicas!r} ('auto' or an integer >= 1 wanted)")
+    B = len(atoms_list)
+    if masses is not None and len(masses) != B:
+        raise ValueError(f"vibrations_batch: {len(masses)} mass arrays for {B} structures")
+    sizes = [len(a) for a in atoms_list]
+    per = _vib_indices(sizes, indices)
+    ms = [structures.masses_of(a, None if masses is None else masses[b]) for b, a in enumerate(atoms_list)]
+    dof = [3 * len(ix) for ix in per]
+    if max(dof + [0]) > backend.VIB_MAX_DOF:
+        raise ValueError(f"vibrations_batch: {max(dof)} degrees of freedom in one structure (at most {backend.VIB_MAX_DOF}: 85 atoms)")
+    if replicas == "auto":
+        per_struct = max(1, VIB_AUTO_CHAINS // max(B, 1))
+        reps = [max(1, min(per_struct, m)) for m in dof]
+    else:
+        reps = [max(1, min(int(replicas), m)) for m in dof]
+    packs, mass, mask = [], [], []
+    for b, a in enumerate(atoms_list):
+        pk = pack(a)
+        v = np.zeros(sizes[b], np.uint8)
+        v[per[b]] = 1
+        for _ in range(reps[b]):
+            packs.append(pk); mass.append(ms[b]); mask.append(v)
+    eng = get_engine()
+    eng.upload(packs)
+    r = eng.vibrations(np.concatenate(mass), vib=np.concatenate(mask), n_rep=reps, delta=delta, nfree=nfree, method=method, temperature=T,
+                       e_min=e_min, want=want, return_hessian=return_hessian, return_modes=return_modes)
+    out = []
+    for b in range(B):
+        d = {"energies": r["energies"][b], "frequencies": r["energies"][b] / backend.EV_PER_INV_CM, "zpe": float(r["zpe"][b]),
+             "helmholtz_vib": float(r["f_vib"][b]), "n_imag": int(r["n_imag"][b]), "n_left_out": int(r["n_left_out"][b]),
+             "energy": float(r["energy"][b]), "stop_reason": int(r["stop_reason"][b]), "indices": per[b], "replicas": reps[b]}
+        if return_hessian:
+            d["hessian"] = r["hessian"][b]
+        if return_modes:
+            d["modes"] = r["modes"][b]
+        out.append(d)
+    return out
+
+
+_VIB_DOC = """Harmonic vibrations of B structures at once on the device (``backend.vibrations``): what ASE's ``Vibrations(atoms, indices,
+        delta=, nfree=)`` + ``HarmonicThermo.get_helmholtz_energy`` (minus the potential energy) give, with every displacement a
+        lock-step evaluation and the eigen-solve on the device.  ``indices``: the atoms that vibrate, one list for all structures or
+        one per structure (None: all atoms; at most 85 per structure).  Held atoms are simply left out (forces are the raw forces).
+        ``masses``: per structure [N] in amu (None: ``structures.masses_of``).  ``delta`` in A, ``nfree`` 2 or 4, ``method``
+        "standard" / "frederiksen", ``temperature`` in K (None: 0), modes with energy <= ``e_min`` eV (imaginary ones included) stay
+        out of the sums.  ``replicas``: how many identical chains share one structure's displacements -- "auto" fills the batch to
+        about ``VIB_AUTO_CHAINS`` chains, never more replicas than degrees of freedom; an integer forces a count.  Returns per
+        structure a dict: ``energies`` (eV, ascending, negative = imaginary), ``frequencies`` (cm^-1 = energies / 1.239841984e-4),
+        ``zpe``, ``helmholtz_vib``, ``n_imag``, ``n_left_out``, ``energy`` (the potential energy), ``stop_reason``
+        (``backend.VIB_STOP_REASONS``), ``indices``, ``replicas``, and with the flags ``hessian`` (eV / A^2) and ``modes``
+        (mass-weighted unit eigenvectors in rows)."""
+
+
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:
     """bool ``[B]``: the reference's out-of-bounds guard (``mcmc/dynamics.py:159-168``) for every chain of a batch -- a non-finite energy
     or force, ``|E| > e_max``, a force component beyond ``f_max``, or a ``saturated`` evaluation."""
@@ -830,6 +921,13 @@ class EnsembleNFFSurface(_Base):
 
     md_batch.__doc__ = _MD_DOC
 
+    def vibrations_batch(self, atoms_list, indices=None, masses=None, delta: float = 0.01, nfree: int = 2, method: str = "standard",
+                         temperature=None, e_min: float = 0.0, replicas="auto", return_hessian: bool = False, return_modes: bool = False):
+        return _vibrations_batch(self._get_engine, structures.as_arrays, atoms_list, indices, masses, delta, nfree, method, temperature, e_min,
+                                 replicas, return_hessian, return_modes, backend.WANT_ALL)
+
+    vibrations_batch.__doc__ = _VIB_DOC
+
 
 def surface_energy_from_counts(energy, counts: dict, chem_pots: dict, offset_data: dict, offset_units: str = "atomic"):
     """:func:`surface_energy_from_energy` for MANY slabs at once: ``energy`` ``[B]`` and ``counts`` = element symbol ->
@@ -1251,6 +1349,13 @@ class _AnalyticSurfCalc(_Base):
                          backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
 
     md_batch.__doc__ = _MD_DOC
+
+    def vibrations_batch(self, atoms_list, indices=None, masses=None, delta: float = 0.01, nfree: int = 2, method: str = "standard",
+                         temperature=None, e_min: float = 0.0, replicas="auto", return_hessian: bool = False, return_modes: bool = False):
+        return _vibrations_batch(self._get_engine, self._pack, atoms_list, indices, masses, delta, nfree, method, temperature, e_min, replicas,
+                                 return_hessian, return_modes, backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
+
+    vibrations_batch.__doc__ = _VIB_DOC
 
     @staticmethod
     def packed_supported(relax: bool, optimizer) -> bool:

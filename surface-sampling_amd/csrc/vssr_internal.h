@@ -413,6 +413,7 @@ struct vssr_handle {
     bool md_vel_valid = false;
     int md_driver = 0;            // VSSR_MD_DRIVER_*: the handle's choice of MD driver (vssr_batch_md_driver; 0 = automatic)
     int md_last_driver = 0;       // the driver the last vssr_batch_md ran: 0 none yet, 1 lock-step, 2 chain-resident
+    vssr::DevBuf d_vib;           // harmonic vibrations (vib.hip): the call's workspace (VibWork)
     uint32_t last_want = 0;                       // outputs produced by the last run
     int64_t slot_cap = 0;
     vssr::PinnedInts h_counters; // pinned: [0] total slots, [1] total real edges, [2] overflow flag
