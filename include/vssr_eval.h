@@ -362,6 +362,64 @@ int vssr_batch_vibrations(vssr_handle *h, const vssr_vib_params *p, const double
                           double *energies /*[G][ld]*/, double *hessian /*[G][ld][ld]*/, double *modes /*[G][ld][ld]*/,
                           double *thermo /*[G][3]*/, int32_t *info /*[G][4]*/);
 
+/* ---- nudged elastic band over the resident batch (csrc/neb.hip) ----
+ * Minimum-energy paths between minima: the improved-tangent NEB (Henkelman & Jonsson, J. Chem. Phys. 113, 9978 (2000)), ASE's
+ * `aseneb` variant and the climbing image (Henkelman, Uberuaga & Jonsson, J. Chem. Phys. 113, 9901 (2000)), relaxed by ASE's FIRE over
+ * the whole band, on every handle kind that evaluates.  Restated from the papers and from ASE's neb.py / fire.py as remembered, NOT
+ * pinned by an executed ASE: the contract is the numpy restatement tests/neb_oracle.py.  Everything is fp64 (PaiNN: fp32 ensemble-mean
+ * forces widened, the fp64 ensemble-mean energy; the analytic kinds: their fp64 forces, never narrowed).
+ * BANDS.  Band g is n_img[g] >= 3 consecutive chains of the resident batch (its images); bands may differ in length and
+ * sum n_img = B.  The images of a band must agree bit for bit in atom count, species, cell, pbc and fixed mask; only positions differ.
+ * The first and the last image never move, not by a bit; neither does an atom under `fixed` (1 = held, NULL = all free).
+ * DISPLACEMENTS.  d(i) = x(i+1) - x(i) per atom, taken to the nearest image along the periodic axes: with s = d cell^-1 the whole
+ * lattice vectors rint(s_a) (fp64, ties to even) are subtracted from d for every periodic axis a (s - rint(s) transformed back, without
+ * rounding d where nothing wraps).  This is the minimum image while every atom moves less than half the smallest periodic cell height
+ * between neighbouring images; there is no full minimum-image search over skewed cells.  |d| = sqrt(sum over all atoms and components).
+ * NEB FORCE of interior image i from F (the raw forces, held atoms zeroed first), the energies E of the band, t1 = d(i-1), t2 = d(i);
+ * imax = the first interior image of maximal energy:
+ *   VSSR_NEB_IMPROVED_TANGENT  t = t2 if E(i+1) > E(i) > E(i-1); t = t1 if E(i+1) < E(i) < E(i-1); else with dmax / dmin the larger /
+ *     smaller of |E(i+1) - E(i)|, |E(i-1) - E(i)|: t = t2 dmax + t1 dmin if E(i+1) > E(i-1), else t = t2 dmin + t1 dmax.  t <- t / |t|,
+ *     fpar = F.t.  Climbing image (climb = 1 and i = imax): G = F - 2 fpar t; any other: G = F - fpar t + k (|t2| - |t1|) t.
+ *   VSSR_NEB_ASENEB  t = t2 for i < imax, t1 for i > imax, t1 + t2 at imax (not normalised); m = t.t, fpar = F.t.
+ *     Climbing image: G = F - 2 (fpar / m) t; any other: G = F - (fpar / m) t - ((k t1 - k t2).t / m) t.
+ * G of a held atom is then set to zero (the tangent runs over all atoms).  An image whose tangent has zero length (two coincident
+ * images) has G = F, and the band stops with reason 4 unless it has converged as it stands.
+ * OPTIMIZER.  ASE FIRE (dt, maxstep, dtmax, nmin, finc, fdec, astart, fa as vssr_fire_params) on the concatenated interior images of a
+ * band: v.G, G.G, v.v and the maxstep norm |dt v| run over the whole band, (dt, a, Nsteps) are per band.  |dt v| of the new velocity
+ * v' = c1 v + c2 G is formed from the three sums (c1^2 v.v + 2 c1 c2 v.G + c2^2 G.G; all terms >= 0 where c1 != 0).
+ * A STEP OPENS WITH THE TEST, on G of the evaluation of the current positions: 1. a non-finite energy or force in any image of the
+ * band: the band goes back to the positions the step opened at and stops, reason 3 (that step is not counted); 2. max over
+ * interior images and atoms of |G_atom| < fmax: converged, reason 1; 3. a zero tangent: reason 4; 4. steps == max_steps: reason 2;
+ * 5. else the FIRE step.  One band's stop is never an error of the call; the other bands are unaffected.
+ * OUTPUTS (each may be NULL).  pos_out [sum N][3]; energy [B]; neb_force [sum N][3] = G at the last test (zero on end images);
+ * band [G][3] = (fmax at the last test, E(imax) - E(first), E(imax) - E(last)); info [G][4] = (steps taken, stop reason, imax as image
+ * index within the band, 0).  neb_force, band and imax of a band that stopped with reason 3 are unspecified.
+ * Afterwards the batch holds the final positions and a complete evaluation of them over all chains: download,
+ * vssr_batch_results_f64, vssr_batch_stress, vssr_batch_stats and vssr_batch_vibrations work at once.  The same call twice gives the
+ * same bits, and a band gives the same bits alone and inside a larger batch (fixed-order reductions, no floating-point atomics).
+ * VSSR_E_BADARG (with a message, before anything moves; the handle stays usable): p or n_img NULL, n_bands < 1, an n_img entry < 3,
+ * n_img not summing to B, an unknown method, climb not 0 or 1, max_steps < 0, k / fmax / dt / maxstep / dtmax not finite and > 0,
+ * finc < 1, fdec or fa outside (0, 1), astart outside (0, 1], nmin < 0, images of a band that differ in anything but positions.
+ * VSSR_E_STATE before vssr_batch_upload.
+ * Out of scope: other optimizers over the band, IDPP interpolation, free-end / string / `eb` / spline variants, per-spring constants,
+ * dynamic relaxation, a full minimum-image search, removal of rotation and translation, taking the fixed end images out of the
+ * lock-step evaluation. */
+enum { VSSR_NEB_IMPROVED_TANGENT = 0, VSSR_NEB_ASENEB = 1 };
+typedef struct {
+    int32_t max_steps;   /* FIRE steps of a band */
+    int32_t method;      /* VSSR_NEB_* */
+    int32_t climb;       /* 0 / 1: climbing image from the first step */
+    double  k;           /* spring constant, eV / A^2 (ASE default 0.1) */
+    double  fmax;        /* convergence: largest |NEB force| of an atom over the band's interior images */
+    double  dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE FIRE: 0.1 0.2 1.0 1.1 0.5 0.1 0.99 */
+    int32_t nmin;        /* 5 */
+} vssr_neb_params;
+int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const uint8_t *fixed /*[sum N] or NULL*/,
+                   const int32_t *n_img /*[G], each >= 3, sum = B*/, int32_t n_bands, uint32_t want,
+                   double *pos_out /*[sum N][3]*/, double *energy /*[B]*/, double *neb_force /*[sum N][3]*/,
+                   double *band /*[G][3]: fmax at the last test, E_max - E_first, E_max - E_last*/,
+                   int32_t *info /*[G][4]: steps taken, stop reason, imax (image index within the band), 0*/);
+
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
  * vssr_profile_read synchronises and returns, for each kernel class, the number of launches and

@@ -40,7 +40,7 @@ EXPORTS = (
     "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
     "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
-    "vssr_batch_md_driver", "vssr_batch_vibrations",
+    "vssr_batch_md_driver", "vssr_batch_vibrations", "vssr_batch_neb",
 )
 
 
@@ -185,6 +185,32 @@ def vib_method_code(method) -> int:
     if not isinstance(method, str) or method not in VIB_METHODS:
         raise ValueError(f"vibrations method {method!r}: one of {', '.join(repr(k) for k in VIB_METHODS)}")
     return VIB_METHODS[method]
+
+
+class NebParams(C.Structure):
+    """vssr_neb_params: eV / A^2, eV / A; ``method`` one of ``NEB_METHODS``; the FIRE fields as ``FireParams``."""
+    _fields_ = [("max_steps", C.c_int32), ("method", C.c_int32), ("climb", C.c_int32), ("k", C.c_double), ("fmax", C.c_double),
+                ("dt", C.c_double), ("maxstep", C.c_double), ("dtmax", C.c_double), ("finc", C.c_double), ("fdec", C.c_double),
+                ("astart", C.c_double), ("fa", C.c_double), ("nmin", C.c_int32)]
+
+    @classmethod
+    def default(cls, max_steps=100, method="improvedtangent", climb=False, k=0.1, fmax=0.05, dt=0.1, maxstep=0.2, dtmax=1.0, finc=1.1,
+                fdec=0.5, astart=0.1, fa=0.99, nmin=5):
+        if climb not in (False, True, 0, 1):
+            raise ValueError(f"climb {climb!r}: a bool")
+        return cls(int(max_steps), neb_method_code(method), int(bool(climb)), float(k), float(fmax), float(dt), float(maxstep), float(dtmax),
+                   float(finc), float(fdec), float(astart), float(fa), int(nmin))
+
+
+NEB_METHODS = {"improvedtangent": 0, "aseneb": 1}
+NEB_STOP_REASONS = {1: "converged", 2: "max steps", 3: "non-finite energy or force", 4: "zero tangent (coincident images)"}
+
+
+def neb_method_code(method) -> int:
+    """The VSSR_NEB_* value of ``"improvedtangent"`` / ``"aseneb"``; ``ValueError`` for anything else."""
+    if not isinstance(method, str) or method not in NEB_METHODS:
+        raise ValueError(f"NEB method {method!r}: one of {', '.join(repr(k) for k in NEB_METHODS)}")
+    return NEB_METHODS[method]
 
 
 # who runs optimizer="BFGSLineSearch" for a calculator: ASE's class on the host, one optimizer per chain ("ase", the default), or the
@@ -336,6 +362,8 @@ def load_library():
     L.vssr_batch_md_get_velocities.argtypes = [vp, dp]
     L.vssr_batch_md_driver.restype = C.c_int
     L.vssr_batch_md_driver.argtypes = [vp, C.c_int32, ip]
+    L.vssr_batch_neb.restype = C.c_int
+    L.vssr_batch_neb.argtypes = [vp, C.POINTER(NebParams), u8p, ip, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_batch_vibrations.restype = C.c_int
     L.vssr_batch_vibrations.argtypes = [vp, C.POINTER(VibParams), dp, u8p, ip, C.c_int32, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_eam_create.restype = C.c_int
@@ -785,6 +813,29 @@ class _Handle:
         if return_modes:
             out["modes"] = [V[g, :ms[g], :ms[g]].copy() for g in range(G)]
         return out
+
+    # -- nudged elastic band --------------------------------------------------------------------------
+    def neb(self, n_img, fixed=None, k=0.1, climb=False, method="improvedtangent", fmax=0.05, max_steps=100, params=None, want=WANT_ALL):
+        """Relax the bands of the resident batch on the device (vssr_batch_neb): band g is ``n_img[g]`` >= 3 consecutive chains that
+        differ in positions only; its first and last image never move.  ``k`` spring constant in eV / A^2, ``climb`` the climbing
+        image, ``method`` ``"improvedtangent"`` / ``"aseneb"``, ``fmax`` in eV / A on the NEB force, FIRE over the whole band for at
+        most ``max_steps`` steps (``params``: a ``NebParams`` instead of all of these).  Returns dict(positions [sum N, 3], energies
+        [B], neb_forces [sum N, 3], fmax / barrier_forward / barrier_reverse [G] (E_max - E_first, E_max - E_last), n_steps /
+        stop_reason (``NEB_STOP_REASONS``) / imax [G]); ``download()`` / ``results_f64()`` / ``stress()`` / ``vibrations()`` serve the
+        final state at once."""
+        N, B = self._n_atoms, self._n_cfg
+        fx = _fixed_arg(fixed, N)
+        imgs = np.ascontiguousarray(n_img, dtype=np.int32).reshape(-1)
+        G = int(imgs.size)
+        p = params or NebParams.default(max_steps, method, climb, k, fmax)
+        pos, e, F = np.zeros((N, 3), np.float64), np.zeros(B, np.float64), np.zeros((N, 3), np.float64)
+        band, info = np.zeros((max(G, 1), 3), np.float64), np.zeros((max(G, 1), 4), np.int32)
+        self._check(self._lib.vssr_batch_neb(self._h, C.byref(p), _ptr(fx, C.c_uint8), _ptr(imgs, C.c_int32), G, int(want), _ptr(pos, C.c_double),
+                                             _ptr(e, C.c_double), _ptr(F, C.c_double), _ptr(band, C.c_double), _ptr(info, C.c_int32)))
+        self.last_relax_counts = self.relax_counts()
+        return {"positions": pos, "energies": e, "neb_forces": F, "fmax": band[:G, 0].copy(), "barrier_forward": band[:G, 1].copy(),
+                "barrier_reverse": band[:G, 2].copy(), "n_steps": info[:G, 0].copy(), "stop_reason": info[:G, 1].copy(),
+                "imax": info[:G, 2].copy()}
 
     def relax_counts(self):
         """``(lock-step evaluations, dispatched chain-evaluations)`` of the last relaxation (vssr_batch_relax_counts)."""

@@ -364,6 +364,82 @@ _VIB_DOC = """Harmonic vibrations of B structures at once on the device (``backe
         (mass-weighted unit eigenvectors in rows)."""
 
 
+def _neb_batch(get_engine, pack, bands, fixed_indices, k, climb, method, fmax, steps, two_stage, want):
+    """``neb_batch`` of every calculator: the argument checks and the interpolation of ``(initial, final, n_images)`` tuples, then on
+    the calculator's engine (``get_engine()``, not touched before) every band uploaded as consecutive chains and ``backend.neb``
+    (twice for ``two_stage``: the resident band goes on with the climbing image and a fresh FIRE state); the per-band dicts."""
+    backend.neb_method_code(method)   # (ValueError before anything is uploaded)
+    if climb not in (False, True, 0, 1) or two_stage not in (False, True, 0, 1):
+        raise ValueError(f"neb_batch: climb {climb!r} and two_stage {two_stage!r} are bools")
+    if not (np.isfinite(float(k)) and float(k) > 0) or not (np.isfinite(float(fmax)) and float(fmax) > 0):
+        raise ValueError(f"neb_batch: k {k} > 0 (eV / A^2) and fmax {fmax} > 0 (eV / A) wanted")
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 0:
+        raise ValueError(f"neb_batch: steps {steps!r} (an integer >= 0 wanted)")
+    bands = list(bands)
+    if not bands:
+        raise ValueError("neb_batch: no bands")
+    images = []
+    for g, band in enumerate(bands):
+        if isinstance(band, tuple):
+            if len(band) != 3:
+                raise ValueError(f"neb_batch: band {g} is a tuple of {len(band)} entries ((initial, final, n_images) wanted)")
+            band = structures.interpolate_band(band[0], band[1], band[2])
+        band = list(band)
+        if len(band) < 3:
+            raise ValueError(f"neb_batch: band {g} has {len(band)} images (>= 3 wanted)")
+        a0 = structures.as_arrays(band[0])
+        for i, img in enumerate(band[1:], 1):
+            a = structures.as_arrays(img)
+            if len(a[0]) != len(a0[0]) or any(not np.array_equal(u, v) for u, v in ((a[0], a0[0]), (a[2], a0[2]), (a[3], a0[3]))):
+                raise ValueError(f"neb_batch: image {i} of band {g} differs from its first image in more than positions")
+        images.append(band)
+    G = len(images)
+    if fixed_indices is not None and len(fixed_indices) != G:
+        raise ValueError(f"neb_batch: {len(fixed_indices)} index lists for {G} bands")
+    n_img = [len(b) for b in images]
+    flat = [img for b in images for img in b]
+    sizes = [len(img) for img in flat]
+    per_image = None if fixed_indices is None else [fixed_indices[g] for g, b in enumerate(images) for _ in b]
+    if per_image is not None:
+        for n, idx in zip(sizes, per_image):
+            if idx is not None and len(idx) and (np.min(idx) < 0 or np.max(idx) >= n):
+                raise ValueError(f"neb_batch: a fixed index outside 0 .. {n - 1}")
+    fixed = _fixed_mask(sizes, per_image)
+    start = _cfg_start(sizes)
+    eng = get_engine()
+    eng.upload([pack(img) for img in flat])
+    r = eng.neb(n_img, fixed=fixed, k=k, climb=bool(climb) and not two_stage, method=method, fmax=fmax, max_steps=int(steps), want=want)
+    n_steps = r["n_steps"].copy()
+    if two_stage:
+        r = eng.neb(n_img, fixed=fixed, k=k, climb=True, method=method, fmax=fmax, max_steps=int(steps), want=want)
+        n_steps = n_steps + r["n_steps"]
+    out, b = [], 0
+    for g, band in enumerate(images):
+        a0, a1 = int(start[b]), int(start[b + n_img[g]])
+        x = r["positions"][a0:a1].reshape(n_img[g], -1, 3).copy()
+        _, _, cell, pbc = structures.as_arrays(band[0])
+        out.append({"images": x, "energies": r["energies"][b:b + n_img[g]].copy(), "path": structures.band_path(x, cell, pbc),
+                    "neb_forces": r["neb_forces"][a0:a1].reshape(n_img[g], -1, 3).copy(),
+                    "barrier_forward": float(r["barrier_forward"][g]), "barrier_reverse": float(r["barrier_reverse"][g]),
+                    "imax": int(r["imax"][g]), "fmax": float(r["fmax"][g]), "n_steps": int(n_steps[g]),
+                    "stop_reason": int(r["stop_reason"][g]), "converged": int(r["stop_reason"][g]) == 1})
+        b += n_img[g]
+    return out
+
+
+_NEB_DOC = """Nudged elastic bands of G paths at once on the device (``backend.neb``): what ASE's ``NEB(images, k=, climb=, method=)`` with
+        ``FIRE(neb).run(fmax, steps)`` gives, with every image of every band a chain of one lock-step evaluation.  ``bands``: per band
+        a list of >= 3 Atoms-like images that differ in positions only, or a tuple ``(initial, final, n_images)`` that
+        ``structures.interpolate_band`` fills in linearly (displacements wrapped to the nearest image).  The end images never move.
+        ``fixed_indices``: per band, the atom indices FixAtoms holds in every image.  ``k`` in eV / A^2, ``method``
+        "improvedtangent" / "aseneb", ``fmax`` in eV / A on the NEB force, at most ``steps`` FIRE steps.  ``two_stage`` runs
+        ``steps`` without the climbing image and then ``steps`` with it, FIRE restarting as a new ASE optimizer would.  Returns per
+        band a dict: ``images`` [n, N, 3], ``energies`` [n], ``path`` [n] (cumulative |d|, the reaction coordinate),
+        ``neb_forces`` [n, N, 3], ``barrier_forward`` / ``barrier_reverse`` (E_max - E_first / E_last over the interior images),
+        ``imax``, ``fmax``, ``n_steps``, ``stop_reason`` (``backend.NEB_STOP_REASONS``), ``converged``.  The saddle's prefactor side
+        is ``vibrations_batch`` on image ``imax`` (one imaginary mode)."""
+
+
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:
     """bool ``[B]``: the reference's out-of-bounds guard (``mcmc/dynamics.py:159-168``) for every chain of a batch -- a non-finite energy
     or force, ``|E| > e_max``, a force component beyond ``f_max``, or a ``saturated`` evaluation."""
@@ -928,6 +1004,13 @@ class EnsembleNFFSurface(_Base):
 
     vibrations_batch.__doc__ = _VIB_DOC
 
+    def neb_batch(self, bands, fixed_indices=None, k: float = 0.1, climb: bool = False, method: str = "improvedtangent", fmax: float = 0.05,
+                  steps: int = 100, two_stage: bool = False):
+        return _neb_batch(self._get_engine, structures.as_arrays, bands, fixed_indices, k, climb, method, fmax, steps, two_stage,
+                          backend.WANT_ALL)
+
+    neb_batch.__doc__ = _NEB_DOC
+
 
 def surface_energy_from_counts(energy, counts: dict, chem_pots: dict, offset_data: dict, offset_units: str = "atomic"):
     """:func:`surface_energy_from_energy` for MANY slabs at once: ``energy`` ``[B]`` and ``counts`` = element symbol ->
@@ -1356,6 +1439,13 @@ class _AnalyticSurfCalc(_Base):
                                  return_hessian, return_modes, backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
 
     vibrations_batch.__doc__ = _VIB_DOC
+
+    def neb_batch(self, bands, fixed_indices=None, k: float = 0.1, climb: bool = False, method: str = "improvedtangent", fmax: float = 0.05,
+                  steps: int = 100, two_stage: bool = False):
+        return _neb_batch(self._get_engine, self._pack, bands, fixed_indices, k, climb, method, fmax, steps, two_stage,
+                          backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
+
+    neb_batch.__doc__ = _NEB_DOC
 
     @staticmethod
     def packed_supported(relax: bool, optimizer) -> bool:

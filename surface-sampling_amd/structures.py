@@ -140,6 +140,59 @@ def as_arrays(atoms):
 
 
 # --------------------------------------------------------------------------------------
+# Bands of images for the nudged elastic band (backend.neb, calculators.neb_batch)
+# --------------------------------------------------------------------------------------
+def wrap_displacements(d, cell, pbc) -> np.ndarray:
+    """Displacements [N, 3] taken to the nearest image along the periodic axes, by the rule of ``vssr_batch_neb``: with
+    s = d cell^-1, the whole lattice vectors rint(s_a) are subtracted for every periodic axis a.  This is the minimum image while every
+    atom moves less than half the smallest periodic cell height; it is no full minimum-image search over skewed cells."""
+    d = np.array(d, dtype=np.float64).reshape(-1, 3)
+    pbc = np.asarray(pbc).astype(bool).reshape(3)
+    if not pbc.any():
+        return d
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    n = np.rint(d @ np.linalg.inv(cell))
+    n[:, ~pbc] = 0.0
+    return d - n @ cell
+
+
+def interpolate_band(initial, final, n_images: int, mic: bool = True) -> list:
+    """``n_images`` >= 3 copies of ``initial`` from its positions to those of ``final`` (both ends included), linear in the
+    displacement; ``mic`` wraps the displacement by :func:`wrap_displacements` first, so an atom that crosses a periodic face goes
+    the short way.  The images keep the cell, pbc and species of ``initial``; the last image holds ``final`` minus the whole lattice
+    vectors the wrap took off (``final`` itself, bit for bit, where no atom wrapped)."""
+    n_images = int(n_images)
+    if n_images < 3:
+        raise ValueError(f"interpolate_band: {n_images} images (>= 3 wanted)")
+    if len(initial) != len(final) or not np.array_equal(np.asarray(initial.get_atomic_numbers()), np.asarray(final.get_atomic_numbers())):
+        raise ValueError("interpolate_band: the end images differ in their atoms")
+    x0 = np.asarray(initial.get_positions(), dtype=np.float64).reshape(-1, 3)
+    x1 = np.asarray(final.get_positions(), dtype=np.float64).reshape(-1, 3)
+    d = x1 - x0
+    if mic:
+        raw = d
+        d = wrap_displacements(raw, initial.get_cell(), initial.get_pbc())
+        x1 = x1 - (raw - d)
+    out = []
+    for i in range(n_images):
+        img = initial.copy()
+        img.set_positions(x1 if i == n_images - 1 else x0 + d * (i / (n_images - 1)))
+        out.append(img)
+    return out
+
+
+def band_path(positions, cell, pbc) -> np.ndarray:
+    """The reaction coordinate of a band: cumulative |d(i)| [n] in A over images ``positions`` [n, N, 3], with the displacements
+    wrapped as ``vssr_batch_neb`` wraps them and |d| over all atoms and components."""
+    x = np.asarray(positions, dtype=np.float64)
+    out = np.zeros(len(x))
+    for i in range(len(x) - 1):
+        d = wrap_displacements(x[i + 1] - x[i], cell, pbc)
+        out[i + 1] = out[i] + np.sqrt(np.vdot(d, d))
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # CIF (ASE-written, P1, orthorhombic or general angles)
 # --------------------------------------------------------------------------------------
 def read_cif(path: str) -> Structure:
