@@ -420,6 +420,76 @@ int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const uint8_t *fixe
                    double *band /*[G][3]: fmax at the last test, E_max - E_first, E_max - E_last*/,
                    int32_t *info /*[G][4]: steps taken, stop reason, imax (image index within the band), 0*/);
 
+/* ---- dimer method over the resident batch (csrc/dimer.hip) ----
+ * Saddle search from ONE structure by min-mode following: the dimer of Henkelman & Jonsson, J. Chem. Phys. 111, 7010 (1999), with the
+ * one-gradient rotation of Heyden, Bell & Keil, J. Chem. Phys. 123, 224101 (2005) and the force extrapolation of Kaestner & Sherwood,
+ * J. Chem. Phys. 128, 014106 (2008), translated by ASE's FIRE as vssr_batch_neb restates it, on every handle kind that evaluates.
+ * Restated from the three papers; it is NOT ASE's MinModeTranslate and is not pinned by any executed library: the contract is the
+ * numpy restatement tests/dimer_oracle.py.  Everything is fp64 (PaiNN: fp32 ensemble-mean forces widened, the fp64 ensemble-mean
+ * energy; the analytic kinds: their fp64 forces, never narrowed).
+ * DIMERS.  The batch holds B = 2 G chains; dimer g is chain 2 g (the midpoint x0) and chain 2 g + 1 (the moving end x1 = x0 + delta N).
+ * The two chains must agree bit for bit in atom count, species, cell, pbc and fixed mask.  The uploaded positions of chain 2 g + 1 are
+ * ignored and overwritten.  mode_in / mode_out are laid out like the batch; their rows of the odd chains are not read and are zero
+ * on output.  An atom under `fixed` (1 = held, NULL = all free) never moves in chain 2 g, and chain 2 g + 1 holds it where chain 2 g does.
+ * MODE.  N is a unit vector over the 3 n components of the dimer's free atoms, zero on held atoms.  From mode_in: held rows are
+ * zeroed, then N <- N / sqrt(N.N).  With mode_in NULL: component c of atom i is a standard normal of the Philox generator of
+ * vssr_batch_md (csrc/md_dev.h: chain key from (seed, dimer_id[g]), draw index n = 0, atom i, tag 2 -- MD draws use tags 0 and 1),
+ * then the same; dimer_id NULL means dimer_id[g] = g.  Then x0 <- x0 + displace N, once, before the first evaluation.
+ * Forces below are the raw forces with held atoms zeroed; sums run over all atoms and components of the dimer.
+ * ONE CYCLE.
+ *  1. Evaluation E: chain 2 g at x0, chain 2 g + 1 at x0 + delta N give E0, F0, F1.  C = (F0.N - F1.N) / delta.  The rotation
+ *     counter of this step is 0.
+ *  2. Rotation test: Fd = 2 (F1 - F0), Fp = Fd - (Fd.N) N, f = |Fp|, b1 = -f / (2 delta), phi1 = atan(f / (2 delta |C|)) / 2 (IEEE
+ *     division: C = 0 gives pi / 4).  A rotation is made only if the counter is below its limit (max_rot_first before the first
+ *     translation, max_rot before every later one), f > 0 and phi1 >= phi_tol; otherwise go to 4.
+ *  3. Trial rotation: T = Fp / f, N* = N cos phi1 + T sin phi1 (not renormalised).  Evaluation R: chain 2 g + 1 at x0 + delta N*;
+ *     chain 2 g is evaluated again at x0, its result is ignored and F0, E0 of evaluation E are kept.  With F1* of evaluation R:
+ *     C1 = (F0.N* - F1*.N*) / delta, a1 = (C - C1 + b1 sin 2 phi1) / (1 - cos 2 phi1), a0 = 2 (C - a1), phim = atan(b1 / a1) / 2 (IEEE
+ *     division), Cm = a0 / 2 + a1 cos 2 phim + b1 sin 2 phim; if Cm > C: phim += pi / 2 and Cm is formed again.  The end force of the
+ *     rotated dimer is extrapolated, no evaluation is spent on it:
+ *     F1 <- [sin(phi1 - phim) / sin phi1] F1 + [sin phim / sin phi1] F1* + [1 - cos phim - sin phim tan(phi1 / 2)] F0.
+ *     N <- N cos phim + T sin phim, divided by its norm; C <- Cm; counter + 1; back to 2 with the extrapolated F1.
+ *  4. Step test, on F0 of the last evaluation E, in this order: a non-finite energy or force in either chain, at E or at R: x0 and N
+ *     go back to the values the step opened at (those of the input after `displace` before the first translation), chain 2 g + 1 to
+ *     x0 + delta N, the dimer stops with reason 3 and that step is not counted; max over atoms of |F0_atom| < fmax and C < 0:
+ *     reason 1; steps == max_steps: reason 2; otherwise translate.  (The finiteness test stands at the head of every visit.)
+ *  5. Translation: G = F0 - 2 (F0.N) N if C < 0, else G = -(F0.N) N.  One ASE FIRE step on G (dt, maxstep, dtmax, nmin, finc, fdec,
+ *     astart, fa and the rule of vssr_batch_neb, the maxstep clamp on |dt v'| formed from the three sums v.v, v.G, G.G); its state
+ *     (v, dt, a, Nsteps) belongs to the dimer.  steps + 1; evaluation E of the next step at the new x0 with the current N.
+ * OUTPUTS (each may be NULL).  pos_out [sum N][3]; energy [B]; mode_out [sum N][3]; dimer [G][4] = (largest |F0_atom| at the last
+ * step test, curvature C, E0, f = |Fp| at the last rotation test); info [G][4] = (translation steps, stop reason, rotations made,
+ * lock-step evaluations the dimer consumed: its E and R evaluations, the one that showed a non-finite value included; the closing
+ * evaluation of the call is not counted).  dimer [g] of a dimer that stopped with reason 3 is that of its last complete step test.
+ * Afterwards chain 2 g holds x0 and chain 2 g + 1 holds x0 + delta N of the final state, and a complete evaluation of all chains is
+ * resident: download, vssr_batch_results_f64, vssr_batch_stress, vssr_batch_stats and vssr_batch_vibrations work at once.  One
+ * dimer's stop is never an error of the call.  The same call twice gives the same bits, and a dimer gives the same bits alone and
+ * inside a larger batch (fixed-order reductions, no floating-point atomics); dimer_id, not the place in the batch, decides a drawn mode.
+ * VSSR_E_BADARG (with a message, before anything moves; the handle stays usable): p NULL, an odd number of chains, max_steps /
+ * max_rot_first / max_rot / nmin < 0, delta / fmax / dt / maxstep / dtmax not finite and > 0, finc < 1, fdec or fa outside (0, 1),
+ * astart outside (0, 1], phi_tol outside (0, pi / 4], a non-finite displace, a mode_in of zero or non-finite length over a dimer's
+ * free atoms (with mode_in NULL: a dimer without a free atom), the two chains of a dimer differing in anything but positions.
+ * VSSR_E_STATE before vssr_batch_upload.
+ * Out of scope: conjugate-gradient or L-BFGS rotation directions, L-BFGS translation, a central-difference dimer, taking the idle
+ * midpoint out of evaluation R, a cap on the distance travelled, removal of rotation and translation, deduplication of the saddles
+ * found. */
+typedef struct {
+    int32_t max_steps;       /* translation steps of a dimer */
+    int32_t max_rot_first;   /* rotations allowed before the first translation (>= 0) */
+    int32_t max_rot;         /* rotations allowed before every later translation (>= 0) */
+    int32_t nmin;            /* FIRE */
+    double  delta;           /* dimer half-length, A: x1 = x0 + delta N */
+    double  phi_tol;         /* rad: a rotation whose trial angle is below this is not made */
+    double  fmax;            /* eV / A: convergence on the largest |F0| of an atom, with C < 0 */
+    double  displace;        /* A: x0 <- x0 + displace N before the first evaluation (0: none) */
+    double  dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE FIRE, as vssr_neb_params */
+    uint64_t seed;           /* starting modes when mode_in is NULL */
+} vssr_dimer_params;
+int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, const uint8_t *fixed /*[sum N] or NULL*/,
+                     const double *mode_in /*[sum N][3] or NULL*/, const uint64_t *dimer_id /*[G] or NULL: g*/, uint32_t want,
+                     double *pos_out /*[sum N][3]*/, double *energy /*[B]*/, double *mode_out /*[sum N][3]*/,
+                     double *dimer /*[G][4]: fmax at the last test, curvature C, E0, largest |F_perp| seen at the last rotation test*/,
+                     int32_t *info /*[G][4]: translation steps, stop reason, rotations made, lock-step evaluations the dimer took part in*/);
+
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
  * vssr_profile_read synchronises and returns, for each kernel class, the number of launches and

@@ -40,7 +40,7 @@ EXPORTS = (
     "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
     "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
-    "vssr_batch_md_driver", "vssr_batch_vibrations", "vssr_batch_neb",
+    "vssr_batch_md_driver", "vssr_batch_vibrations", "vssr_batch_neb", "vssr_batch_dimer",
 )
 
 
@@ -213,6 +213,25 @@ def neb_method_code(method) -> int:
     return NEB_METHODS[method]
 
 
+class DimerParams(C.Structure):
+    """vssr_dimer_params: A, rad, eV / A; the FIRE fields as ``NebParams``."""
+    _fields_ = [("max_steps", C.c_int32), ("max_rot_first", C.c_int32), ("max_rot", C.c_int32), ("nmin", C.c_int32), ("delta", C.c_double),
+                ("phi_tol", C.c_double), ("fmax", C.c_double), ("displace", C.c_double), ("dt", C.c_double), ("maxstep", C.c_double),
+                ("dtmax", C.c_double), ("finc", C.c_double), ("fdec", C.c_double), ("astart", C.c_double), ("fa", C.c_double),
+                ("seed", C.c_uint64)]
+
+    @classmethod
+    def default(cls, max_steps=100, max_rot_first=8, max_rot=1, delta=0.01, phi_tol=np.pi / 180.0, fmax=0.05, displace=0.0, seed=0, dt=0.1,
+                maxstep=0.2, dtmax=1.0, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, nmin=5):
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed {seed!r}: an integer in [0, 2^64)")
+        return cls(int(max_steps), int(max_rot_first), int(max_rot), int(nmin), float(delta), float(phi_tol), float(fmax), float(displace),
+                   float(dt), float(maxstep), float(dtmax), float(finc), float(fdec), float(astart), float(fa), int(seed))
+
+
+DIMER_STOP_REASONS = {1: "converged", 2: "max steps", 3: "non-finite energy or force"}
+
+
 # who runs optimizer="BFGSLineSearch" for a calculator: ASE's class on the host, one optimizer per chain ("ase", the default), or the
 # lock-step device optimizer (vssr_batch_relax_bfgs_linesearch)
 LINESEARCH_DRIVERS = ("ase", "device")
@@ -364,6 +383,8 @@ def load_library():
     L.vssr_batch_md_driver.argtypes = [vp, C.c_int32, ip]
     L.vssr_batch_neb.restype = C.c_int
     L.vssr_batch_neb.argtypes = [vp, C.POINTER(NebParams), u8p, ip, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
+    L.vssr_batch_dimer.restype = C.c_int
+    L.vssr_batch_dimer.argtypes = [vp, C.POINTER(DimerParams), u8p, dp, C.POINTER(C.c_uint64), C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_batch_vibrations.restype = C.c_int
     L.vssr_batch_vibrations.argtypes = [vp, C.POINTER(VibParams), dp, u8p, ip, C.c_int32, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_eam_create.restype = C.c_int
@@ -836,6 +857,43 @@ class _Handle:
         return {"positions": pos, "energies": e, "neb_forces": F, "fmax": band[:G, 0].copy(), "barrier_forward": band[:G, 1].copy(),
                 "barrier_reverse": band[:G, 2].copy(), "n_steps": info[:G, 0].copy(), "stop_reason": info[:G, 1].copy(),
                 "imax": info[:G, 2].copy()}
+
+    # -- dimer method ------------------------------------------------------------------------------------
+    def dimer(self, fixed=None, modes=None, dimer_id=None, seed=0, max_steps=100, max_rot_first=8, max_rot=1, delta=0.01, phi_tol=np.pi / 180.0,
+              fmax=0.05, displace=0.0, params=None, want=WANT_ALL, **fire):
+        """Saddle searches from the resident batch on the device (vssr_batch_dimer): dimer g is chains 2 g (the midpoint) and 2 g + 1
+        (the moving end, whose uploaded positions are ignored), equal in everything but positions.  ``modes`` [sum N, 3] laid out
+        like the batch (the rows of the odd chains are not read) or None: standard normals keyed by (``seed``, ``dimer_id[g]``, atom,
+        component), ``dimer_id`` defaulting to g.  ``delta`` in A, ``phi_tol`` in rad, ``fmax`` in eV / A on the midpoint force (with a
+        negative curvature), ``displace`` in A along the mode before the first evaluation; ``max_rot_first`` / ``max_rot`` rotations
+        before the first / every later of at most ``max_steps`` FIRE translations; ``fire``: ``dt``, ``maxstep``, ``dtmax``, ``finc``,
+        ``fdec``, ``astart``, ``fa``, ``nmin`` of ASE's FIRE (``params``: a ``DimerParams`` instead of all of these).  Returns
+        dict(positions [sum N, 3], energies [B], modes [sum N, 3] (zero on the odd chains), fmax / curvature / e0 / f_perp [G],
+        n_steps / stop_reason (``DIMER_STOP_REASONS``) / n_rot / n_eval [G]); ``download()`` / ``results_f64()`` /
+        ``stress()`` / ``vibrations()`` serve the final state at once."""
+        N, B = self._n_atoms, self._n_cfg
+        G = B // 2
+        fx = _fixed_arg(fixed, N)
+        m = None
+        if modes is not None:
+            m = np.ascontiguousarray(modes, dtype=np.float64)
+            if m.size != 3 * N:
+                raise ValueError("modes do not match the resident batch ([sum N, 3] wanted)")
+        ids = None
+        if dimer_id is not None:
+            ids = np.ascontiguousarray(dimer_id, dtype=np.uint64).reshape(-1)
+            if ids.size != G:
+                raise ValueError(f"{ids.size} dimer ids for {G} dimers")
+        p = params or DimerParams.default(max_steps, max_rot_first, max_rot, delta, phi_tol, fmax, displace, seed, **fire)
+        pos, e, mode = np.zeros((N, 3), np.float64), np.zeros(B, np.float64), np.zeros((N, 3), np.float64)
+        rec, info = np.zeros((max(G, 1), 4), np.float64), np.zeros((max(G, 1), 4), np.int32)
+        self._check(self._lib.vssr_batch_dimer(self._h, C.byref(p), _ptr(fx, C.c_uint8), _ptr(m, C.c_double), _ptr(ids, C.c_uint64), int(want),
+                                               _ptr(pos, C.c_double), _ptr(e, C.c_double), _ptr(mode, C.c_double), _ptr(rec, C.c_double),
+                                               _ptr(info, C.c_int32)))
+        self.last_relax_counts = self.relax_counts()
+        return {"positions": pos, "energies": e, "modes": mode, "fmax": rec[:G, 0].copy(), "curvature": rec[:G, 1].copy(),
+                "e0": rec[:G, 2].copy(), "f_perp": rec[:G, 3].copy(), "n_steps": info[:G, 0].copy(), "stop_reason": info[:G, 1].copy(),
+                "n_rot": info[:G, 2].copy(), "n_eval": info[:G, 3].copy()}
 
     def relax_counts(self):
         """``(lock-step evaluations, dispatched chain-evaluations)`` of the last relaxation (vssr_batch_relax_counts)."""

@@ -440,6 +440,91 @@ _NEB_DOC = """Nudged elastic bands of G paths at once on the device (``backend.n
         is ``vibrations_batch`` on image ``imax`` (one imaginary mode)."""
 
 
+def _dimer_batch(get_engine, pack, atoms_list, modes, fixed_indices, n_starts, seed, steps, fmax, delta, phi_tol, max_rot_first, max_rot,
+                 displace, want):
+    """``dimer_batch`` of every calculator: the argument checks, then on the calculator's engine (``get_engine()``, not touched before)
+    every structure uploaded ``n_starts`` times as the two chains of a dimer and ``backend.dimer``; the per-search dicts."""
+    def whole(v, name, low):
+        if isinstance(v, bool) or int(v) != v or int(v) < low:
+            raise ValueError(f"dimer_batch: {name} {v!r} (an integer >= {low} wanted)")
+        return int(v)
+
+    n_starts, steps = whole(n_starts, "n_starts", 1), whole(steps, "steps", 0)
+    max_rot_first, max_rot = whole(max_rot_first, "max_rot_first", 0), whole(max_rot, "max_rot", 0)
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"dimer_batch: seed {seed!r} (an integer in [0, 2^64) wanted)")
+    for name, v in (("fmax (eV / A)", fmax), ("delta (A)", delta)):
+        if not (np.isfinite(float(v)) and float(v) > 0):
+            raise ValueError(f"dimer_batch: {name} {v} (finite and > 0 wanted)")
+    if not 0.0 < float(phi_tol) <= np.pi / 4:
+        raise ValueError(f"dimer_batch: phi_tol {phi_tol} rad outside (0, pi / 4]")
+    if not np.isfinite(float(displace)):
+        raise ValueError(f"dimer_batch: displace {displace} A is not finite")
+    atoms_list = list(atoms_list)
+    S = len(atoms_list)
+    if not S:
+        raise ValueError("dimer_batch: no structures")
+    if fixed_indices is not None and len(fixed_indices) != S:
+        raise ValueError(f"dimer_batch: {len(fixed_indices)} index lists for {S} structures")
+    if modes is not None and (len(modes) != S or n_starts != 1):
+        raise ValueError(f"dimer_batch: modes are one [n, 3] array per structure ({S}) and go with n_starts = 1")
+    sizes = [len(a) for a in atoms_list]
+    free = []
+    for i, n in enumerate(sizes):
+        idx = None if fixed_indices is None else fixed_indices[i]
+        m = np.ones(n, bool)
+        if idx is not None and len(idx):
+            if np.min(idx) < 0 or np.max(idx) >= n:
+                raise ValueError(f"dimer_batch: a fixed index outside 0 .. {n - 1}")
+            m[np.asarray(idx, int)] = False
+        if not m.any():
+            raise ValueError(f"dimer_batch: structure {i} has no free atom to carry a mode")
+        if modes is not None:
+            v = np.asarray(modes[i], np.float64)
+            if v.shape != (n, 3):
+                raise ValueError(f"dimer_batch: mode {i} has shape {v.shape} ([{n}, 3] wanted)")
+            nn = float((v[m] ** 2).sum())
+            if not (np.isfinite(nn) and nn > 0):
+                raise ValueError(f"dimer_batch: mode {i} has no finite length over the free atoms")
+        free.append(m)
+    # structure i as searches i n_starts .. (i + 1) n_starts - 1, each two chains; dimer ids 0 .. n_starts - 1 per structure
+    flat_sizes = [n for n in sizes for _ in range(2 * n_starts)]
+    per_chain = None if fixed_indices is None else [fixed_indices[i] for i in range(S) for _ in range(2 * n_starts)]
+    fixed = _fixed_mask(flat_sizes, per_chain)
+    start = _cfg_start(flat_sizes)
+    mode_in = None
+    if modes is not None:
+        mode_in = np.vstack([np.vstack([np.asarray(modes[i], np.float64), np.zeros((sizes[i], 3))]) for i in range(S)])
+    ids = np.tile(np.arange(n_starts, dtype=np.uint64), S)
+    eng = get_engine()
+    eng.upload([pack(a) for a in atoms_list for _ in range(2 * n_starts)])
+    r = eng.dimer(fixed=fixed, modes=mode_in, dimer_id=ids, seed=int(seed), max_steps=steps, max_rot_first=max_rot_first, max_rot=max_rot,
+                  delta=float(delta), phi_tol=float(phi_tol), fmax=float(fmax), displace=float(displace), want=want)
+    out = []
+    for g in range(S * n_starts):
+        a0, a1 = int(start[2 * g]), int(start[2 * g + 1])
+        out.append({"structure": g // n_starts, "dimer_id": int(ids[g]), "positions": r["positions"][a0:a1].copy(),
+                    "mode": r["modes"][a0:a1].copy(), "e0": float(r["e0"][g]), "curvature": float(r["curvature"][g]),
+                    "fmax": float(r["fmax"][g]), "n_steps": int(r["n_steps"][g]), "n_rot": int(r["n_rot"][g]), "n_eval": int(r["n_eval"][g]),
+                    "stop_reason": int(r["stop_reason"][g]), "converged": int(r["stop_reason"][g]) == 1})
+    return out
+
+
+_DIMER_DOC = """Saddle searches from single structures on the device (``backend.dimer``): the dimer method (min-mode following) with one
+        gradient per rotation and ASE's FIRE for the translation, every search two chains of one lock-step evaluation.  Every
+        structure of ``atoms_list`` is searched ``n_starts`` times, start k under dimer id k: its starting mode is drawn from
+        (``seed``, k, atom, component), so the starts of a structure differ and a search does not depend on what else is in the
+        call.  ``modes``: one [n, 3] starting mode per structure instead (``n_starts`` = 1).  ``fixed_indices``: per structure, the
+        atom indices FixAtoms holds.  ``fmax`` in eV / A on the midpoint force (with a negative curvature), ``delta`` the dimer
+        half-length in A, ``phi_tol`` in rad, ``max_rot_first`` / ``max_rot`` rotations before the first / every later of at most
+        ``steps`` translations, ``displace`` in A along the mode before the first evaluation.  Returns per search (structure-major)
+        a dict: ``structure``, ``dimer_id``, ``positions`` [n, 3], ``mode`` [n, 3] (unit, zero on held atoms), ``e0``,
+        ``curvature`` (eV / A^2 along the mode), ``fmax``, ``n_steps``, ``n_rot``, ``n_eval``, ``stop_reason``
+        (``backend.DIMER_STOP_REASONS``), ``converged``.  A converged search is a first-order saddle if ``vibrations_batch`` on
+        ``positions`` finds one imaginary mode; several starts may find the same saddle (no deduplication).  Restated from the
+        papers, not ASE's ``MinModeTranslate``."""
+
+
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:
     """bool ``[B]``: the reference's out-of-bounds guard (``mcmc/dynamics.py:159-168``) for every chain of a batch -- a non-finite energy
     or force, ``|E| > e_max``, a force component beyond ``f_max``, or a ``saturated`` evaluation."""
@@ -1011,6 +1096,13 @@ class EnsembleNFFSurface(_Base):
 
     neb_batch.__doc__ = _NEB_DOC
 
+    def dimer_batch(self, atoms_list, modes=None, fixed_indices=None, n_starts: int = 1, seed: int = 0, steps: int = 100, fmax: float = 0.05,
+                    delta: float = 0.01, phi_tol: float = np.pi / 180.0, max_rot_first: int = 8, max_rot: int = 1, displace: float = 0.0):
+        return _dimer_batch(self._get_engine, structures.as_arrays, atoms_list, modes, fixed_indices, n_starts, seed, steps, fmax, delta, phi_tol,
+                            max_rot_first, max_rot, displace, backend.WANT_ALL)
+
+    dimer_batch.__doc__ = _DIMER_DOC
+
 
 def surface_energy_from_counts(energy, counts: dict, chem_pots: dict, offset_data: dict, offset_units: str = "atomic"):
     """:func:`surface_energy_from_energy` for MANY slabs at once: ``energy`` ``[B]`` and ``counts`` = element symbol ->
@@ -1446,6 +1538,13 @@ class _AnalyticSurfCalc(_Base):
                           backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
 
     neb_batch.__doc__ = _NEB_DOC
+
+    def dimer_batch(self, atoms_list, modes=None, fixed_indices=None, n_starts: int = 1, seed: int = 0, steps: int = 100, fmax: float = 0.05,
+                    delta: float = 0.01, phi_tol: float = np.pi / 180.0, max_rot_first: int = 8, max_rot: int = 1, displace: float = 0.0):
+        return _dimer_batch(self._get_engine, self._pack, atoms_list, modes, fixed_indices, n_starts, seed, steps, fmax, delta, phi_tol,
+                            max_rot_first, max_rot, displace, backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
+
+    dimer_batch.__doc__ = _DIMER_DOC
 
     @staticmethod
     def packed_supported(relax: bool, optimizer) -> bool:

@@ -10,7 +10,7 @@ namespace vssr {
 const char *const kKernelClassNames[KC_COUNT] = {
     "neighbor_list", "embed", "message_mlp", "edge_message_fwd", "update_fwd", "readout",
     "update_bwd", "edge_message_bwd", "message_mlp_bwd", "finalize", "tersoff", "layer0_factorised_fwd",
-    "layer0_factorised_bwd", "neb_project", "neb_step"};
+    "layer0_factorised_bwd", "neb_project", "neb_step", "dimer_advance"};
 
 static thread_local std::string g_create_error;   // per thread: handles may be created concurrently (one host thread per engine)
 

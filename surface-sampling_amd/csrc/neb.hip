@@ -24,12 +24,12 @@
 #include <vector>
 
 #include "cg_dev.h"
+#include "neb_dev.h"
 
 namespace vssr {
 
 constexpr int NEB_SLOT = 8;   // doubles per image: v.G, G.G, v.v, max |G_atom|^2, non-finite, zero tangent, 2 spare
 
-struct NebChain { int first, idx, nimg, band; };   // first chain of the band, image index within it, images, band
 struct NebState {   // per chain: every image carries its band's state
     double dt, a;
     int nsteps_pos;  // steps since the last power <= 0 (ASE's Nsteps)
@@ -49,23 +49,6 @@ struct NebView {
     double *band;            // [G][3]
     int *binfo;              // [G][4]
 };
-
-// Images: chain b of index > 0 against the first chain of its band, bit for bit (species, cell, pbc; atom counts and masks were
-// compared on the host).  flag[0] = 1 on any difference.
-__global__ void __launch_bounds__(256)
-k_neb_compare(const NebChain *__restrict__ ch, const int *__restrict__ cfg_start, const int *__restrict__ Z,
-              const unsigned long long *__restrict__ cell, const unsigned char *__restrict__ pbc, int *__restrict__ flag) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const NebChain c = ch[b];
-    if (c.idx == 0) return;
-    const int f = c.first;
-    const int a0 = cfg_start[b], nat = cfg_start[b + 1] - a0, f0 = cfg_start[f];
-    bool diff = false;
-    for (int i = tid; i < nat; i += 256) diff |= Z[a0 + i] != Z[f0 + i];
-    if (tid < 9) diff |= cell[9 * (size_t)b + tid] != cell[9 * (size_t)f + tid];
-    if (tid < 3) diff |= pbc[3 * b + tid] != pbc[3 * f + tid];
-    if (diff) flag[0] = 1;   // (same value from every writer)
-}
 
 __global__ void k_neb_init(int B, double dt0, double astart, NebState *__restrict__ st, unsigned char *__restrict__ active) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;

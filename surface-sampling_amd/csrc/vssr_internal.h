@@ -236,6 +236,7 @@ enum KernelClass {
     KC_L0_BWD,
     KC_NEB_PROJECT,   // nudged elastic band (neb.hip): the tangent / projection kernel
     KC_NEB_STEP,      // and the band-wide FIRE step
+    KC_DIMER,         // dimer method (dimer.hip): the per-dimer state machine behind every evaluation
     KC_COUNT
 };
 extern const char *const kKernelClassNames[KC_COUNT];
@@ -417,6 +418,7 @@ struct vssr_handle {
     int md_last_driver = 0;       // the driver the last vssr_batch_md ran: 0 none yet, 1 lock-step, 2 chain-resident
     vssr::DevBuf d_vib;           // harmonic vibrations (vib.hip): the call's workspace (VibWork)
     vssr::DevBuf d_neb;           // nudged elastic band (neb.hip): NEB forces, per-image partial sums, band records (NebWork)
+    vssr::DevBuf d_dimer;         // dimer method (dimer.hip): modes, kept forces, FIRE state, per-dimer records (DimerWork)
     uint32_t last_want = 0;                       // outputs produced by the last run
     int64_t slot_cap = 0;
     vssr::PinnedInts h_counters; // pinned: [0] total slots, [1] total real edges, [2] overflow flag
