@@ -178,6 +178,8 @@ static void read_env_knobs(vssr_handle *h) {
     if (const char *e = getenv("VSSR_EDGE_SUB_CHUNK")) { const int c = atoi(e); if (c >= 8) { h->sub_chunk_fwd = c; h->sub_chunk_bwd = c; } }
     // 0 | 8 | 16: the 4-feature forward class runs the 4-feature kernel, or the 8- / 16-feature kernel in several passes
     if (const char *e = getenv("VSSR_EDGE_FWD_2PASS")) { const int w = atoi(e); h->fwd_two_pass = (w == 8 || w == 16) ? w : w ? 16 : 0; }
+    // workgroups of the persistent 16-wave forward neighbor sum instead of one per CU; 0: one item per workgroup (tests: the second grid)
+    if (const char *e = getenv("VSSR_EDGE_FWD_GRID")) h->edge_fwd_grid = max(atoi(e), 0);
 }
 
 }  // namespace vssr

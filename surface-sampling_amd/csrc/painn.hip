@@ -682,7 +682,7 @@ int painn_run(vssr_handle *h, uint32_t want) {
                 launch_edge_fwd_mfma(st, cls, N, cls_list[cls], h->n_class[cls], M, l, h->max_class_atoms[cls], MW, G, counters,
                                      (int)(h->slot_cap - 1), sv.s_in[l], sv.v_in[l], sv.phi[l], sv.s_msg[l], sv.v_msg[l],
                                      (cls == EDGE_CLASS_FS4 && h->fwd_two_pass) ? h->d_bundle_sub.as<int4>() : (const int4 *)nullptr,
-                                     h->fwd_two_pass, h->sub_chunk_fwd ? h->sub_chunk_fwd : sub_chunk_max(h->fwd_two_pass));
+                                     h->fwd_two_pass, h->sub_chunk_fwd ? h->sub_chunk_fwd : sub_chunk_max(h->fwd_two_pass), h->edge_fwd_grid);
             if (n_gather)
                 hipLaunchKernelGGL(k_edge_fwd<false>, g_atom, blk, 0, st, N, l, MW, G, counters, h->cutoff, h->excl_vol,
                                    h->excl_sigma, h->excl_power, sv.s_in[l], sv.v_in[l], sv.phi[l], sv.s_msg[l],

@@ -124,6 +124,27 @@ __device__ __forceinline__ u32x4 gload_u32x4(const u32x4 *p) {
     return *p;
 #endif
 }
+// A load that is issued where it is written.  The slice loads of a persistent forward workgroup have to be under way BEFORE the barrier
+// behind which their values are used; written as plain loads from `const __restrict__` memory the compiler sinks them to that use,
+// behind the barrier (seen in the ISA).  So the instruction comes from an asm, and the compiler's wait counts do not know it: the
+// value must not be touched (not even copied) before gload_arrived() has drained the wave's vector-memory queue.  The compiler's waits for
+// its own loads stay sufficient with these in the queue: they are older, and vmcnt retires in order.
+__device__ __forceinline__ f32x4 gload_early(const float *p) {
+    f32x4 v;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p));
+#else
+    v = *reinterpret_cast<const f32x4 *>(p);
+#endif
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void gload_arrived(f32x4 (&v)[N]) {
+    static_assert(N == 7, "one float4 per staged segment");
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]));
+#endif
+}
 // D += W . rho for one 16 x 16 tile
 __device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 acc) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
@@ -273,7 +294,7 @@ template <int NF> __device__ __forceinline__ constexpr int sec_reg(int sec, int 
 // switches to the centre's bundle, one bundle ahead of its use (SLDS = false: 404 B per atom, <= 405 atoms -- 3 x 2 slabs with
 // adsorbates stay on the 16-feature kernels: 18.8 instead of 22.6 ms / step at 368 .. 392 atoms; 8-feature slices: 208 B, <= 787).
 template <int NF, bool SLDS>
-size_t edge_fwd_lds_bytes_t(int max_atoms) {
+constexpr size_t edge_fwd_lds_bytes_t(int max_atoms) {
     return sizeof(float) * ((size_t)max_atoms * (EdgeGeo<NF>::ROW + (SLDS ? EdgeGeo<NF>::FS : 0)) + 4);
 }
 
@@ -406,8 +427,9 @@ struct BundleWalk {
 // XCD-aware 1-D grid: workgroup id -> XCD id % 8 (observed dispatch rule).  All (slice, model) workgroups of one chain get
 // consecutive ids on ONE XCD, so the chain's rho / record tables (~1.3 MB) and its phi / v rows are fetched from HBM once and
 // then served by that XCD's L2.  Returns the chain, or -1 for a workgroup without one; t = (slice, model) index.
-__device__ __forceinline__ int chain_of_workgroup(const GraphView &G, const int *__restrict__ list, int n_list, int per_chain, int &t) {
-    const int wg = blockIdx.x, xcd = wg & 7, rest = wg >> 3;
+// (wg: the workgroup id, or the virtual id of an item of a persistent workgroup -- its grid is a multiple of 8, so id & 7 is still the XCD)
+__device__ __forceinline__ int chain_of_workgroup(const GraphView &G, const int *__restrict__ list, int n_list, int per_chain, int &t, int wg) {
+    const int xcd = wg & 7, rest = wg >> 3;
     t = rest % per_chain;
     const int k = (rest / per_chain) * 8 + xcd;
     if (k >= n_list) return -1;
@@ -432,7 +454,18 @@ template <> struct EdgeOut<true> { typedef float *ptr; };
 
 // (registers: 4 waves per SIMD = 128 everywhere, except the 16-feature multi-pass form, whose extra residual registers need the
 //  256 of an 8-wave workgroup)
-template <int NF, bool SLDS, int WAVES, bool SUB = false>
+// PERSIST (the 16-wave form that owns its CU: nothing else hides its staging): the grid is a multiple of 8 no larger than the CU count
+// and workgroup w takes the items (virtual workgroup ids) w, w + grid, w + 2 grid, ... -- a static stride, the trip count is known at
+// entry and no workgroup ever waits for another.  A wave that leaves its walk issues ALL loads of its threads' share of the next item's
+// slice into the registers its accumulators have just left, then the next walk's weights and bundle entries, while the slower waves
+// of the workgroup are still walking; then a barrier (everybody has finished with the tile), the LDS stores, a second barrier, the
+// first table entries, the walk.  Control flow is uniform: an item without work (inactive chain, padding id) stages nothing and its
+// waves own no bundle, a wave without bundles skips the hot loop, every wave meets every barrier.  Addresses, LDS placement and
+// summation order are those of the one-item kernel this form replaced (the other widths still are one-item kernels): same bits
+// (profiles/r33/NOTES_edge_fwd_persistent.md).
+constexpr int PERSIST_ROUNDS = 2;   // a thread holds one float4 column of up to 2 atoms in flight: 1 024 threads x 2 / 4 columns = 512 atoms
+
+template <int NF, bool SLDS, int WAVES, bool SUB = false, bool PERSIST = false>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu((SUB && NF == 4) ? WAVES / 4 : 4, (SUB && NF == 4) ? WAVES / 4 : 4)))
 k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const int *__restrict__ counters,
                 int zero_slot, int n_models, int max_atoms, const int *__restrict__ list, int n_list,
@@ -442,45 +475,72 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
     using LY = EdgeGeo<NF>;
     constexpr int FS = LY::FS, NSLICE = LY::NSLICE, NT = LY::NT, EDGE_THREADS = 64 * WAVES;
     static_assert(!SUB || !SLDS, "the sub-range form takes its residuals from memory");
+    static_assert(!PERSIST || (SLDS && !SUB), "persistent workgroups: the single-pass form with the residual in LDS");
     extern __shared__ __attribute__((aligned(16))) float tile[];
-    if (counters[2]) return;
-    int t;
-    const int b = chain_of_workgroup(G, list, n_list, NSLICE * n_models, t);
-    if (b < 0) return;
-    const int fs = t % NSLICE, m = t / NSLICE;
-    const int a0 = G.cfg_start[b], Nc = G.cfg_start[b + 1] - a0;
-    const size_t mN = (size_t)m * N;
-    const int tid = threadIdx.x;
-    // staged neighbors: all atoms of the chain, or (SUB) range `pass` of its sub_passes(Nc) ranges
-    int lo = 0, ns = Nc;
-    if constexpr (SUB) {
-        if (pass >= sub_passes(Nc, chunk_max)) return;   // (uniform; this chain needs fewer passes than the launch's largest)
-        const int chunk = sub_chunk(Nc, chunk_max);
-        lo = pass * chunk;
-        ns = min(chunk, Nc - lo);
+    if (counters[2]) return;   // (written by the neighbor build, before this launch: the same answer for every wave of the grid)
+    EPH_INIT
+    // an item's chain: first atom and atom count (none: an inactive chain or a padding id; PERSIST only) and its (slice, model)
+    struct Item { int b, a0, Nc, t; };
+    // PERSIST: chain_of_workgroup and the chain's bounds in two halves, for the item AFTER the current one.  request_next(): behind the
+    // loads of the walk's prologue, no load behind a branch -- the activity flag (a byte: a vector load) and both chain bounds are in
+    // flight together behind the list entry (clamped for a padding id).  arrived(): behind the second barrier, in front of the hot loop,
+    // where the wait for the slice has covered them; the values move to scalar registers there, so that nothing of this is pending
+    // inside the loop.
+    struct Ahead { int t, k, bb, live, s0, s1; };
+    auto request_next = [&](int id) {
+        Ahead q;
+        const int per_chain = NSLICE * n_models, rest = id >> 3;
+        q.t = rest % per_chain;
+        q.k = (rest / per_chain) * 8 + (id & 7);
+        const int kc = min(q.k, n_list - 1);
+        q.bb = list ? list[kc] : kc;
+        // (The three loads take a lane offset of zero that the compiler cannot see through: known to be uniform, their values are
+        //  moved to scalar registers where they are loaded -- a wait for them, and for every older load, on the spot.
+        //  No mask: every chain is live.  Still a load, of a byte that is there: a branch around it makes its merge point wait.)
+        int lane_zero = 0;
+        asm volatile("" : "+v"(lane_zero));
+        q.live = (G.act.mask ? G.act.mask + q.bb : reinterpret_cast<const unsigned char *>(G.cfg_start))[lane_zero];
+        q.s0 = G.cfg_start[q.bb + lane_zero]; q.s1 = G.cfg_start[q.bb + 1 + lane_zero];
+        return q;
+    };
+    auto arrived = [&](const Ahead &q) {
+        Item r;
+        const bool ok = q.k < n_list && (!G.act.mask || __builtin_amdgcn_readfirstlane(q.live));
+        const int s0 = __builtin_amdgcn_readfirstlane(q.s0), s1 = __builtin_amdgcn_readfirstlane(q.s1);
+        r.t = q.t; r.b = ok ? q.bb : -1; r.a0 = ok ? s0 : 0; r.Nc = ok ? s1 - s0 : 0;
+        return r;
+    };
+    int item = blockIdx.x, trips = 1;
+    if constexpr (PERSIST) trips = ((((n_list + 7) / 8) * 8 * NSLICE * n_models) - item + (int)gridDim.x - 1) / (int)gridDim.x;
+    Item cur_item, nxt_item;
+    if constexpr (PERSIST) cur_item = arrived(request_next(item));
+    else {
+        cur_item.b = chain_of_workgroup(G, list, n_list, NSLICE * n_models, cur_item.t, item);
+        if (cur_item.b < 0) return;
+        cur_item.a0 = G.cfg_start[cur_item.b]; cur_item.Nc = G.cfg_start[cur_item.b + 1] - cur_item.a0;
     }
-    const float *res_s = (SUB && pass) ? s_msg : s_in, *res_v = (SUB && pass) ? v_msg : v_in;   // what a centre's sums are added to
-
-    // ---- stage the chain's feature slice: tile[atom][f][seg] ---------------------------------------------------------
-    // NSEG * FS / 4 float4 per atom; loads are issued in batches of 4 per thread before any LDS store so that
-    // the L2 / HBM round trips overlap (one workgroup per CU: nothing else hides them)
-    float *s_tile = tile + (size_t)max_atoms * LY::ROW;                      // [atom][FS] (SLDS only)
-    {
-        constexpr int Q4 = FS / 4;                          // float4 per slice segment
-        constexpr int PER_ATOM = (LY::NSEG + (SLDS ? 1 : 0)) * Q4;   // float4 per atom
-        const int total = ns * PER_ATOM;
-        if constexpr (SUB) {   // the all-zero row behind the staged ones: where slots of the other half point
-            for (int k = tid; k < LY::ROW; k += EDGE_THREADS) tile[(size_t)ns * LY::ROW + k] = 0.f;
+    const int tid = threadIdx.x;
+    for (;;) {
+        const int fs = cur_item.t % NSLICE, m = cur_item.t / NSLICE;
+        [[maybe_unused]] const int b = cur_item.b;
+        const int a0 = cur_item.a0, Nc = cur_item.Nc;
+        const size_t mN = (size_t)m * N;
+        // staged neighbors: all atoms of the chain, or (SUB) range `pass` of its sub_passes(Nc) ranges
+        int lo = 0, ns = Nc;
+        if constexpr (SUB) {
+            if (pass >= sub_passes(Nc, chunk_max)) return;   // (uniform; this chain needs fewer passes than the launch's largest)
+            const int chunk = sub_chunk(Nc, chunk_max);
+            lo = pass * chunk;
+            ns = min(chunk, Nc - lo);
         }
-        auto src_of = [&](int idx) -> const float * {
-            int atom = idx / PER_ATOM, rem = idx - atom * PER_ATOM, seg = rem / Q4, q4 = rem % Q4;
-            const size_t ga = mN + a0 + lo + atom;
-            if (seg == LY::NSEG) return s_in + ga * F + fs * FS + q4 * 4;                  // s slice
-            if (seg < 3) return phi + ga * F3 + seg * F + fs * FS + q4 * 4;                // sections a, b, c
-            return v_in + (ga * 3 + (seg - 3)) * F + fs * FS + q4 * 4;                     // v_x, v_y, v_z
-        };
-        auto put = [&](int idx, const float4 &val) {
-            int atom = idx / PER_ATOM, rem = idx - atom * PER_ATOM, seg = rem / Q4, q4 = rem % Q4;
+        const float *res_s = (SUB && pass) ? s_msg : s_in, *res_v = (SUB && pass) ? v_msg : v_in;   // what a centre's sums are added to
+
+        // ---- stage the chain's feature slice: tile[atom][f][seg] ---------------------------------------------------------
+        // NSEG * FS / 4 float4 per atom; loads are issued in batches of 4 per thread before any LDS store so that
+        // the L2 / HBM round trips overlap (one workgroup per CU: nothing else hides them -- but see PERSIST)
+        float *s_tile = tile + (size_t)max_atoms * LY::ROW;                      // [atom][FS] (SLDS only)
+        constexpr int NSEGS = LY::NSEG + (SLDS ? 1 : 0);                         // segments staged per atom
+        auto put_at = [&](int atom, int seg, int q4, const float4 &val) {
             if (seg == LY::NSEG) {
                 *reinterpret_cast<float4 *>(s_tile + atom * FS + q4 * 4) = val;
             } else {
@@ -488,203 +548,280 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
                 dst[0] = val.x; dst[LY::NSEG] = val.y; dst[2 * LY::NSEG] = val.z; dst[3 * LY::NSEG] = val.w;
             }
         };
-        for (int base = tid; base < total; base += STAGE_BATCH * EDGE_THREADS) {
-            float4 v4[STAGE_BATCH];
-#pragma unroll
-            for (int u = 0; u < STAGE_BATCH; ++u) {
-                const int idx = min(base + u * EDGE_THREADS, total - 1);
-                v4[u] = *reinterpret_cast<const float4 *>(src_of(idx));
+        [[maybe_unused]] f32x4 pre[PERSIST ? PERSIST_ROUNDS : 1][NSEGS];         // PERSIST: the thread's share of the slice, in flight
+        [[maybe_unused]] int tid_i = tid;
+        {
+            constexpr int Q4 = FS / 4;                          // float4 per slice segment
+            constexpr int PER_ATOM = (LY::NSEG + (SLDS ? 1 : 0)) * Q4;   // float4 per atom
+            const int total = ns * PER_ATOM;
+            if constexpr (SUB) {   // the all-zero row behind the staged ones: where slots of the other half point
+                for (int k = tid; k < LY::ROW; k += EDGE_THREADS) tile[(size_t)ns * LY::ROW + k] = 0.f;
             }
+            auto src_of = [&](int idx) -> const float * {
+                int atom = idx / PER_ATOM, rem = idx - atom * PER_ATOM, seg = rem / Q4, q4 = rem % Q4;
+                const size_t ga = mN + a0 + lo + atom;
+                if (seg == LY::NSEG) return s_in + ga * F + fs * FS + q4 * 4;                  // s slice
+                if (seg < 3) return phi + ga * F3 + seg * F + fs * FS + q4 * 4;                // sections a, b, c
+                return v_in + (ga * 3 + (seg - 3)) * F + fs * FS + q4 * 4;                     // v_x, v_y, v_z
+            };
+            auto put = [&](int idx, const float4 &val) {
+                int atom = idx / PER_ATOM, rem = idx - atom * PER_ATOM, seg = rem / Q4, q4 = rem % Q4;
+                put_at(atom, seg, q4, val);
+            };
+            if constexpr (PERSIST) {
+                // The whole share of the thread in flight at once, issued back to back -- by a wave that has just left the previous
+                // item's walk, while the slower waves are still in it.  Same sources and same LDS bytes as above, dealt to the
+                // threads by segment: a thread takes float4 q4 of atom (tid >> 2) + 256 r of EVERY segment, so the segment -- the base
+                // pointer and the row stride -- is a constant of each load and no address needs a division or a branch; always a
+                // load (clamped: the second round of a chain of <= 256 atoms and an item without work re-read one row).  The walk's
+                // own prologue loads (weights, bundle entries) follow below, the two barriers and the LDS stores behind them, in front
+                // of the first table entries (in flight across the stores they cost more registers than there are).
+                // (The thread id passes through an empty asm per item: which atoms a thread stages does not depend on the item, and
+                //  hoisted out of the item loop the addresses' common parts would occupy registers throughout the walk.)
+                // (A walk leaves table entries and a bundle entry in flight that nobody will read.  The explicit wait -- vmcnt(0), the
+                //  other counters untouched -- settles them in front of the slice loads; otherwise the compiler waits for them where it
+                //  recycles their registers, in the middle of these loads, which it cannot see and which that wait would then drain.)
+                static_assert(Q4 == 4 && PER_ATOM / Q4 == NSEGS, "16-feature slices");
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+                asm volatile("" : "+v"(tid_i));
 #pragma unroll
-            for (int u = 0; u < STAGE_BATCH; ++u)
-                if (base + u * EDGE_THREADS < total) put(base + u * EDGE_THREADS, v4[u]);
-        }
-    }
-    __syncthreads();
-
-    const int lane = tid & 63, wave = tid >> 6, p = lane & 15, fq = lane >> 4, e = p & 3;
-    // ---- A operand: fp16 pieces (h, l) of the filter weights carried by tile row p, quarter fq: 2 x 16 B per tile, bias
-    // column included (build_wd16); an empty row of the packed 8-feature tiles is all zero
-    const LayerW &W = MW[m].layer[l];
-    u32x4 wA[NT][2];
+                for (int r = 0; r < PERSIST_ROUNDS; ++r) {
+                    const int i = max(min(tid_i + r * EDGE_THREADS, Q4 * ns - 1), 0);
+                    const size_t ga = mN + a0 + (i >> 2);
+                    const int col = fs * FS + (i & 3) * 4;
 #pragma unroll
-    for (int T = 0; T < NT; ++T) {
-        const int sec = LY::row_section(T, p);
-        const int row = max(sec, 0) * F + fs * FS + LY::row_feature(p);
-        const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(W.wd16) + ((size_t)row * 4 + fq) * 2;
+                    for (int seg = 0; seg < NSEGS; ++seg) {
+                        const float *src = seg == LY::NSEG ? s_in + ga * F : seg < 3 ? phi + ga * F3 + seg * F : v_in + (ga * 3 + (seg - 3)) * F;
+                        pre[r][seg] = gload_early(src + col);
+                    }
+                }
+            } else {
+                for (int base = tid; base < total; base += STAGE_BATCH * EDGE_THREADS) {
+                    float4 v4[STAGE_BATCH];
 #pragma unroll
-        for (int i3 = 0; i3 < 2; ++i3) wA[T][i3] = sec < 0 ? (u32x4){0u, 0u, 0u, 0u} : gload_u32x4(wsrc + i3);
-    }
-
-    // ---- work list: bundles of 4 centres of (nearly) equal slot count, see BundleWalk --------------------------------
-    BundleWalk<EDGE_THREADS / 64> bw;
-    // (SUB, pass >= 1: only the centres with neighbors in that range -- the head of the length-sorted table; the others keep what
-    //  the earlier passes wrote)
-    int n_entries = Nc;   // (an extra early exit here changes the compiler's memory-wait merge at the loop header: measured +5 % on the
-                          //  single-pass reverse kernel; a pass without entries leaves through `bw.nj == 0` like an empty chain)
-    if constexpr (SUB) {
-        if (pass) n_entries = n_entries_tab[(size_t)(pass - 1) * G.n_cfg + b];
-    }
-    bw.init((SUB ? bundle_tab : G.bundle) + a0, n_entries, __builtin_amdgcn_readfirstlane(wave), p >> 2);
-    if (bw.nj == 0) return;   // (no barrier below)
-    float ds[NF], dvx[NF], dvy[NF], dvz[NF];
+                    for (int u = 0; u < STAGE_BATCH; ++u) {
+                        const int idx = min(base + u * EDGE_THREADS, total - 1);
+                        v4[u] = *reinterpret_cast<const float4 *>(src_of(idx));
+                    }
 #pragma unroll
-    for (int r = 0; r < NF; ++r) { ds[r] = 0.f; dvx[r] = 0.f; dvy[r] = 0.f; dvz[r] = 0.f; }
-    const int fcol = fs * FS + NF * fq;            // first of this lane's NF global feature columns
-    // scalar residual of this stream's centre: requested when the wave switches to a bundle (for the bundle after it), used
-    // when that bundle completes -- always a load (clamped row for streams without a centre), like the bundle entries
-    typedef typename FeatVec<NF>::type fres;
-    fres sres_cur, sres_nxt, vres_cur[SUB ? 3 : 1];   // (SUB: the vector residual is requested when its bundle STARTS -- one set of
-                                                       //  registers; a window is several steps long, enough for an L2 round trip)
-    auto load_residual = [&](int cc) {
-        return *reinterpret_cast<const fres *>(res_s + (mN + a0 + min(max(cc, 0), Nc - 1)) * F + fcol);
-    };
-    auto load_residual_v = [&](int cc, int x) {   // (SUB: the centre's own v row may not be among the staged ones)
-        return *reinterpret_cast<const fres *>(res_v + ((mN + a0 + min(max(cc, 0), Nc - 1)) * 3 + x) * F + fcol);
-    };
-    if (!SLDS) { sres_cur = load_residual(bw.cur.x); sres_nxt = load_residual(bw.nxt.x); }
-    if constexpr (SUB) {
-#pragma unroll
-        for (int x = 0; x < 3; ++x) vres_cur[x] = load_residual_v(bw.cur.x, x);
-    }
-
-    // quad-interleaved table (nbr.hip f16_unit): unit = quad * 32 + piece * 16 + fq * 4 + e -> the 4 slot lanes of a quad read
-    // 64 contiguous bytes; exhausted streams read the reserved all-zero quad (filter = 0)
-    const u32x4 *rho_lane = reinterpret_cast<const u32x4 *>(G.rho16) + fq * 4 + e;
-    const int zero_quad = (zero_slot + 1) / 4 - 1;   // zero_slot = capacity - 1; the last complete quad is all zero
-
-    // Two table buffers (rho pieces; they also carry the unit vector and the neighbor id of the slot), one per step parity:
-    // buffer ph is consumed by the step of parity ph and refilled right after that step's MFMAs for the step after next,
-    // so a table load has ~1.6 steps to arrive (L2 / HBM latency is of the order of one step).
-    u32x4 rq[2][2];
-    auto fetch = [&](int buf, int quad_first_slot, bool valid) {   // quad_first_slot: first slot of the stream's quad
-        const u32x4 *rp = rho_lane + (size_t)(unsigned)(valid ? (quad_first_slot >> 2) : zero_quad) * 32;   // (unsigned: no sign extension, one shift-add)
-        rq[buf][0] = rp[0]; rq[buf][1] = rp[16];
-    };
-    {
-        bool v0, v1;
-        const int q0 = bw.quad_ahead(0, v0), q1 = bw.quad_ahead(1, v1);
-        fetch(0, q0, v0);
-        // issue order = consumption order.  Without the barrier the scheduler hoisted the second buffer's loads above the first's in
-        // the forward kernel; seen from the loop header the first buffer was then the YOUNGEST pending load, its wait vmcnt(0), and
-        // -- the header wait being the merge of pre-header and back edge -- every iteration drained the whole prefetch queue.
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(1, q1, v1);
-    }
-
-    // The 4 centres of a bundle complete in the same step: reduce the 4 slot lanes of every quad, add the residual from
-    // the staged slices (no global loads), one vector store per row; all lanes take part.
-    auto flush_bundle = [&]() {
-        quad_sum_n<NF>(ds); quad_sum_n<NF>(dvx); quad_sum_n<NF>(dvy); quad_sum_n<NF>(dvz);
-        const int c = bw.cur.x;
-        if (e == 0 && c >= 0) {
-            const size_t ga = mN + a0 + c;
-            float so[NF], xo[NF], yo[NF], zo[NF];
-            const float *sr = s_tile + c * FS + NF * fq;
-            const float *vc = tile + c * LY::ROW + (NF * fq) * LY::NSEG;
-#pragma unroll
-            for (int r = 0; r < NF; ++r) {
-                so[r] = ds[r] + (SLDS ? sr[r] : sres_cur[r]);
-                xo[r] = dvx[r] + (SUB ? vres_cur[0][r] : vc[r * LY::NSEG + 3]);
-                yo[r] = dvy[r] + (SUB ? vres_cur[SUB ? 1 : 0][r] : vc[r * LY::NSEG + 4]);
-                zo[r] = dvz[r] + (SUB ? vres_cur[SUB ? 2 : 0][r] : vc[r * LY::NSEG + 5]);
+                    for (int u = 0; u < STAGE_BATCH; ++u)
+                        if (base + u * EDGE_THREADS < total) put(base + u * EDGE_THREADS, v4[u]);
+                }
             }
-            store_feat<NF>(s_msg + ga * F + fcol, so);
-            store_feat<NF>(v_msg + (ga * 3 + 0) * F + fcol, xo);
-            store_feat<NF>(v_msg + (ga * 3 + 1) * F + fcol, yo);
-            store_feat<NF>(v_msg + (ga * 3 + 2) * F + fcol, zo);
         }
+        if constexpr (!PERSIST) __syncthreads();
+
+        const int lane = tid & 63, wave = tid >> 6, p = lane & 15, fq = lane >> 4, e = p & 3;
+        // ---- A operand: fp16 pieces (h, l) of the filter weights carried by tile row p, quarter fq: 2 x 16 B per tile, bias
+        // column included (build_wd16); an empty row of the packed 8-feature tiles is all zero
+        const LayerW &W = MW[m].layer[l];
+        u32x4 wA[NT][2];
+#pragma unroll
+        for (int T = 0; T < NT; ++T) {
+            const int sec = LY::row_section(T, p);
+            const int row = max(sec, 0) * F + fs * FS + LY::row_feature(p);
+            const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(W.wd16) + ((size_t)row * 4 + fq) * 2;
+#pragma unroll
+            for (int i3 = 0; i3 < 2; ++i3) wA[T][i3] = sec < 0 ? (u32x4){0u, 0u, 0u, 0u} : gload_u32x4(wsrc + i3);
+        }
+
+        // ---- work list: bundles of 4 centres of (nearly) equal slot count, see BundleWalk --------------------------------
+        BundleWalk<EDGE_THREADS / 64> bw;
+        // (SUB, pass >= 1: only the centres with neighbors in that range -- the head of the length-sorted table; the others keep what
+        //  the earlier passes wrote)
+        int n_entries = Nc;   // (an extra early exit here changes the compiler's memory-wait merge at the loop header: measured +5 % on the
+                              //  single-pass reverse kernel; a pass without entries leaves through `bw.nj == 0` like an empty chain)
+        if constexpr (SUB) {
+            if (pass) n_entries = n_entries_tab[(size_t)(pass - 1) * G.n_cfg + b];
+        }
+        bw.init((SUB ? bundle_tab : G.bundle) + a0, n_entries, __builtin_amdgcn_readfirstlane(wave), p >> 2);
+        if constexpr (!PERSIST) {
+            if (bw.nj == 0) return;   // (no barrier below)
+        }
+        // (PERSIST: a wave without bundles stays for the barriers of the later items: it issues the (clamped, all-zero-quad) prologue
+        //  loads and skips the hot loop)
+        [[maybe_unused]] Ahead ahead;
+        if constexpr (PERSIST) ahead = request_next(item + (int)gridDim.x);   // (past the last item: a padding id)
+        float ds[NF], dvx[NF], dvy[NF], dvz[NF];
 #pragma unroll
         for (int r = 0; r < NF; ++r) { ds[r] = 0.f; dvx[r] = 0.f; dvy[r] = 0.f; dvz[r] = 0.f; }
-    };
-
-    lds_cfloat *trow = lds_base(tile) + (NF * fq) * LY::NSEG;
-    EPH_INIT
-    EPH(0)   // (the prologue is not timed: the clock starts here)
-    while (bw.j < bw.nj) {
+        const int fcol = fs * FS + NF * fq;            // first of this lane's NF global feature columns
+        // scalar residual of this stream's centre: requested when the wave switches to a bundle (for the bundle after it), used
+        // when that bundle completes -- always a load (clamped row for streams without a centre), like the bundle entries
+        typedef typename FeatVec<NF>::type fres;
+        fres sres_cur, sres_nxt, vres_cur[SUB ? 3 : 1];   // (SUB: the vector residual is requested when its bundle STARTS -- one set of
+                                                           //  registers; a window is several steps long, enough for an L2 round trip)
+        auto load_residual = [&](int cc) {
+            return *reinterpret_cast<const fres *>(res_s + (mN + a0 + min(max(cc, 0), Nc - 1)) * F + fcol);
+        };
+        auto load_residual_v = [&](int cc, int x) {   // (SUB: the centre's own v row may not be among the staged ones)
+            return *reinterpret_cast<const fres *>(res_v + ((mN + a0 + min(max(cc, 0), Nc - 1)) * 3 + x) * F + fcol);
+        };
+        if (!SLDS) { sres_cur = load_residual(bw.cur.x); sres_nxt = load_residual(bw.nxt.x); }
+        if constexpr (SUB) {
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {   // two steps per iteration: one table buffer per step parity
-            arrival_fence(rq[ph][0], rq[ph][1]);
-            EPH(1)   // wait for this step's table entries
-            int jn = (int)rq[ph][1][3];           // chain-local neighbor of this lane's slot (last word of the record's unit 1)
-            if constexpr (SUB) {   // staged row of the neighbor, or the zero row for a neighbor of the other half
-                const unsigned jl = (unsigned)(jn - lo);
-                jn = jl < (unsigned)ns ? (int)jl : ns;
-            }
-            if (bw.t == bw.Lc) {   // wave-uniform: the bundle is complete
-                flush_bundle();
-                bw.advance();
-                if (!SLDS) {
-                    sres_cur = sres_nxt;
-                    __builtin_amdgcn_sched_barrier(0);   // the old value leaves its registers before the load that refills them
-                    sres_nxt = load_residual(bw.nxt.x);
-                    if constexpr (SUB) {
-#pragma unroll
-                        for (int x = 0; x < 3; ++x) vres_cur[x] = load_residual_v(bw.cur.x, x);
-                    }
-                }
-                EPH(2)   // bundle completion
-            }
-            // gather this slot's neighbor row: NF features x NSEG values, contiguous in LDS
-            float tv[NF * LY::NSEG];
-            {
-                if constexpr ((NF * LY::NSEG) % 4 == 0) {
-                    lds_cfloat *row = lds_row(trow, jn, LY::ROW);
-#pragma unroll
-                    for (int q = 0; q < NF * LY::NSEG / 4; ++q) {
-                        const f32x4 t4 = lds_read4(row + 4 * q);
-                        tv[4 * q] = t4[0]; tv[4 * q + 1] = t4[1]; tv[4 * q + 2] = t4[2]; tv[4 * q + 3] = t4[3];
-                    }
-                } else {   // 4-feature slices: the lane's six values start 24 fq bytes into the row (8-byte aligned)
-                    lds_cfloat *row = lds_row(trow, jn, LY::ROW);
-#pragma unroll
-                    for (int q = 0; q < NF * LY::NSEG / 2; ++q) {
-                        const f32x2v t2 = lds_read2(row + 2 * q);
-                        tv[2 * q] = t2[0]; tv[2 * q + 1] = t2[1];
-                    }
-                }
-            }
-            // unit vector of this lane's slot: the record's scalar words, all-gathered over the slot's four lanes (slot_scalars)
-            float ux, uy, uz, invd_unused;
-            slot_scalars(take_u(rq[ph][1][2]), ux, uy, uz, invd_unused);   // (moved out first: the buffer must be dead at its refill, see take())
-            u32x4 rb2 = dense_b2(rq[ph][0], rq[ph][1]);   // second B operand
-            mfma_pre_fence(rq[ph][0], rb2);          // gathers are issued before the first MFMA
-            EPH(3)   // gather issue (+ the LDS wait the clock read implies)
-            // ---- filter GEMM  D[tile row][slot] = Wd_ext[row][k] rho[k][slot]  (bias . fc included): 2 instructions per tile ------
-            f32x4 acc[NT];
-            {
-                const u32x4 (*wp[NT])[2], *bp1[NT], *bp2[NT];
-#pragma unroll
-                for (int s2 = 0; s2 < NT; ++s2) { wp[s2] = &wA[s2]; bp1[s2] = &rq[ph][0]; bp2[s2] = &rb2; }
-                filter_tiles_dense<NT>(wp, bp1, bp2, acc);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            EPH(4)   // matrix instructions issued
-            // ---- messages of this lane's slot for its NF features (filter = 0 exactly for pads / foreign slots) ----------
-            auto message = [&](int r) {
-                const float *tr = tv + r * LY::NSEG;
-                const float wa = acc[sec_tile<NF>(0)][sec_reg<NF>(0, r)], wb = acc[sec_tile<NF>(1)][sec_reg<NF>(1, r)],
-                            wc = acc[sec_tile<NF>(2)][sec_reg<NF>(2, r)];
-                ds[r] = fmaf(tr[1], wb, ds[r]);
-                const float mc = tr[2] * wc, ma = tr[0] * wa;
-                dvx[r] = fmaf(mc, ux, dvx[r]); dvy[r] = fmaf(mc, uy, dvy[r]); dvz[r] = fmaf(mc, uz, dvz[r]);
-                dvx[r] = fmaf(ma, tr[3], dvx[r]);
-                dvy[r] = fmaf(ma, tr[4], dvy[r]);
-                dvz[r] = fmaf(ma, tr[5], dvz[r]);
-            };
-            message(0);   // consumes every accumulator tile (NF = 2: wa, wb from tile 0, wc from tile 1)
-            // table entries of the step after next, into the buffer this step has just consumed; see mfma_load_fence
-            bool nv;
-            int nq = bw.quad_ahead(2, nv);
-            mfma_load_fence(nq, ds[0], dvx[0], dvy[0]);
-            EPH(5)   // matrix results arrive + first feature
-            fetch(ph, nq, nv);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int r = 1; r < NF; ++r) message(r);
-            ++bw.t;
-            EPH(6)   // prefetch issue + remaining features
+            for (int x = 0; x < 3; ++x) vres_cur[x] = load_residual_v(bw.cur.x, x);
         }
+
+        // quad-interleaved table (nbr.hip f16_unit): unit = quad * 32 + piece * 16 + fq * 4 + e -> the 4 slot lanes of a quad read
+        // 64 contiguous bytes; exhausted streams read the reserved all-zero quad (filter = 0)
+        const u32x4 *rho_lane = reinterpret_cast<const u32x4 *>(G.rho16) + fq * 4 + e;
+        const int zero_quad = (zero_slot + 1) / 4 - 1;   // zero_slot = capacity - 1; the last complete quad is all zero
+
+        // Two table buffers (rho pieces; they also carry the unit vector and the neighbor id of the slot), one per step parity:
+        // buffer ph is consumed by the step of parity ph and refilled right after that step's MFMAs for the step after next,
+        // so a table load has ~1.6 steps to arrive (L2 / HBM latency is of the order of one step).
+        u32x4 rq[2][2];
+        auto fetch = [&](int buf, int quad_first_slot, bool valid) {   // quad_first_slot: first slot of the stream's quad
+            const u32x4 *rp = rho_lane + (size_t)(unsigned)(valid ? (quad_first_slot >> 2) : zero_quad) * 32;   // (unsigned: no sign extension, one shift-add)
+            rq[buf][0] = rp[0]; rq[buf][1] = rp[16];
+        };
+        if constexpr (PERSIST) {   // the slice into LDS: everybody has left the tile | the loads have arrived, store | the tile is complete
+            __syncthreads();
+            EPH(7)   // end of the previous walk (first item: kernel entry) -> every wave has left the tile
+#pragma unroll
+            for (int r = 0; r < PERSIST_ROUNDS; ++r) gload_arrived(pre[r]);
+            asm volatile("" : "+v"(tid_i));   // (the LDS addresses are formed behind the barrier, not held across it)
+#pragma unroll
+            for (int r = 0; r < PERSIST_ROUNDS; ++r) {
+                const int i = tid_i + r * EDGE_THREADS;
+                if (i < 4 * ns) {
+#pragma unroll
+                    for (int seg = 0; seg < NSEGS; ++seg)
+                        put_at(i >> 2, seg, i & 3, make_float4(pre[r][seg][0], pre[r][seg][1], pre[r][seg][2], pre[r][seg][3]));
+                }
+            }
+            __syncthreads();
+            nxt_item = arrived(ahead);   // (behind the wait for the slice: nothing of the next item is pending inside the hot loop)
+            asm volatile("" : : "s"(nxt_item.a0), "s"(nxt_item.Nc));
+        }
+        {
+            bool v0, v1;
+            const int q0 = bw.quad_ahead(0, v0), q1 = bw.quad_ahead(1, v1);
+            fetch(0, q0, v0);
+            // issue order = consumption order.  Without the barrier the scheduler hoisted the second buffer's loads above the first's in
+            // the forward kernel; seen from the loop header the first buffer was then the YOUNGEST pending load, its wait vmcnt(0), and
+            // -- the header wait being the merge of pre-header and back edge -- every iteration drained the whole prefetch queue.
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(1, q1, v1);
+        }
+
+        // The 4 centres of a bundle complete in the same step: reduce the 4 slot lanes of every quad, add the residual from
+        // the staged slices (no global loads), one vector store per row; all lanes take part.
+        auto flush_bundle = [&]() {
+            quad_sum_n<NF>(ds); quad_sum_n<NF>(dvx); quad_sum_n<NF>(dvy); quad_sum_n<NF>(dvz);
+            const int c = bw.cur.x;
+            if (e == 0 && c >= 0) {
+                const size_t ga = mN + a0 + c;
+                float so[NF], xo[NF], yo[NF], zo[NF];
+                const float *sr = s_tile + c * FS + NF * fq;
+                const float *vc = tile + c * LY::ROW + (NF * fq) * LY::NSEG;
+#pragma unroll
+                for (int r = 0; r < NF; ++r) {
+                    so[r] = ds[r] + (SLDS ? sr[r] : sres_cur[r]);
+                    xo[r] = dvx[r] + (SUB ? vres_cur[0][r] : vc[r * LY::NSEG + 3]);
+                    yo[r] = dvy[r] + (SUB ? vres_cur[SUB ? 1 : 0][r] : vc[r * LY::NSEG + 4]);
+                    zo[r] = dvz[r] + (SUB ? vres_cur[SUB ? 2 : 0][r] : vc[r * LY::NSEG + 5]);
+                }
+                store_feat<NF>(s_msg + ga * F + fcol, so);
+                store_feat<NF>(v_msg + (ga * 3 + 0) * F + fcol, xo);
+                store_feat<NF>(v_msg + (ga * 3 + 1) * F + fcol, yo);
+                store_feat<NF>(v_msg + (ga * 3 + 2) * F + fcol, zo);
+            }
+#pragma unroll
+            for (int r = 0; r < NF; ++r) { ds[r] = 0.f; dvx[r] = 0.f; dvy[r] = 0.f; dvz[r] = 0.f; }
+        };
+
+        lds_cfloat *trow = lds_base(tile) + (NF * fq) * LY::NSEG;
+        EPH(0)   // the prologue; PERSIST: the first barrier -> the walk starts, i.e. the staging that is still exposed
+        while (bw.j < bw.nj) {
+#pragma unroll
+            for (int ph = 0; ph < 2; ++ph) {   // two steps per iteration: one table buffer per step parity
+                arrival_fence(rq[ph][0], rq[ph][1]);
+                EPH(1)   // wait for this step's table entries
+                int jn = (int)rq[ph][1][3];           // chain-local neighbor of this lane's slot (last word of the record's unit 1)
+                if constexpr (SUB) {   // staged row of the neighbor, or the zero row for a neighbor of the other half
+                    const unsigned jl = (unsigned)(jn - lo);
+                    jn = jl < (unsigned)ns ? (int)jl : ns;
+                }
+                if (bw.t == bw.Lc) {   // wave-uniform: the bundle is complete
+                    flush_bundle();
+                    bw.advance();
+                    if (!SLDS) {
+                        sres_cur = sres_nxt;
+                        __builtin_amdgcn_sched_barrier(0);   // the old value leaves its registers before the load that refills them
+                        sres_nxt = load_residual(bw.nxt.x);
+                        if constexpr (SUB) {
+#pragma unroll
+                            for (int x = 0; x < 3; ++x) vres_cur[x] = load_residual_v(bw.cur.x, x);
+                        }
+                    }
+                    EPH(2)   // bundle completion
+                }
+                // gather this slot's neighbor row: NF features x NSEG values, contiguous in LDS
+                float tv[NF * LY::NSEG];
+                {
+                    if constexpr ((NF * LY::NSEG) % 4 == 0) {
+                        lds_cfloat *row = lds_row(trow, jn, LY::ROW);
+#pragma unroll
+                        for (int q = 0; q < NF * LY::NSEG / 4; ++q) {
+                            const f32x4 t4 = lds_read4(row + 4 * q);
+                            tv[4 * q] = t4[0]; tv[4 * q + 1] = t4[1]; tv[4 * q + 2] = t4[2]; tv[4 * q + 3] = t4[3];
+                        }
+                    } else {   // 4-feature slices: the lane's six values start 24 fq bytes into the row (8-byte aligned)
+                        lds_cfloat *row = lds_row(trow, jn, LY::ROW);
+#pragma unroll
+                        for (int q = 0; q < NF * LY::NSEG / 2; ++q) {
+                            const f32x2v t2 = lds_read2(row + 2 * q);
+                            tv[2 * q] = t2[0]; tv[2 * q + 1] = t2[1];
+                        }
+                    }
+                }
+                // unit vector of this lane's slot: the record's scalar words, all-gathered over the slot's four lanes (slot_scalars)
+                float ux, uy, uz, invd_unused;
+                slot_scalars(take_u(rq[ph][1][2]), ux, uy, uz, invd_unused);   // (moved out first: the buffer must be dead at its refill, see take())
+                u32x4 rb2 = dense_b2(rq[ph][0], rq[ph][1]);   // second B operand
+                mfma_pre_fence(rq[ph][0], rb2);          // gathers are issued before the first MFMA
+                EPH(3)   // gather issue (+ the LDS wait the clock read implies)
+                // ---- filter GEMM  D[tile row][slot] = Wd_ext[row][k] rho[k][slot]  (bias . fc included): 2 instructions per tile ------
+                f32x4 acc[NT];
+                {
+                    const u32x4 (*wp[NT])[2], *bp1[NT], *bp2[NT];
+#pragma unroll
+                    for (int s2 = 0; s2 < NT; ++s2) { wp[s2] = &wA[s2]; bp1[s2] = &rq[ph][0]; bp2[s2] = &rb2; }
+                    filter_tiles_dense<NT>(wp, bp1, bp2, acc);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                EPH(4)   // matrix instructions issued
+                // ---- messages of this lane's slot for its NF features (filter = 0 exactly for pads / foreign slots) ----------
+                auto message = [&](int r) {
+                    const float *tr = tv + r * LY::NSEG;
+                    const float wa = acc[sec_tile<NF>(0)][sec_reg<NF>(0, r)], wb = acc[sec_tile<NF>(1)][sec_reg<NF>(1, r)],
+                                wc = acc[sec_tile<NF>(2)][sec_reg<NF>(2, r)];
+                    ds[r] = fmaf(tr[1], wb, ds[r]);
+                    const float mc = tr[2] * wc, ma = tr[0] * wa;
+                    dvx[r] = fmaf(mc, ux, dvx[r]); dvy[r] = fmaf(mc, uy, dvy[r]); dvz[r] = fmaf(mc, uz, dvz[r]);
+                    dvx[r] = fmaf(ma, tr[3], dvx[r]);
+                    dvy[r] = fmaf(ma, tr[4], dvy[r]);
+                    dvz[r] = fmaf(ma, tr[5], dvz[r]);
+                };
+                message(0);   // consumes every accumulator tile (NF = 2: wa, wb from tile 0, wc from tile 1)
+                // table entries of the step after next, into the buffer this step has just consumed; see mfma_load_fence
+                bool nv;
+                int nq = bw.quad_ahead(2, nv);
+                mfma_load_fence(nq, ds[0], dvx[0], dvy[0]);
+                EPH(5)   // matrix results arrive + first feature
+                fetch(ph, nq, nv);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 1; r < NF; ++r) message(r);
+                ++bw.t;
+                EPH(6)   // prefetch issue + remaining features
+            }
+        }
+        if (!PERSIST || --trips == 0) break;
+        cur_item = nxt_item;
+        item += (int)gridDim.x;
     }
     EPH_FLUSH(0)
 }
@@ -735,7 +872,7 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
     extern __shared__ __attribute__((aligned(16))) float tile[];
     if (counters[2]) return;
     int t;
-    const int b = chain_of_workgroup(G, list, n_list, NSG * n_models, t);
+    const int b = chain_of_workgroup(G, list, n_list, NSG * n_models, t, blockIdx.x);
     if (b < 0) return;
     const int fs = t % NSG, m = t / NSG;   // feature slice = partial-gradient group
     const int a0 = G.cfg_start[b], Nc = G.cfg_start[b + 1] - a0;
@@ -1055,11 +1192,16 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
 
 int edge_mfma_init(vssr_handle *h) {
 #define SET_LDS(K) VSSR_HIP(h, hipFuncSetAttribute((const void *)(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-    SET_LDS((k_edge_fwd_mfma<4, true, 16>)); SET_LDS((k_edge_fwd_mfma<4, false, 16>)); SET_LDS((k_edge_fwd_mfma<2, false, 16>)); SET_LDS((k_edge_fwd_mfma<2, false, 16, true>)); SET_LDS((k_edge_fwd_mfma<4, false, SUB16_WAVES, true>));
+    SET_LDS((k_edge_fwd_mfma<4, true, 16, false, true>)); SET_LDS((k_edge_fwd_mfma<4, false, 16>)); SET_LDS((k_edge_fwd_mfma<2, false, 16>)); SET_LDS((k_edge_fwd_mfma<2, false, 16, true>)); SET_LDS((k_edge_fwd_mfma<4, false, SUB16_WAVES, true>));
     SET_LDS((k_edge_fwd_mfma<4, true, 8>)); SET_LDS((k_edge_fwd_mfma<4, true, 4>)); SET_LDS((k_edge_fwd_mfma<1, false, 16>));
     SET_LDS((k_edge_bwd_mfma<1, 4>)); SET_LDS((k_edge_bwd_mfma<1, 8>)); SET_LDS((k_edge_bwd_mfma<2, 4>)); SET_LDS((k_edge_bwd_mfma<2, 8>));
     SET_LDS((k_edge_bwd_mfma<4, 4>)); SET_LDS((k_edge_bwd_mfma<4, 8>)); SET_LDS((k_edge_bwd_mfma<4, 8, true>));
 #undef SET_LDS
+    // grid of the persistent forward form: one workgroup per CU, or what VSSR_EDGE_FWD_GRID caps it at (0: one item per workgroup)
+    int cus = 0;
+    VSSR_HIP(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    if (h->edge_fwd_grid < 0) h->edge_fwd_grid = cus;
+    else if (h->edge_fwd_grid > 0) h->edge_fwd_grid = min(max(h->edge_fwd_grid, 8), cus);
     return VSSR_OK;
 }
 
@@ -1132,7 +1274,8 @@ void launch_edge_bwd_mfma(hipStream_t st, int cls, int N, const int *list, int n
 // 16 or 8 = slice width of the multi-pass form.
 void launch_edge_fwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int max_atoms, const ModelW *MW,
                           const GraphView &G, const int *counters, int zero_slot, const float *s_in, const float *v_in,
-                          const float *phi, float *s_msg, float *v_msg, const int4 *bundle_sub, int sub_width, int sub_chunk) {
+                          const float *phi, float *s_msg, float *v_msg, const int4 *bundle_sub, int sub_width, int sub_chunk,
+                          int persist_grid) {
     if (n_list <= 0) return;
 #define LAUNCH_FWD(NF, SLDS, WAVES)                                                                                                \
     hipLaunchKernelGGL((k_edge_fwd_mfma<NF, SLDS, WAVES>), dim3(((n_list + 7) / 8) * 8 * EdgeGeo<NF>::NSLICE * M), dim3(64 * WAVES), \
@@ -1144,7 +1287,16 @@ void launch_edge_fwd_mfma(hipStream_t st, int cls, int N, const int *list, int n
         const long long wgs = (long long)n_list * EdgeGeo<4>::NSLICE * M;
         if (4 * lds <= 160 * 1024 && wgs > 4 * 256) LAUNCH_FWD(4, true, 4);
         else if (2 * lds <= 160 * 1024 && wgs > 2 * 256) LAUNCH_FWD(4, true, 8);
-        else LAUNCH_FWD(4, true, 16);
+        else {
+            // One workgroup per CU anyway: the 16-wave form is the persistent kernel.  More items than CUs: one workgroup per CU (the grid a
+            // multiple of 8, so that id & 7 stays the XCD) strides over them; otherwise, and with VSSR_EDGE_FWD_GRID=0, one item per
+            // workgroup -- the grid of the one-item form, a single trip through the same code.
+            static_assert(edge_fwd_lds_bytes_t<4, true>(PERSIST_ROUNDS * 64 * 16 / 4) > 160 * 1024, "a slice that fits LDS fits PERSIST_ROUNDS rounds");
+            const long long items = (long long)((n_list + 7) / 8) * 8 * EdgeGeo<4>::NSLICE * M;
+            const int grid = (persist_grid >= 8 && items > persist_grid) ? persist_grid / 8 * 8 : (int)items;
+            hipLaunchKernelGGL((k_edge_fwd_mfma<4, true, 16, false, true>), dim3(grid), dim3(64 * 16), lds, st, N, l, MW, G, counters, zero_slot, M,
+                               max_atoms, list, n_list, s_in, v_in, phi, s_msg, v_msg, (const int4 *)nullptr, (const int *)nullptr, 0, 0);
+        }
     } else if (cls == EDGE_CLASS_FS16M) LAUNCH_FWD(4, false, 16);
     else if (cls == EDGE_CLASS_FS8) LAUNCH_FWD(2, false, 16);
     else if (bundle_sub) {

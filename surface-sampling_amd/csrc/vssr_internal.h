@@ -382,7 +382,9 @@ struct vssr_handle {
     vssr::DevBuf d_bundle_subb;  // per-pass bundle tables of the reverse multi-pass form (its ranges are larger than the forward's)
     int fwd_two_pass = 16;       // VSSR_EDGE_FWD_2PASS = 0 | 8 | 16: chains of 788 .. 1 462 atoms take the 4-feature forward kernel, or the 8- / 16-feature
                                  // kernel in several passes over neighbor sub-ranges
-    vssr::DevBuf d_hits;         // neighbor search: per (centre, candidate) 64-bit hit masks of the counting pass
+    int edge_fwd_grid = -1;      // VSSR_EDGE_FWD_GRID=n: workgroups of the persistent 16-wave forward neighbor sum (edge_mfma_init: the CU count,
+                                 // or n capped by it; a multiple of 8 is used); 0: one item per workgroup
+    vssr::DevBuf d_hits;        // neighbor search: per (centre, candidate) 64-bit hit masks of the counting pass
     // layer-0 species factorisation (painn_l0.hip)
     int l0_enabled = 1, l0_nz = 0;
     bool l0_used = false;                // last run used the factorised layer 0
@@ -643,6 +645,7 @@ void launch_edge_bwd_mfma(hipStream_t st, int cls, int N, const int *list, int n
                           const int4 *bundle_sub, int sub_chunk);
 void launch_edge_fwd_mfma(hipStream_t st, int cls, int N, const int *list, int n_list, int M, int l, int max_atoms, const ModelW *MW,
                           const GraphView &G, const int *counters, int zero_slot, const float *s_in, const float *v_in,
-                          const float *phi, float *s_msg, float *v_msg, const int4 *bundle_sub, int sub_width, int sub_chunk);
+                          const float *phi, float *s_msg, float *v_msg, const int4 *bundle_sub, int sub_width, int sub_chunk,
+                          int persist_grid);   // persist_grid: vssr_handle::edge_fwd_grid
 
 }  // namespace vssr

@@ -32,10 +32,17 @@ if os.environ.get("VSSR_EDGE_BWD_32", "0") != "0":   # the 32x32x16 reverse kern
     for k in range(1, 8):
         print(f"   {names32[k]:52s} {100 * v[8 + k] / tot:6.1f} %")
     sys.exit(0)
-for lo, kern in ((0, "k_edge_fwd_mfma"), (8, "k_edge_bwd_mfma")):
-    tot = v[lo + 1:lo + 8].sum()
+# forward kernel: the clock starts at kernel entry, so slot 0 is what precedes a walk and slot 7 (persistent form only) what follows it
+fwd_names = dict(enumerate(names))
+fwd_names[0] = "staging + prologue in front of a walk (persistent: first barrier -> walk starts = staging still exposed)"
+fwd_names[7] = "persistent: end of a walk -> first barrier (next slice's loads issued, waiting for the slower waves)"
+print(f"VSSR_EDGE_FWD_GRID={os.environ.get('VSSR_EDGE_FWD_GRID', '(default)')}")
+for lo, kern, nm, first in ((0, "k_edge_fwd_mfma", fwd_names, 0), (8, "k_edge_bwd_mfma", dict(enumerate(names)), 1)):
+    tot = v[lo + first:lo + 8].sum()
     print(kern)
-    for k in range(1, 8):
+    for k in list(range(1, 8)) + ([0] if first == 0 else []):
         if v[lo + k]:
-            print(f"   {names[k]:44s} {100 * v[lo + k] / tot:6.1f} %")
+            print(f"   {nm[k]:44s} {100 * v[lo + k] / tot:6.1f} %")
+    if first == 0:
+        print(f"   (share of the walk itself: {100 * v[lo + 1:lo + 7].sum() / tot:.1f} %)")
 eng.close()
