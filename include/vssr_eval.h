@@ -720,8 +720,8 @@ int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vss
  * Refused with VSSR_E_BADARG before any device is touched, besides what vssr_pair_create refuses: ks NULL, charge NULL, g_ewald or
  * k_cut not finite and positive, VSSR_PAIR_COUL_LONG terms that do not cover every type pair or that differ in rc, and a
  * VSSR_PAIR_COUL_LONG term next to a VSSR_PAIR_COUL_DSF term.  vssr_pair_create itself refuses a VSSR_PAIR_COUL_LONG term.
- * vssr_batch_upload refuses a chain with a non-periodic axis (VSSR_E_BADARG: a 3-D Ewald sum needs three periodic axes; no slab
- * correction) and, with VSSR_E_CAPACITY, a chain whose k sphere needs a per-axis index floor(k_cut |a_i| / 2 pi) above 63 or a half
+ * vssr_batch_upload refuses a chain with a non-periodic axis (VSSR_E_BADARG: a 3-D Ewald sum needs three periodic axes; slabs are
+ * served by vssr_pair_create_kspace_slab below) and, with VSSR_E_CAPACITY, a chain whose k sphere needs a per-axis index floor(k_cut |a_i| / 2 pi) above 63 or a half
  * box (m1 + 1)(2 m2 + 1)(2 m3 + 1) of more than 65 536 cells; nothing is ever truncated.
  * Relaxations: FIRE, BFGS, BFGSLineSearch and the lock-step CG serve these handles; the chain-resident CG minimiser does not
  * (VSSR_CG_DRIVER_RESIDENT runs in lock step, same results, as for chains of more than 256 atoms).  Entry points that hand out
@@ -731,6 +731,27 @@ typedef struct vssr_kspace {
 } vssr_kspace;
 int vssr_pair_create_kspace(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
                             const vssr_kspace *ks, vssr_handle **out);
+/* The same handle for slabs: LAMMPS kspace_style ewald + kspace_modify slab F under boundary p p f (Yeh & Berkowitz 1999; Ballenegger,
+ * Arnold & Cerda 2009 for cells with net charge; restated from the papers, no LAMMPS was executed).  Chains have pbc 1 1 0, cell rows
+ * a, b in the xy plane and c along z.  With the extended cell (a, b, F c) of volume V' = F V:
+ *   E_real   over the in-plane images only (the neighbor list of pbc 1 1 0)
+ *   E_k, E_self, E_bg and their pe/atom and forces: the formulas above in the extended cell (V' for V, its reciprocal vectors; the
+ *            capacity limits below are taken on it too)
+ *   E_slab = qqrd2e (2 pi / V') (M^2 - Q R2 - Q^2 L'^2 / 12),   Q = sum q, M = sum q z, R2 = sum q z^2, z_i = r_i . n (never wrapped),
+ *            n = a x b / |a x b|, L' = F |c . n|
+ *   e_i   += qqrd2e (2 pi / V') q_i (z_i M - (R2 + Q z_i^2) / 2 - Q L'^2 / 12)              (sums to E_slab)
+ *   F_i   += -qqrd2e (4 pi / V') q_i (M - Q z_i) n
+ * E_slab does not change under a common shift along z, for Q != 0 either.  vssr_batch_stress includes the slab virial
+ * dE_slab / d eps = E_slab (-1, -1, +1, 0, 0, 0) (Voigt xx yy zz yz xz xy) and divides by the real V = |det cell|, not by V'.
+ * Q, M and R2 are summed in atom order without atomics: a chain's bits depend neither on its batch nor on the run.
+ * Refused with VSSR_E_BADARG at creation: what vssr_pair_create_kspace refuses, and a slab_factor that is not finite or is <= 1.0.
+ * vssr_batch_upload on such a handle refuses with VSSR_E_BADARG a chain whose pbc is not exactly 1 1 0 (the message names the pbc), a
+ * cell whose a or b has a z component or whose c has an x or y component beyond 1e-12 |c| (in-plane skew of a and b is fine), and a
+ * chain whose atoms span more than |c| along z (the vacuum of the extended cell is then not guaranteed; positions that a relaxation
+ * or an MD run moves later are NOT re-checked); with VSSR_E_CAPACITY a chain whose extended cell exceeds the limits above (the
+ * message names the extended length F |c|).  vssr_pair_create_kspace handles keep their refusal of a non-periodic axis. */
+int vssr_pair_create_kspace_slab(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                                 const vssr_kspace *ks, double slab_factor, vssr_handle **out);
 /* same signature and meaning as vssr_tersoff_eval_batch (fp64 energies / per-atom energies / forces) */
 int vssr_pair_eval_batch(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, const int32_t *type, const double *pos,
                          const double *cell, const uint8_t *pbc, uint32_t want, vssr_out *out, double *energy_f64,

@@ -36,7 +36,7 @@ EXPORTS = (
     "vssr_gmm_fit_set_init", "vssr_gmm_fit_run", "vssr_gmm_fit_params", "vssr_gmm_fit_scorer",
     "vssr_cluster_create", "vssr_cluster_append_rows", "vssr_cluster_append_batch", "vssr_cluster_clear", "vssr_cluster_pca",
     "vssr_cluster_pca_params", "vssr_cluster_projected", "vssr_cluster_set_points", "vssr_cluster_linkage",
-    "vssr_pair_create", "vssr_pair_create_kspace", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
+    "vssr_pair_create", "vssr_pair_create_kspace", "vssr_pair_create_kspace_slab", "vssr_pair_eval_batch", "vssr_batch_results_f64", "vssr_batch_relax_cg_driver",
     "vssr_batch_relax_bfgs_linesearch", "vssr_eam_create_adp",
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
     "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
@@ -411,6 +411,9 @@ def load_library():
     L.vssr_pair_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(vp)]
     L.vssr_pair_create_kspace.restype = C.c_int
     L.vssr_pair_create_kspace.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(KSpace), C.POINTER(vp)]
+    L.vssr_pair_create_kspace_slab.restype = C.c_int
+    L.vssr_pair_create_kspace_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PairTerm), dp, C.POINTER(KSpace), C.c_double,
+                                               C.POINTER(vp)]
     L.vssr_pair_eval_batch.restype = C.c_int
     L.vssr_pair_eval_batch.argtypes = L.vssr_tersoff_eval_batch.argtypes
     L.vssr_batch_relax_fire.restype = C.c_int
@@ -1189,8 +1192,9 @@ class PairEngine(_AnalyticEngine):
     def __init__(self, terms, charges=None, n_types=None, device=0, kspace=None):
         """``terms``: a ``pair.PairModel`` (then ``charges`` / ``n_types`` / ``kspace`` come from it), or a list of ``(type_a, type_b,
         style, c, rc, shift)`` with 0-based types, a style code or name of ``pair.STYLES`` and up to five coefficients in LAMMPS
-        order; ``charges``: per-type charges [n_types] (needed by coul/dsf and coul/long); ``kspace``: ``(g_ewald, k_cut)`` or a
-        ``pair.KSpace`` -- the Ewald sum behind the coul/long terms (vssr_pair_create_kspace)."""
+        order; ``charges``: per-type charges [n_types] (needed by coul/dsf and coul/long); ``kspace``: ``(g_ewald, k_cut)``,
+        ``(g_ewald, k_cut, slab)`` or a ``pair.KSpace`` -- the Ewald sum behind the coul/long terms (vssr_pair_create_kspace; with a
+        slab factor other than 0 vssr_pair_create_kspace_slab: chains with pbc (1, 1, 0), the dipole-corrected sum of kspace_modify slab)."""
         super().__init__()
         from . import pair as pair_io
 
@@ -1217,10 +1221,18 @@ class PairEngine(_AnalyticEngine):
             name = "vssr_pair_create"
             rc = self._lib.vssr_pair_create(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double), C.byref(self._h))
         else:
-            name = "vssr_pair_create_kspace"
-            g, kc = (kspace.g_ewald, kspace.k_cut) if hasattr(kspace, "g_ewald") else kspace
-            rc = self._lib.vssr_pair_create_kspace(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double),
-                                                   C.byref(KSpace(float(g), float(kc))), C.byref(self._h))
+            if hasattr(kspace, "g_ewald"):
+                g, kc, slab = kspace.g_ewald, kspace.k_cut, getattr(kspace, "slab", 0.0)
+            else:
+                g, kc, slab = (*kspace, 0.0) if len(kspace) == 2 else kspace
+            if slab != 0.0:   # (also a factor <= 1.0 or NaN, which that entry point refuses)
+                name = "vssr_pair_create_kspace_slab"
+                rc = self._lib.vssr_pair_create_kspace_slab(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double),
+                                                            C.byref(KSpace(float(g), float(kc))), float(slab), C.byref(self._h))
+            else:
+                name = "vssr_pair_create_kspace"
+                rc = self._lib.vssr_pair_create_kspace(int(device), self.n_types, len(terms), arr, _ptr(q, C.c_double),
+                                                       C.byref(KSpace(float(g), float(kc))), C.byref(self._h))
         if rc != 0:
             msg = self._lib.vssr_last_error(None)
             raise BackendError(f"{name} failed ({rc}): {msg.decode() if msg else '?'}")

@@ -1705,32 +1705,44 @@ class PairSurfCalc(_AnalyticSurfCalc):
     the device (periodic in three directions, charged cells with the neutralising background): g = sqrt(-ln A) / rc and
     k_cut = 2 g sqrt(-ln A) unless ``kspace_modify gewald`` / the ``g_ewald=`` and ``k_cut=`` keywords say otherwise.  Energies agree
     with LAMMPS to the accuracy asked for, not digit for digit (LAMMPS picks its k vectors from the atom count and the charges);
-    ``cg_driver="resident"`` runs in lock step for such a model."""
+    ``cg_driver="resident"`` runs in lock step for such a model.
+
+    Slabs: ``boundary p p f`` + ``kspace_modify slab F`` among the commands, or the ``slab=F`` keyword, run the Ewald sum of the cell
+    extended to F times its height with the dipole correction (Yeh & Berkowitz; charged cells as Ballenegger et al.).  Such a model
+    imposes pbc (1, 1, 0) on every structure, whatever the atoms' flags say; the cell needs a and b in the xy plane and c along z."""
 
     name = "pair_mi355x"
 
     def __init__(self, commands=None, text=None, species=None, device="cuda", all_periodic=False, logger=None, g_ewald=None, k_cut=None,
-                 **kwargs):
+                 slab=None, **kwargs):
         """commands: list of LAMMPS command lines, or ``text``: the same as one string; species: symbols in LAMMPS type order;
-        g_ewald / k_cut (1 / A): override what ``kspace_style ewald`` / ``kspace_modify gewald`` give."""
+        g_ewald / k_cut (1 / A): override what ``kspace_style ewald`` / ``kspace_modify gewald`` give; slab: the factor of
+        ``kspace_modify slab`` (overrides the parsed one; 0.0 switches the correction off)."""
         if (commands is None) == (text is None):
             raise ValueError("give the pair commands either as commands=[...] or as text=...")
         if not species:
             raise ValueError("species (LAMMPS type order) are required")
         self.species = list(species)
         self.pair_model = pair_io.parse(text if commands is None else list(commands), len(self.species))
-        if g_ewald is not None or k_cut is not None:
+        if g_ewald is not None or k_cut is not None or slab is not None:
             ks = self.pair_model.kspace
             if ks is None:
-                raise ValueError("g_ewald / k_cut need a */coul/long pair_style with kspace_style ewald")
+                raise ValueError("g_ewald / k_cut / slab need a */coul/long pair_style with kspace_style ewald")
             rc = next(t.rc for t in self.pair_model.terms if t.style == pair_io.STYLES["coul/long"])
             self.pair_model = self.pair_model._replace(kspace=pair_io.ewald_defaults(
-                ks.accuracy, rc, g_ewald=ks.g_ewald if g_ewald is None else g_ewald, k_cut=k_cut))
+                ks.accuracy, rc, g_ewald=ks.g_ewald if g_ewald is None else g_ewald, k_cut=k_cut,
+                slab=ks.slab if slab is None else slab))
         self._init_common(device, all_periodic, logger)
         super().__init__(**kwargs)
 
     def _make_engine(self):
         return backend.PairEngine(self.pair_model, device=_device_index(self.device))
+
+    def _fixed_pbc(self):
+        ks = self.pair_model.kspace
+        if ks is not None and ks.slab > 0:
+            return np.array([1, 1, 0], np.uint8)
+        return super()._fixed_pbc()
 
 
 EAM_STYLES = ("eam", "eam/alloy", "eam/fs", "adp")
@@ -1923,7 +1935,8 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
       ``pair_style sw`` (a KIM model's own per-particle split is not reproduced; totals do not depend on it).  ``lj/cut``,
       ``morse``, ``buck``, ``born``, ``coul/dsf`` and ``hybrid`` / ``hybrid/overlay`` of them take their ``pair_coeff`` /
       ``pair_modify`` / ``set type N charge q`` lines and the ``boundary`` from the energy template (``pair.parse``; no
-      ``potential_file``).  When the opt
+      ``potential_file``); the ``*/coul/long`` styles with ``kspace_style ewald`` need ``boundary p p p``, or ``boundary p p f`` with
+      ``kspace_modify slab F`` (the dipole-corrected slab sum, pbc (1, 1, 0)).  When the opt
       template names another potential the backend lacks (the Si tutorial's SRS model), relaxations raise; single points work.
 
     The potential file is looked up like LAMMPS does (as given, in the run directory, in the working directory, in
@@ -2105,9 +2118,13 @@ class LAMMPSSurfCalc(_AnalyticSurfCalc):
             model = pair_io.parse(text, len(species))
             b = re.search(r"^\s*boundary\s+([^#\n]+)", text, re.M)
             boundary = self._boundary_pbc(b.group(1).split() if b else None)
-            if model.kspace is not None and boundary is not None and not all(boundary):
+            if model.kspace is not None and model.kspace.slab > 0:
+                # (pair.parse took the factor only after a 'boundary p p f' line; the first boundary line is the one that applies here)
+                if boundary is None or list(boundary) != [1, 1, 0]:
+                    raise ValueError(f"boundary {b.group(1).strip() if b else None!r}: kspace_modify slab needs 'boundary p p f'")
+            elif model.kspace is not None and boundary is not None and not all(boundary):
                 raise ValueError(f"boundary {b.group(1).strip()!r}: kspace_style ewald needs 'boundary p p p' (the Ewald sum is periodic in "
-                                 "three directions; the slab correction is not provided)")
+                                 "three directions) or kspace_modify slab F under 'boundary p p f'")
         except ValueError as e:
             raise backend.BackendError(f"{path}: the pair commands cannot be read: {e}") from None
         self.pair_model = model

@@ -1,5 +1,6 @@
 // api_batch.hip — the resident batch: upload, run, download, the relaxation entry points and introspection.
 #include <cmath>
+#include <cstdio>
 
 #include "ewald_dev.h"
 
@@ -76,25 +77,53 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
     }
     if (h->ew_on) {   // the k sphere of every chain from its own cell (ewald_dev.h): capacity, and the stride of the S(k) array
         long long stride = 0;
+        const bool slab = h->ew_slab > 0;
         for (int b = 0; b < n_cfg; ++b) {
-            if (!(pbc[3 * b] && pbc[3 * b + 1] && pbc[3 * b + 2]))
+            const double *c = cell + 9 * b;
+            if (slab) {   // pbc 1 1 0, a and b in the plane, c along z, the atoms within |c| along z (of these positions: later moves are not re-checked)
+                if (!(pbc[3 * b] && pbc[3 * b + 1] && !pbc[3 * b + 2]))
+                    return set_err(h, VSSR_E_BADARG, "configuration %d: a slab Ewald sum needs pbc 1 1 0 (pbc %d %d %d)", b, (int)pbc[3 * b],
+                                   (int)pbc[3 * b + 1], (int)pbc[3 * b + 2]);
+                const double len = std::sqrt(c[6] * c[6] + c[7] * c[7] + c[8] * c[8]), tol = 1e-12 * len;
+                if (std::fabs(c[2]) > tol || std::fabs(c[5]) > tol || std::fabs(c[6]) > tol || std::fabs(c[7]) > tol)
+                    return set_err(h, VSSR_E_BADARG, "configuration %d: a slab Ewald sum needs a and b in the xy plane and c along z (a_z %g, b_z %g, "
+                                   "c_x %g, c_y %g)", b, c[2], c[5], c[6], c[7]);
+                double lo = pos[3 * (size_t)start[b] + 2], hi = lo;
+                for (int i = start[b]; i < start[b + 1]; ++i) {
+                    lo = std::min(lo, pos[3 * (size_t)i + 2]);
+                    hi = std::max(hi, pos[3 * (size_t)i + 2]);
+                }
+                if (hi - lo > len)
+                    return set_err(h, VSSR_E_BADARG, "configuration %d: the atoms span %g A along z, more than |c| = %g A: the extended cell of "
+                                   "%g A would not keep its vacuum", b, hi - lo, len, h->ew_slab * len);
+            } else if (!(pbc[3 * b] && pbc[3 * b + 1] && pbc[3 * b + 2]))
                 return set_err(h, VSSR_E_BADARG, "configuration %d: an Ewald sum needs three periodic axes (pbc %d %d %d; no slab correction)", b,
                                (int)pbc[3 * b], (int)pbc[3 * b + 1], (int)pbc[3 * b + 2]);
             EwaldGeom G;
-            ewald_geom(cell + 9 * b, h->ew_kcut, 1e-9, G);
+            ewald_geom(c, h->ew_kcut, 1e-9, G, h->ew_slab);
+            char ext[96] = "";
+            auto name_extended = [&] {   // (refusal paths only) a slab handle: the capacity refusals name the extended length F |c|
+                if (slab)
+                    snprintf(ext, sizeof ext, " of the cell extended to %g A (slab factor %g)",
+                             h->ew_slab * std::sqrt(c[6] * c[6] + c[7] * c[7] + c[8] * c[8]), h->ew_slab);
+            };
             for (int k = 0; k < 3; ++k)
-                if (G.m[k] > EW_MAX_INDEX)
-                    return set_err(h, VSSR_E_CAPACITY, "configuration %d: k_cut %g 1/A needs the reciprocal index %d along axis %d, the k-space "
+                if (G.m[k] > EW_MAX_INDEX) {
+                    name_extended();
+                    return set_err(h, VSSR_E_CAPACITY, "configuration %d: k_cut %g 1/A needs the reciprocal index %d along axis %d%s, the k-space "
                                    "kernels hold %d at the most (nothing is truncated: lower k_cut with a larger real-space cutoff)",
-                                   b, h->ew_kcut, G.m[k], k, EW_MAX_INDEX);
-            if (G.cells > EW_MAX_CELLS)
-                return set_err(h, VSSR_E_CAPACITY, "configuration %d: k_cut %g 1/A needs a box of %lld reciprocal vectors, the k-space kernels hold "
+                                   b, h->ew_kcut, G.m[k], k, ext, EW_MAX_INDEX);
+                }
+            if (G.cells > EW_MAX_CELLS) {
+                name_extended();
+                return set_err(h, VSSR_E_CAPACITY, "configuration %d: k_cut %g 1/A needs a box of %lld reciprocal vectors%s, the k-space kernels hold "
                                "%d at the most (nothing is truncated: lower k_cut with a larger real-space cutoff)", b, h->ew_kcut, G.cells,
-                               EW_MAX_CELLS);
+                               ext, EW_MAX_CELLS);
+            }
             stride = std::max(stride, G.cells);
         }
         h->ew_stride = (int)stride;
-        if (h->d_ew_S.ensure(sizeof(double) * 2 * (size_t)n_cfg * (size_t)(stride + 1)))
+        if (h->d_ew_S.ensure(sizeof(double) * 2 * (size_t)n_cfg * (size_t)(stride + EW_EXTRA)))
             return set_err(h, VSSR_E_NOMEM, "k-space structure factors: out of device memory");
     }
     if (h->d_pos.ensure(sizeof(double) * 3 * N) || h->d_Z.ensure(sizeof(int) * N) ||

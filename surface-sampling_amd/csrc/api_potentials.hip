@@ -485,9 +485,9 @@ static int pair_derive(const vssr_pair_term &t, int idx, double qq, double g, Pa
     return VSSR_OK;
 }
 
-// vssr_pair_create (ks == nullptr) and vssr_pair_create_kspace
+// vssr_pair_create (ks == nullptr), vssr_pair_create_kspace (slab 0) and vssr_pair_create_kspace_slab (the slab factor, checked there)
 static int pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
-                       const vssr_kspace *ks, vssr_handle **out) {
+                       const vssr_kspace *ks, double slab, vssr_handle **out) {
     if (!terms || !out || n_terms < 1) return set_err(nullptr, VSSR_E_BADARG, "bad pair arguments");
     *out = nullptr;
     if (ks) {
@@ -564,6 +564,7 @@ static int pair_create(int32_t device, int32_t n_types, int32_t n_terms, const v
             h->ew_on = true;
             h->ew_g = ks->g_ewald;
             h->ew_kcut = ks->k_cut;
+            h->ew_slab = slab;
             for (int t = 0; t < n_types; ++t) h->ew_q[t] = charge[t];
         }
         return upload_params(h, tab.data(), sizeof(PairTable), "pair table", "pair table upload failed");
@@ -572,13 +573,21 @@ static int pair_create(int32_t device, int32_t n_types, int32_t n_terms, const v
 
 int vssr_pair_create(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
                      vssr_handle **out) {
-    return pair_create(device, n_types, n_terms, terms, charge, nullptr, out);
+    return pair_create(device, n_types, n_terms, terms, charge, nullptr, 0.0, out);
 }
 
 int vssr_pair_create_kspace(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
                             const vssr_kspace *ks, vssr_handle **out) {
     if (!ks) return set_err(nullptr, VSSR_E_BADARG, "vssr_pair_create_kspace: null k-space parameters");
-    return pair_create(device, n_types, n_terms, terms, charge, ks, out);
+    return pair_create(device, n_types, n_terms, terms, charge, ks, 0.0, out);
+}
+
+int vssr_pair_create_kspace_slab(int32_t device, int32_t n_types, int32_t n_terms, const vssr_pair_term *terms, const double *charge,
+                                 const vssr_kspace *ks, double slab_factor, vssr_handle **out) {
+    if (!ks) return set_err(nullptr, VSSR_E_BADARG, "vssr_pair_create_kspace_slab: null k-space parameters");
+    if (!std::isfinite(slab_factor) || !(slab_factor > 1.0))
+        return set_err(nullptr, VSSR_E_BADARG, "pair: bad slab parameter %g (the slab factor must be finite and > 1.0)", slab_factor);
+    return pair_create(device, n_types, n_terms, terms, charge, ks, slab_factor, out);
 }
 
 }  // extern "C"

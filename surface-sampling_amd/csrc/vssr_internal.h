@@ -359,11 +359,12 @@ struct vssr_handle {
     int n_types = 0;
     double pot_cutoff = 0;       // Tersoff, SW, pair: largest cutoff of the table (EAM: eam_grid.cutoff)
     // pair handles with k-space (vssr_pair_create_kspace, ewald.hip): Ewald damping g, reciprocal cutoff, per-type charges; ew_stride:
-    // k cells per chain in d_ew_S = the largest half box of the uploaded batch (ewald_dev.h), [n_cfg][ew_stride + 1] double2
+    // k cells per chain in d_ew_S = the largest half box of the uploaded batch (ewald_dev.h), [n_cfg][ew_stride + EW_EXTRA] double2
     // (vssr_batch_upload is the only writer of d_cell: any new entry point that changes a cell must recompute ew_stride and re-size
     // d_ew_S as it does; a chain whose half box exceeds the stride gets NaN results from the kernels, never a partial sum)
     bool ew_on = false;
     double ew_g = 0, ew_kcut = 0, ew_q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double ew_slab = 0;   // vssr_pair_create_kspace_slab: the factor F of the extended cell (a, b, F c); 0: three periodic axes
     int ew_stride = 0;
     vssr::DevBuf d_ew_S;
     vssr::DevBuf pot_params;     // Tersoff: double[nt^3][14]; SW: SwP[nt^3] (sw_dev.h); EAM: spline tables (eam.hip); pair: PairTable (pair_dev.h)

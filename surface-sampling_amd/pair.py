@@ -2,8 +2,8 @@
 
 Read: ``pair_style`` (``lj/cut``, ``morse``, ``buck``, ``born``, ``coul/dsf``, ``coul/long``, ``buck/coul/long``,
 ``born/coul/long``, ``lj/cut/coul/long``, and ``hybrid`` / ``hybrid/overlay`` of these), ``pair_coeff`` with LAMMPS' type wildcards,
-``pair_modify shift`` / ``mix``, ``set type N charge q``, ``kspace_style ewald A`` and ``kspace_modify gewald G``; every other
-command of the template is skipped.  Units are LAMMPS ``metal``.  Whatever cannot be read raises ``ValueError`` with the offending
+``pair_modify shift`` / ``mix``, ``set type N charge q``, ``kspace_style ewald A``, ``kspace_modify gewald G``, ``boundary`` and
+``kspace_modify slab F``; every other command of the template is skipped.  Units are LAMMPS ``metal``.  Whatever cannot be read raises ``ValueError`` with the offending
 line.
 
 The ``*/coul/long`` styles become their short-range term plus a ``coul/long`` term (the real-space part of the Ewald sum, cutoff
@@ -11,6 +11,10 @@ The ``*/coul/long`` styles become their short-range term plus a ``coul/long`` te
 L = sqrt(-ln A), g = L / rc, k_cut = 2 g L (``kspace_modify gewald G``: g = G).  This rule depends on (A, rc) only -- LAMMPS' own
 estimator also looks at the atom count and the charges, which would change g between the proposals of a semigrand MC run -- so
 energies agree with LAMMPS to the accuracy asked for, not digit for digit.
+
+``kspace_modify slab F`` (F > 1) after a ``boundary p p f`` line sets ``kspace.slab``: the Ewald sum of the cell extended to F times
+its height with the dipole correction of Yeh & Berkowitz, evaluated with pbc (1, 1, 0).  Without such a boundary line LAMMPS stops
+("incorrect boundaries with slab Ewald") and so does ``parse``; ``slab nozforce`` and ``slab ew2d`` are not provided.
 """
 
 from __future__ import annotations
@@ -33,11 +37,13 @@ QQRD2E = 14.399645
 Term = namedtuple("Term", "type_a type_b style c rc shift")      # 0-based types with a <= b, style code, c [5], cutoff, 0 / 1
 # charges: [n_types] or None (no ``set type ... charge``); kspace: None, or the Ewald sum behind the coul/long terms
 PairModel = namedtuple("PairModel", "n_types terms charges cutoff kspace", defaults=(None,))
-KSpace = namedtuple("KSpace", "accuracy g_ewald k_cut")   # relative accuracy A asked for, damping g and reciprocal cutoff (1 / A)
+# relative accuracy A asked for, damping g and reciprocal cutoff (1 / A), slab factor F of kspace_modify slab (0.0: periodic in three directions)
+KSpace = namedtuple("KSpace", "accuracy g_ewald k_cut slab", defaults=(0.0,))
 
 
-def ewald_defaults(accuracy, rc, g_ewald=None, k_cut=None) -> KSpace:
-    """``kspace_style ewald A`` with the real-space cutoff ``rc``: L = sqrt(-ln A), g = L / rc, k_cut = 2 g L unless given."""
+def ewald_defaults(accuracy, rc, g_ewald=None, k_cut=None, slab=0.0) -> KSpace:
+    """``kspace_style ewald A`` with the real-space cutoff ``rc``: L = sqrt(-ln A), g = L / rc, k_cut = 2 g L unless given;
+    ``slab``: the factor of ``kspace_modify slab`` (0.0: none)."""
     if not (0.0 < accuracy < 1.0):
         raise ValueError(f"kspace accuracy {accuracy} must lie in (0, 1)")
     L = math.sqrt(-math.log(accuracy))
@@ -45,7 +51,10 @@ def ewald_defaults(accuracy, rc, g_ewald=None, k_cut=None) -> KSpace:
     kc = 2.0 * g * L if k_cut is None else float(k_cut)
     if not (math.isfinite(g) and g > 0 and math.isfinite(kc) and kc > 0):
         raise ValueError(f"k-space parameters g_ewald {g}, k_cut {kc} must be finite and > 0")
-    return KSpace(float(accuracy), g, kc)
+    slab = float(slab)
+    if slab != 0.0 and not (math.isfinite(slab) and slab > 1.0):
+        raise ValueError(f"slab factor {slab} must be finite and > 1.0 (0.0: no slab correction)")
+    return KSpace(float(accuracy), g, kc, slab)
 
 
 def _number(tok, line, what):
@@ -146,7 +155,7 @@ def parse(lines, n_types) -> PairModel:
     none = set()          # pairs a hybrid line switched off (pair_coeff i j none)
     shift, mix = 0, "geometric"
     charges, has_charge = np.zeros(n_types), False
-    accuracy, gewald = None, None
+    accuracy, gewald, boundary, slab = None, None, None, 0.0
     for line in _commands(lines):
         tok = line.split()
         cmd = tok[0]
@@ -213,9 +222,20 @@ def parse(lines, n_types) -> PairModel:
                 if not gewald > 0:
                     raise ValueError(f"{line!r}: gewald must be > 0")
             elif len(tok) > 1 and tok[1] == "slab":
-                raise ValueError(f"{line!r}: the slab correction is not provided (the Ewald sum is periodic in three directions)")
+                if boundary != ["p", "p", "f"]:
+                    raise ValueError(f"{line!r}: the slab correction needs a 'boundary p p f' line before it (incorrect boundaries with "
+                                     "slab Ewald); without one the Ewald sum is periodic in three directions")
+                if len(tok) != 3 or tok[2] in ("nozforce", "ew2d"):
+                    raise ValueError(f"{line!r}: only 'kspace_modify slab F' with a number F > 1.0 is provided (no nozforce, no ew2d)")
+                slab = _number(tok[2], line, "slab factor")
+                if not slab > 1.0:
+                    raise ValueError(f"{line!r}: bad slab parameter: the slab factor must be > 1.0")
             else:
                 raise ValueError(f"{line!r}: kspace_modify {' '.join(tok[1:])!r} is not provided (gewald G)")
+        elif cmd == "boundary":
+            boundary = tok[1:]
+            if boundary != ["p", "p", "f"] and slab:
+                raise ValueError(f"{line!r}: incorrect boundaries with slab Ewald (kspace_modify slab needs 'boundary p p f')")
         elif cmd == "set" and "charge" in tok:
             if len(tok) != 5 or tok[1] != "type" or tok[3] != "charge":
                 raise ValueError(f"{line!r}: charges are per type ('set type N charge q')")
@@ -275,5 +295,7 @@ def parse(lines, n_types) -> PairModel:
             terms.append(Term(i - 1, j - 1, STYLES["coul/long"], (0.0,) * 5, float(long_rc[0]), 0))
     if not terms:
         raise ValueError("every type pair is 'none': nothing to evaluate")
-    kspace = ewald_defaults(accuracy, long_rc[0], g_ewald=gewald) if long_rc else None
+    if slab and not long_rc:
+        raise ValueError("kspace_modify slab without a */coul/long pair_style and kspace_style ewald")
+    kspace = ewald_defaults(accuracy, long_rc[0], g_ewald=gewald, slab=slab) if long_rc else None
     return PairModel(n_types, terms, charges if has_charge else None, max(t.rc for t in terms), kspace)

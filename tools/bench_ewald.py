@@ -14,7 +14,12 @@ The k-space share of an evaluation comes from the profiler, in a run of its own:
     python tools/bench_ewald.py --stats OUT/ew_results.db
 prints the share of the k_ewald_* kernels in the total kernel time of that run, from the dispatch table of the rocpd database
 rocprofv3 writes.
-Usage: python tools/bench_ewald.py [--chains 256,1024,4096] [--accuracy 1e-5,1e-8] [--rc 10.0] [--reps 5] [--relax-steps 20] [--no-dsf]"""
+--slab F measures the slab handle instead (kspace_modify slab F, the same slabs with pbc 1 1 0) against the 3-D handle on the same atoms
+in a fully periodic cell with c multiplied by F: the same k box, so the same reciprocal work, and the same real-space pairs (the vacuum
+exceeds the cutoff).  Per (chains, accuracy): resident evaluations/s of both, the slab / 3-D ratio, the 3-D figure of --repeats
+independent measurements (fresh handle each, the two handles alternating) with their spread, and the per-kernel times of one profiled run of each handle.
+Usage: python tools/bench_ewald.py [--chains 256,1024,4096] [--accuracy 1e-5,1e-8] [--rc 10.0] [--reps 5] [--relax-steps 20] [--no-dsf]
+                                   [--slab 3.0 [--repeats 5]]"""
 import argparse, json, os, sqlite3, sys, time
 
 import numpy as np
@@ -51,8 +56,9 @@ def batch(struct, B, sigma=0.05):
     return (np.full(B, len(T1), np.int32), np.tile(T1, B), pos, np.tile(Cl.reshape(1, 9), (B, 1)), np.tile(pbc.reshape(1, 3), (B, 1)))
 
 
-def measure(lines, struct, B, reps, relax_steps):
-    """(resident evaluations/s, whole-call evaluations/s, CG relaxations/s or None, mean CG evaluations or None)"""
+def measure(lines, struct, B, reps, relax_steps, profile=None):
+    """(resident evaluations/s, whole-call evaluations/s, CG relaxations/s or None, mean CG evaluations or None); ``profile``: a dict
+    that receives the handle's per-kernel counters of one more run."""
     from surface_sampling_amd import backend, pair
 
     eng = backend.PairEngine(pair.parse(lines, 2), device=0)
@@ -80,8 +86,44 @@ def measure(lines, struct, B, reps, relax_steps):
         t0 = time.perf_counter()
         out = eng.relax_cg_arrays_f64(*arrays, fixed=held, max_iter=relax_steps, rerun=False)
         cg, n_eval = B / (time.perf_counter() - t0), float(out[5].mean())
+    if profile is not None:
+        eng.profile_enable(True)
+        eng.profile_reset()
+        eng.run(want)
+        eng.synchronize()
+        profile.update({k: round(v["total_ms"], 4) for k, v in eng.profile_read().items() if v["launches"]})
+        eng.profile_enable(False)
     eng.close()
     return run, call, cg, n_eval
+
+
+def slab_compare(args, s):
+    """The slab handle on the slabs (pbc 1 1 0) against the 3-D handle on the same atoms in the cell with c multiplied by F."""
+    from surface_sampling_amd import pair
+
+    T, X, Cl, _ = s
+    F = args.slab
+    tall = Cl.copy()
+    tall[2] *= F
+    open_z, periodic = (T, X, Cl, np.array([1, 1, 0], np.uint8)), (T, X, tall, np.ones(3, np.uint8))
+    for B in [int(x) for x in args.chains.split(",") if x]:
+        for A in [float(x) for x in args.accuracy.split(",") if x]:
+            lines3 = ewald_lines(args.rc, A)
+            k = next(n for n, ln in enumerate(lines3) if ln.startswith("kspace_style"))
+            lines2 = ["boundary p p f", *lines3[:k + 1], f"kspace_modify slab {F}", *lines3[k + 1:]]
+            ks = pair.parse(lines2, 2).kspace
+            prof3, prof2 = {}, {}
+            three, two = [], []
+            for n in range(args.repeats):   # alternating, so that warm-up and clock drift fall on both sides alike
+                three.append(measure(lines3, periodic, B, args.reps, 0, profile=prof3 if n == 0 else None)[0])
+                two.append(measure(lines2, open_z, B, args.reps, 0, profile=prof2 if n == 0 else None)[0])
+            m3, m2 = float(np.median(three)), float(np.median(two))
+            print(json.dumps({"metric": f"slab Ewald sum (F {F:g}) against the 3-D sum of the same k box, rocksalt slab ({len(T)} atoms, rc {args.rc}, "
+                                        f"A {A:g})", "chains": B, "g_ewald": round(ks.g_ewald, 5), "k_cut": round(ks.k_cut, 5),
+                              "slab_evals_per_s_resident": [round(x, 1) for x in two], "three_d_evals_per_s_resident": [round(x, 1) for x in three],
+                              "slab_median": round(m2, 1), "three_d_median": round(m3, 1), "slab_over_three_d": round(m2 / m3, 4),
+                              "three_d_spread": round((max(three) - min(three)) / m3, 4), "slab_spread": round((max(two) - min(two)) / m2, 4),
+                              "profile_ms_three_d": prof3, "profile_ms_slab": prof2}), flush=True)
 
 
 def stats_share(path):
@@ -104,6 +146,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--relax-steps", type=int, default=20)
     ap.add_argument("--no-dsf", action="store_true")
+    ap.add_argument("--slab", type=float, default=0.0, metavar="F", help="compare the slab handle (slab factor F) with the 3-D handle of the same k box")
+    ap.add_argument("--repeats", type=int, default=5, help="independent measurements per figure of --slab (run-to-run spread)")
     ap.add_argument("--stats", metavar="DB", help="print the k-space share from the rocpd database of a rocprofv3 --kernel-trace run and exit")
     args = ap.parse_args()
     if args.stats is not None:
@@ -111,6 +155,8 @@ def main():
     from surface_sampling_amd import pair
 
     s = slab()
+    if args.slab:
+        return slab_compare(args, s)
     for B in [int(x) for x in args.chains.split(",") if x]:
         ref = None if args.no_dsf else measure(dsf_lines(args.rc), s, B, args.reps, args.relax_steps)
         if ref:
