@@ -525,6 +525,42 @@ _DIMER_DOC = """Saddle searches from single structures on the device (``backend.
         papers, not ASE's ``MinModeTranslate``."""
 
 
+class _DynamicsFrontEnds:
+    """``md_batch`` / ``vibrations_batch`` / ``neb_batch`` / ``dimer_batch`` of a calculator with ``_get_engine``, in terms of two
+    hooks of the class: ``_pack(atoms) -> (Z or types, pos, cell, pbc)`` and ``_dynamics_want``, the outputs an evaluation produces."""
+
+    _dynamics_want = 0
+
+    def md_batch(self, atoms_list, fixed_indices=None, steps: int = 100, timestep: float = 1.0, thermostat: str = "nve",
+                 temperature: float = 300.0, temperature_end=None, friction: float = 0.01, seed: int = 0, first_chain: int = 0,
+                 velocities=None, masses=None, thermo_interval: int = 1, md_driver=None):
+        return _md_batch(self._get_engine, [self._pack(a) for a in atoms_list], atoms_list, fixed_indices, steps, timestep, thermostat,
+                         temperature, temperature_end, friction, seed, first_chain, velocities, masses, thermo_interval, md_driver,
+                         self._dynamics_want)
+
+    md_batch.__doc__ = _MD_DOC
+
+    def vibrations_batch(self, atoms_list, indices=None, masses=None, delta: float = 0.01, nfree: int = 2, method: str = "standard",
+                         temperature=None, e_min: float = 0.0, replicas="auto", return_hessian: bool = False, return_modes: bool = False):
+        return _vibrations_batch(self._get_engine, self._pack, atoms_list, indices, masses, delta, nfree, method, temperature, e_min, replicas,
+                                 return_hessian, return_modes, self._dynamics_want)
+
+    vibrations_batch.__doc__ = _VIB_DOC
+
+    def neb_batch(self, bands, fixed_indices=None, k: float = 0.1, climb: bool = False, method: str = "improvedtangent", fmax: float = 0.05,
+                  steps: int = 100, two_stage: bool = False):
+        return _neb_batch(self._get_engine, self._pack, bands, fixed_indices, k, climb, method, fmax, steps, two_stage, self._dynamics_want)
+
+    neb_batch.__doc__ = _NEB_DOC
+
+    def dimer_batch(self, atoms_list, modes=None, fixed_indices=None, n_starts: int = 1, seed: int = 0, steps: int = 100, fmax: float = 0.05,
+                    delta: float = 0.01, phi_tol: float = np.pi / 180.0, max_rot_first: int = 8, max_rot: int = 1, displace: float = 0.0):
+        return _dimer_batch(self._get_engine, self._pack, atoms_list, modes, fixed_indices, n_starts, seed, steps, fmax, delta, phi_tol,
+                            max_rot_first, max_rot, displace, self._dynamics_want)
+
+    dimer_batch.__doc__ = _DIMER_DOC
+
+
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:
     """bool ``[B]``: the reference's out-of-bounds guard (``mcmc/dynamics.py:159-168``) for every chain of a batch -- a non-finite energy
     or force, ``|E| > e_max``, a force component beyond ``f_max``, or a ``saturated`` evaluation."""
@@ -577,7 +613,7 @@ class _LockstepProxy(_Base):
         self.results = {"energy": float(e), "forces": np.asarray(f, dtype=np.float64)}
 
 
-class EnsembleNFFSurface(_Base):
+class EnsembleNFFSurface(_DynamicsFrontEnds, _Base):
     """PaiNN-ensemble surface calculator on MI355X (drop-in for the reference class of the same name).
 
     Args:
@@ -607,6 +643,8 @@ class EnsembleNFFSurface(_Base):
     # virial of the same evaluation, Voigt 6-vector in eV / A^3 (what ase.Atoms.get_stress asks a calculator for)
     implemented_properties = ("energy", "forces", "stress", "energy_std", "forces_std", "stress_std", "surface_energy", "embedding")
     name = "ensemble_nff_surface_mi355x"
+    _pack = staticmethod(structures.as_arrays)   # the hooks of _DynamicsFrontEnds
+    _dynamics_want = backend.WANT_ALL
 
     def __init__(self, models, device="cuda", model_units="kcal/mol", prediction_units="eV",
                  offset_units="atomic", cutoff=None, hparams=None, logger=None, properties=("energy", "forces"),
@@ -1073,37 +1111,6 @@ class EnsembleNFFSurface(_Base):
         return out
 
 
-    def md_batch(self, atoms_list, fixed_indices=None, steps: int = 100, timestep: float = 1.0, thermostat: str = "nve",
-                 temperature: float = 300.0, temperature_end=None, friction: float = 0.01, seed: int = 0, first_chain: int = 0,
-                 velocities=None, masses=None, thermo_interval: int = 1, md_driver=None):
-        return _md_batch(self._get_engine, [structures.as_arrays(a) for a in atoms_list], atoms_list, fixed_indices, steps, timestep,
-                         thermostat, temperature, temperature_end, friction, seed, first_chain, velocities, masses, thermo_interval,
-                         md_driver, backend.WANT_ALL)
-
-    md_batch.__doc__ = _MD_DOC
-
-    def vibrations_batch(self, atoms_list, indices=None, masses=None, delta: float = 0.01, nfree: int = 2, method: str = "standard",
-                         temperature=None, e_min: float = 0.0, replicas="auto", return_hessian: bool = False, return_modes: bool = False):
-        return _vibrations_batch(self._get_engine, structures.as_arrays, atoms_list, indices, masses, delta, nfree, method, temperature, e_min,
-                                 replicas, return_hessian, return_modes, backend.WANT_ALL)
-
-    vibrations_batch.__doc__ = _VIB_DOC
-
-    def neb_batch(self, bands, fixed_indices=None, k: float = 0.1, climb: bool = False, method: str = "improvedtangent", fmax: float = 0.05,
-                  steps: int = 100, two_stage: bool = False):
-        return _neb_batch(self._get_engine, structures.as_arrays, bands, fixed_indices, k, climb, method, fmax, steps, two_stage,
-                          backend.WANT_ALL)
-
-    neb_batch.__doc__ = _NEB_DOC
-
-    def dimer_batch(self, atoms_list, modes=None, fixed_indices=None, n_starts: int = 1, seed: int = 0, steps: int = 100, fmax: float = 0.05,
-                    delta: float = 0.01, phi_tol: float = np.pi / 180.0, max_rot_first: int = 8, max_rot: int = 1, displace: float = 0.0):
-        return _dimer_batch(self._get_engine, structures.as_arrays, atoms_list, modes, fixed_indices, n_starts, seed, steps, fmax, delta, phi_tol,
-                            max_rot_first, max_rot, displace, backend.WANT_ALL)
-
-    dimer_batch.__doc__ = _DIMER_DOC
-
-
 def surface_energy_from_counts(energy, counts: dict, chem_pots: dict, offset_data: dict, offset_units: str = "atomic"):
     """:func:`surface_energy_from_energy` for MANY slabs at once: ``energy`` ``[B]`` and ``counts`` = element symbol ->
     ``[B]`` atom counts, the dict's key order being the order in which the elements first appear in the slabs' atom lists
@@ -1303,7 +1310,7 @@ class NFFPourbaix(EnsembleNFFSurface):
                 "surface_energy", self.surface_energy_of(self.results["energy"], self.atoms if atoms is None else atoms))
 
 
-class _AnalyticSurfCalc(_Base):
+class _AnalyticSurfCalc(_DynamicsFrontEnds, _Base):
     """Shared front end of the analytic potentials that the reference evaluates through LAMMPS (Tersoff, EAM): fp64
     ``energy`` / ``per_atom_energies`` / ``forces`` from the device, ``surface_energy`` = potential energy
     (reference ``calculators.py:707-719,766-777``), batched evaluation and lock-step relaxation for ``mc.ChainEnsemble``.
@@ -1316,6 +1323,7 @@ class _AnalyticSurfCalc(_Base):
     _default_properties = ("energy", "relaxed_energy", "forces", "per_atom_energies", "surface_energy")
     implemented_properties = (*_default_properties, "stress")
     species: list = []
+    _dynamics_want = backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM   # (_DynamicsFrontEnds; its other hook is _pack)
 
     def _init_common(self, device, all_periodic, logger):
         self.device = device
@@ -1515,36 +1523,6 @@ class _AnalyticSurfCalc(_Base):
                 r["stress"] = stress[b].copy()
             out.append((relaxed, _traj_of_chain(traj, b, a0, a1, atoms), self.ENERGY_THRESHOLD if oob[b] else r["energy"], bool(oob[b]), r))
         return out
-
-    def md_batch(self, atoms_list, fixed_indices=None, steps: int = 100, timestep: float = 1.0, thermostat: str = "nve",
-                 temperature: float = 300.0, temperature_end=None, friction: float = 0.01, seed: int = 0, first_chain: int = 0,
-                 velocities=None, masses=None, thermo_interval: int = 1, md_driver=None):
-        return _md_batch(self._get_engine, [self._pack(a) for a in atoms_list], atoms_list, fixed_indices, steps, timestep, thermostat,
-                         temperature, temperature_end, friction, seed, first_chain, velocities, masses, thermo_interval, md_driver,
-                         backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
-
-    md_batch.__doc__ = _MD_DOC
-
-    def vibrations_batch(self, atoms_list, indices=None, masses=None, delta: float = 0.01, nfree: int = 2, method: str = "standard",
-                         temperature=None, e_min: float = 0.0, replicas="auto", return_hessian: bool = False, return_modes: bool = False):
-        return _vibrations_batch(self._get_engine, self._pack, atoms_list, indices, masses, delta, nfree, method, temperature, e_min, replicas,
-                                 return_hessian, return_modes, backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
-
-    vibrations_batch.__doc__ = _VIB_DOC
-
-    def neb_batch(self, bands, fixed_indices=None, k: float = 0.1, climb: bool = False, method: str = "improvedtangent", fmax: float = 0.05,
-                  steps: int = 100, two_stage: bool = False):
-        return _neb_batch(self._get_engine, self._pack, bands, fixed_indices, k, climb, method, fmax, steps, two_stage,
-                          backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
-
-    neb_batch.__doc__ = _NEB_DOC
-
-    def dimer_batch(self, atoms_list, modes=None, fixed_indices=None, n_starts: int = 1, seed: int = 0, steps: int = 100, fmax: float = 0.05,
-                    delta: float = 0.01, phi_tol: float = np.pi / 180.0, max_rot_first: int = 8, max_rot: int = 1, displace: float = 0.0):
-        return _dimer_batch(self._get_engine, self._pack, atoms_list, modes, fixed_indices, n_starts, seed, steps, fmax, delta, phi_tol,
-                            max_rot_first, max_rot, displace, backend.WANT_ENERGY | backend.WANT_FORCES | backend.WANT_PER_ATOM)
-
-    dimer_batch.__doc__ = _DIMER_DOC
 
     @staticmethod
     def packed_supported(relax: bool, optimizer) -> bool:

@@ -305,17 +305,7 @@ int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint
     h->cg_last_driver = resident ? VSSR_CG_DRIVER_RESIDENT : VSSR_CG_DRIVER_LOCKSTEP;
     h->graph_partial = resident;     // (the lock-step driver ends with a full batch-wide evaluation of the final positions; the
                                      //  chain-resident one numbers its rows per chain: introspection wants one plain run first)
-    rc = sync_and_check(h);          // ... which may itself have overflowed the neighbor capacity: grow and repeat it
-    if (rc) return rc;
-    if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
-    std::vector<int> rep((size_t)3 * h->n_cfg);
-    VSSR_HIP(h, hipMemcpy(rep.data(), h->d_relax_steps.p, sizeof(int) * rep.size(), hipMemcpyDeviceToHost));
-    for (int b = 0; b < h->n_cfg; ++b) {
-        if (n_iter) n_iter[b] = rep[3 * b];
-        if (n_eval) n_eval[b] = rep[3 * b + 1];
-        if (stop_reason) stop_reason[b] = rep[3 * b + 2];
-    }
-    return VSSR_OK;
+    return relax_results(h, pos_out, {n_iter, n_eval, stop_reason});
 }
 
 int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_used) {
@@ -345,16 +335,7 @@ int vssr_batch_relax_bfgs_linesearch(vssr_handle *h, const vssr_bfgsls_params *p
     h->last_want = want | VSSR_WANT_FORCES;
     if (int rc = relax_bfgsls(h, p, fixed, want)) return rc;
     h->graph_partial = false;        // (the driver ends with a batch-wide evaluation of the final positions)
-    if (int rc = sync_and_check(h)) return rc;   // ... which may itself have overflowed the neighbor capacity: grow and repeat it
-    if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
-    std::vector<int> rep((size_t)3 * h->n_cfg);
-    VSSR_HIP(h, hipMemcpy(rep.data(), h->d_relax_steps.p, sizeof(int) * rep.size(), hipMemcpyDeviceToHost));
-    for (int b = 0; b < h->n_cfg; ++b) {
-        if (n_steps) n_steps[b] = rep[3 * b];
-        if (n_eval) n_eval[b] = rep[3 * b + 1];
-        if (stop_reason) stop_reason[b] = rep[3 * b + 2];
-    }
-    return VSSR_OK;
+    return relax_results(h, pos_out, {n_steps, n_eval, stop_reason});
 }
 
 int vssr_batch_relax_bfgs(vssr_handle *h, const vssr_bfgs_params *params, const uint8_t *fixed, uint32_t want,

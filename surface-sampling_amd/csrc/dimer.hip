@@ -3,10 +3,9 @@
 // J. Chem. Phys. 123, 224101 (2005), the force extrapolation of Kaestner & Sherwood, J. Chem. Phys. 128, 014106 (2008), and ASE's FIRE
 // step as neb.hip restates it for the translation.  Restated from the three papers; NOT ASE's MinModeTranslate and not pinned by any
 // executed library: the contract is the header comment of vssr_batch_dimer and the numpy restatement tests/dimer_oracle.py.
-// A DIMER is two consecutive chains: 2 g holds the midpoint x0, 2 g + 1 the moving end x0 + delta N.  The driver frame is neb.hip's:
+// A DIMER is two consecutive chains: 2 g holds the midpoint x0, 2 g + 1 the moving end x0 + delta N.  The driver frame is lockstep.h's:
 // one batch-wide evaluation per visit, ONE launch behind it (k_dimer_advance, one 256-thread workgroup per dimer, which owns both
-// chains: no slot exchange, no second launch), a poll every few visits, relax_regrow after a neighbor-capacity overflow (the kernel
-// returns at once behind an overflowed evaluation and state advances nowhere else, so a repeated evaluation moves nothing twice).
+// chains: no slot exchange, no second launch; state advances nowhere else, so an evaluation repeated after a regrow moves nothing twice).
 // A visit finds the dimer in one of two phases: behind an evaluation E (x0, x0 + delta N) or behind an evaluation R (x0,
 // x0 + delta N*).  It closes the rotation in flight, runs the rotation test, and either opens the next trial rotation (-> R) or runs
 // the step test and the FIRE translation (-> E).  Every vector loop is strided by ATOM with the same stride, so a thread only ever
@@ -23,6 +22,8 @@
 #include <cstring>
 #include <vector>
 
+#include "fire_dev.h"
+#include "lockstep.h"
 #include "md_dev.h"
 #include "neb_dev.h"
 
@@ -39,8 +40,9 @@ struct DimerState {   // per dimer
     int steps, reason, phase, rot, n_rot, n_eval;
 };
 struct DimerParams {
-    int max_steps, max_rot_first, max_rot, nmin;
-    double delta, phi_tol, fmax, maxstep, dtmax, finc, fdec, astart, fa;
+    int max_steps, max_rot_first, max_rot;
+    double delta, phi_tol, fmax;
+    FireKnobs fire;
 };
 struct DimerView {
     DimerState *st;                 // [G]
@@ -295,24 +297,8 @@ k_dimer_advance(const int *__restrict__ cfg_start, const int *__restrict__ count
     vG = block_sum(vG, red);
     GG = block_sum(GG, red);
     vv = block_sum(vv, red);
-    double mix_a = 0.0, mix_s = 0.0, c1 = 0.0;
-    bool mix = false;
-    if (S.has_v) {
-        if (vG > 0.0) {
-            mix = true;
-            mix_a = S.a;
-            mix_s = S.a * sqrt(vv / GG);   // v = (1 - a) v + a G |v| / |G|
-            c1 = 1.0 - mix_a;
-            if (S.nsteps_pos > P.nmin) { S.dt = fmin(S.dt * P.finc, P.dtmax); S.a *= P.fa; }
-            S.nsteps_pos += 1;
-        } else {
-            S.a = P.astart; S.dt *= P.fdec; S.nsteps_pos = 0;
-        }
-    }
-    const double c2 = mix_s + S.dt;
-    const double nv2 = (c1 * c1) * vv + (2.0 * c1 * c2) * vG + (c2 * c2) * GG;
-    const double normdr = S.dt * sqrt(nv2);
-    const double scale = normdr > P.maxstep ? P.maxstep / normdr : 1.0;
+    const FireMix M = fire_update(S, P.fire, vG, GG, vv);
+    const double scale = fire_step_scale(S.dt, M, P.fire, vG, GG, vv);
     for (int i = tid; i < nat; i += nt) {
         const bool held = fx && fx[i];
         for (int k = 0; k < 3; ++k) {
@@ -321,7 +307,7 @@ k_dimer_advance(const int *__restrict__ cfg_start, const int *__restrict__ count
             No[t] = N[t];
             if (!held) {
                 const double G = saddle ? F0[t] - gn * N[t] : (-gn) * N[t];
-                double vk = mix ? (1.0 - mix_a) * v[t] + mix_s * G : 0.0;
+                double vk = M.mix ? (1.0 - M.mix_a) * v[t] + M.mix_s * G : 0.0;
                 vk += S.dt * G;
                 v[t] = vk;
                 x0[t] += scale * (S.dt * vk);
@@ -350,53 +336,21 @@ struct DimerWork {
 static void dimer_launch(vssr_handle *h, const DimerWork &W) {
     hipStream_t st = h->stream;
     h->prof.begin(KC_DIMER, st);
-    if (is_analytic(h))
-        hipLaunchKernelGGL(k_dimer_advance<double>, dim3(W.ng), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                           h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), W.fixed, W.P, h->d_pos.as<double>(), W.V,
+    with_forces(h, [&](const double *energy, auto *forces) {
+        hipLaunchKernelGGL(k_dimer_advance<force_type<decltype(forces)>>, dim3(W.ng), dim3(256), 0, st, h->d_cfg_start.as<int>(),
+                           h->d_counters.as<int>(), energy, forces, W.fixed, W.P, h->d_pos.as<double>(), W.V,
                            h->d_active.as<unsigned char>(), W.flags);
-    else
-        hipLaunchKernelGGL(k_dimer_advance<float>, dim3(W.ng), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                           h->d_energy64.as<double>(), h->d_forces.as<float>(), W.fixed, W.P, h->d_pos.as<double>(), W.V,
-                           h->d_active.as<unsigned char>(), W.flags);
+    });
     h->prof.end(st);
 }
 
 static int dimer_lockstep(vssr_handle *h, const DimerWork &W, uint32_t want) {
-    hipStream_t st = h->stream;
-    const int B = h->n_cfg;
-    // As relax_lockstep: the activity mask reaches the evaluation kernels only once a dimer has stopped
-    h->active_mask = nullptr;
-    bool masked = false;
-    const int POLL = 8;
     // evaluations a dimer can consume: one E per step and the last test, and every rotation it is allowed
-    const long long max_launch = (long long)W.P.max_steps + 1 + W.P.max_rot_first + (long long)W.P.max_steps * W.P.max_rot;
-    int stopped[2] = {0, 0};
-    int rc = VSSR_OK;
-    for (long long it = 0; !rc; ++it) {
-        const bool spent = it >= max_launch;
-        const bool poll_it = spent || (it + 1) % POLL == 0;
-        if (!spent) {
-            if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) break;
-            ++h->relax_lockstep;
-            h->relax_chain_evals += B;
-            dimer_launch(h, W);
-        }
-        if (!poll_it) continue;
-        VSSR_HIP(h, hipMemcpyAsync(stopped, W.flags, sizeof(stopped), hipMemcpyDeviceToHost, st));
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (h->h_counters[2]) { rc = relax_regrow(h, 64, it, POLL + spent); continue; }
-        if (spent || stopped[0] == W.ng) break;
-        if (!masked && stopped[0] > 0) { h->active_mask = h->d_active.as<unsigned char>(); masked = true; }
-    }
-    h->active_mask = nullptr;
-    if (rc) return rc;
-    if (stopped[0] != W.ng) return set_err(h, VSSR_E_DEVICE, "vssr_batch_dimer: the dimer loop did not finish");
-    // The closing evaluation over all chains, where the last one of the loop is not that already
-    if (stopped[1] > 0 || masked) {
-        if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) return rc;
-        ++h->relax_lockstep;
-        h->relax_chain_evals += B;
-    }
+    LockstepPlan plan{8, (long long)W.P.max_steps + 1 + W.P.max_rot_first + (long long)W.P.max_steps * W.P.max_rot, LOCKSTEP_MASK_AT_STOP};
+    plan.stopped = W.flags; plan.groups = W.ng;
+    bool finished;
+    if (int rc = lockstep_run(h, plan, want, finished, [&] { dimer_launch(h, W); })) return rc;
+    if (!finished) return set_err(h, VSSR_E_DEVICE, "vssr_batch_dimer: the dimer loop did not finish");
     return VSSR_OK;
 }
 
@@ -414,17 +368,13 @@ extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, cons
     if (p->max_steps < 0) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: max_steps %d < 0", (int)p->max_steps);
     if (p->max_rot_first < 0) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: max_rot_first %d < 0", (int)p->max_rot_first);
     if (p->max_rot < 0) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: max_rot %d < 0", (int)p->max_rot);
+    // (a negative nmin has always been reported ahead of delta and fmax here: it keeps its place; fire_check finds it in order otherwise)
     if (p->nmin < 0) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: nmin %d < 0", (int)p->nmin);
     auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
     if (!positive(p->delta)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: delta %g A (finite and > 0 wanted)", p->delta);
     if (!positive(p->fmax)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: fmax %g eV/A (finite and > 0 wanted)", p->fmax);
-    if (!positive(p->dt)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: dt %g (finite and > 0 wanted)", p->dt);
-    if (!positive(p->maxstep)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: maxstep %g A (finite and > 0 wanted)", p->maxstep);
-    if (!positive(p->dtmax)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: dtmax %g (finite and > 0 wanted)", p->dtmax);
-    if (!(std::isfinite(p->finc) && p->finc >= 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: finc %g (finite and >= 1 wanted)", p->finc);
-    if (!(p->fdec > 0.0 && p->fdec < 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: fdec %g outside (0, 1)", p->fdec);
-    if (!(p->fa > 0.0 && p->fa < 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: fa %g outside (0, 1)", p->fa);
-    if (!(p->astart > 0.0 && p->astart <= 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: astart %g outside (0, 1]", p->astart);
+    const FireKnobs fire{p->dtmax, p->finc, p->fdec, p->astart, p->fa, p->maxstep, p->nmin};
+    if (int rc = fire_check(h, __func__, p->dt, fire)) return rc;
     if (!(p->phi_tol > 0.0 && p->phi_tol <= 0.25 * M_PI))
         return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: phi_tol %g rad outside (0, pi / 4]", p->phi_tol);
     if (!std::isfinite(p->displace)) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: displace %g A is not finite", p->displace);
@@ -476,21 +426,13 @@ extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, cons
     W.V.info = ip; ip += 4 * (size_t)ng;
     W.flags = ip;
     W.ng = ng;
-    W.P = {p->max_steps, p->max_rot_first, p->max_rot, p->nmin, p->delta, p->phi_tol, p->fmax, p->maxstep, p->dtmax, p->finc, p->fdec,
-           p->astart, p->fa};
+    W.P = {p->max_steps, p->max_rot_first, p->max_rot, p->delta, p->phi_tol, p->fmax, fire};
     std::vector<unsigned long long> ids(ng);
     for (int g = 0; g < ng; ++g) ids[g] = dimer_id ? (unsigned long long)dimer_id[g] : (unsigned long long)g;
-    VSSR_HIP(h, hipMemcpyAsync(W.ch, ch.data(), sizeof(NebChain) * B, hipMemcpyHostToDevice, st));
     VSSR_HIP(h, hipMemcpyAsync(W.ids, ids.data(), sizeof(unsigned long long) * ng, hipMemcpyHostToDevice, st));
-    VSSR_HIP(h, hipMemsetAsync(W.flags, 0, sizeof(int) * 4, st));
-    int mismatch = 0;
-    hipLaunchKernelGGL(k_neb_compare, dim3(B), dim3(256), 0, st, W.ch, h->d_cfg_start.as<int>(), h->d_Z.as<int>(),
-                       h->d_cell.as<unsigned long long>(), h->d_pbc.as<unsigned char>(), W.flags + 2);
-    VSSR_HIP(h, hipGetLastError());
-    VSSR_HIP(h, hipMemcpyAsync(&mismatch, W.flags + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-    VSSR_HIP(h, hipStreamSynchronize(st));   // (the host vectors leave scope with the call; nothing has moved yet)
-    if (mismatch)
-        return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: the two chains of a dimer differ in more than positions (species, cell or pbc; the comparison is bitwise)");
+    if (int rc = neb_compare_groups(h, ch, W.ch, W.flags,
+                                    "vssr_batch_dimer: the two chains of a dimer differ in more than positions (species, cell or pbc; the comparison is bitwise)"))
+        return rc;
 
     W.fixed = nullptr;
     if (int rc = relax_begin(h, fixed, 2, W.fixed)) return rc;
@@ -513,8 +455,7 @@ extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, cons
     if (int rc = sync_and_check(h)) return rc;   // (the last evaluation may itself have overflowed the capacity: grow and repeat it)
 
     if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * n3, hipMemcpyDeviceToHost));
-    if (energy)
-        VSSR_HIP(h, hipMemcpy(energy, is_analytic(h) ? h->d_pot_e.p : h->d_energy64.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+    if (energy) VSSR_HIP(h, hipMemcpy(energy, chain_energy64(h), sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
     if (mode_out) VSSR_HIP(h, hipMemcpy(mode_out, W.V.N, sizeof(double) * n3, hipMemcpyDeviceToHost));
     if (dimer) VSSR_HIP(h, hipMemcpy(dimer, W.V.rec, sizeof(double) * 4 * (size_t)ng, hipMemcpyDeviceToHost));
     if (info) VSSR_HIP(h, hipMemcpy(info, W.V.info, sizeof(int) * 4 * (size_t)ng, hipMemcpyDeviceToHost));

@@ -1,9 +1,8 @@
 // md.hip — molecular dynamics of every chain of the resident batch, on every handle kind that relaxes: velocity Verlet (NVE) and
 // Langevin BAOAB.  The lock-step driver: one batch-wide evaluation per time step, one k_md_step launch behind it (one workgroup per
-// chain, the integrator of md_dev.h); positions, velocities and forces never leave HBM.  The driver frame is relax_bfgsls.hip's:
-// relax_begin, a poll every few evaluations, relax_regrow after a neighbor-capacity overflow (the step kernels behind an overflowed
-// evaluation moved nothing, and every random number is keyed by the chain's own step counter, so a repeated evaluation retraces
-// nothing twice).  The analytic kinds integrate their fp64 forces (d_pot_f), PaiNN its fp32 forces widened and the fp64
+// chain, the integrator of md_dev.h); positions, velocities and forces never leave HBM.  The driver frame is lockstep.h's (every
+// random number is keyed by the chain's own step counter, so an evaluation repeated after a regrow retraces nothing twice).  The
+// analytic kinds integrate their fp64 forces (d_pot_f), PaiNN its fp32 forces widened and the fp64
 // ensemble-mean energy.  The chain-resident driver (k_md_chain, chain_min.hip) runs the same md_step_chain; the entry points below
 // choose between the two.
 // Out of scope: variable cells, thermostats other than Langevin, constraints other than FixAtoms, centre-of-mass removal (slabs hold
@@ -11,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <vector>
+#include "lockstep.h"
 #include "md_dev.h"
 
 namespace vssr {
@@ -118,49 +118,19 @@ int md_end(vssr_handle *h, const MdWork &W, double *thermo_out) {
 }
 
 int md_lockstep(vssr_handle *h, const MdWork &W, uint32_t want) {
-    hipStream_t st = h->stream;
     const int B = h->n_cfg;
-    unsigned char *active = h->d_active.as<unsigned char>();
-    // As relax_lockstep: the activity mask reaches the evaluation kernels only once a chain has stopped early (a non-finite chain);
-    // an ordinary run never pays for the masked forms of the kernels, and all its chains finish in the same launch.
-    h->active_mask = nullptr;
-    bool masked = false;
-    const bool f64 = is_analytic(h);
-    const int POLL = 8;
-    const long long max_launch = (long long)W.P.n_steps + 1;   // evaluations a chain needs: the initial state and one per step
-    int stopped[2] = {0, 0};
-    int rc = VSSR_OK;
-    for (long long it = 0; !rc; ++it) {
-        const bool spent = it >= max_launch;
-        const bool poll_it = spent || (it + 1) % POLL == 0;
-        if (!spent) {
-            if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) break;
-            ++h->relax_lockstep;
-            h->relax_chain_evals += B;
-            if (f64)
-                hipLaunchKernelGGL(k_md_step<double>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                   h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), W.fixed, W.P, h->d_pos.as<double>(), W.V, active, W.stopped);
-            else
-                hipLaunchKernelGGL(k_md_step<float>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                   h->d_energy64.as<double>(), h->d_forces.as<float>(), W.fixed, W.P, h->d_pos.as<double>(), W.V, active, W.stopped);
-        }
-        if (!poll_it) continue;
-        VSSR_HIP(h, hipMemcpyAsync(stopped, W.stopped, sizeof(stopped), hipMemcpyDeviceToHost, st));
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (h->h_counters[2]) { rc = relax_regrow(h, 64, it, POLL + spent); continue; }
-        if (spent || stopped[0] == B) break;
-        if (!masked && stopped[0] > 0) { h->active_mask = active; masked = true; }
-    }
-    h->active_mask = nullptr;
-    if (rc) return rc;
-    // A chain that stopped early went back to its last completed step, and the evaluations behind that may have skipped it: one
-    // evaluation over all chains leaves the batch complete.  Otherwise the last evaluation of the loop is that evaluation already.
-    if (stopped[1] > 0 || masked) {
-        if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) return rc;
-        ++h->relax_lockstep;
-        h->relax_chain_evals += B;
-    }
-    return VSSR_OK;
+    // evaluations a chain needs: the initial state and one per step.  Only a non-finite chain stops early: it went back to its last
+    // completed step, which asks for the closing evaluation.  (A loop the budget ended is no error here.)
+    LockstepPlan plan{8, (long long)W.P.n_steps + 1, LOCKSTEP_MASK_AT_STOP};
+    plan.stopped = W.stopped; plan.groups = B;
+    bool finished;
+    return lockstep_run(h, plan, want, finished, [&] {
+        with_forces(h, [&](const double *energy, auto *forces) {
+            hipLaunchKernelGGL(k_md_step<force_type<decltype(forces)>>, dim3(B), dim3(256), 0, h->stream, h->d_cfg_start.as<int>(),
+                               h->d_counters.as<int>(), energy, forces, W.fixed, W.P, h->d_pos.as<double>(), W.V,
+                               h->d_active.as<unsigned char>(), W.stopped);
+        });
+    });
 }
 
 static int md_masses_ok(vssr_handle *h, const char *func, const double *mass) {
@@ -264,15 +234,7 @@ int vssr_batch_md(vssr_handle *h, const vssr_md_params *p, const double *mass, c
     h->md_last_driver = resident ? VSSR_MD_DRIVER_RESIDENT : VSSR_MD_DRIVER_LOCKSTEP;
     h->graph_partial = resident;     // (the lock-step driver leaves the batch-wide graph of its last evaluation, the chain-resident one
                                      //  numbers its rows per chain: introspection wants one plain run first)
-    if (int rc = sync_and_check(h)) return rc;   // (a last batch-wide evaluation may itself have overflowed the capacity: grow and repeat it)
-    if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
-    std::vector<int> rep((size_t)2 * h->n_cfg);
-    VSSR_HIP(h, hipMemcpy(rep.data(), h->d_relax_steps.p, sizeof(int) * rep.size(), hipMemcpyDeviceToHost));
-    for (int b = 0; b < h->n_cfg; ++b) {
-        if (n_done) n_done[b] = rep[2 * b];
-        if (stop_reason) stop_reason[b] = rep[2 * b + 1];
-    }
-    return VSSR_OK;
+    return relax_results(h, pos_out, {n_done, stop_reason});
 }
 
 int vssr_batch_md_driver(vssr_handle *h, int32_t driver, int32_t *last_used) {

@@ -2,10 +2,9 @@
 // Jonsson, J. Chem. Phys. 113, 9978 (2000)), ASE's `aseneb` variant, the climbing image (Henkelman, Uberuaga & Jonsson, J. Chem. Phys.
 // 113, 9901 (2000)) and ASE's FIRE over the concatenated interior images of a band.  Restated from the papers and from ASE's neb.py /
 // fire.py as remembered, NOT pinned by an executed ASE; the contract is the numpy restatement tests/neb_oracle.py.
-// A BAND is n_img consecutive chains (its images).  The driver frame is md.hip's / vib.hip's: one batch-wide evaluation per step, two
-// launches behind it (one workgroup per chain each), a poll every few steps, relax_regrow after a neighbor-capacity overflow (both
-// kernels return at once behind an overflowed evaluation, and state advances only in k_neb_step, so a repeated evaluation moves
-// nothing twice).
+// A BAND is n_img consecutive chains (its images).  The driver frame is lockstep.h's: one batch-wide evaluation per step, two
+// launches behind it (one workgroup per chain each; state advances only in k_neb_step, so an evaluation repeated after a regrow
+// moves nothing twice).
 //   k_neb_project  an interior image reads its two neighbours' positions and the band's energies, forms t1, t2 and the tangent, writes
 //                  G [3 N] and its partial sums (v.G, G.G, v.v, max |G_atom|^2, non-finite flag, zero-tangent flag) to its own slot;
 //                  an end image writes zeros and its non-finite flag.
@@ -13,8 +12,7 @@
 //                  the same band scalars without a third launch or a grid sync; every image carries its own copy of the band's FIRE
 //                  state (nothing another workgroup writes is read in the same launch) and moves its own v and x.  The first
 //                  interior image writes the band's outputs and counts the band as stopped.
-// The norm |dt v'| of the new velocity v' = c1 v + c2 G over the band follows from the three sums, which is what saves the second
-// reduction pass of a step.  Chains of a stopped band leave the evaluation through d_active, as in relax_lockstep; one last unmasked
+// The FIRE update is fire_dev.h's, with the step length from the three sums.  Chains of a stopped band leave the evaluation through d_active, as in relax_lockstep; one last unmasked
 // evaluation restores the complete graph where the mask was installed or a band went back to the positions its step opened at.
 // Out of scope: other optimizers over the band, IDPP interpolation, free-end / string / eb / spline variants, per-spring constants,
 // dynamic relaxation, a full minimum-image search, removal of rotation and translation, taking the end images out of the evaluation.
@@ -24,6 +22,8 @@
 #include <vector>
 
 #include "cg_dev.h"
+#include "fire_dev.h"
+#include "lockstep.h"
 #include "neb_dev.h"
 
 namespace vssr {
@@ -37,8 +37,9 @@ struct NebState {   // per chain: every image carries its band's state
     int steps, reason, imax, pad;
 };
 struct NebParams {
-    int max_steps, method, climb, nmin;
-    double k, fmax, maxstep, dtmax, finc, fdec, astart, fa;
+    int max_steps, method, climb;
+    double k, fmax;
+    FireKnobs fire;
 };
 struct NebView {
     NebState *st;            // [B]
@@ -261,24 +262,8 @@ k_neb_step(const int *__restrict__ cfg_start, const int *__restrict__ counters, 
     if (zt) { stop(4, 0); return; }
     if (S.steps >= P.max_steps) { stop(2, 0); return; }
     // ASE FIRE on the band: v' = c1 v + c2 G
-    double mix_a = 0.0, mix_s = 0.0, c1 = 0.0;
-    bool mix = false;
-    if (S.has_v) {
-        if (vG > 0.0) {
-            mix = true;
-            mix_a = S.a;
-            mix_s = S.a * sqrt(vv / GG);   // v = (1 - a) v + a G |v| / |G|
-            c1 = 1.0 - mix_a;
-            if (S.nsteps_pos > P.nmin) { S.dt = fmin(S.dt * P.finc, P.dtmax); S.a *= P.fa; }
-            S.nsteps_pos += 1;
-        } else {
-            S.a = P.astart; S.dt *= P.fdec; S.nsteps_pos = 0;
-        }
-    }
-    const double c2 = mix_s + S.dt;
-    const double nv2 = (c1 * c1) * vv + (2.0 * c1 * c2) * vG + (c2 * c2) * GG;
-    const double normdr = S.dt * sqrt(nv2);
-    const double scale = normdr > P.maxstep ? P.maxstep / normdr : 1.0;
+    const FireMix M = fire_update(S, P.fire, vG, GG, vv);
+    const double scale = fire_step_scale(S.dt, M, P.fire, vG, GG, vv);
     if (interior)
         for (int i = tid; i < nat; i += nt) {
             const bool held = fx && fx[i];
@@ -286,7 +271,7 @@ k_neb_step(const int *__restrict__ cfg_start, const int *__restrict__ counters, 
                 const int t = 3 * i + k;
                 xp[t] = x[t];
                 if (held) continue;
-                double vk = mix ? (1.0 - mix_a) * v[t] + mix_s * G[t] : 0.0;
+                double vk = M.mix ? (1.0 - M.mix_a) * v[t] + M.mix_s * G[t] : 0.0;
                 vk += S.dt * G[t];
                 v[t] = vk;
                 x[t] += scale * (S.dt * vk);
@@ -320,58 +305,26 @@ static void neb_launch(vssr_handle *h, const NebWork &W) {
     hipStream_t st = h->stream;
     const int B = h->n_cfg;
     h->prof.begin(KC_NEB_PROJECT, st);
-    if (is_analytic(h))
-        hipLaunchKernelGGL(k_neb_project<double>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                           h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), W.fixed, h->d_cell.as<double>(), h->d_invcell.as<double>(),
+    with_forces(h, [&](const double *energy, auto *forces) {
+        hipLaunchKernelGGL(k_neb_project<force_type<decltype(forces)>>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(),
+                           h->d_counters.as<int>(), energy, forces, W.fixed, h->d_cell.as<double>(), h->d_invcell.as<double>(),
                            h->d_pbc.as<unsigned char>(), W.P, h->d_pos.as<double>(), W.V);
-    else
-        hipLaunchKernelGGL(k_neb_project<float>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                           h->d_energy64.as<double>(), h->d_forces.as<float>(), W.fixed, h->d_cell.as<double>(), h->d_invcell.as<double>(),
-                           h->d_pbc.as<unsigned char>(), W.P, h->d_pos.as<double>(), W.V);
+    });
     h->prof.end(st);
     h->prof.begin(KC_NEB_STEP, st);
-    hipLaunchKernelGGL(k_neb_step, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                       is_analytic(h) ? h->d_pot_e.as<double>() : h->d_energy64.as<double>(), W.fixed, W.P, h->d_pos.as<double>(), W.V,
-                       h->d_active.as<unsigned char>(), W.flags);
+    hipLaunchKernelGGL(k_neb_step, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(), chain_energy64(h), W.fixed,
+                       W.P, h->d_pos.as<double>(), W.V, h->d_active.as<unsigned char>(), W.flags);
     h->prof.end(st);
 }
 
 static int neb_lockstep(vssr_handle *h, const NebWork &W, uint32_t want) {
-    hipStream_t st = h->stream;
-    const int B = h->n_cfg;
-    // As relax_lockstep: the activity mask reaches the evaluation kernels only once a band has stopped
-    h->active_mask = nullptr;
-    bool masked = false;
-    const int POLL = 8;
-    const long long max_launch = (long long)W.P.max_steps + 1;   // evaluations a band needs: one per step and the last test
-    int stopped[2] = {0, 0};
-    int rc = VSSR_OK;
-    for (long long it = 0; !rc; ++it) {
-        const bool spent = it >= max_launch;
-        const bool poll_it = spent || (it + 1) % POLL == 0;
-        if (!spent) {
-            if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) break;
-            ++h->relax_lockstep;
-            h->relax_chain_evals += B;
-            neb_launch(h, W);
-        }
-        if (!poll_it) continue;
-        VSSR_HIP(h, hipMemcpyAsync(stopped, W.flags, sizeof(stopped), hipMemcpyDeviceToHost, st));
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (h->h_counters[2]) { rc = relax_regrow(h, 64, it, POLL + spent); continue; }
-        if (spent || stopped[0] == W.nb) break;
-        if (!masked && stopped[0] > 0) { h->active_mask = h->d_active.as<unsigned char>(); masked = true; }
-    }
-    h->active_mask = nullptr;
-    if (rc) return rc;
-    if (stopped[0] != W.nb) return set_err(h, VSSR_E_DEVICE, "vssr_batch_neb: the band loop did not finish");
-    // A band that went back to the positions its step opened at, or chains the masked evaluations skipped: one evaluation over all
-    // chains leaves the batch complete.  Otherwise the last evaluation of the loop is that evaluation already.
-    if (stopped[1] > 0 || masked) {
-        if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) return rc;
-        ++h->relax_lockstep;
-        h->relax_chain_evals += B;
-    }
+    // evaluations a band needs: one per step and the last test.  A band that went back to the positions its step opened at asks
+    // for the closing evaluation.
+    LockstepPlan plan{8, (long long)W.P.max_steps + 1, LOCKSTEP_MASK_AT_STOP};
+    plan.stopped = W.flags; plan.groups = W.nb;
+    bool finished;
+    if (int rc = lockstep_run(h, plan, want, finished, [&] { neb_launch(h, W); })) return rc;
+    if (!finished) return set_err(h, VSSR_E_DEVICE, "vssr_batch_neb: the band loop did not finish");
     return VSSR_OK;
 }
 
@@ -393,14 +346,8 @@ extern "C" int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const ui
     auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
     if (!positive(p->k)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: spring constant k %g eV/A^2 (finite and > 0 wanted)", p->k);
     if (!positive(p->fmax)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: fmax %g eV/A (finite and > 0 wanted)", p->fmax);
-    if (!positive(p->dt)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: dt %g (finite and > 0 wanted)", p->dt);
-    if (!positive(p->maxstep)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: maxstep %g A (finite and > 0 wanted)", p->maxstep);
-    if (!positive(p->dtmax)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: dtmax %g (finite and > 0 wanted)", p->dtmax);
-    if (!(std::isfinite(p->finc) && p->finc >= 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: finc %g (finite and >= 1 wanted)", p->finc);
-    if (!(p->fdec > 0.0 && p->fdec < 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: fdec %g outside (0, 1)", p->fdec);
-    if (!(p->fa > 0.0 && p->fa < 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: fa %g outside (0, 1)", p->fa);
-    if (!(p->astart > 0.0 && p->astart <= 1.0)) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: astart %g outside (0, 1]", p->astart);
-    if (p->nmin < 0) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: nmin %d < 0", (int)p->nmin);
+    const FireKnobs fire{p->dtmax, p->finc, p->fdec, p->astart, p->fa, p->maxstep, p->nmin};
+    if (int rc = fire_check(h, __func__, p->dt, fire)) return rc;
     const int B = h->n_cfg, N = h->n_atoms, nb = n_bands;
     {
         long long sum = 0;
@@ -450,18 +397,11 @@ extern "C" int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const ui
     W.V.st = h->d_opt_state.as<NebState>();
     W.V.vel = h->d_opt_vec.as<double>(); W.V.xprev = W.V.vel + n3;
     W.nb = nb;
-    W.P = {p->max_steps, p->method, p->climb, p->nmin, p->k, p->fmax, p->maxstep, p->dtmax, p->finc, p->fdec, p->astart, p->fa};
-    VSSR_HIP(h, hipMemcpyAsync(W.ch, ch.data(), sizeof(NebChain) * B, hipMemcpyHostToDevice, st));
+    W.P = {p->max_steps, p->method, p->climb, p->k, p->fmax, fire};
     VSSR_HIP(h, hipMemcpyAsync(W.gfirst, gfirst.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
-    VSSR_HIP(h, hipMemsetAsync(W.flags, 0, sizeof(int) * 4, st));
-    int mismatch = 0;
-    hipLaunchKernelGGL(k_neb_compare, dim3(B), dim3(256), 0, st, W.ch, h->d_cfg_start.as<int>(), h->d_Z.as<int>(),
-                       h->d_cell.as<unsigned long long>(), h->d_pbc.as<unsigned char>(), W.flags + 2);
-    VSSR_HIP(h, hipGetLastError());
-    VSSR_HIP(h, hipMemcpyAsync(&mismatch, W.flags + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-    VSSR_HIP(h, hipStreamSynchronize(st));   // (the host vectors leave scope with the call; nothing has moved yet)
-    if (mismatch)
-        return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: the images of a band differ in more than positions (species, cell or pbc; the comparison is bitwise)");
+    if (int rc = neb_compare_groups(h, ch, W.ch, W.flags,
+                                    "vssr_batch_neb: the images of a band differ in more than positions (species, cell or pbc; the comparison is bitwise)"))
+        return rc;
 
     W.fixed = nullptr;
     if (int rc = relax_begin(h, fixed, 2, W.fixed)) return rc;
@@ -480,8 +420,7 @@ extern "C" int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const ui
     if (int rc = sync_and_check(h)) return rc;   // (the last evaluation may itself have overflowed the capacity: grow and repeat it)
 
     if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * n3, hipMemcpyDeviceToHost));
-    if (energy)
-        VSSR_HIP(h, hipMemcpy(energy, is_analytic(h) ? h->d_pot_e.p : h->d_energy64.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+    if (energy) VSSR_HIP(h, hipMemcpy(energy, chain_energy64(h), sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
     if (neb_force) VSSR_HIP(h, hipMemcpy(neb_force, W.V.G, sizeof(double) * n3, hipMemcpyDeviceToHost));
     if (band) VSSR_HIP(h, hipMemcpy(band, W.V.band, sizeof(double) * 3 * (size_t)nb, hipMemcpyDeviceToHost));
     if (info) VSSR_HIP(h, hipMemcpy(info, W.V.binfo, sizeof(int) * 4 * (size_t)nb, hipMemcpyDeviceToHost));

@@ -25,5 +25,21 @@ k_neb_compare(const NebChain *__restrict__ ch, const int *__restrict__ cfg_start
     if (diff) flag[0] = 1;   // (same value from every writer)
 }
 
+// The host side of it: the chain table to ch_d, the call's four flags cleared, the comparison into flags[2]; VSSR_E_BADARG with the
+// caller's text where a group's chains differ.  Synchronises: host arrays the caller queued for upload before may leave scope after.
+static int neb_compare_groups(vssr_handle *h, const std::vector<NebChain> &ch, NebChain *ch_d, int *flags, const char *differ_text) {
+    hipStream_t st = h->stream;
+    const int B = h->n_cfg;
+    VSSR_HIP(h, hipMemcpyAsync(ch_d, ch.data(), sizeof(NebChain) * B, hipMemcpyHostToDevice, st));
+    VSSR_HIP(h, hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    int mismatch = 0;
+    hipLaunchKernelGGL(k_neb_compare, dim3(B), dim3(256), 0, st, ch_d, h->d_cfg_start.as<int>(), h->d_Z.as<int>(),
+                       h->d_cell.as<unsigned long long>(), h->d_pbc.as<unsigned char>(), flags + 2);
+    VSSR_HIP(h, hipGetLastError());
+    VSSR_HIP(h, hipMemcpyAsync(&mismatch, flags + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    VSSR_HIP(h, hipStreamSynchronize(st));   // (nothing has moved yet)
+    return mismatch ? set_err(h, VSSR_E_BADARG, "%s", differ_text) : (int)VSSR_OK;
+}
+
 }  // namespace vssr
 #endif

@@ -25,9 +25,11 @@
 // solved by cyclic Jacobi rotations in LDS, fp64.  Pinned against the reference's stored BFGS traces through
 // tests/bfgs_oracle.py (dense restatement of ASE's algorithm) -- tests/test_bfgs.py.
 //
-// Both run in one driver frame, relax_lockstep<FireWork | BfgsWork>; its prologue and regrow also serve the CG driver (relax_cg.hip).
+// Both run in one driver frame, relax_lockstep<FireWork | BfgsWork>; its prologue and regrow also serve the frame of the other
+// lock-step drivers (lockstep.h).
 #include <algorithm>
 #include "cg_dev.h"
+#include "fire_dev.h"
 
 namespace vssr {
 
@@ -91,27 +93,16 @@ k_fire_step(const int *__restrict__ cfg_start, const int *__restrict__ counters,
     vf = block_sum(vf, red);
     ff = block_sum(ff, red);
     vv = block_sum(vv, red);
-    double mix_a = 0.0, mix_s = 0.0;
-    bool zero_v = false;
-    if (S.has_v) {
-        if (vf > 0.0) {
-            mix_a = S.a;
-            mix_s = S.a * sqrt(vv / ff);   // v = (1 - a) v + a f |v| / |f|
-            if (S.nsteps_pos > nmin) { S.dt = fmin(S.dt * finc, dtmax); S.a *= fa; }
-            S.nsteps_pos += 1;
-        } else {
-            zero_v = true;
-            S.a = astart; S.dt *= fdec; S.nsteps_pos = 0;
-        }
-    }
+    const FireKnobs K{dtmax, finc, fdec, astart, fa, maxstep, nmin};
+    const FireMix M = fire_update(S, K, vf, ff, vv);
     // v <- mix(v, f) + dt f ; dr = dt v
     double dr2 = 0.0;
     for (int i = a0 + tid; i < a1; i += blockDim.x) {
         const bool fx_ = fixed && fixed[i];
         for (int x = 0; x < 3; ++x) {
             double f = fx_ ? 0.0 : (double)forces[3 * i + x];
-            double v = (S.has_v && !zero_v) ? vel[3 * i + x] : 0.0;
-            if (S.has_v && !zero_v) v = (1.0 - mix_a) * v + mix_s * f;
+            double v = M.mix ? vel[3 * i + x] : 0.0;
+            if (M.mix) v = (1.0 - M.mix_a) * v + M.mix_s * f;
             v += S.dt * f;
             vel[3 * i + x] = v;
             dr2 += (S.dt * v) * (S.dt * v);
@@ -456,7 +447,7 @@ k_traj_record(const int *__restrict__ cfg_start, const int *__restrict__ counter
     }
 }
 
-// ---- shared by the relaxation drivers (relax_lockstep below, relax_cg.hip; relax_begin also chain_min.hip) ------------------
+// ---- shared by the lock-step drivers (relax_lockstep below, lockstep.h; relax_begin also chain_min.hip) ---------------------
 // Per-relaxation buffers, the FixAtoms mask on the device (`fixed`: null without a mask), the work counters at zero.
 int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed) {
     const size_t B = h->n_cfg, N = h->n_atoms;
@@ -475,6 +466,21 @@ int relax_regrow(vssr_handle *h, int cap, long long &it, int window) {
     if (int rc = grow_slot_cap(h)) return rc;
     if (++h->relax_regrows > cap) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
     it = std::max(it - window, -1LL);
+    return VSSR_OK;
+}
+
+int relax_results(vssr_handle *h, double *pos_out, std::initializer_list<int32_t *> cols) {
+    if (int rc = sync_and_check(h)) return rc;   // (a last batch-wide evaluation may itself have overflowed the capacity: grow and repeat it)
+    if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
+    const size_t k = cols.size();
+    std::vector<int> rep(k * h->n_cfg);
+    VSSR_HIP(h, hipMemcpy(rep.data(), h->d_relax_steps.p, sizeof(int) * rep.size(), hipMemcpyDeviceToHost));
+    size_t c = 0;
+    for (int32_t *col : cols) {
+        if (col)
+            for (int b = 0; b < h->n_cfg; ++b) col[b] = rep[k * b + c];
+        ++c;
+    }
     return VSSR_OK;
 }
 

@@ -1,11 +1,12 @@
 // relax_bfgsls.hip — lock-step BFGSLineSearch on every handle kind (the reference's `optimizer: "BFGSLineSearch"`, mcmc/dynamics.py:119-127
 // -> ase.optimize.BFGSLineSearch): the driver that steps every chain's state machine (bfgsls_dev.h) once per batch-wide evaluation, with
-// the prologue and regrow of relax.hip.  Evaluation-counted like relax_cg: a trial of a line search costs one lock-step evaluation, and
+// the frame of lockstep.h.  Evaluation-counted like relax_cg: a trial of a line search costs one lock-step evaluation, and
 // the evaluation that ends a line search opens the next step.  Not pinned by an executed ASE: see the header of bfgsls_dev.h.
 // Out of scope here: live-chain compaction (relax_cg.hip's Compactor) and a chain-resident form (chain_min.hip); finished chains are
 // skipped through the activity mask only.
 #include <algorithm>
 #include "bfgsls_dev.h"
+#include "lockstep.h"
 
 namespace vssr {
 
@@ -73,40 +74,20 @@ int relax_bfgsls(vssr_handle *h, const vssr_bfgsls_params *bp, const uint8_t *fi
     const BlsParams P{bp->max_steps, bp->max_eval, bp->fmax, bp->alpha, bp->maxstep, bp->c1, bp->c2, bp->stpmax, 1e-8, 1e-14, 1.1, 4.0};
     unsigned char *active = h->d_active.as<unsigned char>();
     hipLaunchKernelGGL(k_bls_init, dim3((B + 127) / 128), dim3(128), 0, st, B, V.st, active);
-    h->active_mask = active;
-    int *running_d = h->d_counters.as<int>() + 3;
-    const bool f64 = is_analytic(h);   // fp64 energies and forces of the potential; PaiNN: the fp64 ensemble mean and fp32 forces, widened
-    const int POLL = 4;
-    // every launch is one evaluation for every chain still running, and a chain stops once it has spent max_eval of them
-    const long long max_launch = (long long)bp->max_eval + 2;
-    int rc = VSSR_OK;
-    for (long long it = 0; !rc; ++it) {
-        const bool spent = it >= max_launch;   // the budget ran out between two polls: look at the last window as well
-        const bool poll_it = spent || (it + 1) % POLL == 0;
-        if (!spent) {
-            if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) break;
-            ++h->relax_lockstep;
-            h->relax_chain_evals += B;
-            if (poll_it) VSSR_HIP(h, hipMemsetAsync(running_d, 0, sizeof(int), st));
-            if (f64)
-                hipLaunchKernelGGL(k_bls_step<double>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                   h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), fixed, P, h->d_pos.as<double>(), V, active, running_d);
-            else
-                hipLaunchKernelGGL(k_bls_step<float>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                                   h->d_energy64.as<double>(), h->d_forces.as<float>(), fixed, P, h->d_pos.as<double>(), V, active, running_d);
-            if (poll_it) VSSR_HIP(h, hipMemcpyAsync(h->h_counters + 3, running_d, sizeof(int), hipMemcpyDeviceToHost, st));
-        }
-        if (!poll_it) continue;
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (h->h_counters[2]) { rc = relax_regrow(h, 64, it, POLL + spent); continue; }
-        if (spent || h->h_counters[3] == 0) break;   // no chain asked for another evaluation
-    }
-    h->active_mask = nullptr;
+    // every launch is one evaluation for every chain still running (counted into counters[3]), and a chain stops once it has spent
+    // max_eval of them; finished chains leave the evaluation at once, so the closing evaluation always runs
+    LockstepPlan plan{4, (long long)bp->max_eval + 2, LOCKSTEP_MASK_FROM_START};
+    plan.always_close = true;
+    bool finished;
+    int rc = lockstep_run(h, plan, want, finished, [&] {
+        // fp64 energies and forces of the potential; PaiNN: the fp64 ensemble mean and fp32 forces, widened
+        with_forces(h, [&](const double *energy, auto *forces) {
+            hipLaunchKernelGGL(k_bls_step<force_type<decltype(forces)>>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(),
+                               h->d_counters.as<int>(), energy, forces, fixed, P, h->d_pos.as<double>(), V, active,
+                               h->d_counters.as<int>() + 3);
+        });
+    });
     if (rc) return rc;
-    // the results of the final positions for every chain (they were switched off at different times): the batch is left complete
-    if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) return rc;
-    ++h->relax_lockstep;
-    h->relax_chain_evals += B;
     hipLaunchKernelGGL(k_bls_report, dim3((B + 127) / 128), dim3(128), 0, st, B, V.st, h->d_relax_steps.as<int>());
     VSSR_HIP(h, hipGetLastError());
     h->ran = true;

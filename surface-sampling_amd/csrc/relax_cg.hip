@@ -1,8 +1,9 @@
 // relax_cg.hip — lock-step LAMMPS-style conjugate gradients on the fp64 potentials (the reference's `optimizer: "LAMMPS"`): the driver
-// that steps every chain's state machine (cg_dev.h) once per batch-wide evaluation, with the prologue and regrow of relax.hip, and
-// the Compactor that shrinks the resident batch to the chains still running.
+// that steps every chain's state machine (cg_dev.h) once per batch-wide evaluation in the frame of lockstep.h, and the Compactor
+// that shrinks the resident batch to the chains still running.
 #include <algorithm>
 #include "cg_dev.h"
+#include "lockstep.h"
 
 namespace vssr {
 
@@ -229,42 +230,26 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
     if (int e = CgWork::ensure(h, W)) return e;
     unsigned char *active = h->d_active.as<unsigned char>();
     hipLaunchKernelGGL(k_cg_init, dim3((h->n_cfg + 127) / 128), dim3(128), 0, st, h->n_cfg, W.st, active);
-    h->active_mask = active;
-    int *n_active_d = h->d_counters.as<int>() + 3;
-    const int POLL = 8;
     Compactor C{h, W, fixed, active, h->n_cfg, h->n_atoms, h->n_cfg, h->n_atoms};
     // every launch is one evaluation; max_eval is tested between line searches, and a line search ends after at most ~60
-    // halvings of alpha (fp64), so the launch budget is max_eval plus one line search plus setup / reset evaluations
-    const long long max_launch = (long long)cp->max_eval + 72;
-    int rc = VSSR_OK;
-    for (long long it = 0; !rc; ++it) {
-        const bool spent = it >= max_launch;   // the budget ran out between two polls: look at the last window as well
-        // the count of chains still running is read at the polls only: it is cleared and copied back in those iterations (the
-        // step kernels in between add to a value nobody looks at) -- two dispatches less per evaluation, ~15 of them at 48 atoms
-        const bool poll_it = spent || (it + 1) % POLL == 0;
-        if (!spent) {
-            if ((rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) break;
-            ++h->relax_lockstep;
-            h->relax_chain_evals += C.B_cur;
-            if (poll_it) VSSR_HIP(h, hipMemsetAsync(n_active_d, 0, sizeof(int), st));
+    // halvings of alpha (fp64), so the launch budget is max_eval plus one line search plus setup / reset evaluations.  The step
+    // kernel counts the chains still running into counters[3]; finished chains were switched off at different times, so the closing
+    // evaluation always runs.
+    LockstepPlan plan{8, (long long)cp->max_eval + 72, LOCKSTEP_MASK_FROM_START};
+    plan.always_close = true;
+    bool finished;
+    int rc = lockstep_run(
+        h, plan, want, finished,
+        [&] {
             hipLaunchKernelGGL(k_cg_step, dim3(C.B_cur), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                               h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), fixed, cp->max_iter, cp->max_eval, cp->etol,
-                               cp->ftol, cp->dmax, h->d_pos.as<double>(), W.x0, W.hh, W.gg, W.st, active, n_active_d);
-            if (poll_it) VSSR_HIP(h, hipMemcpyAsync(h->h_counters + 3, n_active_d, sizeof(int), hipMemcpyDeviceToHost, st));
-        }
-        if (!poll_it) continue;
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        // (spent: `it` is one past the window's last launch)
-        if (h->h_counters[2]) { rc = relax_regrow(h, 64, it, POLL + spent); continue; }
-        if (spent || h->h_counters[3] == 0) break;   // every chain has finished
-        if (C.due(h->h_counters[3])) rc = C.compact();
-    }
-    h->active_mask = nullptr;
-    if (rc) return C.abandon(rc);
-    // the uploaded batch again, then the results of the final positions for every chain (finished chains were switched off at different times)
-    if ((rc = C.restore()) || (rc = evaluator(h).run(h, want | VSSR_WANT_FORCES))) return rc;
-    ++h->relax_lockstep;
-    h->relax_chain_evals += C.B;
+                               h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), fixed, cp->max_iter, cp->max_eval, cp->etol, cp->ftol,
+                               cp->dmax, h->d_pos.as<double>(), W.x0, W.hh, W.gg, W.st, active, h->d_counters.as<int>() + 3);
+        },
+        [&](bool closing) -> int {   // the uploaded batch again before the closing evaluation; at a poll, a smaller resident batch where due
+            if (closing) return C.restore();
+            return C.due(h->h_counters[3]) ? C.compact() : (int)VSSR_OK;
+        });
+    if (rc) return C.abandon(rc);   // (nothing to abandon once restore has run)
     hipLaunchKernelGGL(k_cg_report, dim3((C.B + 127) / 128), dim3(128), 0, st, C.B, W.st, h->d_relax_steps.as<int>());
     VSSR_HIP(h, hipGetLastError());
     h->ran = true;

@@ -4,10 +4,9 @@
 // remembered; the contract is the numpy restatement tests/vib_oracle.py.
 // A GROUP is one structure, resident as n_rep identical consecutive chains (replicas).  Its m = 3 (vib atoms) degrees of freedom are
 // numbered by (vib atom in chain order, x / y / z); the replica of rank k works through the degrees of freedom r = k, k + n_rep, ...,
-// so that one structure's displacements fill the batch.  The driver frame is md.hip's: one batch-wide evaluation per displacement,
-// one k_vib_step launch behind it (one workgroup per chain), a poll every few evaluations, relax_regrow after a neighbor-capacity
-// overflow (the step kernel behind an overflowed evaluation does nothing, and what a chain does next follows from its own state, so a
-// repeated evaluation writes no row twice and skips none).  A displaced coordinate is x0 + k delta in one fp64 operation from a saved
+// so that one structure's displacements fill the batch.  The driver frame is lockstep.h's: one batch-wide evaluation per displacement,
+// one k_vib_step launch behind it (one workgroup per chain; what a chain does next follows from its own state, so an evaluation
+// repeated after a regrow writes no row twice and skips none).  A displaced coordinate is x0 + k delta in one fp64 operation from a saved
 // copy of x0, and goes back by copying the saved value.  nfree (largest share of a replica) + 1 evaluations; the last is at x0 over
 // all chains.  Rows of a group are written by different workgroups to disjoint rows: no atomics on results, the same bits every run.
 // Then, per group: k_vib_sym (H + H^T and D H D), k_vib_eigh (the cyclic Jacobi of jacobi_dev.h, from LDS where two m x m matrices fit
@@ -21,6 +20,7 @@
 #include <vector>
 
 #include "jacobi_dev.h"
+#include "lockstep.h"
 #include "md_dev.h"
 
 namespace vssr {
@@ -290,34 +290,28 @@ struct VibWork {
 static int vib_lockstep(vssr_handle *h, const VibWork &W, uint32_t want) {
     hipStream_t st = h->stream;
     const int B = h->n_cfg;
-    const bool f64 = is_analytic(h);
-    const int POLL = 8;
     const long long need = (long long)W.V.nfree * W.max_share;   // evaluations at displaced positions
-    h->active_mask = nullptr;
-    int stopped = 0;
+    int stopped = 0;   // (chains with nothing to displace stopped in k_vib_place)
     VSSR_HIP(h, hipMemcpyAsync(&stopped, W.flags, sizeof(int), hipMemcpyDeviceToHost, st));
     VSSR_HIP(h, hipStreamSynchronize(st));
-    for (long long it = 0; stopped < B; ++it) {
-        if (it > need + 64LL * (POLL + 1)) return set_err(h, VSSR_E_DEVICE, "vssr_batch_vibrations: the displacement loop did not finish");
-        if (int rc = evaluator(h).run(h, want | VSSR_WANT_FORCES)) return rc;
-        ++h->relax_lockstep;
-        h->relax_chain_evals += B;
-        if (f64)
-            hipLaunchKernelGGL(k_vib_step<double>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                               h->d_pot_e.as<double>(), h->d_pot_f.as<double>(), h->d_pos.as<double>(), W.V, W.flags);
-        else
-            hipLaunchKernelGGL(k_vib_step<float>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_counters.as<int>(),
-                               h->d_energy64.as<double>(), h->d_forces.as<float>(), h->d_pos.as<double>(), W.V, W.flags);
-        if ((it + 1) % POLL != 0 && it + 1 < need) continue;
-        VSSR_HIP(h, hipMemcpyAsync(&stopped, W.flags, sizeof(int), hipMemcpyDeviceToHost, st));
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (h->h_counters[2])
-            if (int rc = relax_regrow(h, 64, it, POLL)) return rc;
-    }
-    // every chain is back at x0: the evaluation that leaves the batch complete
-    if (int rc = evaluator(h).run(h, want | VSSR_WANT_FORCES)) return rc;
-    ++h->relax_lockstep;
-    h->relax_chain_evals += B;
+    // The longest chain stops behind evaluation `need`: every iteration polls from there on, so the loop ends with that evaluation.
+    // The budget leaves room for the windows 64 regrows give back.  Every chain ends back at x0, where the closing evaluation
+    // leaves the batch complete; no chain ever leaves the evaluation.
+    LockstepPlan plan{8, 0, LOCKSTEP_MASK_NEVER};
+    plan.max_launch = need + 64LL * (plan.poll + 1) + 1;
+    plan.stopped = W.flags; plan.stop_ints = 1; plan.groups = B;
+    plan.always_close = true;
+    plan.poll_all_from = need;
+    plan.finished_at_start = stopped == B;
+    bool finished;
+    int rc = lockstep_run(h, plan, want, finished, [&] {
+        with_forces(h, [&](const double *energy, auto *forces) {
+            hipLaunchKernelGGL(k_vib_step<force_type<decltype(forces)>>, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(),
+                               h->d_counters.as<int>(), energy, forces, h->d_pos.as<double>(), W.V, W.flags);
+        });
+    });
+    if (rc) return rc;
+    if (!finished) return set_err(h, VSSR_E_DEVICE, "vssr_batch_vibrations: the displacement loop did not finish");
     return VSSR_OK;
 }
 
@@ -463,7 +457,7 @@ extern "C" int vssr_batch_vibrations(vssr_handle *h, const vssr_vib_params *p, c
                        W.w2, W.jinfo);
     const double s_unit = VIB_HBAR * 1e10 / std::sqrt(1.602176634e-19 * 1.66053906660e-27);
     hipLaunchKernelGGL(k_vib_modes, dim3(G), dim3(256), 0, st, W.gm, W.gfirst, W.V.gbad, W.jinfo, W.ld, W.w2, W.Vt,
-                       is_analytic(h) ? h->d_pot_e.as<double>() : h->d_energy64.as<double>(), s_unit, MD_KB * p->temperature, p->e_min, W.en,
+                       chain_energy64(h), s_unit, MD_KB * p->temperature, p->e_min, W.en,
                        W.modes, W.thermo, W.info);
     VSSR_HIP(h, hipGetLastError());
     VSSR_HIP(h, hipStreamSynchronize(st));

@@ -7,8 +7,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -576,12 +578,24 @@ struct Evaluator {
 };
 const Evaluator &evaluator(const vssr_handle *h);
 inline bool is_analytic(const vssr_handle *h) { return evaluator(h).f64; }
+// What an evaluation of the handle fills, for the drivers behind it: the fp64 energy per chain (the potential's, or PaiNN's ensemble
+// mean) and the forces -- fp64 of an analytic potential, PaiNN's fp32.  fn(const double *energy, const FT *forces), FT = double | float.
+inline const double *chain_energy64(const vssr_handle *h) { return is_analytic(h) ? h->d_pot_e.as<double>() : h->d_energy64.as<double>(); }
+template <class Fn>
+void with_forces(const vssr_handle *h, Fn fn) {
+    if (is_analytic(h)) fn(chain_energy64(h), (const double *)h->d_pot_f.as<double>());
+    else fn(chain_energy64(h), (const float *)h->d_forces.as<float>());
+}
+template <class P>
+using force_type = std::remove_cv_t<std::remove_pointer_t<P>>;   // FT of a `forces` argument, for a kernel's template argument
 void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1][7]*/);
 // lock-step FIRE / BFGS relaxation (relax.hip, relax_lockstep<FireWork | BfgsWork>); results in d_relax_steps [B], d_relax_conv [B]; fixed_host may be null
 int relax_fire(vssr_handle *h, const vssr_fire_params &p, const uint8_t *fixed_host, uint32_t want);
 int relax_bfgs(vssr_handle *h, const vssr_bfgs_params &p, const uint8_t *fixed_host, uint32_t want);
 int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed);   // buffers, mask (-> fixed), counters
 int relax_regrow(vssr_handle *h, int cap, long long &it, int window);   // after an overflow seen at a poll: grow, give the poll window back
+// the tail of a driver's entry point: sync_and_check, the positions, and d_relax_steps [B][k] de-interleaved into its k columns (null: not wanted)
+int relax_results(vssr_handle *h, double *pos_out, std::initializer_list<int32_t *> cols);
 // lock-step LAMMPS-style CG for the fp64 potentials (relax_cg.hip); results in d_relax_steps [B][3] = {iterations, evaluations, stop reason}
 int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want);
 // lock-step BFGSLineSearch on every kind that relaxes (relax_bfgsls.hip, bfgsls_dev.h); results in d_relax_steps [B][3] = {steps, evaluations, stop reason}

@@ -209,6 +209,29 @@ def test_budgets_and_a_start_at_a_minimum(bench):
     assert np.array_equal(again["positions"], relaxed["positions"])
 
 
+# (lock-step evaluations roomy, tight; regrows) of the run below as commit 809cdf4 returns them
+REGROW_COUNTS_809CDF4 = (41, 45, 1)
+
+
+def test_capacity_regrow_in_the_middle_of_a_relaxation(bench):
+    """Pools of 4 slots per atom, regrown to the exact need (a row takes at least 8, and the rows grow as the chains contract): the
+    evaluations overflow, the driver regrows, gives the poll window back and ends with the bits of the roomy run."""
+    import cg_cases as cc
+
+    params, cases = bc.batches("pair", bench.golden)[0]
+    roomy = bench.run("pair", 0)
+    eng = bench.backend.PairEngine(cc.LJ_TERMS, n_types=cc.LJ_NTYPES, device=0)
+    eng.debug_capacity(slots_per_atom=4, tight=1)
+    tight = bench.relax(eng, cases, params)
+    regrows = eng.debug_capacity()
+    eng.close()
+    print(f"roomy counts {roomy['counts']}; tight counts {tight['counts']} regrows {regrows}")
+    assert regrows >= 1 and tight["counts"][0] > roomy["counts"][0]
+    for key in ("positions", "n_steps", "n_eval", "stop_reason", "e", "ea", "f"):
+        assert np.array_equal(tight[key], roomy[key]), key
+    assert (roomy["counts"][0], tight["counts"][0], regrows) == REGROW_COUNTS_809CDF4
+
+
 def test_the_trajectory_holds_the_step_opens_and_no_trial_point(bench):
     """record_interval = 2: the records are those of steps 0, 2, 4, ... of the restatement's trajectory (positions, energies, forces
     with FixAtoms applied); a line-search trial is never recorded."""

@@ -160,6 +160,26 @@ def test_pools_of_four_slots_per_atom_overflow_regrow_and_resume(bench, kind):
     _assert_equal(again, lock, kind)
 
 
+# (lock-step evaluations roomy, tight; regrows) of the run below as commit 809cdf4 returns them
+LOCKSTEP_REGROW_COUNTS_809CDF4 = (57, 81, 3)
+
+
+def test_the_lock_step_driver_regrows_and_gives_its_poll_window_back(bench):
+    """The same pools under the lock-step driver, regrown to the exact need: the evaluations of a poll window overflow, the driver
+    regrows and repeats the window.  Bit-equal to the run without overflow."""
+    kind = rc.KINDS[0]
+    structs, mask, max_iter, lock, _ = bench.ragged(kind)
+    small = rc.engine(kind)
+    small.debug_capacity(slots_per_atom=4, tight=1)
+    again = _relax(small, structs, mask, "lockstep", max_iter)
+    regrows = small.debug_capacity()
+    small.close()
+    print(f"{kind}: roomy counts {lock['counts']}; tight counts {again['counts']} regrows {regrows}")
+    assert again["driver"] == "lockstep" and regrows >= 1 and again["counts"][0] > lock["counts"][0]
+    _assert_equal(again, lock, kind)
+    assert (lock["counts"][0], again["counts"][0], regrows) == LOCKSTEP_REGROW_COUNTS_809CDF4
+
+
 # 4 ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", rc.KINDS)
 def test_a_different_cell_on_every_chain(bench, kind):
