@@ -490,6 +490,60 @@ int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, const uint8_t *
                      double *dimer /*[G][4]: fmax at the last test, curvature C, E0, largest |F_perp| seen at the last rotation test*/,
                      int32_t *info /*[G][4]: translation steps, stop reason, rotations made, lock-step evaluations the dimer took part in*/);
 
+/* ---- variable-cell relaxation of the resident batch (csrc/relax_cell.hip) ------------------------------------------------------
+ * Atoms and cell of every chain relaxed together on the device, in lock step: ASE's UnitCellFilter (ase/filters.py) under ASE's FIRE
+ * (ase/optimize/fire.py), in fp64.  SERVED: every handle kind that evaluates (PaiNN, Tersoff, SW, EAM / ADP, Vashishta, pair) except
+ * pair handles with k-space, which are refused with VSSR_E_STATE (the message names ew_stride: the S(k) array was sized from the
+ * uploaded cells).  CONTRACT: restated from ASE as remembered -- ASE was not installed where this was written, so it is not pinned by
+ * an executed ASE.  The contract is this comment and the numpy restatement tests/cellrelax_oracle.py, whose row force is checked
+ * to be the exact negative gradient of the enthalpy E + p V (tests/test_cellrelax_cpu.py).
+ * COORDINATES (row vectors; cell rows are lattice vectors).  Per chain, fixed when the call starts: the cell C0 and c = cell_factor
+ * (<= 0: the chain's atom count, as ASE).  State: s [N][3] and the deformation gradient F [3][3], from s = x and F = I.  Physical
+ * state: x = s F^T, C = C0 F^T.  The optimizer sees N + 3 rows: s, then c F.  After an evaluation and its stress (sigma: the 3 x 3 of
+ * vssr_batch_stress, ASE's sign; PaiNN: the ensemble mean), with V = |det C| and p = scalar_pressure, the row forces are formed in
+ * this order:
+ *  1. atoms: g_i = f_i F; rows of atoms under `fixed` are zero (they still ride the cell through x = s F^T);
+ *  2. cell: W = -V (sigma + p I) F^-T;
+ *  3. hydrostatic_strain: W <- (tr W / 3) I;
+ *  4. W <- W o mask, the 3 x 3 of 0 / 1 built from the Voigt-6 mask (xx yy zz yz xz xy);
+ *  5. the three cell rows are W / c.
+ * Convergence is ASE's over all N + 3 rows, max_row |row| < fmax, tested when a step opens.  The step is ASE FIRE (dt, maxstep,
+ * dtmax, nmin, finc, fdec, astart, fa) over the 3 N + 9 numbers; maxstep bounds the norm of the WHOLE step (|dt v'| formed from the
+ * three sums v.v, v.G, G.G, as vssr_batch_neb); the cell rows move F by (step of c F) / c.
+ * STOPS (stop_reason; one chain's stop is never an error of the call): 1 converged; 2 max_steps reached; 3 a non-finite energy,
+ * force or stress: the chain goes back to the state its step opened at and that step is not counted; 4 the step's new cell would need
+ * more periodic images along an axis than vssr_batch_upload gave that chain (floor(cutoff / height) + 1; fewer are fine), or has
+ * det F <= 0, or is not finite: the step is not taken and the chain stays at the state it was evaluated at.
+ * OUTPUTS (each may be NULL): pos_out [sum N][3], cell_out [B][9], n_steps [B], stop_reason [B], result [B][3] = (largest row force
+ * at the last test, E, V at that test).  Afterwards the batch holds the final cells and positions and a complete evaluation of
+ * them over all chains: download, vssr_batch_results_f64, vssr_batch_stress and vssr_batch_stats work at once, and a later
+ * vssr_batch_set_positions / vssr_batch_run uses the relaxed cells until the next vssr_batch_upload.  The same call twice gives the
+ * same bits, and a chain gives the same bits alone and inside any batch (fixed-order reductions, no floating-point atomics).
+ * VSSR_E_BADARG (with a message, before anything moves; the handle stays usable): p NULL, max_steps < 0, fmax not finite and > 0, a
+ * non-finite scalar_pressure or cell_factor, a mask entry other than 0 or 1, dt / maxstep / dtmax not finite and > 0, finc < 1, fdec
+ * or fa outside (0, 1), astart outside (0, 1], nmin < 0; a chain with an open axis k unless lattice vector k lies along one
+ * Cartesian axis, the other two lattice vectors have no component along that axis and the mask frees no strain component that
+ * involves it (a slab p p f along z with mask 1 1 0 0 0 1 is the supported surface case).  VSSR_E_STATE before vssr_batch_upload
+ * and for a pair handle with k-space.
+ * Out of scope: constant_volume, ExpCellFilter / FrechetCellFilter, other optimizers over the filter, trajectory rings, k-space
+ * handles. */
+typedef struct {
+    int32_t max_steps;
+    int32_t nmin;                 /* FIRE */
+    int32_t hydrostatic_strain;   /* 0 / 1 */
+    int32_t mask[6];              /* 0 / 1 per strain component, Voigt order xx yy zz yz xz xy */
+    double  fmax;                 /* eV / A over all N + 3 rows */
+    double  scalar_pressure;      /* eV / A^3 */
+    double  cell_factor;          /* <= 0: the chain's atom count */
+    double  dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE FIRE, as vssr_neb_params */
+} vssr_cell_relax_params;
+int vssr_batch_relax_cell(vssr_handle *h, const vssr_cell_relax_params *p, const uint8_t *fixed /*[sum N] or NULL*/, uint32_t want,
+                          double *pos_out /*[sum N][3]*/, double *cell_out /*[B][9]*/, int32_t *n_steps /*[B]*/, int32_t *stop_reason /*[B]*/,
+                          double *result /*[B][3]: fmax at the last test, E, V*/);
+/* The cells of the resident batch as the device holds them, [B][9] (synchronises): those of vssr_batch_upload bit for bit, or what
+ * vssr_batch_relax_cell left.  VSSR_E_STATE before vssr_batch_upload. */
+int vssr_batch_get_cell(vssr_handle *h, double *cell /*[B][9]*/);
+
 /* ---- introspection used by tests and bench (no effect on results) ---------------------- */
 /* Per-kernel timing with HIP events on the handle's own stream.  enable=1 starts recording;
  * vssr_profile_read synchronises and returns, for each kernel class, the number of launches and

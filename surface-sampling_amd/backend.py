@@ -41,6 +41,7 @@ EXPORTS = (
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
     "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
     "vssr_batch_md_driver", "vssr_batch_vibrations", "vssr_batch_neb", "vssr_batch_dimer",
+    "vssr_batch_relax_cell", "vssr_batch_get_cell",
 )
 
 
@@ -232,6 +233,30 @@ class DimerParams(C.Structure):
 DIMER_STOP_REASONS = {1: "converged", 2: "max steps", 3: "non-finite energy or force"}
 
 
+class CellRelaxParams(C.Structure):
+    """vssr_cell_relax_params: eV / A, eV / A^3; ``mask`` in Voigt order xx yy zz yz xz xy; the FIRE fields as ``NebParams``."""
+    _fields_ = [("max_steps", C.c_int32), ("nmin", C.c_int32), ("hydrostatic_strain", C.c_int32), ("mask", C.c_int32 * 6),
+                ("fmax", C.c_double), ("scalar_pressure", C.c_double), ("cell_factor", C.c_double), ("dt", C.c_double),
+                ("maxstep", C.c_double), ("dtmax", C.c_double), ("finc", C.c_double), ("fdec", C.c_double), ("astart", C.c_double),
+                ("fa", C.c_double)]
+
+    @classmethod
+    def default(cls, max_steps=100, fmax=0.05, scalar_pressure=0.0, mask=None, hydrostatic_strain=False, cell_factor=0.0, dt=0.1,
+                maxstep=0.2, dtmax=1.0, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, nmin=5):
+        m = [1] * 6 if mask is None else list(mask)
+        if len(m) != 6 or any(v not in (0, 1) for v in m):
+            raise ValueError(f"mask {mask!r}: six entries 0 or 1 (Voigt order xx yy zz yz xz xy)")
+        if hydrostatic_strain not in (False, True, 0, 1):
+            raise ValueError(f"hydrostatic_strain {hydrostatic_strain!r}: a bool")
+        return cls(int(max_steps), int(nmin), int(bool(hydrostatic_strain)), (C.c_int32 * 6)(*[int(v) for v in m]), float(fmax),
+                   float(scalar_pressure), float(cell_factor), float(dt), float(maxstep), float(dtmax), float(finc), float(fdec),
+                   float(astart), float(fa))
+
+
+CELL_STOP_REASONS = {1: "converged", 2: "max steps", 3: "non-finite energy, force or stress",
+                     4: "cell left the image range of the upload or degenerated"}
+
+
 # who runs optimizer="BFGSLineSearch" for a calculator: ASE's class on the host, one optimizer per chain ("ase", the default), or the
 # lock-step device optimizer (vssr_batch_relax_bfgs_linesearch)
 LINESEARCH_DRIVERS = ("ase", "device")
@@ -385,6 +410,10 @@ def load_library():
     L.vssr_batch_neb.argtypes = [vp, C.POINTER(NebParams), u8p, ip, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_batch_dimer.restype = C.c_int
     L.vssr_batch_dimer.argtypes = [vp, C.POINTER(DimerParams), u8p, dp, C.POINTER(C.c_uint64), C.c_uint32, dp, dp, dp, dp, ip]
+    L.vssr_batch_relax_cell.restype = C.c_int
+    L.vssr_batch_relax_cell.argtypes = [vp, C.POINTER(CellRelaxParams), u8p, C.c_uint32, dp, dp, ip, ip, dp]
+    L.vssr_batch_get_cell.restype = C.c_int
+    L.vssr_batch_get_cell.argtypes = [vp, dp]
     L.vssr_batch_vibrations.restype = C.c_int
     L.vssr_batch_vibrations.argtypes = [vp, C.POINTER(VibParams), dp, u8p, ip, C.c_int32, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_eam_create.restype = C.c_int
@@ -897,6 +926,36 @@ class _Handle:
         return {"positions": pos, "energies": e, "modes": mode, "fmax": rec[:G, 0].copy(), "curvature": rec[:G, 1].copy(),
                 "e0": rec[:G, 2].copy(), "f_perp": rec[:G, 3].copy(), "n_steps": info[:G, 0].copy(), "stop_reason": info[:G, 1].copy(),
                 "n_rot": info[:G, 2].copy(), "n_eval": info[:G, 3].copy()}
+
+    # -- variable-cell relaxation ------------------------------------------------------------------------
+    def relax_cell(self, fixed=None, max_steps=100, fmax=0.05, scalar_pressure=0.0, mask=None, hydrostatic_strain=False, cell_factor=0.0,
+                   params=None, want=WANT_ALL, **fire):
+        """Atoms and cells of the resident batch relaxed together on the device (vssr_batch_relax_cell): ASE's ``UnitCellFilter`` under
+        ASE's FIRE as tests/cellrelax_oracle.py restates them (not an executed ASE).  ``fixed`` [sum N]: atoms whose fractional
+        coordinates stay; ``fmax`` in eV / A over the N + 3 rows (atoms and cell); ``scalar_pressure`` in eV / A^3; ``mask``: six 0 / 1
+        in Voigt order xx yy zz yz xz xy (None: all free; a slab p p f along z takes 1 1 0 0 0 1); ``hydrostatic_strain``: the cell only
+        scales; ``cell_factor`` <= 0: the atom count; ``fire``: ``dt``, ``maxstep``, ``dtmax``, ``finc``, ``fdec``, ``astart``, ``fa``,
+        ``nmin`` (``params``: a ``CellRelaxParams`` instead of all of these).  Every kind but pair handles with k-space.  Returns
+        dict(positions [sum N, 3], cells [B, 3, 3], n_steps / stop_reason (``CELL_STOP_REASONS``) [B], fmax / energy / volume [B] as of
+        the last convergence test); ``download()`` / ``results_f64()`` / ``stress()`` serve the final state at once, and later
+        ``set_positions`` / ``run`` keep the relaxed cells until the next upload."""
+        N, B = self._n_atoms, self._n_cfg
+        fx = _fixed_arg(fixed, N)
+        p = params or CellRelaxParams.default(max_steps, fmax, scalar_pressure, mask, hydrostatic_strain, cell_factor, **fire)
+        pos, cells, rec = np.zeros((N, 3), np.float64), np.zeros((max(B, 1), 3, 3), np.float64), np.zeros((max(B, 1), 3), np.float64)
+        steps, reason = np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int32)
+        self._check(self._lib.vssr_batch_relax_cell(self._h, C.byref(p), _ptr(fx, C.c_uint8), int(want), _ptr(pos, C.c_double),
+                                                    _ptr(cells, C.c_double), _ptr(steps, C.c_int32), _ptr(reason, C.c_int32),
+                                                    _ptr(rec, C.c_double)))
+        self.last_relax_counts = self.relax_counts()
+        return {"positions": pos, "cells": cells[:B], "n_steps": steps[:B], "stop_reason": reason[:B], "fmax": rec[:B, 0].copy(),
+                "energy": rec[:B, 1].copy(), "volume": rec[:B, 2].copy()}
+
+    def get_cell(self):
+        """The cells of the resident batch as the device holds them, [B, 3, 3] (vssr_batch_get_cell)."""
+        cells = np.zeros((max(self._n_cfg, 1), 3, 3), np.float64)
+        self._check(self._lib.vssr_batch_get_cell(self._h, _ptr(cells, C.c_double)))
+        return cells[:self._n_cfg]
 
     def relax_counts(self):
         """``(lock-step evaluations, dispatched chain-evaluations)`` of the last relaxation (vssr_batch_relax_counts)."""

@@ -525,8 +525,63 @@ _DIMER_DOC = """Saddle searches from single structures on the device (``backend.
         papers, not ASE's ``MinModeTranslate``."""
 
 
+def _relax_cell_batch(get_engine, pack, atoms_list, fixed_indices, mask, scalar_pressure, hydrostatic_strain, cell_factor, steps, fmax, want):
+    """``relax_cell_batch`` of every calculator: the argument checks, then on the calculator's engine (``get_engine()``, not touched
+    before) the packed structures and ``backend.relax_cell``; the per-structure dicts."""
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 0:
+        raise ValueError(f"relax_cell_batch: steps {steps!r} (an integer >= 0 wanted)")
+    if not (np.isfinite(float(fmax)) and float(fmax) > 0):
+        raise ValueError(f"relax_cell_batch: fmax {fmax} eV / A (finite and > 0 wanted)")
+    if not np.isfinite(float(scalar_pressure)):
+        raise ValueError(f"relax_cell_batch: scalar_pressure {scalar_pressure} eV / A^3 is not finite")
+    if cell_factor is not None and not np.isfinite(float(cell_factor)):
+        raise ValueError(f"relax_cell_batch: cell_factor {cell_factor} is not finite")
+    atoms_list = list(atoms_list)
+    B = len(atoms_list)
+    if not B:
+        raise ValueError("relax_cell_batch: no structures")
+    if fixed_indices is not None and len(fixed_indices) != B:
+        raise ValueError(f"relax_cell_batch: {len(fixed_indices)} index lists for {B} structures")
+    sizes = [len(a) for a in atoms_list]
+    for n, idx in zip(sizes, fixed_indices or ()):
+        if idx is not None and len(idx) and (np.min(idx) < 0 or np.max(idx) >= n):
+            raise ValueError(f"relax_cell_batch: a fixed index outside 0 .. {n - 1}")
+    p = backend.CellRelaxParams.default(int(steps), float(fmax), float(scalar_pressure), mask, hydrostatic_strain,
+                                        0.0 if cell_factor is None else float(cell_factor))   # (ValueError for a bad mask)
+    start = _cfg_start(sizes)
+    fixed = _fixed_mask(sizes, fixed_indices)
+    eng = get_engine()
+    eng.upload([pack(a) for a in atoms_list])
+    r = eng.relax_cell(fixed=fixed, params=p, want=want)
+    out = []
+    for b, atoms in enumerate(atoms_list):
+        a0, a1 = int(start[b]), int(start[b + 1])
+        final = atoms.copy()
+        if hasattr(final, "set_cell"):
+            final.set_cell(r["cells"][b].copy(), scale_atoms=False)
+        else:
+            final.cell = r["cells"][b].copy()
+        final.set_positions(r["positions"][a0:a1])
+        out.append({"atoms": final, "cell": r["cells"][b].copy(), "energy": float(r["energy"][b]), "volume": float(r["volume"][b]),
+                    "fmax": float(r["fmax"][b]), "n_steps": int(r["n_steps"][b]), "stop_reason": int(r["stop_reason"][b]),
+                    "converged": int(r["stop_reason"][b]) == 1})
+    return out
+
+
+_CELL_DOC = """Atoms and cells of B structures relaxed together on the device (``backend.relax_cell``): ASE's ``UnitCellFilter`` under ASE's
+        FIRE, every structure a chain of one lock-step evaluation, its stress consumed where it is computed.  ``fixed_indices``: per
+        structure, the atom indices FixAtoms holds (their fractional coordinates stay).  ``mask``: six 0 / 1 in Voigt order xx yy zz
+        yz xz xy, the strain components that are free (None: all; a slab periodic in x and y takes (1, 1, 0, 0, 0, 1));
+        ``scalar_pressure`` in eV / A^3; ``hydrostatic_strain``: the cell only scales; ``cell_factor``: None = the atom count, as
+        ASE; ``fmax`` in eV / A over atoms and cell rows; at most ``steps`` FIRE steps.  Returns per structure a dict: ``atoms`` (a
+        copy with the relaxed cell and positions), ``cell`` [3, 3], ``energy`` / ``volume`` / ``fmax`` as of the last convergence
+        test, ``n_steps``, ``stop_reason`` (``backend.CELL_STOP_REASONS``), ``converged``.  Served by every calculator but pair
+        models with k-space.  The contract is the numpy restatement tests/cellrelax_oracle.py, not an executed ASE; constant_volume,
+        ExpCellFilter / FrechetCellFilter and other optimizers over the filter are out of scope."""
+
+
 class _DynamicsFrontEnds:
-    """``md_batch`` / ``vibrations_batch`` / ``neb_batch`` / ``dimer_batch`` of a calculator with ``_get_engine``, in terms of two
+    """``md_batch`` / ``vibrations_batch`` / ``neb_batch`` / ``dimer_batch`` / ``relax_cell_batch`` of a calculator with ``_get_engine``, in terms of two
     hooks of the class: ``_pack(atoms) -> (Z or types, pos, cell, pbc)`` and ``_dynamics_want``, the outputs an evaluation produces."""
 
     _dynamics_want = 0
@@ -559,6 +614,13 @@ class _DynamicsFrontEnds:
                             max_rot_first, max_rot, displace, self._dynamics_want)
 
     dimer_batch.__doc__ = _DIMER_DOC
+
+    def relax_cell_batch(self, atoms_list, fixed_indices=None, mask=None, scalar_pressure: float = 0.0, hydrostatic_strain: bool = False,
+                         cell_factor=None, steps: int = 100, fmax: float = 0.05):
+        return _relax_cell_batch(self._get_engine, self._pack, atoms_list, fixed_indices, mask, scalar_pressure, hydrostatic_strain, cell_factor,
+                                 steps, fmax, self._dynamics_want)
+
+    relax_cell_batch.__doc__ = _CELL_DOC
 
 
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:

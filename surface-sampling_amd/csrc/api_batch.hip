@@ -2,31 +2,8 @@
 #include <cmath>
 #include <cstdio>
 
+#include "cell_dev.h"
 #include "ewald_dev.h"
-
-namespace vssr {
-
-static void cell_host_setup(const double *cell, const uint8_t *pbc, double cutoff, double inv[9], int nimg[3],
-                            bool &ok) {
-    const double *a = cell, *b = cell + 3, *c = cell + 6;
-    double bc[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
-    double ca[3] = {c[1] * a[2] - c[2] * a[1], c[2] * a[0] - c[0] * a[2], c[0] * a[1] - c[1] * a[0]};
-    double ab[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-    double vol = a[0] * bc[0] + a[1] * bc[1] + a[2] * bc[2];
-    ok = true;
-    for (int x = 0; x < 9; ++x) inv[x] = 0.0;
-    nimg[0] = nimg[1] = nimg[2] = 0;
-    if (!(pbc[0] || pbc[1] || pbc[2])) return;
-    if (std::fabs(vol) < 1e-12) { ok = false; return; }
-    for (int x = 0; x < 3; ++x) { inv[x] = bc[x] / vol; inv[3 + x] = ca[x] / vol; inv[6 + x] = ab[x] / vol; }
-    double hgt[3] = {std::fabs(vol) / std::sqrt(bc[0] * bc[0] + bc[1] * bc[1] + bc[2] * bc[2]),
-                     std::fabs(vol) / std::sqrt(ca[0] * ca[0] + ca[1] * ca[1] + ca[2] * ca[2]),
-                     std::fabs(vol) / std::sqrt(ab[0] * ab[0] + ab[1] * ab[1] + ab[2] * ab[2])};
-    for (int k = 0; k < 3; ++k)
-        if (pbc[k]) nimg[k] = (int)std::floor(cutoff / hgt[k]) + 1;
-}
-
-}  // namespace vssr
 
 using namespace vssr;
 
@@ -61,7 +38,7 @@ int vssr_batch_upload(vssr_handle *h, int32_t n_cfg, const int32_t *n_atoms, con
     const double rc = evaluator(h).cutoff(h);
     for (int b = 0; b < n_cfg; ++b) {
         bool ok;
-        cell_host_setup(cell + 9 * b, pbc + 3 * b, rc, inv.data() + 9 * b, nimg.data() + 3 * b, ok);
+        cell_setup(cell + 9 * b, pbc + 3 * b, rc, inv.data() + 9 * b, nimg.data() + 3 * b, ok);
         if (!ok) return set_err(h, VSSR_E_BADARG, "configuration %d: periodic but singular cell", b);
         for (int k = 0; k < 3; ++k)
             if (nimg[3 * b + k] > 100) {

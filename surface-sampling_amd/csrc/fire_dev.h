@@ -1,6 +1,7 @@
 // fire_dev.h -- ASE's FIRE update (ase/optimize/fire.py), once: the dt / a / Nsteps bookkeeping with the mixing coefficients, the
 // step length from three sums, the knobs and their check.  Serves k_fire_step (relax.hip: per chain, with its own reduction of the
-// step length), k_neb_step (neb.hip: over a band) and k_dimer_advance (dimer.hip: the translation).  G is the force the step follows.
+// step length), k_neb_step (neb.hip: over a band), k_dimer_advance (dimer.hip: the translation) and k_cell_step (relax_cell.hip: over
+// atoms and strain).  G is the force the step follows.
 #ifndef VSSR_FIRE_DEV_H
 #define VSSR_FIRE_DEV_H
 #include <cmath>
