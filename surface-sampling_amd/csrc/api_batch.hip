@@ -267,22 +267,19 @@ static int relax_finish(vssr_handle *h, double *pos_out, int32_t *n_steps, uint8
 
 int vssr_batch_relax_cg(vssr_handle *h, const vssr_cg_params *params, const uint8_t *fixed, uint32_t want, double *pos_out,
                         int32_t *n_iter, int32_t *n_eval, int32_t *stop_reason) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_cg before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!params || params->max_iter < 0 || params->max_eval < 0 || !(params->etol >= 0) || !(params->ftol >= 0) || !(params->dmax > 0))
         return set_err(h, VSSR_E_BADARG, "bad CG parameters");
     VSSR_HIP(h, hipSetDevice(h->device));
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
     // one workgroup minimises one chain from start to stop (chain_min.hip: analytic kinds, chains of <= 256 atoms, where the handle's
     // driver setting / VSSR_CG_FUSED / the automatic rule choose it); else the lock-step driver (relax_cg.hip).  Same results bit for bit.
     const bool resident = chain_min_supported(h);
     int rc = resident ? chain_min_cg(h, params, fixed, want) : relax_cg(h, params, fixed, want);
     if (rc) return rc;
     h->cg_last_driver = resident ? VSSR_CG_DRIVER_RESIDENT : VSSR_CG_DRIVER_LOCKSTEP;
-    h->graph_partial = resident;     // (the lock-step driver ends with a full batch-wide evaluation of the final positions; the
-                                     //  chain-resident one numbers its rows per chain: introspection wants one plain run first)
-    return relax_results(h, pos_out, {n_iter, n_eval, stop_reason});
+    // (the lock-step driver ends with a full batch-wide evaluation of the final positions; the chain-resident one numbers its rows per
+    // chain: introspection wants one plain run first)
+    return relax_results(h, resident, pos_out, {n_iter, n_eval, stop_reason});
 }
 
 int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_used) {
@@ -297,8 +294,7 @@ int vssr_batch_relax_cg_driver(vssr_handle *h, int32_t driver, int32_t *last_use
 
 int vssr_batch_relax_bfgs_linesearch(vssr_handle *h, const vssr_bfgsls_params *p, const uint8_t *fixed, uint32_t want, double *pos_out,
                                      int32_t *n_steps, int32_t *n_eval, int32_t *stop_reason) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_bfgs_linesearch before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!p) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: null");
     if (p->max_steps < 0) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: max_steps %d < 0", (int)p->max_steps);
     if (p->max_eval < 1) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: max_eval %d < 1", (int)p->max_eval);
@@ -308,35 +304,26 @@ int vssr_batch_relax_bfgs_linesearch(vssr_handle *h, const vssr_bfgsls_params *p
     if (!(p->c2 > 0 && p->c2 < 1)) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: c2 %g outside (0, 1)", p->c2);
     if (!(p->stpmax >= 1)) return set_err(h, VSSR_E_BADARG, "bad BFGSLineSearch parameters: stpmax %g < 1", p->stpmax);
     VSSR_HIP(h, hipSetDevice(h->device));
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
     if (int rc = relax_bfgsls(h, p, fixed, want)) return rc;
-    h->graph_partial = false;        // (the driver ends with a batch-wide evaluation of the final positions)
-    return relax_results(h, pos_out, {n_steps, n_eval, stop_reason});
+    return relax_results(h, false, pos_out, {n_steps, n_eval, stop_reason});   // (the driver ends with a batch-wide evaluation of the final positions)
 }
 
 int vssr_batch_relax_bfgs(vssr_handle *h, const vssr_bfgs_params *params, const uint8_t *fixed, uint32_t want,
                           double *pos_out, int32_t *n_steps, uint8_t *converged) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_bfgs before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!params || params->max_steps < 0 || !(params->fmax > 0) || !(params->alpha > 0) || !(params->maxstep > 0))
         return set_err(h, VSSR_E_BADARG, "bad BFGS parameters");
     VSSR_HIP(h, hipSetDevice(h->device));
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
     if (int rc = relax_bfgs(h, *params, fixed, want)) return rc;
     return relax_finish(h, pos_out, n_steps, converged);
 }
 
 int vssr_batch_relax_fire(vssr_handle *h, const vssr_fire_params *params, const uint8_t *fixed, uint32_t want,
                           double *pos_out, int32_t *n_steps, uint8_t *converged) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_fire before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!params || params->max_steps < 0 || !(params->fmax > 0) || !(params->dt > 0) || !(params->maxstep > 0))
         return set_err(h, VSSR_E_BADARG, "bad FIRE parameters");
     VSSR_HIP(h, hipSetDevice(h->device));
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
     if (int rc = relax_fire(h, *params, fixed, want)) return rc;
     return relax_finish(h, pos_out, n_steps, converged);
 }

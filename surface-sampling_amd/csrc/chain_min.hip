@@ -29,6 +29,7 @@
 // The evaluation phase is the device function template cm_evaluate<Site>; a second kernel template, k_md_chain<Site>, puts the
 // molecular-dynamics integrator of md_dev.h behind it instead of the CG state machine (further down; host side: chain_md).
 #include <algorithm>
+#include "arena.h"
 #include "cg_dev.h"
 #include "md_dev.h"
 #include "nbr_dev.h"
@@ -489,28 +490,29 @@ static CmCommon cm_batch_args(const vssr_handle *h, const uint8_t *fixed, unsign
     return A;
 }
 
-// Same contract as relax_cg (relax_cg.hip): afterwards the batch holds the minimised positions, d_pot_e / _ea / _f the static results of
-// those geometries, d_relax_steps [B][3] = (iterations, evaluations, stop reason) per chain.
-int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want) {
-    (void)want;
+// One chain-resident call, the part the minimiser and the integrator share: the graph scratch and result buffers, d_cm carved into
+// [arguments (1 KB) | flags [8] | evaluations [B]], then launch attempts with slot pools of `cap` slots per atom until no chain
+// overflowed its pool, and the evaluations the chains spent.  `who` names the driver in the out-of-memory message; reset(n_evals)
+// enqueues what clears the evaluation counts ahead of the first attempt, fill(A) sets the driver's own fields of an attempt's CmCommon
+// (md != null: the integrator, which has none), report() enqueues what the driver reads out of its state behind the last attempt.
+template <class Reset, class Fill, class Report>
+static int cm_run(vssr_handle *h, const char *who, const uint8_t *fixed, const CmMd *md, Reset reset, Fill fill, Report report) {
     const int B = h->n_cfg, N = h->n_atoms;
     hipStream_t st = h->stream;
-    const uint8_t *fixed = nullptr;
-    CgWork W;
-    if (int e = relax_begin(h, fixed_host, 3, fixed)) return e;
-    if (int e = CgWork::ensure(h, W)) return e;
-    if (h->d_cm.ensure(sizeof(int) * ((size_t)B + 8) + 1024) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
+    char *d_args = nullptr;
+    int *flags = nullptr, *n_evals = nullptr;
+    auto layout = [&](Arena &a) { a.place(d_args, 1024); a.place(flags, 8); a.place(n_evals, (size_t)B); };
+    if (h->d_cm.ensure(arena_size(layout)) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
         h->d_wrap.ensure(sizeof(int) * 3 * (size_t)N) || h->d_deg.ensure(sizeof(int) * (size_t)N) ||
         h->d_row_start.ensure(sizeof(int) * ((size_t)N + B + 1)) || h->d_pot_e.ensure(sizeof(double) * (size_t)B) ||
         h->d_pot_ea.ensure(sizeof(double) * (size_t)N) || h->d_pot_f.ensure(sizeof(double) * 3 * (size_t)N))
-        return set_err(h, VSSR_E_NOMEM, "chain-resident minimiser: out of device memory");
-    void *d_args = h->d_cm.as<char>();   // [arguments (1 KB) | flags [8] | evaluations [B]]
-    int *flags = reinterpret_cast<int *>(h->d_cm.as<char>() + 1024), *n_evals = flags + 8;
-    hipLaunchKernelGGL(k_cm_init, dim3((B + 127) / 128), dim3(128), 0, st, B, W.st, h->d_active.as<unsigned char>(), n_evals);
+        return set_err(h, VSSR_E_NOMEM, "chain-resident %s: out of device memory", who);
+    arena_carve(h->d_cm.p, layout);
+    VSSR_HIP(h, reset(n_evals));
     const double rc = evaluator(h).cutoff(h);   // (EAM: the file's cutoff, as eam_run; the others: the table's largest)
-    // slots per atom of the per-chain pools: the handle's capacity, or what an earlier chain-resident relaxation had to grow to.  The
-    // grown value stays with THIS driver (cm_cap_per_atom): the batch-wide runs size their buffers from cap_per_atom and repair an
-    // overflow exactly, they must not inherit up to 64x from a pool that doubles (advisor r5)
+    // slots per atom of the per-chain pools: the handle's capacity, or what an earlier chain-resident call had to grow to.  The
+    // grown value stays with THIS driver family (cm_cap_per_atom): the batch-wide runs size their buffers from cap_per_atom and repair
+    // an overflow exactly, they must not inherit up to 64x from a pool that doubles (advisor r5)
     int cap = std::max(h->cap_per_atom, h->cm_cap_per_atom);
     for (int attempt = 0;; ++attempt) {
         // slot pools: every chain owns n_atoms x cap slots
@@ -526,25 +528,22 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
             hits_buf = h->d_hits.as<unsigned long long>();
         VSSR_HIP(h, hipMemsetAsync(flags, 0, sizeof(int) * 8, st));
         CmCommon A = cm_batch_args(h, fixed, hits_buf, hits_stride, cap, rc, flags, n_evals);
-        A.max_iter = cp->max_iter; A.max_eval = cp->max_eval; A.etol = cp->etol; A.ftol = cp->ftol; A.dmax = cp->dmax;
-        A.x0 = W.x0; A.hh = W.hh; A.gg = W.gg;
-        A.st = W.st;
-        A.max_launch = (long long)cp->max_eval + 72;   // the lock-step driver's launch budget (relax_cg.hip), per chain here
-        if (int e = cm_launch_kind(h, d_args, A)) return e;
+        fill(A);
+        if (int e = cm_launch_kind(h, d_args, A, md)) return e;
         ++h->relax_lockstep;
         int over = 0;
         VSSR_HIP(h, hipMemcpyAsync(&over, flags, sizeof(int), hipMemcpyDeviceToHost, st));
         VSSR_HIP(h, hipStreamSynchronize(st));
         if (!over) break;
         // a chain needed more slots per atom than its pool holds: chains that were stopped kept their state (nothing is stepped on
-        // an overflowed evaluation) and continue in the next launch with larger pools
+        // an overflowed evaluation) and continue in the next launch, from their own counters, with larger pools
         // (ten doublings: a pair cutoff over several images of a small cell gives rows of several hundred slots, 2^31 slots bound the rest)
         if (attempt >= 10) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
         cap *= 2;
         ++h->relax_regrows;
     }
     h->cm_cap_per_atom = cap;
-    hipLaunchKernelGGL(k_cm_report, dim3((B + 127) / 128), dim3(128), 0, st, B, W.st, h->d_relax_steps.as<int>());
+    report();
     std::vector<int> ne(B);
     VSSR_HIP(h, hipMemcpyAsync(ne.data(), n_evals, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
     VSSR_HIP(h, hipStreamSynchronize(st));
@@ -553,9 +552,32 @@ int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_
     h->relax_chain_evals = tot;
     h->active_mask = nullptr;
     h->h_counters[2] = 0;      // (no batch-wide neighbor build ran: nothing for vssr_synchronize to repair)
-    h->ran = true;
-    h->graph_partial = true;   // (the rows are numbered per chain: the batch-wide introspection calls want one plain run first)
     return VSSR_OK;
+}
+
+// Same contract as relax_cg (relax_cg.hip): afterwards the batch holds the minimised positions, d_pot_e / _ea / _f the static results of
+// those geometries, d_relax_steps [B][3] = (iterations, evaluations, stop reason) per chain.  (The rows are numbered per chain: the
+// entry point closes the call with graph_partial set, the batch-wide introspection calls want one plain run first.)
+int chain_min_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want) {
+    const int B = h->n_cfg;
+    hipStream_t st = h->stream;
+    const uint8_t *fixed = nullptr;
+    CgWork W;
+    if (int e = driver_open(h, fixed_host, 3, fixed, want)) return e;
+    if (int e = CgWork::ensure(h, W)) return e;
+    return cm_run(
+        h, "minimiser", fixed, nullptr,
+        [&](int *n_evals) {
+            hipLaunchKernelGGL(k_cm_init, dim3((B + 127) / 128), dim3(128), 0, st, B, W.st, h->d_active.as<unsigned char>(), n_evals);
+            return hipSuccess;
+        },
+        [&](CmCommon &A) {
+            A.max_iter = cp->max_iter; A.max_eval = cp->max_eval; A.etol = cp->etol; A.ftol = cp->ftol; A.dmax = cp->dmax;
+            A.x0 = W.x0; A.hh = W.hh; A.gg = W.gg;
+            A.st = W.st;
+            A.max_launch = (long long)cp->max_eval + 72;   // the lock-step driver's launch budget (relax_cg.hip), per chain here
+        },
+        [&] { hipLaunchKernelGGL(k_cm_report, dim3((B + 127) / 128), dim3(128), 0, st, B, W.st, h->d_relax_steps.as<int>()); });
 }
 
 // ---- the integrator's host side ---------------------------------------------------------------------------------------------------
@@ -571,56 +593,11 @@ bool chain_md_supported(const vssr_handle *h) {
 
 // Same contract as md_lockstep (md.hip): afterwards the batch holds the final positions, d_md_vel the velocities, d_pot_e / _ea / _f the
 // static results of the final state of every chain, the workspace the step counts, stop reasons and thermo records.
-int chain_md(vssr_handle *h, const MdWork &W, uint32_t want) {
-    (void)want;
-    const int B = h->n_cfg, N = h->n_atoms;
-    hipStream_t st = h->stream;
-    if (h->d_cm.ensure(sizeof(int) * ((size_t)B + 8) + 1024) || h->d_wpos.ensure(sizeof(double) * 3 * (size_t)N) ||
-        h->d_wrap.ensure(sizeof(int) * 3 * (size_t)N) || h->d_deg.ensure(sizeof(int) * (size_t)N) ||
-        h->d_row_start.ensure(sizeof(int) * ((size_t)N + B + 1)) || h->d_pot_e.ensure(sizeof(double) * (size_t)B) ||
-        h->d_pot_ea.ensure(sizeof(double) * (size_t)N) || h->d_pot_f.ensure(sizeof(double) * 3 * (size_t)N))
-        return set_err(h, VSSR_E_NOMEM, "chain-resident integrator: out of device memory");
-    void *d_args = h->d_cm.as<char>();   // [arguments (1 KB) | flags [8] | evaluations [B]], as chain_min_cg
-    int *flags = reinterpret_cast<int *>(h->d_cm.as<char>() + 1024), *n_evals = flags + 8;
-    VSSR_HIP(h, hipMemsetAsync(n_evals, 0, sizeof(int) * (size_t)B, st));
+int chain_md(vssr_handle *h, const MdWork &W) {
     const CmMd M{W.P, W.V, W.stopped};
-    const double rc = evaluator(h).cutoff(h);
-    int cap = std::max(h->cap_per_atom, h->cm_cap_per_atom);   // (the pools of this driver family grow on their own: chain_min_cg)
-    for (int attempt = 0;; ++attempt) {
-        const long long slots = (long long)N * cap + 64;
-        if (slots > 2147483000LL) return set_err(h, VSSR_E_CAPACITY, "neighbor list exceeds 2^31 slots");
-        if (h->slot_cap < slots) h->slot_cap = slots;
-        if (h->d_edge.ensure(sizeof(float4) * h->slot_cap) || h->d_edge_S.ensure(sizeof(int) * h->slot_cap) ||
-            h->d_rev.ensure(sizeof(int) * h->slot_cap))
-            return set_err(h, VSSR_E_NOMEM, "neighbor buffers: out of device memory");
-        unsigned long long *hits_buf = nullptr;
-        const int hits_stride = (h->max_cfg_atoms + 63) & ~63;
-        if (h->max_images <= 64 && (size_t)N * hits_stride * 8 <= ((size_t)1 << 30) && !h->d_hits.ensure((size_t)N * hits_stride * 8))
-            hits_buf = h->d_hits.as<unsigned long long>();
-        VSSR_HIP(h, hipMemsetAsync(flags, 0, sizeof(int) * 8, st));
-        const CmCommon A = cm_batch_args(h, W.fixed, hits_buf, hits_stride, cap, rc, flags, n_evals);
-        if (int e = cm_launch_kind(h, d_args, A, &M)) return e;
-        ++h->relax_lockstep;
-        int over = 0;
-        VSSR_HIP(h, hipMemcpyAsync(&over, flags, sizeof(int), hipMemcpyDeviceToHost, st));
-        VSSR_HIP(h, hipStreamSynchronize(st));
-        if (!over) break;
-        // a chain needed more slots per atom than its pool holds: it kept its state (nothing is stepped on an overflowed evaluation)
-        // and resumes from its own step counter in the next launch
-        if (attempt >= 10) return set_err(h, VSSR_E_CAPACITY, "neighbor capacity could not be satisfied");
-        cap *= 2;
-        ++h->relax_regrows;
-    }
-    h->cm_cap_per_atom = cap;
-    std::vector<int> ne(B);
-    VSSR_HIP(h, hipMemcpyAsync(ne.data(), n_evals, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
-    VSSR_HIP(h, hipStreamSynchronize(st));
-    long long tot = 0;
-    for (int b = 0; b < B; ++b) tot += ne[b];
-    h->relax_chain_evals = tot;
-    h->active_mask = nullptr;
-    h->h_counters[2] = 0;      // (no batch-wide neighbor build ran: nothing for vssr_synchronize to repair)
-    return VSSR_OK;
+    return cm_run(
+        h, "integrator", W.fixed, &M,
+        [&](int *n_evals) { return hipMemsetAsync(n_evals, 0, sizeof(int) * (size_t)h->n_cfg, h->stream); }, [](CmCommon &) {}, [] {});
 }
 
 }  // namespace vssr

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "arena.h"
 #include "fire_dev.h"
 #include "lockstep.h"
 #include "md_dev.h"
@@ -360,8 +361,7 @@ using namespace vssr;
 
 extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, const uint8_t *fixed, const double *mode_in, const uint64_t *dimer_id,
                                 uint32_t want, double *pos_out, double *energy, double *mode_out, double *dimer, int32_t *info) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_dimer before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!p) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: null parameters");
     const int B = h->n_cfg, N = h->n_atoms, ng = B / 2;
     if (B < 2 || B % 2) return set_err(h, VSSR_E_BADARG, "vssr_batch_dimer: %d chains (an even number wanted: a dimer is two chains)", B);
@@ -405,26 +405,17 @@ extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, cons
     hipStream_t st = h->stream;
     VSSR_HIP(h, hipStreamSynchronize(st));
     const size_t n3 = 3 * (size_t)N;
-    const size_t n_dbl = 7 * n3 + 4 * (size_t)ng;
-    const size_t n_int = 4 * (size_t)B + 4 * (size_t)ng + 4;
-    const size_t bytes = sizeof(double) * n_dbl + sizeof(unsigned long long) * ng + sizeof(DimerState) * ng + sizeof(int) * n_int;
-    if (h->d_dimer.ensure(bytes)) return set_err(h, VSSR_E_NOMEM, "dimer workspace: out of device memory");
     DimerWork W;
-    double *d = h->d_dimer.as<double>();
-    W.V.N = d; d += n3;
-    W.V.Nopen = d; d += n3;
-    W.V.xopen = d; d += n3;
-    W.V.F0 = d; d += n3;
-    W.V.F1 = d; d += n3;
-    W.V.theta = d; d += n3;
-    W.V.vel = d; d += n3;
-    W.V.rec = d; d += 4 * (size_t)ng;
-    W.ids = reinterpret_cast<unsigned long long *>(d);
-    W.V.st = reinterpret_cast<DimerState *>(W.ids + ng);   // (8-byte aligned: DimerState is a multiple of 8 bytes)
-    int *ip = reinterpret_cast<int *>(W.V.st + ng);
-    W.ch = reinterpret_cast<NebChain *>(ip); ip += 4 * (size_t)B;
-    W.V.info = ip; ip += 4 * (size_t)ng;
-    W.flags = ip;
+    size_t dbl_bytes = 0;   // the doubles at the head of d_dimer, cleared in one piece
+    auto layout = [&](Arena &a) {
+        a.place(W.V.N, n3); a.place(W.V.Nopen, n3); a.place(W.V.xopen, n3); a.place(W.V.F0, n3); a.place(W.V.F1, n3);
+        a.place(W.V.theta, n3); a.place(W.V.vel, n3); a.place(W.V.rec, 4 * (size_t)ng);
+        dbl_bytes = a.offset();
+        a.place(W.ids, (size_t)ng); a.place(W.V.st, (size_t)ng);
+        a.place(W.ch, (size_t)B); a.place(W.V.info, 4 * (size_t)ng); a.place(W.flags, 4);
+    };
+    if (h->d_dimer.ensure(arena_size(layout))) return set_err(h, VSSR_E_NOMEM, "dimer workspace: out of device memory");
+    arena_carve(h->d_dimer.p, layout);
     W.ng = ng;
     W.P = {p->max_steps, p->max_rot_first, p->max_rot, p->delta, p->phi_tol, p->fmax, fire};
     std::vector<unsigned long long> ids(ng);
@@ -435,10 +426,8 @@ extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, cons
         return rc;
 
     W.fixed = nullptr;
-    if (int rc = relax_begin(h, fixed, 2, W.fixed)) return rc;
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
-    VSSR_HIP(h, hipMemsetAsync(W.V.N, 0, sizeof(double) * n_dbl, st));
+    if (int rc = driver_open(h, fixed, 2, W.fixed, want)) return rc;
+    VSSR_HIP(h, hipMemsetAsync(W.V.N, 0, dbl_bytes, st));
     VSSR_HIP(h, hipMemsetAsync(W.V.info, 0, sizeof(int) * 4 * (size_t)ng, st));
     if (mode_in) {
         VSSR_HIP(h, hipMemcpyAsync(W.V.theta, mode_in, sizeof(double) * n3, hipMemcpyHostToDevice, st));
@@ -450,9 +439,7 @@ extern "C" int vssr_batch_dimer(vssr_handle *h, const vssr_dimer_params *p, cons
                        (double)p->dt, (double)p->astart, h->d_pos.as<double>(), W.V, h->d_active.as<unsigned char>());
     VSSR_HIP(h, hipGetLastError());
     if (int rc = dimer_lockstep(h, W, want)) return rc;
-    h->ran = true;
-    h->graph_partial = false;
-    if (int rc = sync_and_check(h)) return rc;   // (the last evaluation may itself have overflowed the capacity: grow and repeat it)
+    if (int rc = driver_close(h, false)) return rc;
 
     if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * n3, hipMemcpyDeviceToHost));
     if (energy) VSSR_HIP(h, hipMemcpy(energy, chain_energy64(h), sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));

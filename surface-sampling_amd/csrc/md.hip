@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <vector>
+#include "arena.h"
 #include "lockstep.h"
 #include "md_dev.h"
 
@@ -64,37 +65,42 @@ __global__ void k_md_draw(int N, const int *__restrict__ atom_cfg, const int *__
     for (int c = 0; c < 3; ++c) vel[3 * i + c] = sigma * z[c];
 }
 
-// d_md_aux: [stop counters (16 bytes) | chain ids [B] | thermo records]
-static size_t aux_ids() { return 16; }
-static size_t aux_thermo(int B) { return 16 + sizeof(unsigned long long) * (size_t)B; }
+// d_md_aux: [stop counters (16 bytes) | chain ids [B] | thermo records [nrec][B][2]]
+struct MdAux {
+    int *stopped;
+    unsigned long long *ids;
+    double *thermo;
+};
 
-// chain ids on the device (null: 0 .. B-1); d_md_aux holds at least `bytes` afterwards
-static int md_upload_ids(vssr_handle *h, const uint64_t *chain_id, size_t bytes) {
-    const int B = h->n_cfg;
-    if (h->d_md_aux.ensure(std::max(bytes, aux_thermo(B)))) return set_err(h, VSSR_E_NOMEM, "molecular dynamics state: out of device memory");
+// d_md_aux carved for nrec thermo records (0: a caller that draws velocities ahead of the run, which knows no count yet and needs the
+// ids only), chain ids on the device (null: 0 .. B-1)
+static int md_upload_ids(vssr_handle *h, const uint64_t *chain_id, size_t nrec, MdAux &X) {
+    const size_t B = h->n_cfg;
+    auto layout = [&](Arena &a) { a.place(X.stopped, 4); a.place(X.ids, B); a.place(X.thermo, 2 * B * nrec); };
+    if (h->d_md_aux.ensure(arena_size(layout))) return set_err(h, VSSR_E_NOMEM, "molecular dynamics state: out of device memory");
+    arena_carve(h->d_md_aux.p, layout);
     std::vector<unsigned long long> ids(B);
-    for (int b = 0; b < B; ++b) ids[b] = chain_id ? (unsigned long long)chain_id[b] : (unsigned long long)b;
-    VSSR_HIP(h, hipMemcpyAsync(h->d_md_aux.as<char>() + aux_ids(), ids.data(), sizeof(unsigned long long) * (size_t)B, hipMemcpyHostToDevice,
-                               h->stream));
+    for (size_t b = 0; b < B; ++b) ids[b] = chain_id ? (unsigned long long)chain_id[b] : (unsigned long long)b;
+    VSSR_HIP(h, hipMemcpyAsync(X.ids, ids.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, h->stream));
     VSSR_HIP(h, hipStreamSynchronize(h->stream));   // (ids leaves scope)
     return VSSR_OK;
 }
 
-int md_begin(vssr_handle *h, const vssr_md_params *p, const double *mass, const uint8_t *fixed_host, const uint64_t *chain_id, MdWork &W) {
+int md_begin(vssr_handle *h, const vssr_md_params *p, const double *mass, const uint8_t *fixed_host, const uint64_t *chain_id, uint32_t want,
+             MdWork &W) {
     hipStream_t st = h->stream;
     const size_t B = h->n_cfg, N = h->n_atoms;
     W.fixed = nullptr;
-    if (int e = relax_begin(h, fixed_host, 2, W.fixed)) return e;
+    if (int e = driver_open(h, fixed_host, 2, W.fixed, want)) return e;
     W.nrec = p->n_steps / p->thermo_interval + 1;
     const size_t thermo_bytes = sizeof(double) * 2 * B * (size_t)W.nrec;
     if (h->d_opt_state.ensure(sizeof(MdState) * B) || h->d_opt_vec.ensure(sizeof(double) * 7 * N))
         return set_err(h, VSSR_E_NOMEM, "molecular dynamics state: out of device memory");
-    if (int e = md_upload_ids(h, chain_id, aux_thermo((int)B) + thermo_bytes)) return e;
-    char *aux = h->d_md_aux.as<char>();
-    W.stopped = reinterpret_cast<int *>(aux);
+    MdAux X;
+    if (int e = md_upload_ids(h, chain_id, (size_t)W.nrec, X)) return e;
+    W.stopped = X.stopped;
     double *w = h->d_opt_vec.as<double>();
-    W.V = {h->d_opt_state.as<MdState>(), h->d_md_vel.as<double>(), w, w + 3 * N, w + 6 * N,
-           reinterpret_cast<const unsigned long long *>(aux + aux_ids()), reinterpret_cast<double *>(aux + aux_thermo((int)B))};
+    W.V = {h->d_opt_state.as<MdState>(), h->d_md_vel.as<double>(), w, w + 3 * N, w + 6 * N, X.ids, X.thermo};
     VSSR_HIP(h, hipMemsetAsync(W.stopped, 0, 16, st));
     VSSR_HIP(h, hipMemsetAsync(W.V.thermo, 0xFF, thermo_bytes, st));   // records a chain never reaches read as NaN
     VSSR_HIP(h, hipMemcpyAsync(w + 6 * N, mass, sizeof(double) * N, hipMemcpyHostToDevice, st));   // (pageable source: copied before the call returns)
@@ -113,7 +119,6 @@ int md_end(vssr_handle *h, const MdWork &W, double *thermo_out) {
     VSSR_HIP(h, hipGetLastError());
     if (thermo_out)
         VSSR_HIP(h, hipMemcpyAsync(thermo_out, W.V.thermo, sizeof(double) * 2 * (size_t)B * (size_t)W.nrec, hipMemcpyDeviceToHost, h->stream));
-    h->ran = true;
     return VSSR_OK;
 }
 
@@ -176,14 +181,14 @@ int vssr_batch_md_draw_velocities(vssr_handle *h, const double *mass, const uint
     h->md_vel_valid = false;
     if (h->d_md_vel.ensure(sizeof(double) * 3 * (size_t)N) || h->d_opt_vec.ensure(sizeof(double) * 7 * (size_t)N) || h->d_fixed.ensure((size_t)N))
         return set_err(h, VSSR_E_NOMEM, "velocities: out of device memory");
-    if (int rc = md_upload_ids(h, chain_id, 0)) return rc;
+    MdAux X;
+    if (int rc = md_upload_ids(h, chain_id, 0, X)) return rc;
     double *d_mass = h->d_opt_vec.as<double>() + 6 * (size_t)N;   // (where md_begin puts the masses)
     VSSR_HIP(h, hipMemcpy(d_mass, mass, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
     if (fixed) VSSR_HIP(h, hipMemcpy(h->d_fixed.p, fixed, (size_t)N, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_md_draw, dim3((N + 255) / 256), dim3(256), 0, h->stream, N, h->d_atom_cfg.as<int>(), h->d_cfg_start.as<int>(), d_mass,
                        fixed ? h->d_fixed.as<uint8_t>() : nullptr,
-                       reinterpret_cast<const unsigned long long *>(h->d_md_aux.as<char>() + aux_ids()), temperature, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), h->d_md_vel.as<double>());
+                       X.ids, temperature, (uint32_t)seed, (uint32_t)(seed >> 32), h->d_md_vel.as<double>());
     VSSR_HIP(h, hipGetLastError());
     VSSR_HIP(h, hipStreamSynchronize(h->stream));
     h->md_vel_valid = true;
@@ -203,8 +208,7 @@ int vssr_batch_md_get_velocities(vssr_handle *h, double *vel) {
 
 int vssr_batch_md(vssr_handle *h, const vssr_md_params *p, const double *mass, const uint8_t *fixed, const uint64_t *chain_id, uint32_t want,
                   double *pos_out, double *thermo, int32_t *n_done, int32_t *stop_reason) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_md before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!p) return set_err(h, VSSR_E_BADARG, "vssr_batch_md: null parameters");
     if (p->n_steps < 0) return set_err(h, VSSR_E_BADARG, "vssr_batch_md: n_steps %d < 0", (int)p->n_steps);
     if (p->thermo_interval < 1) return set_err(h, VSSR_E_BADARG, "vssr_batch_md: thermo_interval %d < 1", (int)p->thermo_interval);
@@ -222,19 +226,17 @@ int vssr_batch_md(vssr_handle *h, const vssr_md_params *p, const double *mass, c
     if (!h->md_vel_valid)
         return set_err(h, VSSR_E_STATE, "vssr_batch_md: the resident batch has no velocities (vssr_batch_md_set_velocities / _draw_velocities)");
     VSSR_HIP(h, hipSetDevice(h->device));
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
     // one workgroup integrates one chain for the whole call (k_md_chain, chain_min.hip: where the handle's driver setting asks for it
     // and the kernel applies); else the lock-step driver above.  Same results bit for bit.
     const bool resident = chain_md_supported(h);
     MdWork W;
-    if (int rc = md_begin(h, p, mass, fixed, chain_id, W)) return rc;
-    if (int rc = resident ? chain_md(h, W, want) : md_lockstep(h, W, want)) return rc;
+    if (int rc = md_begin(h, p, mass, fixed, chain_id, want, W)) return rc;
+    if (int rc = resident ? chain_md(h, W) : md_lockstep(h, W, want)) return rc;
     if (int rc = md_end(h, W, thermo)) return rc;
     h->md_last_driver = resident ? VSSR_MD_DRIVER_RESIDENT : VSSR_MD_DRIVER_LOCKSTEP;
-    h->graph_partial = resident;     // (the lock-step driver leaves the batch-wide graph of its last evaluation, the chain-resident one
-                                     //  numbers its rows per chain: introspection wants one plain run first)
-    return relax_results(h, pos_out, {n_done, stop_reason});
+    // (the lock-step driver leaves the batch-wide graph of its last evaluation, the chain-resident one numbers its rows per chain:
+    // introspection wants one plain run first)
+    return relax_results(h, resident, pos_out, {n_done, stop_reason});
 }
 
 int vssr_batch_md_driver(vssr_handle *h, int32_t driver, int32_t *last_used) {

@@ -195,15 +195,16 @@ struct MdWork {
     int *stopped;           // [2]: chains that stopped, of those with reason 2
     int nrec;
 };
-// relax_begin, the workspace, masses / chain ids / mask on the device, every chain at step 0 of this call, held atoms at v = 0
-int md_begin(vssr_handle *h, const vssr_md_params *p, const double *mass, const uint8_t *fixed_host, const uint64_t *chain_id, MdWork &W);
+// driver_open, the workspace, masses / chain ids / mask on the device, every chain at step 0 of this call, held atoms at v = 0
+int md_begin(vssr_handle *h, const vssr_md_params *p, const double *mass, const uint8_t *fixed_host, const uint64_t *chain_id, uint32_t want,
+             MdWork &W);
 // d_relax_steps [B][2] = (steps completed, stop reason); the thermo records into thermo_out (may be null; stream-ordered copy)
 int md_end(vssr_handle *h, const MdWork &W, double *thermo_out);
 int md_lockstep(vssr_handle *h, const MdWork &W, uint32_t want);
 // chain_min.hip: the same integration with one workgroup per chain.  chain_md_supported: this call takes it (the kernel applies AND
 // the handle's md_driver asks for it)
 bool chain_md_supported(const vssr_handle *h);
-int chain_md(vssr_handle *h, const MdWork &W, uint32_t want);
+int chain_md(vssr_handle *h, const MdWork &W);
 
 }  // namespace vssr
 #endif

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "arena.h"
 #include "cg_dev.h"
 #include "fire_dev.h"
 #include "lockstep.h"
@@ -334,8 +335,7 @@ using namespace vssr;
 
 extern "C" int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const uint8_t *fixed, const int32_t *n_img, int32_t n_bands,
                               uint32_t want, double *pos_out, double *energy, double *neb_force, double *band, int32_t *info) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_neb before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!p) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: null parameters");
     if (!n_img) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: null n_img");
     if (n_bands < 1) return set_err(h, VSSR_E_BADARG, "vssr_batch_neb: n_bands %d < 1", (int)n_bands);
@@ -378,21 +378,17 @@ extern "C" int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const ui
     hipStream_t st = h->stream;
     VSSR_HIP(h, hipStreamSynchronize(st));
     const size_t n3 = 3 * (size_t)N;
-    const size_t n_dbl = n3 + (size_t)NEB_SLOT * B + 3 * (size_t)nb;
-    const size_t n_int = 4 * (size_t)B + 5 * (size_t)nb + 4;
-    if (h->d_neb.ensure(sizeof(double) * n_dbl + sizeof(int) * n_int) || h->d_opt_state.ensure(sizeof(NebState) * (size_t)B) ||
+    NebWork W;
+    size_t dbl_bytes = 0;   // the doubles at the head of d_neb, cleared in one piece
+    auto layout = [&](Arena &a) {
+        a.place(W.V.G, n3); a.place(W.V.slot, (size_t)NEB_SLOT * B); a.place(W.V.band, 3 * (size_t)nb);
+        dbl_bytes = a.offset();
+        a.place(W.ch, (size_t)B); a.place(W.V.binfo, 4 * (size_t)nb); a.place(W.gfirst, (size_t)nb); a.place(W.flags, 4);
+    };
+    if (h->d_neb.ensure(arena_size(layout)) || h->d_opt_state.ensure(sizeof(NebState) * (size_t)B) ||
         h->d_opt_vec.ensure(sizeof(double) * 2 * n3))
         return set_err(h, VSSR_E_NOMEM, "nudged elastic band workspace: out of device memory");
-    NebWork W;
-    double *d = h->d_neb.as<double>();
-    W.V.G = d; d += n3;
-    W.V.slot = d; d += (size_t)NEB_SLOT * B;
-    W.V.band = d; d += 3 * (size_t)nb;
-    int *ip = reinterpret_cast<int *>(d);
-    W.ch = reinterpret_cast<NebChain *>(ip); ip += 4 * (size_t)B;
-    W.V.binfo = ip; ip += 4 * (size_t)nb;
-    W.gfirst = ip; ip += nb;
-    W.flags = ip;
+    arena_carve(h->d_neb.p, layout);
     W.V.ch = W.ch;
     W.V.st = h->d_opt_state.as<NebState>();
     W.V.vel = h->d_opt_vec.as<double>(); W.V.xprev = W.V.vel + n3;
@@ -404,20 +400,16 @@ extern "C" int vssr_batch_neb(vssr_handle *h, const vssr_neb_params *p, const ui
         return rc;
 
     W.fixed = nullptr;
-    if (int rc = relax_begin(h, fixed, 2, W.fixed)) return rc;
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
+    if (int rc = driver_open(h, fixed, 2, W.fixed, want)) return rc;
     VSSR_HIP(h, hipMemsetAsync(W.V.vel, 0, sizeof(double) * 2 * n3, st));
-    VSSR_HIP(h, hipMemsetAsync(W.V.G, 0, sizeof(double) * n_dbl, st));
+    VSSR_HIP(h, hipMemsetAsync(W.V.G, 0, dbl_bytes, st));
     hipLaunchKernelGGL(k_neb_init, dim3((B + 127) / 128), dim3(128), 0, st, B, (double)p->dt, (double)p->astart, W.V.st,
                        h->d_active.as<unsigned char>());
     VSSR_HIP(h, hipGetLastError());
     if (int rc = neb_lockstep(h, W, want)) return rc;
     hipLaunchKernelGGL(k_neb_report, dim3((nb + 127) / 128), dim3(128), 0, st, nb, W.gfirst, W.V.st, W.V.binfo);
     VSSR_HIP(h, hipGetLastError());
-    h->ran = true;
-    h->graph_partial = false;
-    if (int rc = sync_and_check(h)) return rc;   // (the last evaluation may itself have overflowed the capacity: grow and repeat it)
+    if (int rc = driver_close(h, false)) return rc;
 
     if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * n3, hipMemcpyDeviceToHost));
     if (energy) VSSR_HIP(h, hipMemcpy(energy, chain_energy64(h), sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));

@@ -447,9 +447,15 @@ k_traj_record(const int *__restrict__ cfg_start, const int *__restrict__ counter
     }
 }
 
-// ---- shared by the lock-step drivers (relax_lockstep below, lockstep.h; relax_begin also chain_min.hip) ---------------------
+// ---- the frame of a driver call (vssr_internal.h), shared by every driver's entry point ---------------------------------------
+int driver_guard(vssr_handle *h, const char *func) {
+    if (int rc = check_kind(h, KINDS_EVAL, func)) return rc;
+    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "%s before vssr_batch_upload", func);
+    return VSSR_OK;
+}
+
 // Per-relaxation buffers, the FixAtoms mask on the device (`fixed`: null without a mask), the work counters at zero.
-int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed) {
+int driver_open(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed, uint32_t want) {
     const size_t B = h->n_cfg, N = h->n_atoms;
     if (h->d_fixed.ensure(N) || h->d_relax_steps.ensure(sizeof(int) * steps_ints_per_chain * B) || h->d_relax_conv.ensure(B) ||
         h->d_active.ensure(B) || h->d_counters.ensure(sizeof(int) * 4))
@@ -457,7 +463,15 @@ int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_ch
     if (fixed_host) VSSR_HIP(h, hipMemcpyAsync(h->d_fixed.p, fixed_host, N, hipMemcpyHostToDevice, h->stream));
     fixed = fixed_host ? h->d_fixed.as<uint8_t>() : nullptr;
     h->relax_lockstep = h->relax_chain_evals = h->relax_compactions = 0;
+    h->relax_regrows = 0;
+    h->last_want = want | VSSR_WANT_FORCES;
     return VSSR_OK;
+}
+
+int driver_close(vssr_handle *h, bool partial) {
+    h->ran = true;
+    h->graph_partial = partial;
+    return sync_and_check(h);
 }
 
 // Neighbor capacity overflow seen at a poll: grow (at most `cap` times per relaxation) and give the polling window back: the step
@@ -469,8 +483,8 @@ int relax_regrow(vssr_handle *h, int cap, long long &it, int window) {
     return VSSR_OK;
 }
 
-int relax_results(vssr_handle *h, double *pos_out, std::initializer_list<int32_t *> cols) {
-    if (int rc = sync_and_check(h)) return rc;   // (a last batch-wide evaluation may itself have overflowed the capacity: grow and repeat it)
+int relax_results(vssr_handle *h, bool partial, double *pos_out, std::initializer_list<int32_t *> cols) {
+    if (int rc = driver_close(h, partial)) return rc;
     if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * 3 * h->n_atoms, hipMemcpyDeviceToHost));
     const size_t k = cols.size();
     std::vector<int> rep(k * h->n_cfg);
@@ -550,7 +564,7 @@ int relax_lockstep(vssr_handle *h, const typename Work::Params &p, const uint8_t
     const int max_steps = p.max_steps;
     const uint8_t *fixed = nullptr;
     Work w;
-    if (int e = relax_begin(h, fixed_host, 1, fixed)) return e;
+    if (int e = driver_open(h, fixed_host, 1, fixed, want)) return e;
     if (int e = w.init(h, p)) return e;
     int rc = VSSR_OK;
     unsigned char *active = h->d_active.as<unsigned char>();

@@ -68,7 +68,7 @@ int relax_bfgsls(vssr_handle *h, const vssr_bfgsls_params *bp, const uint8_t *fi
     const int B = h->n_cfg;
     const uint8_t *fixed = nullptr;
     BlsView V;
-    if (int e = relax_begin(h, fixed_host, 3, fixed)) return e;
+    if (int e = driver_open(h, fixed_host, 3, fixed, want)) return e;
     if (int e = bls_workspace(h, bp->max_steps, V)) return e;
     // ASE's defaults for what the ABI does not expose: stpmin, xtol, xtrapl, xtrapu
     const BlsParams P{bp->max_steps, bp->max_eval, bp->fmax, bp->alpha, bp->maxstep, bp->c1, bp->c2, bp->stpmax, 1e-8, 1e-14, 1.1, 4.0};
@@ -90,7 +90,6 @@ int relax_bfgsls(vssr_handle *h, const vssr_bfgsls_params *bp, const uint8_t *fi
     if (rc) return rc;
     hipLaunchKernelGGL(k_bls_report, dim3((B + 127) / 128), dim3(128), 0, st, B, V.st, h->d_relax_steps.as<int>());
     VSSR_HIP(h, hipGetLastError());
-    h->ran = true;
     return VSSR_OK;
 }
 

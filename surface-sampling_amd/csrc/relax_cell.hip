@@ -21,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "arena.h"
 #include "cell_dev.h"
 #include "cg_dev.h"
 #include "fire_dev.h"
@@ -319,8 +320,7 @@ extern "C" int vssr_batch_get_cell(vssr_handle *h, double *cell) {
 
 extern "C" int vssr_batch_relax_cell(vssr_handle *h, const vssr_cell_relax_params *p, const uint8_t *fixed, uint32_t want, double *pos_out,
                                      double *cell_out, int32_t *n_steps, int32_t *stop_reason, double *result) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_cell before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!evaluator(h).stress) return set_err(h, VSSR_E_STATE, "vssr_batch_relax_cell: this handle serves no stress");
     if (h->ew_on)
         return set_err(h, VSSR_E_STATE, "vssr_batch_relax_cell: a pair handle with k-space is not served: the S(k) stride (ew_stride = %d reciprocal "
@@ -370,21 +370,14 @@ extern "C" int vssr_batch_relax_cell(vssr_handle *h, const vssr_cell_relax_param
     }
 
     const size_t n3 = 3 * (size_t)N;
-    const size_t n_dbl = 3 * n3 + 3 * (size_t)B;
-    const size_t bytes = sizeof(double) * n_dbl + sizeof(CellState) * B + sizeof(int) * (2 * (size_t)B + 2);
-    if (h->d_cellrelax.ensure(bytes) || h->d_stress.ensure(sizeof(double) * 12 * (size_t)B))
-        return set_err(h, VSSR_E_NOMEM, "cell relaxation workspace: out of device memory");
     CellWork W;
-    double *d = h->d_cellrelax.as<double>();
-    W.V.s = d; d += n3;
-    W.V.sopen = d; d += n3;
-    W.V.vel = d; d += n3;
-    W.V.rec = d; d += 3 * (size_t)B;
-    W.V.st = reinterpret_cast<CellState *>(d);   // (8-byte aligned: CellState is a multiple of 8 bytes)
-    static_assert(sizeof(CellState) % 8 == 0, "CellState keeps the ints behind it aligned");
-    int *ip = reinterpret_cast<int *>(W.V.st + B);
-    W.V.info = ip; ip += 2 * (size_t)B;
-    W.flags = ip;
+    auto layout = [&](Arena &a) {
+        a.place(W.V.s, n3); a.place(W.V.sopen, n3); a.place(W.V.vel, n3); a.place(W.V.rec, 3 * (size_t)B);
+        a.place(W.V.st, (size_t)B); a.place(W.V.info, 2 * (size_t)B); a.place(W.flags, 2);
+    };
+    if (h->d_cellrelax.ensure(arena_size(layout)) || h->d_stress.ensure(sizeof(double) * 12 * (size_t)B))
+        return set_err(h, VSSR_E_NOMEM, "cell relaxation workspace: out of device memory");
+    arena_carve(h->d_cellrelax.p, layout);
     W.P.max_steps = p->max_steps; W.P.hydrostatic = p->hydrostatic_strain != 0;
     W.P.fmax = p->fmax; W.P.pressure = p->scalar_pressure; W.P.cutoff = evaluator(h).cutoff(h);
     static const int voigt_of[9] = {0, 5, 4, 5, 1, 3, 4, 3, 2};
@@ -392,18 +385,14 @@ extern "C" int vssr_batch_relax_cell(vssr_handle *h, const vssr_cell_relax_param
     W.P.fire = fire;
 
     W.fixed = nullptr;
-    if (int rc = relax_begin(h, fixed, 2, W.fixed)) return rc;
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
+    if (int rc = driver_open(h, fixed, 2, W.fixed, want)) return rc;
     h->ran = false;   // (until the loop has left a complete evaluation: a failure in between leaves moved cells behind)
     VSSR_HIP(h, hipMemsetAsync(W.flags, 0, sizeof(int) * 2, st));
     hipLaunchKernelGGL(k_cell_init, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), (double)p->dt, (double)p->astart, (double)p->cell_factor,
                        h->d_pos.as<double>(), h->d_cell.as<double>(), h->d_nimg.as<int>(), W.V);
     VSSR_HIP(h, hipGetLastError());
     if (int rc = cell_lockstep(h, W, want)) return rc;
-    h->ran = true;
-    h->graph_partial = false;
-    if (int rc = sync_and_check(h)) return rc;   // (the last evaluation may itself have overflowed the capacity: grow and repeat it)
+    if (int rc = driver_close(h, false)) return rc;
 
     if (pos_out) VSSR_HIP(h, hipMemcpy(pos_out, h->d_pos.p, sizeof(double) * n3, hipMemcpyDeviceToHost));
     if (cell_out) VSSR_HIP(h, hipMemcpy(cell_out, h->d_cell.p, sizeof(double) * 9 * (size_t)B, hipMemcpyDeviceToHost));

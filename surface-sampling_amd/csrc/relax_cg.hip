@@ -2,6 +2,7 @@
 // that steps every chain's state machine (cg_dev.h) once per batch-wide evaluation in the frame of lockstep.h, and the Compactor
 // that shrinks the resident batch to the chains still running.
 #include <algorithm>
+#include "arena.h"
 #include "cg_dev.h"
 #include "lockstep.h"
 
@@ -124,7 +125,7 @@ __global__ void k_cg_report(int B, const CgState *__restrict__ st, int *__restri
     out[3 * b] = st[b].niter; out[3 * b + 1] = st[b].neval; out[3 * b + 2] = st[b].reason;
 }
 
-// The field list of a CmpView, once: fn(member, elements, role) per array of a layout with B chains / N atoms.  The arena's carve,
+// The field list of a CmpView, once: fn(member, elements, role) per array of a layout with B chains / N atoms.  The arena's layout,
 // the save of the uploaded batch and its restore walk this list; element sizes come from the members' types.
 enum CmpRole { CMP_INPUT, CMP_RESULT, CMP_WORK };   // uploaded inputs < what a relaxation leaves (positions, state) < optimizer vectors
 template <class Fn>
@@ -158,19 +159,15 @@ struct Compactor {
     // whatever the live share, and the compaction (four launches + a host read) would only add to it (measured, 256
     // chains x 48 atoms: -3 %; profiles/r05/NOTES_tersoff.md)
     bool due(int n_live) const { return knob != 0 && N_cur >= (knob > 1 ? knob : 65536) && (long long)n_live * 4 <= (long long)B_cur * 3; }
-    int carve() {
-        for (int pass = 0; pass < 2; ++pass) {   // sizes first, then pointers
-            char *p = pass ? h->d_cmp.as<char>() : nullptr;
-            size_t off = 0;
-            auto place = [&](auto *&f, size_t n) {
-                if (p) f = reinterpret_cast<decltype(f + 0)>(p + off);
-                off += (n * sizeof(*f) + 255) & ~(size_t)255;
-            };
-            for_each_field(B, N, [&](auto m, size_t n, CmpRole role) { if (role != CMP_WORK) place(orig.*m, n); });
-            place(live, B); place(live_new, B); place(src, B); place(start_new, (size_t)B + 1); place(totals, 4);
-            for_each_field(B, N, [&](auto m, size_t n, CmpRole) { place(tmp.*m, n); });
-            if (!pass && h->d_cmp.ensure(off)) return -1;
-        }
+    int carve() {   // every block on 256-byte lines of its own, the last one included
+        auto layout = [&](Arena &a) {
+            for_each_field(B, N, [&](auto m, size_t n, CmpRole role) { if (role != CMP_WORK) a.place(orig.*m, n); });
+            a.place(live, B); a.place(live_new, B); a.place(src, B); a.place(start_new, (size_t)B + 1); a.place(totals, 4);
+            for_each_field(B, N, [&](auto m, size_t n, CmpRole) { a.place(tmp.*m, n); });
+            a.align(256);
+        };
+        if (h->d_cmp.ensure(arena_size(layout, 256))) return -1;
+        arena_carve(h->d_cmp.p, layout, 256);
         return 0;
     }
     int copy_fields(const CmpView &to, const CmpView &from, CmpRole upto) {   // the arrays of roles <= upto, at the uploaded batch's sizes
@@ -226,7 +223,7 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
         return set_err(h, VSSR_E_STATE, "conjugate gradients need an fp64 potential (Tersoff / EAM / SW handle); use BFGS or FIRE");
     const uint8_t *fixed = nullptr;
     CgWork W;
-    if (int e = relax_begin(h, fixed_host, 3, fixed)) return e;
+    if (int e = driver_open(h, fixed_host, 3, fixed, want)) return e;
     if (int e = CgWork::ensure(h, W)) return e;
     unsigned char *active = h->d_active.as<unsigned char>();
     hipLaunchKernelGGL(k_cg_init, dim3((h->n_cfg + 127) / 128), dim3(128), 0, st, h->n_cfg, W.st, active);
@@ -252,7 +249,6 @@ int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host
     if (rc) return C.abandon(rc);   // (nothing to abandon once restore has run)
     hipLaunchKernelGGL(k_cg_report, dim3((C.B + 127) / 128), dim3(128), 0, st, C.B, W.st, h->d_relax_steps.as<int>());
     VSSR_HIP(h, hipGetLastError());
-    h->ran = true;
     return VSSR_OK;
 }
 

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "arena.h"
 #include "jacobi_dev.h"
 #include "lockstep.h"
 #include "md_dev.h"
@@ -322,8 +323,7 @@ using namespace vssr;
 extern "C" int vssr_batch_vibrations(vssr_handle *h, const vssr_vib_params *p, const double *mass, const uint8_t *vib, const int32_t *n_rep,
                                      int32_t n_groups, int32_t ld, uint32_t want, double *energies, double *hessian, double *modes,
                                      double *thermo, int32_t *info) {
-    if (int rc = check_kind(h, KINDS_EVAL, __func__)) return rc;
-    if (!h->batch_valid) return set_err(h, VSSR_E_STATE, "vssr_batch_vibrations before vssr_batch_upload");
+    if (int rc = driver_guard(h, __func__)) return rc;
     if (!p) return set_err(h, VSSR_E_BADARG, "vssr_batch_vibrations: null parameters");
     if (!mass) return set_err(h, VSSR_E_BADARG, "vssr_batch_vibrations: null masses");
     if (p->nfree != 2 && p->nfree != 4) return set_err(h, VSSR_E_BADARG, "vssr_batch_vibrations: nfree %d is neither 2 nor 4", (int)p->nfree);
@@ -385,33 +385,20 @@ extern "C" int vssr_batch_vibrations(vssr_handle *h, const vssr_vib_params *p, c
     VSSR_HIP(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
     VSSR_HIP(h, hipStreamSynchronize(st));
-    const size_t n_dbl = n3 * 5 + N + 5 * mat + 2 * (size_t)G * ldd + 3 * (size_t)G;
-    const size_t n_int = 4 * (size_t)B * 2 + (B + 1) + vib_list.size() + 1 + 9 * (size_t)G + 4;
-    if (h->d_vib.ensure(sizeof(double) * n_dbl + sizeof(int) * n_int)) return set_err(h, VSSR_E_NOMEM, "vibrations workspace: out of device memory");
     VibWork W;
-    double *d = h->d_vib.as<double>();
-    W.V.x0 = d; d += n3;
-    W.V.Fs = d; d += 4 * n3;
-    W.mass = d; d += N;
-    W.V.K = d; W.modes = d; d += mat;   // (the rows are consumed by k_vib_sym before k_vib_modes writes the modes)
-    W.Hs = d; d += mat;
-    W.A = d; d += mat;
-    W.W = d; d += mat;
-    W.Vt = d; d += mat;
-    W.w2 = d; d += (size_t)G * ldd;
-    W.en = d; d += (size_t)G * ldd;
-    W.thermo = d; d += 3 * (size_t)G;
-    int *ip = reinterpret_cast<int *>(d);
-    W.ch = reinterpret_cast<VibChain *>(ip); ip += 4 * (size_t)B;
-    W.V.st = reinterpret_cast<VibState *>(ip); ip += 4 * (size_t)B;
-    W.vib_start = ip; ip += B + 1;
-    W.vib_list = ip; ip += vib_list.size() + 1;
-    W.gm = ip; ip += G;
-    W.gfirst = ip; ip += G;
-    W.V.gbad = ip; ip += G;
-    W.jinfo = ip; ip += 2 * (size_t)G;
-    W.info = ip; ip += 4 * (size_t)G;
-    W.flags = ip;
+    auto layout = [&](Arena &a) {
+        const size_t nB = B, nG = G;
+        a.place(W.V.x0, n3); a.place(W.V.Fs, 4 * n3); a.place(W.mass, (size_t)N);
+        a.place(W.V.K, mat); a.place(W.Hs, mat); a.place(W.A, mat); a.place(W.W, mat); a.place(W.Vt, mat);
+        a.place(W.w2, nG * ldd); a.place(W.en, nG * ldd); a.place(W.thermo, 3 * nG);
+        a.place(W.ch, nB); a.place(W.V.st, nB);
+        a.place(W.vib_start, nB + 1); a.place(W.vib_list, vib_list.size() + 1);
+        a.place(W.gm, nG); a.place(W.gfirst, nG); a.place(W.V.gbad, nG); a.place(W.jinfo, 2 * nG); a.place(W.info, 4 * nG);
+        a.place(W.flags, 4);
+    };
+    if (h->d_vib.ensure(arena_size(layout))) return set_err(h, VSSR_E_NOMEM, "vibrations workspace: out of device memory");
+    arena_carve(h->d_vib.p, layout);
+    W.modes = W.V.K;   // (an alias: the rows are consumed by k_vib_sym before k_vib_modes writes the modes)
     W.V.ch = W.ch; W.V.vib_start = W.vib_start; W.V.vib_list = W.vib_list;
     W.V.n3 = n3; W.V.ld = (int)ldd; W.V.nfree = p->nfree; W.V.method = p->method; W.V.delta = p->delta;
     W.G = G; W.ld = (int)ldd; W.max_share = max_share;
@@ -436,15 +423,11 @@ extern "C" int vssr_batch_vibrations(vssr_handle *h, const vssr_vib_params *p, c
         return set_err(h, VSSR_E_BADARG, "vssr_batch_vibrations: the replicas of a group differ (species, cell, pbc or positions; the comparison is bitwise)");
 
     const uint8_t *unused = nullptr;
-    if (int rc = relax_begin(h, nullptr, 2, unused)) return rc;
-    h->relax_regrows = 0;
-    h->last_want = want | VSSR_WANT_FORCES;
+    if (int rc = driver_open(h, nullptr, 2, unused, want)) return rc;
     hipLaunchKernelGGL(k_vib_place, dim3(B), dim3(256), 0, st, h->d_cfg_start.as<int>(), h->d_pos.as<double>(), W.V, W.flags);
     VSSR_HIP(h, hipGetLastError());
     if (int rc = vib_lockstep(h, W, want)) return rc;
-    h->ran = true;
-    h->graph_partial = false;
-    if (int rc = sync_and_check(h)) return rc;   // (the last evaluation may itself have overflowed the capacity: grow and repeat it)
+    if (int rc = driver_close(h, false)) return rc;
 
     hipLaunchKernelGGL(k_vib_sym, dim3(G), dim3(256), 0, st, W.gm, W.gfirst, h->d_cfg_start.as<int>(), W.vib_start, W.vib_list, W.mass,
                        W.V.gbad, W.ld, W.V.K, W.Hs, W.A);

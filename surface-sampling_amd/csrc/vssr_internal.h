@@ -595,10 +595,17 @@ void eam_build_spline(const double *f, int n, double delta, double *spl /*[n + 1
 // lock-step FIRE / BFGS relaxation (relax.hip, relax_lockstep<FireWork | BfgsWork>); results in d_relax_steps [B], d_relax_conv [B]; fixed_host may be null
 int relax_fire(vssr_handle *h, const vssr_fire_params &p, const uint8_t *fixed_host, uint32_t want);
 int relax_bfgs(vssr_handle *h, const vssr_bfgs_params &p, const uint8_t *fixed_host, uint32_t want);
-int relax_begin(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed);   // buffers, mask (-> fixed), counters
+// The frame of a driver call (relax.hip).  driver_guard: first in every entry point -- the handle's kind, then "<func> before
+// vssr_batch_upload".  driver_open: behind the last argument check, so that a refused call leaves the handle as it was -- the
+// per-relaxation buffers, the mask (-> fixed), the work and regrow counters at zero, last_want = want | forces.  driver_close: the batch
+// holds a finished evaluation (partial: of the chains of the last iteration only, or numbered per chain) -- ran, graph_partial,
+// sync_and_check (that evaluation may itself have overflowed the capacity: grow and repeat it).
+int driver_guard(vssr_handle *h, const char *func);
+int driver_open(vssr_handle *h, const uint8_t *fixed_host, int steps_ints_per_chain, const uint8_t *&fixed, uint32_t want);
+int driver_close(vssr_handle *h, bool partial);
 int relax_regrow(vssr_handle *h, int cap, long long &it, int window);   // after an overflow seen at a poll: grow, give the poll window back
-// the tail of a driver's entry point: sync_and_check, the positions, and d_relax_steps [B][k] de-interleaved into its k columns (null: not wanted)
-int relax_results(vssr_handle *h, double *pos_out, std::initializer_list<int32_t *> cols);
+// the tail of a driver's entry point: driver_close, the positions, and d_relax_steps [B][k] de-interleaved into its k columns (null: not wanted)
+int relax_results(vssr_handle *h, bool partial, double *pos_out, std::initializer_list<int32_t *> cols);
 // lock-step LAMMPS-style CG for the fp64 potentials (relax_cg.hip); results in d_relax_steps [B][3] = {iterations, evaluations, stop reason}
 int relax_cg(vssr_handle *h, const vssr_cg_params *cp, const uint8_t *fixed_host, uint32_t want);
 // lock-step BFGSLineSearch on every kind that relaxes (relax_bfgsls.hip, bfgsls_dev.h); results in d_relax_steps [B][3] = {steps, evaluations, stop reason}

@@ -1,7 +1,7 @@
 """Bit-equality record of the fp64 analytic potentials and the relaxation drivers: evaluates a fixed set of small cases on the library VSSR_EVAL_LIB names (as
 every tool here) and prints one JSON object {case: {array: SHA-256 of its bytes}}.  Run it once per build and diff the outputs: a
-refactor of tersoff.hip / sw.hip / pair.hip / eam.hip / pot_common.hip / relax.hip / relax_cg.hip / chain_min.hip must leave every
-digest as it was.
+refactor of tersoff.hip / sw.hip / pair.hip / eam.hip / pot_common.hip / relax.hip / relax_cg.hip / chain_min.hip or of a driver
+(relax_bfgsls.hip, md.hip, vib.hip, neb.hip, dimer.hip, relax_cell.hip) must leave every digest as it was.
 
 Cases (the smallest that reach every kernel and branch of those files):
   tersoff_gan       GaN.tersoff: the 3x3 slab + 12 Ga adatoms (48 atoms), the bare slab (36), a 43-atom dense box whose rows
@@ -19,6 +19,15 @@ lock-step relaxation drivers).  Beyond those, on the GaN batch (whose chains sto
   traj_fire / traj_bfgs   FIRE and BFGS with record_interval=3: the trajectory records (n_records, positions, forces, energies)
 and one PaiNN (fp32) handle, the drivers' other force path:
   painn_fire / painn_bfgs   two 60-atom SrTiO3 chains with different FixAtoms masks, 6 steps
+and the other drivers, each at the smallest shape that reaches its host branches, on the GaN handle (gan_*, and gan_*_tight where the
+capacity is regrown inside the driver's loop or the chain-resident pools double) and on the PaiNN handle (painn_*), every returned
+array plus relax_counts(), and the regrow count in clear:
+  bfgsls            BFGSLineSearch, 6 steps
+  md_{lockstep,resident}_{nve,langevin}   6 steps from drawn velocities, a thermo record every 2 (resident: the GaN handle only)
+  vib               three chains, n_rep = [2, 1]: a replica group and a single chain, 4 vib atoms each
+  neb               a band of 3 images and a band of 4 in one batch, 5 steps
+  dimer             two dimers, drawn modes, 4 steps
+  cell_hydrostatic / cell_slab   relax_cell of a fully periodic chain with hydrostatic strain; of two chains under the slab mask
 Usage: VSSR_EVAL_LIB=build/variants/lib_x.so python tools/dump_analytic.py > out.json"""
 import hashlib, json, os, sys
 
@@ -105,6 +114,61 @@ def relaxations_beyond(eng, structs):
                positions=out["positions"], n_steps=out["n_steps"], converged=out["converged"])
 
 
+def flat(v):
+    return np.concatenate([np.ravel(x) for x in v]) if isinstance(v, list) else v
+
+
+def drivers(eng, prefix, tight, a, b, box, masses_of, resident):
+    """Every driver beyond CG / FIRE / BFGS on one handle.  a, b: two structures (T, X, cell, pbc) of different positions (and, on
+    the GaN handle, sizes); box: a fully periodic one; masses_of(T): amu per atom."""
+    from surface_sampling_amd import backend
+
+    def case(name, structs, call):
+        if tight:
+            eng.debug_capacity(slots_per_atom=1, tight=1)
+        eng.upload(structs)
+        try:
+            out = call(structs)
+        except backend.BackendError as err:   # (in clear: the same refusal from both builds is a record too)
+            OUT[f"{prefix}_{name}"] = {"error": str(err)}
+            return
+        record(f"{prefix}_{name}", relax_counts=np.array(eng.last_relax_counts, np.int64), **{k: flat(v) for k, v in out.items()})
+        OUT[f"{prefix}_{name}"]["regrows"] = eng.debug_capacity()   # (in clear: > 0 shows that a *_tight case did regrow)
+
+    def held(structs):
+        return np.concatenate([np.arange(len(s[0])) % 5 == 0 for s in structs]).astype(np.uint8)
+
+    def masses(structs):
+        return np.concatenate([masses_of(s[0]) for s in structs])
+
+    def moved(s, k, n):   # image k of n on a straight line from s to a displaced copy of it
+        d = np.random.default_rng(len(s[0])).normal(0, 0.08, s[1].shape)
+        return (s[0], s[1] + d * k / (n - 1), s[2], s[3])
+
+    def results(out):   # with the static results the driver left on the device
+        if hasattr(eng, "results_f64"):
+            e, ea, f = eng.results_f64()
+            return dict(out, dev_energy=e, dev_e_atom=ea, dev_forces=f)
+        res = eng.download()
+        return dict(out, dev_energy=res["energy_f64"], dev_forces=res["forces"], dev_energy_std=res["energy_std"])
+
+    case("bfgsls", [a, b], lambda S: results(eng.relax_bfgs_linesearch(fixed=held(S), max_steps=6, fmax=0.01)))
+    for driver in ("lockstep", "resident") if resident else ("lockstep",):
+        for thermostat in ("nve", "langevin"):
+            def md(S):
+                eng.draw_velocities(masses(S), 300.0, seed=5, fixed=held(S))
+                return eng.md(masses(S), 6, 1.0, thermostat=thermostat, temperature=300.0, friction=0.01, seed=9, fixed=held(S),
+                              thermo_interval=2, driver=driver)
+            case(f"md_{driver}_{thermostat}", [a, b], md)
+    case("vib", [a, a, b], lambda S: eng.vibrations(masses(S), vib=np.concatenate([np.arange(len(s[0])) < 4 for s in S]), n_rep=[2, 1],
+                                                     temperature=300.0, return_hessian=True, return_modes=True))
+    bands = [moved(a, k, 3) for k in range(3)] + [moved(b, k, 4) for k in range(4)]
+    case("neb", bands, lambda S: results(eng.neb([3, 4], fixed=held(S), climb=True, max_steps=5)))
+    case("dimer", [a, a, b, b], lambda S: results(eng.dimer(fixed=held(S), seed=3, max_steps=4)))
+    case("cell_hydrostatic", [box], lambda S: results(eng.relax_cell(hydrostatic_strain=True, max_steps=5)))
+    case("cell_slab", [a, b], lambda S: results(eng.relax_cell(fixed=held(S), mask=(1, 1, 0, 0, 0, 1), max_steps=5)))
+
+
 def painn_relaxations():
     """The fp32 force path of the lock-step drivers: a PaiNN ensemble, two chains, different FixAtoms masks."""
     from surface_sampling_amd import backend
@@ -123,6 +187,8 @@ def painn_relaxations():
         res = eng.download()
         record(f"painn_{opt.lower()}", positions=out["positions"], n_steps=out["n_steps"], converged=out["converged"],
                energy=res["energy"], forces=res["forces"], energy_std=res["energy_std"])
+    amu = {38: 87.62, 22: 47.867, 8: 15.999}
+    drivers(eng, "painn", False, chains[0], chains[1], chains[0], lambda T: np.array([amu[int(z)] for z in T]), resident=False)
     eng.close()
 
 
@@ -147,6 +213,7 @@ def main():
         relaxations(eng, gan, tag, tight)
         if not tight:
             relaxations_beyond(eng, gan)
+        drivers(eng, "gan" + tag, tight, gan[1], gan[0], gan[2], lambda T: np.where(np.asarray(T) == 0, 69.723, 14.007), resident=True)
         eng.close()
         eng = backend.PairEngine(m, device=0)
         single_point("pair_rocksalt" + tag, eng, [rock], tight)
