@@ -864,7 +864,13 @@ enum { VSSR_GMM_COV_FULL = 0, VSSR_GMM_COV_TIED = 1, VSSR_GMM_COV_DIAG = 2, VSSR
 /* GIVEN: the start comes from vssr_gmm_fit_set_init (all of means / weights / precisions, or labels, or both: explicit values win as in
  * sklearn's _initialize).  KMEANS: Lloyd iterations on the device from K distinct rows drawn with Philox4x32-10 keyed by `seed`;
  * RANDOM_FROM_DATA: K distinct rows drawn the same way get responsibility 1 for one component each.  The draws do not reproduce numpy's
- * streams.  Explicit values from set_init override what either produces. */
+ * streams.  Explicit values from set_init override what either produces.
+ * KMEANS in full: the first centre is row min(N - 1, floor(u N)); every later one is drawn by D^2 sampling over the running minimum
+ * squared distances (one candidate per centre; the cumulative walk runs over the sums of 256-row blocks, then inside the block, and
+ * passes over a row at distance zero while another is left).  Lloyd rounds assign every row to its nearest centre (the first on ties)
+ * and move each centre to the mean of its members, until the inertia repeats or for 300 rounds.  A cluster that ends without members is
+ * not relocated: its sum is divided by 10 eps like any other, so its centre is the origin, and its component starts with n_k = 10 eps
+ * (weight 10 eps / N), mean 0 and covariance reg_covar I (an ill-defined covariance when reg_covar = 0). */
 enum { VSSR_GMM_INIT_GIVEN = 0, VSSR_GMM_INIT_KMEANS = 1, VSSR_GMM_INIT_RANDOM_FROM_DATA = 2 };
 typedef struct {
     uint32_t struct_size;    /* sizeof(vssr_gmm_fit_config) */

@@ -344,11 +344,9 @@ k_fit_prec_diag(const double *__restrict__ cov, int spherical, int D, int Dp, co
         Pk[idx] = i == j ? p[i] : 0.0;
     }
     if (t < Dp) c[(size_t)k * Dp + t] = t < D ? means[(size_t)k * Dp + t] * p[t] : 0.0;
-    if (t == 0) {
-        double ld = 0.0;
-        if (spherical) ld = (double)D * log(p[0]);
-        else
-            for (int d = 0; d < D; ++d) ld += log(p[d]);
+    if (t == 0) {   // summed term by term for both types, as gmm_upload sums the diagonal of an expanded factor: the scorer of a fit
+        double ld = 0.0;   // and an engine built from its downloaded parameters hold the same bits
+        for (int d = 0; d < D; ++d) ld += log(p[d]);
         kc[k] = ld;
     }
     const int NB = Dp >> 4;

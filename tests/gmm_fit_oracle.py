@@ -1,5 +1,6 @@
 """Independent numpy fp64 restatement of the Gaussian-mixture EM fit (reference mcmc/uncertainty/gmm.py, i.e. sklearn's
-GaussianMixture / BaseMixture.fit): E step, M step in the centred form, precision Cholesky factors, the stopping rule; and the
+GaussianMixture / BaseMixture.fit): E step, M step in the centred form, precision Cholesky factors, the stopping rule; the seeded
+initialisers of the device fit as include/vssr_eval.h defines them (Philox draws, "random_from_data", k-means++ and Lloyd); and the
 loader of the reference fixtures tests/golden/gmm_fit_*.npz (written by tools/make_gmm_fit_golden.py)."""
 import glob
 import os
@@ -115,6 +116,99 @@ def em_iteration(X, weights, means, prec_chol, cov_type, reg_covar):
     lb, resp = e_step(X, weights, means, prec_chol, cov_type)
     nk, m, cov = m_step(X, resp, reg_covar, cov_type)
     return lb, nk / nk.sum(), m, cov, precision_cholesky(cov, cov_type)
+
+
+# ---- the seeded initialisers (csrc/gmm_fit.hip: fit_uniform, fit_draw_rows, fit_kmeans; include/vssr_eval.h) -------------------------
+KMEANS_ROUNDS = 300
+
+
+def uniform(seed, restart, draw):
+    """u(seed, restart, draw) in [0, 1): Philox4x32-10 on counter (draw, restart, 0x676d6d, 0), key = seed; 53 bits of words 0, 1."""
+    from surface_sampling_amd import mc
+
+    seed = int(seed) & (2 ** 64 - 1)
+    c = mc.philox4x32(np.array([draw, restart, 0x676D6D, 0], np.uint64), np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64))
+    return float(((int(c[0]) << 32 | int(c[1])) >> 11) * 2.0 ** -53)
+
+
+def random_from_data_labels(n, K, seed, restart):
+    """Labels of the "random_from_data" start: K distinct rows (repeats rejected, draws numbered from 0) own one component each,
+    every other row has none (-1)."""
+    rows, draw = [], 0
+    while len(rows) < K:
+        r = min(n - 1, int(uniform(seed, restart, draw) * n))
+        draw += 1
+        if r not in rows:
+            rows.append(r)
+    labels = np.full(n, -1, np.int32)
+    labels[rows] = np.arange(K)
+    return labels
+
+
+def _sqdist(X, c):
+    return ((X - c) ** 2).sum(axis=1)
+
+
+def kmeans(X, K, seed, restart):
+    """The "kmeans" start: k-means++ seeding by D^2 sampling (one candidate per centre; the cumulative walk runs over the sums of
+    256-row blocks, then inside the block; a row at distance zero is passed over while another is left), then Lloyd rounds (nearest
+    centre, the first on ties; means of the members over n_k + 10 eps, so a centre without members moves to the origin) until the
+    inertia repeats or 300 rounds.  Returns (labels, centres, margins): ``margins["walk"]`` is the smallest |cumulative sum - target|
+    / total over every comparison of the seeding, ``margins["tie"]`` the smallest (d2 - d1) / d2 of the two nearest centres of a
+    row over every Lloyd round -- where either is not far above rounding, another summation order may pick differently;
+    ``margins["exact_ties"]`` counts the rows whose two nearest centres were exactly as far."""
+    X = np.asarray(X, dtype=np.float64)
+    n = len(X)
+    n_blk = (n + 255) // 256
+    walk, tie, exact = np.inf, np.inf, 0
+    first = min(n - 1, int(uniform(seed, restart, 0) * n))
+    cen = [X[first].copy()]
+    mind2 = np.full(n, np.inf)
+    for c in range(1, K):
+        mind2 = np.minimum(mind2, _sqdist(X, cen[c - 1]))
+        hp = [float(mind2[256 * b:256 * (b + 1)].sum()) for b in range(n_blk)]
+        tot = 0.0
+        for v in hp:
+            tot += v
+        target = uniform(seed, restart, c) * tot
+        blk, run = 0, 0.0
+        while blk < n_blk - 1:
+            if tot > 0:
+                walk = min(walk, abs(run + hp[blk] - target) / tot)
+            if not run + hp[blk] <= target:
+                break
+            run += hp[blk]
+            blk += 1
+        hm = mind2[256 * blk:256 * (blk + 1)]
+        pick = 0
+        while pick < len(hm) - 1:
+            if tot > 0:
+                walk = min(walk, abs(run + hm[pick] - target) / tot)
+            if not run + hm[pick] <= target:
+                break
+            run += hm[pick]
+            pick += 1
+        while pick < len(hm) - 1 and not hm[pick] > 0.0:
+            pick += 1
+        cen.append(X[256 * blk + pick].copy())
+    cen = np.array(cen)
+    prev, labels = -1.0, None
+    for _ in range(KMEANS_ROUNDS):
+        d2 = np.stack([_sqdist(X, cen[k]) for k in range(K)], axis=1)
+        labels = np.argmin(d2, axis=1)           # (the first on ties)
+        if K > 1:
+            two = np.sort(d2, axis=1)[:, :2]
+            apart = two[:, 1] > two[:, 0]          # (an exact tie is counted, not measured: identical centres tie on any hardware)
+            exact += int((~apart).sum())
+            if apart.any():
+                tie = min(tie, float(((two[apart, 1] - two[apart, 0]) / two[apart, 1]).min()))
+        inertia = float(d2[np.arange(n), labels].sum())
+        if inertia == prev:
+            break
+        prev = inertia
+        r = one_hot(labels, K)
+        cen = r.T @ X / (r.sum(axis=0) + 10 * np.finfo(np.float64).eps)[:, None]
+    return labels.astype(np.int32), cen, {"walk": walk, "tie": tie, "exact_ties": exact}
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------------

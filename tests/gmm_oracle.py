@@ -25,15 +25,20 @@ def log_prob(X, means, P, log2pi):
     n, D = X.shape
     out = np.empty((n, len(means)))
     for k in range(len(means)):
-        y = np.einsum("nd,de->ne", X, P[k]) - np.einsum("d,de->e", means[k], P[k])
+        y = X @ P[k] - means[k] @ P[k]
         out[:, k] = -0.5 * (D * log2pi + np.einsum("ne,ne->n", y, y)) + np.sum(np.log(np.diagonal(P[k])))
     return out
 
 
-def nll(X, means, P, weights, log2pi):
-    w = log_prob(X, means, P, log2pi) + np.log(np.asarray(weights, dtype=np.float64))
+def nll_of_log_prob(lp, weights):
+    """NLL [n] from logp_k [n][K]: the logsumexp over the weighted components."""
+    w = lp + np.log(np.asarray(weights, dtype=np.float64))
     m = np.max(w, axis=1, keepdims=True)
     return -(m[:, 0] + np.log(np.exp(w - m).sum(axis=1)))
+
+
+def nll(X, means, P, weights, log2pi):
+    return nll_of_log_prob(log_prob(X, means, P, log2pi), weights)
 
 
 def system_val(val, num_atoms, order):
