@@ -312,6 +312,75 @@ int vssr_batch_md(vssr_handle *h, const vssr_md_params *p, const double *mass /*
                   double *thermo /*[n_steps / thermo_interval + 1][B][2]*/, int32_t *n_done, int32_t *stop_reason);
 int vssr_batch_md_driver(vssr_handle *h, int32_t driver, int32_t *last_used);
 
+/* ---- constant-pressure and weakly-coupled MD of the resident batch (csrc/md_npt.hip) ----
+ * The step of vssr_batch_md with a Berendsen thermostat, a Berendsen barostat (isotropic or per axis) or stochastic cell rescaling
+ * around it, on every handle kind vssr_batch_md serves.  LOCK STEP ONLY: one evaluation per time step, with a barostat the kind's
+ * stress kernels behind it, then one kernel launch; vssr_batch_md_driver(RESIDENT) does not apply to this entry point.
+ * CONTRACT: restated from ASE (NVTBerendsen, NPTBerendsen, Inhomogeneous_NPTBerendsen) and from Bernetti & Bussi, J. Chem. Phys. 153,
+ * 114107 (2020) as remembered -- not pinned by an executed library.  The contract is this comment and the numpy restatement
+ * tests/npt_oracle.py.  Units as vssr_batch_md (A, eV, fs, amu, K, its kB and its eV / amu); pressure in eV / A^3, compressibility
+ * beta in A^3 / eV.  All arithmetic is fp64.  Row vectors; cell rows are lattice vectors.
+ * Per chain, behind one evaluation (E, f, and with a barostat the virial stress sigma in the sign and volume convention of
+ * vssr_batch_stress; PaiNN: the ensemble mean), with n = step0 + (steps completed in this call):
+ *  1. a non-finite E, force or (with a barostat) stress component: positions, velocities AND cell (with its inverse and image
+ *     counts) go back to the last completed step; stop reason 2.
+ *  2. a step in flight is closed: v += (dt/2) a, exactly as vssr_batch_md.
+ *  3. every thermo_interval steps a record (E_pot, E_kin, V, P): E_kin = 1/2 sum m v^2, V = |det C|, P = tr Pi / 3 with the pressure
+ *     tensor Pi = -sigma + (1/V) sum m v v^T (held atoms have v = 0).  Without a barostat no stress is evaluated and P is NaN.
+ *  4. after n_steps: stop reason 1.
+ *  5. step n is opened, in this order:
+ *     a. thermostat.  T_n: the linear ramp of vssr_batch_md (any thermostat but NONE).  NONE and LANGEVIN do nothing here (LANGEVIN
+ *        takes the BAOAB step in d).  BERENDSEN: kT_kin = 2 E_kin / (3 N_free), lambda = sqrt(1 + (dt / taut)(kB T_n / kT_kin - 1))
+ *        (0 where the argument is negative), clamped to [0.9, 1.1]; lambda = 1 if E_kin = 0 or no atom is free; v <- lambda v, and
+ *        the kinetic part of Pi used in b is scaled by lambda^2.
+ *     b. barostat, with Pi_kk the diagonal of Pi, P0 = pressure and mask[3] of 0 / 1 per Cartesian axis.  NONE: nothing (and no
+ *        stress kernel runs at all).  BERENDSEN, ISOTROPIC: P = mean of Pi_kk over the masked axes, mu = 1 - (dt beta / (3 taup))
+ *        (P0 - P) on the masked axes (mask 1 1 1: NPTBerendsen).  BERENDSEN, PER_AXIS: mu_k = 1 - (dt beta / (3 taup))(P0 - Pi_kk)
+ *        per masked axis (mask 1 1 1, orthorhombic cell: Inhomogeneous_NPTBerendsen).  Both: D = diag(mu_k), 1 on unmasked axes;
+ *        C <- C D, x <- x D for EVERY atom (held atoms ride the cell, as in vssr_batch_relax_cell), v unchanged.
+ *        CRESCALE (isotropic only): d eps = -(beta / taup)(P0 - tr Pi / 3) dt + sqrt(2 kB T_n beta dt / (V taup)) xi,
+ *        mu = exp(d eps / 3), C <- mu C, x <- mu x, v <- v / mu.  xi: one standard normal of the chain's Philox stream (key from
+ *        (seed, chain id), counter (n, atom 0), draw tag 3, first normal of pair 0: csrc/md_dev.h; MD draws use tags 0 and 1, the dimer
+ *        2).  For an ideal gas this Euler form has the stationary density p(V) ~ V^N exp(-P0 V / kB T).
+ *     c. cell check, before anything of a and b is written: the new cell must be finite, its determinant keep its sign, and it must
+ *        need no more periodic images along any axis (floor(cutoff / height) + 1) than the chain had when the call began; otherwise
+ *        the chain stops with reason 3 at the state it was evaluated at (the step is not taken).
+ *     d. integrate with the forces of this evaluation: v += (dt/2) a; x += dt v, or the Langevin BAOAB update of vssr_batch_md.
+ *        ONE evaluation per step: forces are NOT recomputed after the rescaling (a stated choice of this contract).
+ * thermo (may be NULL): [n_steps / thermo_interval + 1][B][4]; records a chain did not reach are NaN.  n_done [B] steps completed;
+ * stop_reason [B]: 1 all n_steps taken, 2 non-finite, 3 the cell check.  One chain's stop is never an error of the call.  pos_out
+ * [sum N][3], cell_out [B][9], thermo, n_done, stop_reason may each be NULL.  fixed, chain_id, mass, want as vssr_batch_md.
+ * RESUMABLE: two calls of n steps, the second with step0 = n, leave what one call of 2 n steps leaves, bit for bit (positions,
+ * velocities, cells, records), as long as no chain meets the image-count limit of 5c, which the second call takes from the cells the
+ * first one left.  BATCH-INDEPENDENT: a chain gives the same bits alone and inside any batch.  AFTERWARDS the batch holds a complete
+ * evaluation of the final state: download, vssr_batch_results_f64, vssr_batch_stress, vssr_batch_get_cell and vssr_batch_stats work at
+ * once, and later runs use the new cells until the next vssr_batch_upload.
+ * VSSR_E_STATE (before anything moves): no velocities; any barostat on a pair handle with k-space (as vssr_batch_relax_cell;
+ * thermostat-only calls are served there).  VSSR_E_BADARG (with a message, before anything moves; the handle stays usable): p or
+ * mass NULL, a non-finite parameter, n_steps < 0, thermo_interval < 1, dt <= 0, an unknown thermostat / barostat / coupling, a bad
+ * mass; with a thermostat a negative temperature or ramp_steps < 0; LANGEVIN friction <= 0; BERENDSEN thermostat taut <= 0; a mask
+ * entry other than 0 / 1; with a barostat taup <= 0, compressibility <= 0, an empty mask; CRESCALE with thermostat NONE, with
+ * PER_AXIS, with a mask other than 1 1 1, or on a chain with an open axis; a Berendsen barostat on a chain with an open axis k
+ * unless lattice vector k lies along one Cartesian axis m, the other two lattice vectors have no component along m (the rule of
+ * vssr_batch_relax_cell) and mask[m] = 0 (a slab p p f along z with mask 1 1 0 is the supported surface case). */
+enum { VSSR_NPT_THERMOSTAT_NONE = 0, VSSR_NPT_THERMOSTAT_LANGEVIN = 1, VSSR_NPT_THERMOSTAT_BERENDSEN = 2 };
+enum { VSSR_NPT_BAROSTAT_NONE = 0, VSSR_NPT_BAROSTAT_BERENDSEN = 1, VSSR_NPT_BAROSTAT_CRESCALE = 2 };
+enum { VSSR_NPT_COUPLING_ISOTROPIC = 0, VSSR_NPT_COUPLING_PER_AXIS = 1 };
+typedef struct {
+    int32_t n_steps, thermostat, barostat, coupling, thermo_interval;   /* thermo_interval >= 1 */
+    int32_t mask[3];                                /* 0 / 1 per Cartesian axis x y z (barostat) */
+    double dt;                                      /* fs */
+    double temperature, temperature_end, friction;  /* K, K, 1/fs (Langevin) */
+    double taut, taup;                              /* fs: Berendsen thermostat; barostat */
+    double pressure, compressibility;               /* eV / A^3, A^3 / eV */
+    int64_t ramp_steps, step0;
+    uint64_t seed;
+} vssr_npt_params;
+int vssr_batch_md_npt(vssr_handle *h, const vssr_npt_params *p, const double *mass /*[sum N] amu*/, const uint8_t *fixed /*or NULL*/,
+                      const uint64_t *chain_id /*[B], NULL = 0..B-1*/, uint32_t want, double *pos_out /*[sum N][3]*/,
+                      double *cell_out /*[B][9]*/, double *thermo /*[n_steps / thermo_interval + 1][B][4]*/, int32_t *n_done,
+                      int32_t *stop_reason);
+
 /* ---- harmonic vibrations of the resident batch (csrc/vib.hip, csrc/jacobi_dev.h) ----
  * Finite-difference Hessian, modes, zero-point energy and vibrational Helmholtz energy of every structure of the resident batch, on
  * every handle kind that evaluates (PaiNN: fp32 ensemble-mean forces widened to fp64; Tersoff, SW, EAM / ADP, Vashishta and pair

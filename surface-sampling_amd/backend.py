@@ -41,7 +41,7 @@ EXPORTS = (
     "vssr_vashishta_create", "vssr_vashishta_create_from_text", "vssr_vashishta_eval_batch",
     "vssr_batch_md", "vssr_batch_md_set_velocities", "vssr_batch_md_draw_velocities", "vssr_batch_md_get_velocities",
     "vssr_batch_md_driver", "vssr_batch_vibrations", "vssr_batch_neb", "vssr_batch_dimer",
-    "vssr_batch_relax_cell", "vssr_batch_get_cell",
+    "vssr_batch_relax_cell", "vssr_batch_get_cell", "vssr_batch_md_npt",
 )
 
 
@@ -166,6 +166,46 @@ def md_thermostat_code(thermostat) -> int:
     if not isinstance(thermostat, str) or thermostat not in MD_THERMOSTATS:
         raise ValueError(f"thermostat {thermostat!r}: one of {', '.join(repr(k) for k in MD_THERMOSTATS)}")
     return MD_THERMOSTATS[thermostat]
+
+
+class NptParams(C.Structure):
+    """vssr_npt_params: fs, K, 1 / fs, eV / A^3, A^3 / eV; ``thermostat`` / ``barostat`` / ``coupling`` one of ``NPT_THERMOSTATS`` /
+    ``NPT_BAROSTATS`` / ``NPT_COUPLINGS``; ``mask`` 0 / 1 per Cartesian axis."""
+    _fields_ = [("n_steps", C.c_int32), ("thermostat", C.c_int32), ("barostat", C.c_int32), ("coupling", C.c_int32),
+                ("thermo_interval", C.c_int32), ("mask", C.c_int32 * 3), ("dt", C.c_double), ("temperature", C.c_double),
+                ("temperature_end", C.c_double), ("friction", C.c_double), ("taut", C.c_double), ("taup", C.c_double),
+                ("pressure", C.c_double), ("compressibility", C.c_double), ("ramp_steps", C.c_int64), ("step0", C.c_int64),
+                ("seed", C.c_uint64)]
+
+
+NPT_THERMOSTATS = {"none": 0, "langevin": 1, "berendsen": 2}
+NPT_BAROSTATS = {"none": 0, "berendsen": 1, "crescale": 2}
+NPT_COUPLINGS = {"isotropic": 0, "per_axis": 1}
+NPT_STOP_REASONS = {1: "all steps taken", 2: "non-finite energy, force or stress",
+                    3: "cell left the image range it began with or degenerated"}
+
+
+def _npt_code(table, what, value) -> int:
+    if not isinstance(value, str) or value not in table:
+        raise ValueError(f"{what} {value!r}: one of {', '.join(repr(k) for k in table)}")
+    return table[value]
+
+
+def npt_params(steps, timestep, thermostat="none", barostat="none", coupling="isotropic", temperature=0.0, temperature_end=None,
+               friction=0.0, taut=100.0, taup=1000.0, pressure=0.0, compressibility=1.0, mask=None, ramp_steps=None, step0=0, seed=0,
+               thermo_interval=1) -> NptParams:
+    """The ``NptParams`` of ``_Handle.npt``; ``ValueError`` for an unknown name or a mask that is not three 0 / 1 (before any library
+    call; the numeric ranges are the library's to refuse)."""
+    m = [1, 1, 1] if mask is None else list(mask)
+    if len(m) != 3 or any(v not in (0, 1) for v in m):
+        raise ValueError(f"mask {mask!r}: three entries 0 or 1 (Cartesian x y z)")
+    t_end = temperature if temperature_end is None else temperature_end
+    if ramp_steps is None:
+        ramp_steps = 0 if temperature_end is None else int(steps)
+    return NptParams(int(steps), _npt_code(NPT_THERMOSTATS, "thermostat", thermostat), _npt_code(NPT_BAROSTATS, "barostat", barostat),
+                     _npt_code(NPT_COUPLINGS, "coupling", coupling), int(thermo_interval), (C.c_int32 * 3)(*[int(v) for v in m]),
+                     float(timestep), float(temperature), float(t_end), float(friction), float(taut), float(taup), float(pressure),
+                     float(compressibility), int(ramp_steps), int(step0), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
 class VibParams(C.Structure):
@@ -414,6 +454,8 @@ def load_library():
     L.vssr_batch_relax_cell.argtypes = [vp, C.POINTER(CellRelaxParams), u8p, C.c_uint32, dp, dp, ip, ip, dp]
     L.vssr_batch_get_cell.restype = C.c_int
     L.vssr_batch_get_cell.argtypes = [vp, dp]
+    L.vssr_batch_md_npt.restype = C.c_int
+    L.vssr_batch_md_npt.argtypes = [vp, C.POINTER(NptParams), dp, u8p, u64p, C.c_uint32, dp, dp, dp, ip, ip]
     L.vssr_batch_vibrations.restype = C.c_int
     L.vssr_batch_vibrations.argtypes = [vp, C.POINTER(VibParams), dp, u8p, ip, C.c_int32, C.c_int32, C.c_uint32, dp, dp, dp, dp, ip]
     L.vssr_eam_create.restype = C.c_int
@@ -821,6 +863,30 @@ class _Handle:
         self.last_md_driver = self.md_driver()
         return {"positions": pos, "velocities": self.get_velocities(), "epot": thermo[:, :, 0].copy(), "ekin": thermo[:, :, 1].copy(),
                 "n_done": done, "stop_reason": why}
+
+    def npt(self, masses, steps, timestep, fixed=None, chain_id=None, want=WANT_ALL, params=None, **kw):
+        """Constant-pressure / weakly coupled MD of the resident batch on the device, in lock step (vssr_batch_md_npt; the contract is
+        its header comment and tests/npt_oracle.py).  ``kw``: the keywords of ``npt_params`` -- ``thermostat`` ``"none"`` /
+        ``"langevin"`` / ``"berendsen"`` (``temperature``, ``temperature_end``, ``ramp_steps``, ``friction`` 1 / fs, ``taut`` fs),
+        ``barostat`` ``"none"`` / ``"berendsen"`` / ``"crescale"`` (``pressure`` eV / A^3, ``compressibility`` A^3 / eV, ``taup`` fs,
+        ``mask`` three 0 / 1 per Cartesian axis, ``coupling`` ``"isotropic"`` / ``"per_axis"``), ``step0``, ``seed``,
+        ``thermo_interval`` (``params``: an ``NptParams`` instead).  The batch needs velocities.  Returns dict(positions [sum N, 3],
+        velocities [sum N, 3], cells [B, 3, 3], epot / ekin / volume / pressure [steps // thermo_interval + 1, B] (pressure NaN
+        without a barostat), n_done [B], stop_reason [B] (``NPT_STOP_REASONS``)); ``download()`` / ``results_f64()`` / ``stress()`` /
+        ``get_cell()`` serve the final state at once, and later runs keep the new cells until the next upload."""
+        N, B = self._n_atoms, self._n_cfg
+        p = params or npt_params(steps, timestep, **kw)
+        m, fx, ids = self._masses(masses), _fixed_arg(fixed, N), self._chain_ids(chain_id)
+        nrec = max(int(p.n_steps), 0) // max(int(p.thermo_interval), 1) + 1
+        pos, cells, thermo = np.zeros((N, 3), np.float64), np.zeros((max(B, 1), 3, 3), np.float64), np.zeros((nrec, B, 4), np.float64)
+        done, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._check(self._lib.vssr_batch_md_npt(self._h, C.byref(p), _ptr(m, C.c_double), _ptr(fx, C.c_uint8), _ptr(ids, C.c_uint64),
+                                                int(want), _ptr(pos, C.c_double), _ptr(cells, C.c_double), _ptr(thermo, C.c_double),
+                                                _ptr(done, C.c_int32), _ptr(why, C.c_int32)))
+        self.last_relax_counts = self.relax_counts()
+        return {"positions": pos, "velocities": self.get_velocities(), "cells": cells[:B], "epot": thermo[:, :, 0].copy(),
+                "ekin": thermo[:, :, 1].copy(), "volume": thermo[:, :, 2].copy(), "pressure": thermo[:, :, 3].copy(), "n_done": done,
+                "stop_reason": why}
 
     # -- harmonic vibrations -------------------------------------------------------------------------
     def vibrations(self, masses, vib=None, n_rep=None, delta=0.01, nfree=2, method="standard", temperature=0.0, e_min=0.0, want=WANT_ALL,

@@ -580,8 +580,80 @@ _CELL_DOC = """Atoms and cells of B structures relaxed together on the device (`
         ExpCellFilter / FrechetCellFilter and other optimizers over the filter are out of scope."""
 
 
+def _npt_batch(get_engine, pack, atoms_list, fixed_indices, steps, timestep, thermostat, barostat, pressure, compressibility, taut, taup, mask,
+               coupling, temperature, temperature_end, friction, seed, first_chain, velocities, masses, thermo_interval, want):
+    """``npt_batch`` of every calculator: the argument checks, then on the calculator's engine (``get_engine()``, not touched before)
+    the packed structures, velocities (given, else Maxwell-Boltzmann at ``temperature``) and ``backend.npt``; the per-structure dicts."""
+    p = backend.npt_params(steps, timestep, thermostat=thermostat, barostat=barostat, coupling=coupling, temperature=temperature,
+                           temperature_end=temperature_end, friction=friction, taut=taut, taup=taup, pressure=pressure,
+                           compressibility=compressibility, mask=mask, seed=seed, thermo_interval=thermo_interval)   # (ValueError: names, mask)
+    finite = all(np.isfinite(float(v)) for v in (timestep, temperature, friction, taut, taup, pressure, compressibility))
+    if int(steps) < 0 or not (finite and float(timestep) > 0) or int(thermo_interval) < 1:
+        raise ValueError(f"npt_batch: steps {steps} >= 0, timestep {timestep} > 0 fs, thermo_interval {thermo_interval} >= 1 and finite parameters wanted")
+    if float(temperature) < 0 or (temperature_end is not None and not float(temperature_end) >= 0):
+        raise ValueError("npt_batch: a temperature is negative")
+    if thermostat == "langevin" and not float(friction) > 0:
+        raise ValueError(f"npt_batch: Langevin friction {friction} > 0 (1 / fs) wanted")
+    if thermostat == "berendsen" and not float(taut) > 0:
+        raise ValueError(f"npt_batch: taut {taut} > 0 (fs) wanted")
+    if barostat != "none":
+        if not (float(taup) > 0 and float(compressibility) > 0):
+            raise ValueError(f"npt_batch: taup {taup} > 0 (fs) and compressibility {compressibility} > 0 (A^3 / eV) wanted")
+        if not any(p.mask):
+            raise ValueError("npt_batch: a barostat with an empty mask")
+        if barostat == "crescale" and (thermostat == "none" or coupling != "isotropic" or not all(p.mask)):
+            raise ValueError("npt_batch: stochastic cell rescaling is isotropic (coupling 'isotropic', mask (1, 1, 1)) and needs a thermostat")
+    atoms_list = list(atoms_list)
+    B = len(atoms_list)
+    if not B:
+        raise ValueError("npt_batch: no structures")
+    for name, per in (("index lists", fixed_indices), ("mass arrays", masses), ("velocity arrays", velocities)):
+        if per is not None and len(per) != B:
+            raise ValueError(f"npt_batch: {len(per)} {name} for {B} structures")
+    sizes = [len(a) for a in atoms_list]
+    start = _cfg_start(sizes)
+    m = np.concatenate([structures.masses_of(a, None if masses is None else masses[b]) for b, a in enumerate(atoms_list)])
+    fixed = _fixed_mask(sizes, fixed_indices)
+    ids = np.arange(B, dtype=np.uint64) + np.uint64(int(first_chain))
+    eng = get_engine()
+    eng.upload([pack(a) for a in atoms_list])
+    if velocities is not None:
+        eng.set_velocities(np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]))
+    else:
+        eng.draw_velocities(m, temperature, seed=seed, fixed=fixed, chain_id=ids)
+    r = eng.npt(m, steps, timestep, fixed=fixed, chain_id=ids, want=want, params=p)
+    out = []
+    for b, atoms in enumerate(atoms_list):
+        a0, a1 = int(start[b]), int(start[b + 1])
+        final = atoms.copy()
+        if hasattr(final, "set_cell"):
+            final.set_cell(r["cells"][b].copy(), scale_atoms=False)
+        else:
+            final.cell = r["cells"][b].copy()
+        final.set_positions(r["positions"][a0:a1])
+        n_free = (a1 - a0) - (int(fixed[a0:a1].sum()) if fixed is not None else 0)
+        ekin = r["ekin"][:, b].copy()
+        out.append({"atoms": final, "cell": r["cells"][b].copy(), "velocities": r["velocities"][a0:a1].copy(), "epot": r["epot"][:, b].copy(),
+                    "ekin": ekin, "temperature": 2.0 * ekin / (3.0 * n_free * backend.KB_EV) if n_free else np.zeros_like(ekin),
+                    "volume": r["volume"][:, b].copy(), "pressure": r["pressure"][:, b].copy(), "n_done": int(r["n_done"][b]),
+                    "stop_reason": int(r["stop_reason"][b])})
+    return out
+
+
+_NPT_DOC = """Constant-pressure / weakly coupled MD of B independent structures at once on the device (``backend.npt``, lock step): the step
+        of ``md_batch`` with ``thermostat`` "none" / "langevin" (``friction`` 1 / fs) / "berendsen" (``taut`` fs) and ``barostat``
+        "none" / "berendsen" (``coupling`` "isotropic" = ASE's NPTBerendsen, "per_axis" = Inhomogeneous_NPTBerendsen) / "crescale"
+        (stochastic cell rescaling, isotropic, needs a thermostat).  ``pressure`` in eV / A^3, ``compressibility`` in A^3 / eV, ``taup``
+        in fs, ``mask``: three 0 / 1 per Cartesian axis (a slab periodic in x and y takes (1, 1, 0)).  Held atoms keep v = 0 and ride
+        the cell.  ``velocities`` / ``masses`` / ``seed`` / ``first_chain`` / ``thermo_interval`` as ``md_batch``.  Returns per structure
+        a dict: ``atoms`` (a copy with the final cell and positions), ``cell`` [3, 3], ``velocities``, ``epot`` / ``ekin`` /
+        ``temperature`` / ``volume`` / ``pressure`` after 0, k, 2k, ... steps (pressure NaN without a barostat), ``n_done``,
+        ``stop_reason`` (``backend.NPT_STOP_REASONS``).  Served by every calculator; a barostat not by pair models with k-space.  The
+        contract is the numpy restatement tests/npt_oracle.py, not an executed ASE."""
+
+
 class _DynamicsFrontEnds:
-    """``md_batch`` / ``vibrations_batch`` / ``neb_batch`` / ``dimer_batch`` / ``relax_cell_batch`` of a calculator with ``_get_engine``, in terms of two
+    """``md_batch`` / ``vibrations_batch`` / ``neb_batch`` / ``dimer_batch`` / ``relax_cell_batch`` / ``npt_batch`` of a calculator with ``_get_engine``, in terms of two
     hooks of the class: ``_pack(atoms) -> (Z or types, pos, cell, pbc)`` and ``_dynamics_want``, the outputs an evaluation produces."""
 
     _dynamics_want = 0
@@ -621,6 +693,16 @@ class _DynamicsFrontEnds:
                                  steps, fmax, self._dynamics_want)
 
     relax_cell_batch.__doc__ = _CELL_DOC
+
+    def npt_batch(self, atoms_list, fixed_indices=None, steps: int = 100, timestep: float = 1.0, thermostat: str = "berendsen",
+                  barostat: str = "berendsen", pressure: float = 0.0, compressibility: float = 1.0, taut: float = 100.0, taup: float = 1000.0,
+                  mask=None, coupling: str = "isotropic", temperature: float = 300.0, temperature_end=None, friction: float = 0.01,
+                  seed: int = 0, first_chain: int = 0, velocities=None, masses=None, thermo_interval: int = 1):
+        return _npt_batch(self._get_engine, self._pack, atoms_list, fixed_indices, steps, timestep, thermostat, barostat, pressure,
+                          compressibility, taut, taup, mask, coupling, temperature, temperature_end, friction, seed, first_chain, velocities,
+                          masses, thermo_interval, self._dynamics_want)
+
+    npt_batch.__doc__ = _NPT_DOC
 
 
 def _oob_flags(energy, forces, cfg_start, saturated=None, *, e_max, f_max) -> np.ndarray:

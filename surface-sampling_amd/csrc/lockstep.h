@@ -1,4 +1,4 @@
-// lockstep.h -- the host frame of the lock-step drivers (md.hip, vib.hip, neb.hip, dimer.hip, relax_cell.hip, relax_bfgsls.hip, relax_cg.hip): evaluate
+// lockstep.h -- the host frame of the lock-step drivers (md.hip, md_npt.hip, vib.hip, neb.hip, dimer.hip, relax_cell.hip, relax_bfgsls.hip, relax_cg.hip): evaluate
 // the batch, enqueue the driver's kernels behind the evaluation, poll every few evaluations, regrow after a neighbor-capacity
 // overflow, stop, leave the batch complete.  A driver brings its kernels (`launch`), a plan, and where it has work at a poll (CG's
 // Compactor) a `poll` callable.  The host only enqueues between polls: a driver's kernels test counters[2] and move nothing behind

@@ -5,8 +5,9 @@
 // analytic kinds integrate their fp64 forces (d_pot_f), PaiNN its fp32 forces widened and the fp64
 // ensemble-mean energy.  The chain-resident driver (k_md_chain, chain_min.hip) runs the same md_step_chain; the entry points below
 // choose between the two.
-// Out of scope: variable cells, thermostats other than Langevin, constraints other than FixAtoms, centre-of-mass removal (slabs hold
-// their bottom layers), neighbor-list reuse with a skin, live-chain compaction.
+// Variable cells and the Berendsen / stochastic-cell-rescaling couplings are md_npt.hip's (vssr_batch_md_npt, lock step only).
+// Out of scope: constraints other than FixAtoms, centre-of-mass removal (slabs hold their bottom layers), neighbor-list reuse with a
+// skin, live-chain compaction.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -138,7 +139,7 @@ int md_lockstep(vssr_handle *h, const MdWork &W, uint32_t want) {
     });
 }
 
-static int md_masses_ok(vssr_handle *h, const char *func, const double *mass) {
+int md_masses_ok(vssr_handle *h, const char *func, const double *mass) {
     if (!mass) return set_err(h, VSSR_E_BADARG, "%s: null masses", func);
     for (int i = 0; i < h->n_atoms; ++i)
         if (!(std::isfinite(mass[i]) && mass[i] > 0.0)) return set_err(h, VSSR_E_BADARG, "%s: mass of atom %d is %g (finite and > 0 wanted)", func, i, mass[i]);

@@ -201,6 +201,8 @@ int md_begin(vssr_handle *h, const vssr_md_params *p, const double *mass, const 
 // d_relax_steps [B][2] = (steps completed, stop reason); the thermo records into thermo_out (may be null; stream-ordered copy)
 int md_end(vssr_handle *h, const MdWork &W, double *thermo_out);
 int md_lockstep(vssr_handle *h, const MdWork &W, uint32_t want);
+// VSSR_E_BADARG (message under `func`) unless mass is [n_atoms] finite values > 0 (md.hip; md_npt.hip asks the same)
+int md_masses_ok(vssr_handle *h, const char *func, const double *mass);
 // chain_min.hip: the same integration with one workgroup per chain.  chain_md_supported: this call takes it (the kernel applies AND
 // the handle's md_driver asks for it)
 bool chain_md_supported(const vssr_handle *h);

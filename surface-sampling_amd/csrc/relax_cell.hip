@@ -18,6 +18,7 @@
 // that stopped simply stop moving.  Reductions are block_sum / block_max in a fixed order, no floating-point atomics: a chain gives the
 // same bits alone and inside any batch.
 // Out of scope: constant_volume, ExpCellFilter / FrechetCellFilter, other optimizers over the filter, trajectory rings, k-space handles.
+// (Cells that move under a barostat at finite temperature: md_npt.hip.)
 #include <cmath>
 #include <vector>
 

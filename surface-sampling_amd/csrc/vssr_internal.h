@@ -364,7 +364,7 @@ struct vssr_handle {
     // k cells per chain in d_ew_S = the largest half box of the uploaded batch (ewald_dev.h), [n_cfg][ew_stride + EW_EXTRA] double2
     // (vssr_batch_upload is the only writer of d_cell on a handle with k-space: vssr_batch_relax_cell, which changes the cells of the
     // resident chains on the device, refuses such a handle with VSSR_E_STATE -- serving it means recomputing ew_stride and re-sizing
-    // d_ew_S as the upload does, a follow-up.  Any other new entry point that changes a cell must do the one or the other; a chain whose
+    // d_ew_S as the upload does, a follow-up; vssr_batch_md_npt refuses a barostat there likewise.  Any other new entry point that changes a cell must do the one or the other; a chain whose
     // half box exceeds the stride gets NaN results from the kernels, never a partial sum)
     bool ew_on = false;
     double ew_g = 0, ew_kcut = 0, ew_q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -426,6 +426,7 @@ struct vssr_handle {
     vssr::DevBuf d_vib;           // harmonic vibrations (vib.hip): the call's workspace (VibWork)
     vssr::DevBuf d_neb;           // nudged elastic band (neb.hip): NEB forces, per-image partial sums, band records (NebWork)
     vssr::DevBuf d_dimer;         // dimer method (dimer.hip): modes, kept forces, FIRE state, per-dimer records (DimerWork)
+    vssr::DevBuf d_npt;           // constant-pressure MD (md_npt.hip): pre-step copies, masses, thermo records, per-chain state (NptWork)
     vssr::DevBuf d_cellrelax;     // variable-cell relaxation (relax_cell.hip): reference positions, velocities, per-chain state (CellWork)
     uint32_t last_want = 0;                       // outputs produced by the last run
     int64_t slot_cap = 0;
