@@ -263,6 +263,18 @@ struct FeatVec1 {
 };
 template <> struct FeatVec<1> { typedef FeatVec1 type; };
 
+// take() of every feature
+template <int NF>
+__device__ __forceinline__ typename FeatVec<NF>::type take_fv(const typename FeatVec<NF>::type &src) {
+    typename FeatVec<NF>::type d;
+    if constexpr (NF == 1) d.v = take(src.v);
+    else {
+#pragma unroll
+        for (int r = 0; r < NF; ++r) d[r] = take(src[r]);
+    }
+    return d;
+}
+
 // LDS slice layout: tile[atom][feature f][NSEG] with NSEG = {a, b, c, v_x, v_y, v_z}: the values a lane needs for its NF
 // features of one neighbor are NF * 24 contiguous bytes.  (Layer 0 never comes here: it is either
 // factorised by species, painn_l0.hip, or -- more than 8 species / VSSR_L0_FACTORISE=0 -- runs the gather kernels.)
@@ -409,9 +421,17 @@ struct BundleWalk {
     // bundle complete: move on.  Past the wave's last bundle the entries are empty (no centre, no real slot, 2 steps): the
     // hot loops test `j < nj` only between iterations, so a finished wave runs at most a few empty steps instead of
     // leaving the loop from its middle (an exit there makes the compiler's memory waits conservative on every step).
+    // PIN (reverse kernel): the old value of `pend` is taken out before the load that refills it is issued.  Left to itself the
+    // scheduler sinks the select of `pend.x` below that load; the register allocator then gives the loaded centre index a
+    // second home and copies it there at the end of the switch -- a wait for a load issued a few instructions earlier.
+    template <bool PIN = false>
     __device__ __forceinline__ void advance() {
         ++j;
         cur = nxt; nxt = select(pend, pend_ok);
+        if constexpr (PIN) {
+            asm volatile("; entry taken" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z) : : "memory");
+            __builtin_amdgcn_sched_barrier(0);
+        }
         pend = load(j + 2, pend_ok);
         t = 0; Lc = Ln; Ln = steps(nxt);
     }
@@ -845,7 +865,8 @@ k_edge_fwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G, const 
 // workgroup per CU).  (8-feature slices, 145 registers: 4 / 6 / 8 waves at two workgroups per CU measured 13.1 / 13.4 / 23.7 ms
 // per step on 490-atom chains -- 8 waves x 2 workgroups spill at 128 registers.)
 template <int NF, int WAVES>
-constexpr int cen_floats() { return WAVES * 4 * 4 * 6 * NF; }   // current-centre store: [stream][feature quarter][phi a, b, c, v x, y, z][NF]
+constexpr int cen_floats() { return WAVES * 4 * 4 * 6 * NF; }   // former current-centre store behind the slice (the record lives in registers
+                                                                // now); still allocated: the tile size sets the chain-class boundaries
 template <int NF, int WAVES>
 size_t edge_bwd_lds_bytes_t(int max_atoms) { return sizeof(float) * ((size_t)max_atoms * EdgeGeo<NF>::ROWB + cen_floats<NF, WAVES>()); }
 
@@ -960,13 +981,14 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
     if (bw.nj == 0) return;   // (no barrier below)
 
     // ---- per-centre data of this lane's NF features: phi_c (a, b, c) and v_c -------------------------------------------
-    // The CURRENT centre's values live in a small LDS record per (stream, feature quarter) and are re-read every step
-    // next to the neighbor gathers (6 broadcast LDS reads); the NEXT bundle's values are in flight in registers
-    // and are parked in the record when the wave moves on.  (Keeping both sets in registers made the compiler
-    // rotate ~50 registers per completed centre and wait on the prefetch it had just issued.)
-    const int cen_idx = max_atoms * ROWB + ((wave * 4 + (p >> 2)) * 4 + fq) * 6 * NF;   // float index in tile[]
-    fvx *cen = reinterpret_cast<fvx *>(tile + cen_idx);
-    fvx nx[6];
+    // Both sets live in registers: cv, the CURRENT centre's values (loop-carried, 6 NF registers; a step's only LDS reads are its
+    // NF neighbor gathers), and nx, the NEXT bundle's values, in flight since the last switch.  When the wave moves on, cv <- nx
+    // goes through explicit moves (take()) in front of a scheduling barrier and only then nx is requested again: the loads land in
+    // the registers the moves have just left.  Written as plain copies the compiler rotated ~50 registers per completed centre and
+    // waited on the prefetch it had just issued; that is why the current record used to be parked in LDS behind the slice and
+    // re-read on every step (6 of the 10 16-byte LDS reads per lane and step).  The same accident in small: BundleWalk::advance<true>.
+    // Registers (gfx950): 204 -> 202 with 16-feature slices, 0 spilled; the park area is still part of the tile size.
+    fvx nx[6], cv[6];
     auto load_centre = [&](int cc) {   // always a load (any valid row for streams without a centre)
         const size_t ga = mN + a0 + min(max(cc, 0), Nc - 1);
         const float *pr = phi + ga * F3 + fcol;
@@ -977,12 +999,13 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
         nx[4] = *reinterpret_cast<const fvx *>(v_in + (ga * 3 + 1) * F + fcol);
         nx[5] = *reinterpret_cast<const fvx *>(v_in + (ga * 3 + 2) * F + fcol);
     };
-    auto park_centre = [&]() {   // the quad's 4 slot lanes hold identical values: any of them may write
+    auto next_centre = [&]() {   // cv <- nx; the wait for nx is here, where it is written
 #pragma unroll
-        for (int q = 0; q < 6; ++q) cen[q] = nx[q];
+        for (int q = 0; q < 6; ++q) cv[q] = take_fv<NF>(nx[q]);
     };
     load_centre(bw.cur.x);
-    park_centre();
+    next_centre();
+    __builtin_amdgcn_sched_barrier(0);
     load_centre(bw.nxt.x);
     // (SUB) what the centre's sums are added to, requested when its bundle starts: vbar_msg_c (pass 0: the residual, the centre's own
     // row may not be staged) resp. the phibar_c / vbar_c the earlier passes wrote
@@ -1009,7 +1032,6 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
         const int c = bw.cur.x;
         if (e == 0 && c >= 0) {
             const size_t ga = mN + a0 + c;
-            const fvx cv[6] = {cen[0], cen[1], cen[2], cen[3], cen[4], cen[5]};   // record of the completed centre
             float a_[NF], x_[NF], y_[NF], z_[NF];
             const float *res = tile + c * ROWB + (NF * fq) * 4;   // [r][sbar, vbar_x, vbar_y, vbar_z]
 #pragma unroll
@@ -1082,8 +1104,8 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
             }
             if (bw.t == bw.Lc) {   // wave-uniform: the bundle is complete
                 flush_bundle();
-                bw.advance();
-                park_centre();                       // centre data of the bundle that starts now
+                bw.template advance<true>();
+                next_centre();                       // centre data of the bundle that starts now
                 __builtin_amdgcn_sched_barrier(0);   // the old values leave their registers before the loads that refill them are issued
                 load_centre(bw.nxt.x);
                 if constexpr (SUB) load_rres(bw.cur.x);
@@ -1099,17 +1121,6 @@ k_edge_bwd_mfma(int N, int l, const ModelW *__restrict__ MW, GraphView G,
                     const f32x4 t4 = lds_read4(row + 4 * q);
                     tb[4 * q] = t4[0]; tb[4 * q + 1] = t4[1]; tb[4 * q + 2] = t4[2]; tb[4 * q + 3] = t4[3];
                 }
-            }
-            // (the record's index passes through an empty asm: otherwise the compiler forwards the parked registers to these
-            // reads, hoists them into the tail of the previous step and shuffles / waits on the registers of the prefetch
-            // it has just issued)
-            fvx cv[6];
-            {
-                int ci = cen_idx;   // (the INDEX is laundered: a laundered pointer loses its LDS address space -> flat loads)
-                asm volatile("" : "+v"(ci));
-                const fvx *cr = reinterpret_cast<const fvx *>(tile + ci);
-#pragma unroll
-                for (int q = 0; q < 6; ++q) cv[q] = cr[q];
             }
             // unit vector c -> n (edge (n -> c) has -u) and 1 / d: the record's scalar words, all-gathered over the slot's four lanes
             float ux, uy, uz, invd;
