@@ -14,11 +14,11 @@ import os
 import numpy as np
 import pytest
 
+from painn_config_cases import E_TOL, F_TOL, STD_TOL, check
 from painn_shapes import checkpoint_bytes, reshape_ensemble
 
 pytestmark = pytest.mark.gpu
 
-E_TOL, F_TOL, STD_TOL = 1e-4, 2e-4, 2e-4
 SHAPES = [(16, 8), (32, 12), (64, 16), (96, 20), (192, 24), (256, 32)]
 
 
@@ -49,22 +49,8 @@ def _ohp(oracle_mod, hp):
 
 
 def _check(golden, oracle_mod, blobs, hp, s, e, f, std, tag=""):
-    """Device results of one structure against the fp64 oracle; returns (dE, dF, dstd)."""
-    table, const = golden.offset_table()
-    ref = oracle_mod.ensemble(blobs, s.numbers, s.positions, s.cell, s.pbc, 64, table, const, hp=_ohp(oracle_mod, hp))
-    de, df, ds = abs(e - ref["energy"]), float(np.abs(f - ref["forces"]).max()) if len(f) else 0.0, abs(std - ref["energy_std"])
-    r32 = oracle_mod.ensemble(blobs, s.numbers, s.positions, s.cell, s.pbc, 32, table, const, hp=_ohp(oracle_mod, hp))
-    de32 = abs(r32["energy"] - ref["energy"])
-    df32 = float(np.abs(r32["forces"] - ref["forces"]).max()) if len(f) else 0.0
-    ds32 = abs(r32["energy_std"] - ref["energy_std"])
-    print(f"deviation from the fp64 oracle {tag} N={len(s.numbers)}: device dE {de:.2e} dF {df:.2e} dstd {ds:.2e} | "
-          f"oracle fp32 dE {de32:.2e} dF {df32:.2e} dstd {ds32:.2e}")
-    if de <= E_TOL and df <= F_TOL and ds <= STD_TOL:
-        return de, df, ds
-    assert de <= max(E_TOL, 2 * de32), (tag, de, de32)
-    assert df <= max(F_TOL, 2 * df32), (tag, df, df32)
-    assert ds <= max(STD_TOL, 2 * ds32), (tag, ds, ds32)
-    return de, df, ds
+    """Device results of one structure against the fp64 oracle (the rule of painn_config_cases.check); returns (dE, dF, dstd)."""
+    return check(golden, oracle_mod, blobs, _ohp(oracle_mod, hp), s, e, f, std, tag)
 
 
 def test_forced_general_path_on_the_shipped_ensemble(golden, oracle_mod):
